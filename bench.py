@@ -69,6 +69,21 @@ def build_model(w, H, W, device, n_fine=64, compute_dtype="f32"):
     return model.to(device), usd, msd
 
 
+DUMP_MAX_ELEMS = {"denoise_sample": 1 << 23, "images_render": 1 << 21, "depths_render": 1 << 21, "masks_render": 1 << 21}
+DUMP_SEED = 0  # (56 MB of float32 at most: under the 64 MB --dump-outputs allows)
+
+
+def dump_array(t: torch.Tensor, max_elems: int) -> np.ndarray:
+    """float32 host copy of `t` for --dump-outputs: the whole tensor when it has at most `max_elems` elements, else the
+    elements at `max_elems` sorted flat (C-order) indices drawn by numpy's default_rng(DUMP_SEED), the same positions on
+    every run for the same shape."""
+    t = t.detach().contiguous()
+    if t.numel() <= max_elems:
+        return t.float().cpu().numpy()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), size=max_elems, replace=False))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+
+
 def barrier_sync(world):
     torch.cuda.synchronize()
     if world > 1:
@@ -395,7 +410,14 @@ def main():
     ap.add_argument("--no-opt-in", action="store_true", help="skip the side measurements of the opt-in arithmetic modes")
     ap.add_argument("--dry-run", action="store_true", help="launch plumbing only (rendezvous + reductions), no kernels")
     ap.add_argument("--conv-iters", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32, rank 0): denoise_sample (the chain's sample after the last timed step) and images_render / "
+                         "depths_render / masks_render (the timed render call); an array above its element budget is written as a "
+                         "fixed, seeded sample of its flattened elements (dump_array)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_torchrun(args.gpus)  # does not return
@@ -464,6 +486,9 @@ def main():
     if args.noise == "device" and cl_chain:
         img = img.permute(0, 4, 1, 2, 3).contiguous()
     assert torch.isfinite(img).all()
+    dumps = {}  # --dump-outputs: host copies taken outside the timed regions, written at the end
+    if args.dump_outputs and rank == 0:
+        dumps["denoise_sample"] = dump_array(img, DUMP_MAX_ELEMS["denoise_sample"])
     steps_per_s = world * K / dt
     # the other noise path over the same K timesteps (side figure, this rank only)
     other_mode = "torch" if args.noise == "device" else "device"
@@ -505,6 +530,9 @@ def main():
         dtr = time.perf_counter() - t0
     dtr = max_over_ranks(dtr, world, device)
     assert torch.isfinite(out["images_render"]).all()
+    if args.dump_outputs and rank == 0:  # (before the later render calls can reuse the renderer's output buffers)
+        for k in ("images_render", "depths_render", "masks_render"):
+            dumps[k] = dump_array(out[k], DUMP_MAX_ELEMS[k])
     rays_per_s = world * F * H * W / dtr
     # the same leg at a second call size (default: the 8-frame call round 1 reported): a secondary figure
     F40 = args.flyaround_frames
@@ -888,6 +916,12 @@ def main():
             "side_workloads": side,
             "opt_in_modes_not_reported": alt,
         }
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for k, v in dumps.items():
+                np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
+            print(f"# bench.py: wrote {', '.join(f'{k}{tuple(v.shape)}' for k, v in dumps.items())} to {args.dump_outputs}",
+                  file=sys.stderr)
         print(json.dumps(line))
 
 

@@ -47,12 +47,13 @@ def test_gather_frames_gloo_world2():
 
 def test_bench_gpus_flag_spawns_that_many_ranks():
     """`python bench.py --gpus 2` with no launcher must start 2 ranks itself and report the LIVE world size
-    (--dry-run: rendezvous + reductions only, gloo on CPU here, RCCL on the GPU node)."""
+    (--dry-run: rendezvous + reductions only, over gloo with no HIP device visible to the ranks)."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"  # (a GPU node may have fewer GPUs than ranks)
     res = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--dry-run"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert res.returncode == 0, res.stderr[-2000:]

@@ -38,6 +38,17 @@ def _experiment(tmp_path):
     return str(d)
 
 
+def _host_env():
+    """The environment of the launched ranks: no launcher variables inherited, and no HIP device visible, so that these
+    cases run the gloo / host path they assert on a GPU node too (the emulation library cannot take device pointers).  A
+    few torch threads per rank: on a many-core host, every rank's idle OpenMP workers spinning between ops starve the
+    emulation's lane threads."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    env["OMP_NUM_THREADS"] = "4"
+    return env
+
+
 def _run(cmd, env):
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env)
     assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-3000:]
@@ -47,7 +58,7 @@ def _run(cmd, env):
 def test_generate_cli_world2_gloo_equals_single_process(tmp_path):
     exp = _experiment(tmp_path)
     script = os.path.join(REPO, "tests", "support", "generate_cli_stub.py")
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    env = _host_env()
     args = ["num_samples=3", "n_eval_cameras=2", "render_size=[12,10]", "seed=5"]
     port = 29600 + os.getpid() % 1500
     out2 = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
@@ -67,11 +78,21 @@ def test_generate_cli_world2_gloo_equals_single_process(tmp_path):
     assert not torch.equal(a0, a1)
 
 
-_HAVE_EMU = os.path.isfile(os.path.join(REPO, "tests", "emu", "libholo_emu.so"))
+@pytest.fixture(scope="module")
+def emu_library():
+    """tests/emu/libholo_emu.so, built or brought up to date from the kernel sources (`make -C holo_diffusion_amd/csrc emu`):
+    a clean checkout has none, and one left from older sources would test stale code.  The emulation stands in for the
+    GPU on a machine without one; on a GPU node the `-m gpu` tests run the kernels themselves (and lane-per-thread
+    emulation on a many-core host outruns any CPU-suite time budget)."""
+    if torch.cuda.is_available():
+        pytest.skip("host emulation of the kernels: for a machine without a GPU")
+    res = subprocess.run(["make", "-C", os.path.join(REPO, "holo_diffusion_amd", "csrc"), "emu"], capture_output=True,
+                         text=True, timeout=1800)
+    assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-3000:]
+    return os.path.join(REPO, "tests", "emu", "libholo_emu.so")
 
 
-@pytest.mark.skipif(not _HAVE_EMU, reason="needs the host emulation library (`make -C holo_diffusion_amd/csrc emu`)")
-def test_generate_cli_world2_gloo_on_the_emulated_kernels_short(tmp_path):
+def test_generate_cli_world2_gloo_on_the_emulated_kernels_short(tmp_path, emu_library):
     """The multi-rank product entry with the REAL model on the host emulation of the kernels, cheap enough for every CPU
     suite: chains subsampled to 2 of their 20 steps (the launcher's HOLO_TEST_MAX_ITER), 2 samples over 2 ranks, 2 cameras at
     8 x 8 - equal, bit for bit, to the single-process run."""
@@ -79,9 +100,9 @@ def test_generate_cli_world2_gloo_on_the_emulated_kernels_short(tmp_path):
 
 
 @pytest.mark.slow
-@pytest.mark.skipif(os.environ.get("HOLO_TEST_EMU_SLOW") != "1" or not _HAVE_EMU,
-                    reason="opt-in (HOLO_TEST_EMU_SLOW=1 + `make -C holo_diffusion_amd/csrc emu`): ~15 minutes of host emulation")
-def test_generate_cli_world2_gloo_on_the_emulated_kernels(tmp_path):
+@pytest.mark.skipif(os.environ.get("HOLO_TEST_EMU_SLOW") != "1",
+                    reason="opt-in (HOLO_TEST_EMU_SLOW=1): ~15 minutes of host emulation")
+def test_generate_cli_world2_gloo_on_the_emulated_kernels(tmp_path, emu_library):
     """The same with the whole 20-step schedule."""
     _emulated_cli_case(tmp_path, max_iter=None)
 
@@ -105,7 +126,7 @@ def _emulated_cli_case(tmp_path, max_iter, tiny=False):
     kw, _ = ck.model_args_from_expconfig(ck.read_expconfig(str(d))[0])
     torch.save(_reference_like_state(hda.HoloDiffusionModel(**kw), 11), str(d / "model_epoch_00000001.pth"))
     script = os.path.join(REPO, "tests", "support", "generate_cli_emu.py")
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    env = _host_env()
     if max_iter:
         env["HOLO_TEST_MAX_ITER"] = str(max_iter)
     args = ["num_samples=2", "n_eval_cameras=2", "render_size=[8,8]", "seed=5"]

@@ -29,10 +29,15 @@ def test_schedule_tables_bit_equal(golden_dir):
 
 
 def test_timestep_embedding(golden_dir):
+    """Bit-equal on the CPU the vectors were recorded on (make_golden.py asserts it there).  Other CPUs round exp / cos / sin
+    differently in the last bit: one ulp of a frequency moves t * freq by up to t ulps, so each element is held to
+    4 ulps of (1 + t) in float32."""
     g = np.load(os.path.join(golden_dir, "timestep_embedding.npz"))
     ts = torch.from_numpy(g["t"])
+    tol = 4 * torch.finfo(torch.float32).eps * (1.0 + ts.double()[:, None])
     for dim in (32, 64):
-        assert torch.equal(uo.timestep_embedding(ts, dim), torch.from_numpy(g[f"emb{dim}"]))
+        err = (uo.timestep_embedding(ts, dim).double() - torch.from_numpy(g[f"emb{dim}"]).double()).abs()
+        assert (err <= tol).all(), (dim, (err / tol).max().item())
 
 
 def test_tiny_unet_and_blocks(golden_dir):
@@ -221,7 +226,11 @@ def test_images_from_preds_vs_reference_body(golden_dir):
 
 def test_oracle_autograd_vs_reference_module_gradients(golden_dir):
     """Autograd through the oracle's forward reproduces the gradients of the REFERENCE UNetModel (ref_unet_backward.npz):
-    this is what lets the `-m gpu` backward tests use the oracle as their gradient reference for other net shapes."""
+    this is what lets the `-m gpu` backward tests use the oracle as their gradient reference for other net shapes.
+    Tolerance: 1e-5 of the larger of the tensor's own scale and the net's median gradient scale.  The rounding error of a
+    float32 gradient follows the size of the terms summed into it, not its own size: a gradient that is mathematically
+    zero (a bias in front of a GroupNorm of single-channel groups) is roundoff of the net's gradient scale, and another
+    CPU's kernels sum in another order."""
     g = np.load(os.path.join(golden_dir, "ref_unet_backward.npz"))
     cfg = TINY_CFG
     sd = synth_state_dict(uo.unet_param_shapes(cfg), int(g["seed"]))
@@ -231,9 +240,10 @@ def test_oracle_autograd_vs_reference_module_gradients(golden_dir):
     xr = x.clone().requires_grad_(True)
     with torch.enable_grad():
         uo.unet_forward.__wrapped__(sdr, cfg, xr, t).mean().backward()
+    net_scale = float(np.median([float(g[f"mean.scale.{k}"]) for k in sd]))
     for k in list(sd) + ["grad_x"]:
         f = (xr.grad if k == "grad_x" else sdr[k].grad).reshape(-1)
         if f.numel() > 4096:
             f = f[torch.cat([torch.arange(2048), torch.linspace(2048, f.numel() - 1, 2048).long()])]
-        scale = max(float(g[f"mean.scale.{k}"]), float(g["mean.floor"]))
+        scale = max(float(g[f"mean.scale.{k}"]), net_scale)
         assert (f - torch.from_numpy(g[f"mean.{k}"])).abs().max().item() <= 1e-5 * scale, k
