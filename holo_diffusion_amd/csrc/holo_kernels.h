@@ -21,6 +21,22 @@ namespace holo {
 // the tile is staged, zero padding applied AFTER the activation; optional nearest x2 upsample on load;
 // optional virtual channel concat of two sources (UNet skip connection, unet.py:829).
 // ---------------------------------------------------------------------------------------------
+// The kernel conv_plan chose for a launch.  The values are the HoloOpTiming.kernel ids of holo_unet_time_ops
+// (include/holo_abi.h); id 3, the retired depth-only Winograd form, is not used.
+enum class ConvKernel : int32_t {
+  Gather = 0,          // per-tap gather kernel (conv_igemm_kernel)
+  Halo = 1,            // LDS voxel-halo kernel (conv_halo_kernel; conv_halo_split_kernel in the bf16x3 mode)
+  RowTile = 2,         // row-tile kernel (conv_small_kernel): 1x1x1, strided and deepest-level convolutions
+  Wino2 = 4,           // (z,y) Winograd form of the 128-voxel halo kernel (conv_wino2_kernel)
+  Bf16Wide = 5,        // bf16 wide-tile kernel (conv_bf16t_kernel)
+  Wino3 = 6,           // F(2x2x2, 3x3x3) Winograd form (conv_wino3_kernel, kernels_conv3.hip)
+  Stream1x1 = 7,       // streaming 1x1x1 kernel (conv1x1_stream_kernel): large grids, raw input
+  Bf16Persistent = 8,  // the wide-tile kernel's persistent wave-specialised form (conv_bf16p_kernel, kernels_conv_bf16p.hip)
+  S2Bf16 = 9,          // stride-2 bf16 halo kernel (conv_s2_bf16_kernel, kernels_conv_s2.hip)
+  Qkv = 10,            // qkv convolution fused with the attention's operand packing (conv1x1_qkv_bf16_kernel)
+  Bf16Stream1x1 = 11,  // streaming 1x1x1 convolution on bf16 storage (conv1x1_bf16_stream_kernel)
+};
+
 struct ConvParams {
   const float* src0;
   const float* src1;  // may be null
@@ -58,25 +74,17 @@ struct ConvParams {
   int nsplit;             // split-K factor over (tap, cin-chunk) chunks
   int chunks_per_split;
   int skip_chunks_per_split;  // halo kernel with a fused skip: skip chunks are dealt evenly to the same splits
-  int tz;                 // halo kernel tile depth (set by conv_plan)
+  int tz;                 // halo forms: tile depth (set by conv_plan; left 0 for the other kernels)
   int grid_x;             // halo kernel: persistent workgroups along x (set by conv_plan)
   int stagger_ticks;      // halo kernel: phase offset (100 MHz ticks) of the workgroup in the odd slot of a CU
   unsigned long long* dbg;  // optional timeline probe (scripts/conv_timeline.cpp): [tile][8] {t_start, t_first_halo,
                             // t_loops_done, t_end (100 MHz wall clock), HW_ID, XCC_ID, 0, 0}; null in production
-  int mode;               // set by conv_plan: 0 = per-tap gather kernel, 1 = LDS voxel-halo kernel, 2 = row-tile kernel,
-                          // 3 = streaming 1x1x1 kernel (large grids, raw input), 4 = stride-2 bf16 halo kernel (kernels_conv_s2.hip),
-                          // 5 = qkv convolution fused with the attention's operand packing, 6 = streaming 1x1x1 convolution on bf16
-                          // storage (kernels_conv1x1_bf16.hip)
-  // Winograd-in-depth form of the 128-voxel halo kernel (conv_wino_kernel): weights pre-transformed along kz,
-  // U_xi = sum_kz G[xi][kz] w[kz], packed like w with 36 pseudo-taps xi*9 + ky*3 + kx; the fused skip as 2 pseudo-taps
-  // (+w/2, -w/2).  Null = not prepared for this conv (the direct kernel runs).
-  const float* w_wino;
-  const float* skip_w_wino;
+  ConvKernel kernel;      // set by conv_plan
   // (z,y) Winograd form (conv_wino2_kernel): U = sum_kz,ky G[xi_z][kz] G[xi_y][ky] w[kz][ky][kx], 48 pseudo-taps
-  // (xi_z*4 + xi_y)*3 + kx; the fused skip as 4 pseudo-taps (xi_z,xi_y in {1,2}^2: +-w/4)
+  // (xi_z*4 + xi_y)*3 + kx; the fused skip as 4 pseudo-taps (xi_z,xi_y in {1,2}^2: +-w/4).  Null = not prepared for this
+  // conv (the direct kernel runs).
   const float* w_wino2;
   const float* skip_w_wino2;
-  int wino;               // set by conv_plan: 0 direct, 1 Winograd in depth, 2 Winograd in depth and height, 3 all three axes
   // F(2x2x2, 3x3x3) form (conv_wino3_kernel, kernels_conv3.hip): the 64 pseudo-taps in the wave's consumption order
   // (repack_conv_weight_wino3_launch); the fused skip as 8 signed copies of the 1x1x1 weight
   const float* w_wino3;
@@ -86,16 +94,13 @@ struct ConvParams {
   // (tap, 16-channel chunk, 32-Cout slice); lane's 8 values are channels 8*(lane>>5) .. +7 of output channel lane&31
   const uint16_t* w_bft;
   const uint16_t* skip_w_bft;
-  int bf16t;              // set by conv_plan: the launch runs on conv_bf16t_kernel
-  int bf16p;              // set by conv_plan (with bf16t): ... on its persistent wave-specialised form, conv_bf16p_kernel
-                          // (kernels_conv_bf16p.hip: grid_x workgroups of 8 waves, 4 consumers + 4 producers, no split-K)
   // bf16 STORAGE (compute mode bf16): the buffers behind these float* are bf16 (uint16_t) channels-last tensors;
   // coefficients, bias, statistics and split-K scratch stay fp32 / double
   int in_bf16;            // src0 / src1 / skip_src0 / skip_src1
   int res_bf16;           // residual
   int out_bf16;           // out
   // the qkv convolution of an AttentionBlock fused with the operand packing of the bf16 attention (kernels_conv1x1_bf16.hip;
-  // set by the planner when the launch may take that form, conv_plan decides: mode 5): `out` is then NOT written
+  // set by the planner when the launch may take that form, conv_plan decides: ConvKernel::Qkv): `out` is then NOT written
   uint16_t* qkv_q;        // bf16 [sample, head][T][CH], scaled by qkv_scale
   uint16_t* qkv_k;        // bf16 [sample, head][T][CH]
   uint16_t* qkv_vt;       // bf16 [sample, head][CH][T]
@@ -133,7 +138,7 @@ size_t conv_plan(ConvParams& p, int num_cus);
 int conv_launch(const ConvParams& p, void* stream);
 int conv_stats_slabs(const ConvParams& p);
 double conv_flops(const ConvParams& p);       // algorithmic (the reference's multiply-adds x 2)
-double conv_exec_flops(const ConvParams& p);  // issued to the matrix pipe (differs for the Winograd-in-depth kernel)
+double conv_exec_flops(const ConvParams& p);  // issued to the matrix pipe (differs for the Winograd kernels)
 
 // ---------------------------------------------------------------------------------------------
 // batched GEMM on fp32 MFMA (kernels_gemm.hip):  C[b] = alpha * A[b] * B[b]^T
@@ -244,10 +249,10 @@ int clip_launch(const float* x, float* y, float lo, float hi, int64_t n, void* s
 int repack_conv_weight_bf16_launch(const float* w, uint16_t* out, int Cout, int Cin, int taps, int CoutP, int CinP,
                                    void* stream);
 // OIDHW [Cout][Cin][taps] -> zero padded MFMA-fragment-packed layout (see ConvParams::w)
-// OIDHW 3x3x3 (src_taps = 27) -> 36 Winograd-in-depth pseudo-taps, or a 1x1x1 skip weight (src_taps = 1) -> its 2
+// OIDHW 3x3x3 (src_taps = 27) -> 48 (z,y) Winograd pseudo-taps, or a 1x1x1 skip weight (src_taps = 1) -> its 4
 // pseudo-taps; same packed layout as repack_conv_weight_launch
-int repack_conv_weight_wino_launch(const float* w, float* out, int Cout, int Cin, int src_taps, int CoutP, int CinP,
-                                   void* stream, int dims = 1);  // dims 2: (z,y) form, 48 / 4 pseudo-taps
+int repack_conv_weight_wino2_launch(const float* w, float* out, int Cout, int Cin, int src_taps, int CoutP, int CinP,
+                                    void* stream);
 int repack_conv_weight_launch(const float* w, float* out, int Cout, int Cin, int taps, int CoutP, int CinP,
                               void* stream);
 

@@ -756,10 +756,10 @@ __device__ __forceinline__ float4 pack_bf16x8(const float (&f)[8]) {
                      __uint_as_float(pack_bf16x2(f[4], f[5])), __uint_as_float(pack_bf16x2(f[6], f[7])));
 }
 
-// SCHED: 2 = one operand request behind each MFMA of a tap (measured 6-7 % faster than 0 = requests in a clump between
-// the taps' MFMA groups; leaving the order to the compiler was 13 % slower than 0).  HT: the tap under which the next
+// Schedule: one operand request behind each MFMA of a tap (measured 6-7 % faster than requests in a clump between the
+// taps' MFMA groups; leaving the order to the compiler was 13 % slower than the clump).  HT: the tap under which the next
 // chunk's halo is requested (8, 16, 20 and 23 measured within run-to-run noise of each other)
-template <int NT, bool SKIP, bool IOBF, int SCHED = 2, int HT = 16>
+template <int NT, bool SKIP, bool IOBF, int HT = 16>
 __global__ __launch_bounds__(256, 2) void conv_bf16t_kernel(ConvParams p) {
   constexpr int ES = IOBF ? 2 : 4;  // bytes per activation element in HBM
   constexpr int NV = IOBF ? 1 : 2;  // 16-byte loads per staging item
@@ -950,9 +950,8 @@ __global__ __launch_bounds__(256, 2) void conv_bf16t_kernel(ConvParams p) {
       if (tap + 1 < 27) load_a(A[(tap + 1) & 1], tap + 1);
       if (tap + 2 < 27) load_b(B[(tap + 2) % 3], cc, tap + 2);
       if (tap == HT && has_next) halo_issue(cc + 1);  // the next chunk's raw halo flies under taps HT..26
-      if (SCHED == 0) __builtin_amdgcn_sched_barrier(0);  // (0: all requests AHEAD of the tap's MFMAs)
       mfma_tap(A[tap & 1], B[tap % 3]);
-      if (SCHED == 2 && tap != HT) {  // one operand request behind each MFMA instead of a clump after the eighth
+      if (tap != HT) {  // one operand request behind each MFMA instead of a clump after the eighth
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -1177,339 +1176,23 @@ __global__ __launch_bounds__(256, 2) void conv_bf16t_kernel(ConvParams p) {
 
 
 // ---------------------------------------------------------------------------------------------
-// Winograd-in-depth form of the halo kernel for the 128-voxel tiles (the 64^3 level: 80 % of the FLOPs).
+// Winograd form of the halo kernel for the 128-voxel tiles (the 64^3 level: 80 % of the FLOPs): F(2x2, 3x3) over (z, y).
 //
 // The exact-fp32 MFMA runs at the vector rate, so the only way below the 27-tap multiply count in fp32 is to multiply
-// less.  The 2 x 8 x 8 output tile needs exactly the 4 input planes of ONE Winograd F(2,3) tile along z:
+// less.  In depth: the 2 x 8 x 8 output tile needs exactly the 4 input planes of ONE Winograd F(2,3) tile along z:
 //   V_xi = (B^T d)_xi        d = the 4 activated halo planes of a (y,x) column    B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
 //   M_xi = sum_{ky,kx,ci} U_xi[ky][kx][ci][co] * V_xi(y+ky, x+kx, ci)              U_xi = sum_kz G[xi][kz] w[kz]  (prepared once)
 //   out(z0) = M_0 + M_1 + M_2,   out(z1) = M_1 - M_2 - M_3
 // i.e. 4 x 9 = 36 pseudo-taps produce TWO output planes where the direct form spends 2 x 27 = 54: 2/3 of the MFMAs,
 // same data movement.  The transform of the inputs happens ONCE per workgroup while the halo is committed to LDS (the
 // thread that stages a (y,x) column holds its four planes): the four LDS planes simply hold V_0..V_3 instead of the raw
-// planes, and the tap loop below is the direct kernel's with "plane" read as "xi".  The output transform is lane-local
-// (a lane's accumulators of the four xi belong to the same voxels).  Arithmetic: fp32 throughout; F(2,3) adds one
-// rounding of an add before and after the products (measured against float64: same error as the direct form).
-// The fused 1x1x1 skip connection (centre tap) becomes the two pseudo-taps xi = 1, 2 with weights +w/2, -w/2.
-// ---------------------------------------------------------------------------------------------
-template <bool SKIP>
-__global__ __launch_bounds__(256, 2) void conv_wino_kernel(ConvParams p) {
-  constexpr int RS = LDK;
-  constexpr int MT = 4;                // 16-voxel tiles of the 8 x 8 plane (each accumulates four xi)
-  constexpr int PLANE = HY * HX;       // 100 (y,x) columns of the halo
-  constexpr int HALO_VOX = 4 * PLANE;  // four xi planes
-  constexpr int COLS_IT = (PLANE * 8 + 255) / 256;  // (column, channel quad) items per thread: 4
-  __shared__ __attribute__((aligned(16))) float s_halo[HALO_VOX * RS];
-  __shared__ int s_hcol[COLS_IT * 256];  // clamped source (y,x) offset of every item, per tile
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wn = tid >> 6;  // the wave owns output channels [16 wn, 16 wn + 16) of the block's 64
-  const int lj = lane & 15;
-  const int kq = lane >> 4;
-  const int Cin = p.C0 + p.C1;
-  const int ncc = (Cin + BK - 1) / BK;
-  const int ntx = p.OW >> 3, nty = p.OH >> 3, ntz = p.OD >> 1;
-  int tile = blockIdx.x;
-  const int tx0 = (tile % ntx) << 3;
-  tile /= ntx;
-  const int ty0 = (tile % nty) << 3;
-  tile /= nty;
-  const int tz0 = (tile % ntz) * 2;
-  const int n = tile / ntz;
-  const int n0 = blockIdx.y * 64;
-  const int SCin = p.skip_C0 + p.skip_C1;
-  const int nsk = SKIP ? (SCin + BK - 1) / BK : 0;
-  const int cc_begin = blockIdx.z * p.chunks_per_split;
-  int cc_end = cc_begin + p.chunks_per_split;
-  if (cc_end > ncc) cc_end = ncc;
-  const int sk_begin = ncc + blockIdx.z * p.skip_chunks_per_split;
-  int sk_end = sk_begin + p.skip_chunks_per_split;
-  if (sk_end > ncc + nsk) sk_end = ncc + nsk;
-  const int SD = p.ups ? (p.ID >> 1) : p.ID;
-  const int SH = p.ups ? (p.IH >> 1) : p.IH;
-  const int SW = p.ups ? (p.IW >> 1) : p.IW;
-
-  // ---- staging: item = ((y,x) column, channel quad); the thread loads the column's four planes, activates them,
-  //      applies the input transform along z and writes the four xi values
-  const int q = tid & 7;
-  float4 hreg[COLS_IT][4];
-  unsigned cvalid = 0;  // bit i: column of item i is inside the volume (y,x)
-  unsigned zvalid = 0;  // bit pl: plane pl is inside the volume (z), uniform
-  int zsrc[4];
-#pragma unroll
-  for (int pl = 0; pl < 4; ++pl) {
-    int z = tz0 + pl - 1;
-    zvalid |= (z >= 0 && z < p.ID ? 1u : 0u) << pl;
-    z = min(max(z, 0), p.ID - 1);
-    if (p.ups) z >>= 1;
-    zsrc[pl] = z * SH * SW;
-  }
-#pragma unroll
-  for (int i = 0; i < COLS_IT; ++i) {
-    const int col = min((tid >> 3) + 32 * i, PLANE - 1);
-    const int hy = col / HX, hx = col - hy * HX;
-    int y = ty0 + hy - 1, x = tx0 + hx - 1;
-    const bool ok = y >= 0 && y < p.IH && x >= 0 && x < p.IW;
-    y = min(max(y, 0), p.IH - 1);
-    x = min(max(x, 0), p.IW - 1);
-    if (p.ups) {
-      y >>= 1;
-      x >>= 1;
-    }
-    s_hcol[i * 256 + tid] = y * SW + x;
-    cvalid |= (ok ? 1u : 0u) << i;
-  }
-  int hcoef_c = 0;
-  bool h_is_skip = false;
-  bool h_cvalid = false;
-  auto halo_issue = [&](int cc) {
-    h_is_skip = SKIP && cc >= ncc;
-    int c = (h_is_skip ? cc - ncc : cc) * BK + q * 4;
-    hcoef_c = c;
-    h_cvalid = c < (h_is_skip ? SCin : Cin);
-    if (!h_cvalid) c = 0;  // clamped, masked below
-    const float* src = h_is_skip ? p.skip_src0 : p.src0;
-    const int C0s = h_is_skip ? p.skip_C0 : p.C0;
-    int Cs = C0s, cs = c;
-    if (c >= C0s) {
-      src = h_is_skip ? p.skip_src1 : p.src1;
-      Cs = h_is_skip ? p.skip_C1 : p.C1;
-      cs = c - C0s;
-    }
-    // unconditional loads from clamped addresses, masked afterwards; uniform base + 32-bit byte offsets
-    const char* sbase = reinterpret_cast<const char*>(src + (int64_t)n * SD * SH * SW * Cs);
-    const unsigned cbytes = (unsigned)Cs * 4u, cofs = (unsigned)cs * 4u;
-    int tl = tid;
-    HOLO_LAUNDER(tl);
-#pragma unroll
-    for (int i = 0; i < COLS_IT; ++i) {
-      const unsigned yx = (unsigned)s_hcol[i * 256 + tl];
-#pragma unroll
-      for (int pl = 0; pl < 4; ++pl)
-        hreg[i][pl] = *reinterpret_cast<const float4*>(sbase + (((unsigned)zsrc[pl] + yx) * cbytes + cofs));
-    }
-  };
-  auto halo_commit = [&]() {
-    f32x2 a01 = f32x2{1.f, 1.f}, b01 = f32x2{0.f, 0.f}, a23 = a01, b23 = b01;
-    const bool xform = p.coef && !h_is_skip;  // the skip path reads the raw block input
-    if (xform) {
-      const int cc4 = hcoef_c < Cin ? hcoef_c : 0;
-      const float4* cf = reinterpret_cast<const float4*>(p.coef + ((int64_t)n * Cin + cc4) * 2);
-      const float4 c01 = cf[0], c23 = cf[1];  // (a,b) interleaved per channel
-      a01 = f32x2{c01.x, c01.z};
-      b01 = f32x2{c01.y, c01.w};
-      a23 = f32x2{c23.x, c23.z};
-      b23 = f32x2{c23.y, c23.w};
-    }
-#pragma unroll
-    for (int i = 0; i < COLS_IT; ++i) {
-      const int col = (tid >> 3) + 32 * i;
-      f32x2 v01[4], v23[4];
-#pragma unroll
-      for (int pl = 0; pl < 4; ++pl) {
-        v01[pl] = f32x2{hreg[i][pl].x, hreg[i][pl].y};
-        v23[pl] = f32x2{hreg[i][pl].z, hreg[i][pl].w};
-        if (xform) {
-          v01[pl] = pk_fma(v01[pl], a01, b01);
-          v23[pl] = pk_fma(v23[pl], a23, b23);
-          if (p.act) {
-            v01[pl] = f32x2{silu_f(v01[pl].x), silu_f(v01[pl].y)};
-            v23[pl] = f32x2{silu_f(v23[pl].x), silu_f(v23[pl].y)};
-          }
-        }
-        // zero padding is applied AFTER the activation
-        const float keep = (h_cvalid && ((cvalid >> i) & 1u) && ((zvalid >> pl) & 1u)) ? 1.f : 0.f;
-        const f32x2 k2 = f32x2{keep, keep};
-        v01[pl] = pk_mul(v01[pl], k2);
-        v23[pl] = pk_mul(v23[pl], k2);
-      }
-      if (col < PLANE) {
-        // B^T d: xi0 = d0 - d2, xi1 = d1 + d2, xi2 = d2 - d1, xi3 = d1 - d3
-        const f32x2 x0a = pk_sub(v01[0], v01[2]), x0b = pk_sub(v23[0], v23[2]);
-        const f32x2 x1a = pk_add(v01[1], v01[2]), x1b = pk_add(v23[1], v23[2]);
-        const f32x2 x2a = pk_sub(v01[2], v01[1]), x2b = pk_sub(v23[2], v23[1]);
-        const f32x2 x3a = pk_sub(v01[1], v01[3]), x3b = pk_sub(v23[1], v23[3]);
-        float* dst = s_halo + col * RS + q * 4;
-        *reinterpret_cast<float4*>(dst + 0 * PLANE * RS) = make_float4(x0a.x, x0a.y, x0b.x, x0b.y);
-        *reinterpret_cast<float4*>(dst + 1 * PLANE * RS) = make_float4(x1a.x, x1a.y, x1b.x, x1b.y);
-        *reinterpret_cast<float4*>(dst + 2 * PLANE * RS) = make_float4(x2a.x, x2a.y, x2b.x, x2b.y);
-        *reinterpret_cast<float4*>(dst + 3 * PLANE * RS) = make_float4(x3a.x, x3a.y, x3b.x, x3b.y);
-      }
-    }
-  };
-
-  f32x4 acc[4][MT];  // [xi][16-voxel tile of the plane]
-#pragma unroll
-  for (int xi = 0; xi < 4; ++xi)
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[xi][t][r] = 0.f;
-
-  // A addressing (as in the direct kernel): the 16 voxels of tile t are x = 0..7 of rows y = t and t + 4
-  int a_off[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) a_off[t] = ((t + 4 * (lj >> 3)) * HX + (lj & 7)) * RS + kq * 8;
-  const int wncc = p.CinP / BK, wnsl = p.CoutP >> 4;
-  constexpr int WBLK = 512;
-  const float* w_lane = p.w_wino + (int64_t)((n0 >> 4) + wn) * WBLK + lane * 4;
-
-  auto load_a = [&](float4 (&a)[MT], int pt, int half) {  // pseudo-tap pt = xi * 9 + ky * 3 + kx
-    const int xi = pt / 9, kh = (pt - xi * 9) / 3, kw = pt - xi * 9 - kh * 3;
-    const int toff = ((xi * HY + kh) * HX + kw) * RS + half * 4;
-#pragma unroll
-    for (int t = 0; t < MT; ++t) a[t] = *reinterpret_cast<const float4*>(s_halo + a_off[t] + toff);
-  };
-  auto load_b = [&](float4 (&b)[2], int cc, int pt) {
-    const float* wp = w_lane + (int64_t)(pt * wncc + cc) * wnsl * WBLK;
-    b[0] = *reinterpret_cast<const float4*>(wp);
-    b[1] = *reinterpret_cast<const float4*>(wp + 256);
-  };
-  auto mfma_half = [&](f32x4 (&ac)[MT], const float4 (&a)[MT], const float4& b) {
-#pragma unroll
-    for (int t = 0; t < MT; ++t) ac[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].x, b.x, ac[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < MT; ++t) ac[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].y, b.y, ac[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < MT; ++t) ac[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].z, b.z, ac[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < MT; ++t) ac[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].w, b.w, ac[t], 0, 0, 0);
-  };
-
-  float4 aA[MT] = {}, aB[MT] = {}, aC[MT] = {};  // first half of this pseudo-tap, second half, first half of the next
-  float4 b0[2] = {}, b1[2] = {};
-  auto tap_body = [&](f32x4 (&ac)[MT], float4 (&cur)[MT], float4 (&nxt)[MT], float4 (&bc)[2], float4 (&bn)[2], int cc,
-                      int pt, bool prefetch) {
-    load_a(aB, pt, 1);
-    if (prefetch) load_b(bn, cc, pt + 1);
-    __builtin_amdgcn_sched_barrier(0);  // keep the requests above AHEAD of the MFMAs that hide their latency
-    mfma_half(ac, cur, bc[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    if (prefetch) load_a(nxt, pt + 1, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_half(ac, aB, bc[1]);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  HOLO_PHASE_DELAY(p.stagger_ticks);
-  for (int cc = cc_begin; cc < cc_end; ++cc) {
-    halo_issue(cc);
-    halo_commit();
-    load_b(b0, cc, 0);
-    __syncthreads();  // transformed halo of chunk cc visible
-    load_a(aA, 0, 0);
-#pragma unroll
-    for (int pt = 0; pt < 36; pt += 2) {  // fully unrolled: the accumulator set acc[pt / 9] is a compile-time choice
-      tap_body(acc[pt / 9], aA, aC, b0, b1, cc, pt, true);
-      tap_body(acc[(pt + 1) / 9], aC, aA, b1, b0, cc, pt + 1, pt + 1 < 35);
-    }
-    __syncthreads();  // everyone done reading this halo before it is overwritten
-  }
-  if (SKIP) {
-    // fused 1x1x1 skip connection: centre (ky,kx) of the block-input halo, pseudo-taps xi = 1, 2 (weights +w/2, -w/2)
-    for (int cc = sk_begin; cc < sk_end; ++cc) {
-      halo_issue(cc);
-      halo_commit();
-      const float* wp = p.skip_w_wino + ((int64_t)(cc - ncc) * wnsl + (n0 >> 4) + wn) * WBLK + lane * 4;
-      const int64_t tap_stride = (int64_t)(p.skip_CinP / BK) * wnsl * WBLK;
-      b0[0] = *reinterpret_cast<const float4*>(wp);
-      b0[1] = *reinterpret_cast<const float4*>(wp + 256);
-      b1[0] = *reinterpret_cast<const float4*>(wp + tap_stride);
-      b1[1] = *reinterpret_cast<const float4*>(wp + tap_stride + 256);
-      __syncthreads();
-      load_a(aA, 1 * 9 + 4, 0);
-      load_a(aB, 1 * 9 + 4, 1);
-      mfma_half(acc[1], aA, b0[0]);
-      mfma_half(acc[1], aB, b0[1]);
-      load_a(aA, 2 * 9 + 4, 0);
-      load_a(aB, 2 * 9 + 4, 1);
-      mfma_half(acc[2], aA, b1[0]);
-      mfma_half(acc[2], aB, b1[1]);
-      __syncthreads();
-    }
-  }
-
-  // ---- output transform (lane-local) + epilogue.  16x16x4 D layout: col = lane&15 (Cout), row = 4*(lane>>4) + r
-  const int64_t M = (int64_t)p.N * p.OD * p.OH * p.OW;
-  const int co = n0 + wn * 16 + lj;
-  const int coc = co < p.Cout ? co : p.Cout - 1;
-  float bv = (p.nsplit == 1 && p.bias) ? p.bias[coc] : 0.f;
-  if (p.nsplit == 1 && p.skip_bias) bv += p.skip_bias[coc];
-  float ssum = 0.f, ssq = 0.f;
-  const int64_t tbase = ((((int64_t)n * p.OD + tz0) * p.OH + ty0) * p.OW + tx0) * p.Cout;
-  const int zstride = p.OH * p.OW * p.Cout;
-  int off[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) off[t] = ((t + 4 * (kq >> 1)) * p.OW + 4 * (kq & 1)) * p.Cout;
-  // out(z0) = M0 + M1 + M2, out(z1) = M1 - M2 - M3, written over acc[0] / acc[3]
-#pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float m0 = acc[0][t][r], m1 = acc[1][t][r], m2 = acc[2][t][r], m3 = acc[3][t][r];
-      acc[0][t][r] = (m0 + m1) + m2;
-      acc[3][t][r] = (m1 - m2) - m3;
-    }
-  if (p.nsplit == 1) {
-#pragma unroll
-    for (int z = 0; z < 2; ++z) {
-      f32x4 (&o)[MT] = z ? acc[3] : acc[0];
-      if (p.residual) {
-        const float* rp = p.residual + tbase + z * (int64_t)zstride + coc;
-        float res[MT][4];
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) res[t][r] = rp[off[t] + r * p.Cout];
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[t][r] += res[t][r];
-      }
-      float* op = p.out + tbase + z * (int64_t)zstride + coc;
-#pragma unroll
-      for (int t = 0; t < MT; ++t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = o[t][r] + bv;
-          if (co < p.Cout) op[off[t] + r * p.Cout] = v;
-          ssum += v;
-          ssq += v * v;
-        }
-      }
-    }
-  } else if (co < p.Cout) {
-    float* pp = p.partial + (int64_t)blockIdx.z * M * p.Cout + tbase + co;
-#pragma unroll
-    for (int z = 0; z < 2; ++z) {
-      f32x4 (&o)[MT] = z ? acc[3] : acc[0];
-#pragma unroll
-      for (int t = 0; t < MT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pp[z * (int64_t)zstride + off[t] + r * p.Cout] = o[t][r];
-    }
-  }
-  // GroupNorm statistics of the tensor just produced: one slab per workgroup, as the direct 128-voxel kernel
-  if (p.stats && p.nsplit == 1) {
-    ssum += __shfl_xor(ssum, 16);
-    ssq += __shfl_xor(ssq, 16);
-    ssum += __shfl_xor(ssum, 32);
-    ssq += __shfl_xor(ssq, 32);
-    if (kq == 0 && co < p.Cout) {
-      const int tiles_per_sample = ntx * nty * ntz;
-      const int slab = (int)blockIdx.x % tiles_per_sample;
-      double* d = p.stats + (((int64_t)n * tiles_per_sample + slab) * p.Cout + co) * 2;
-      d[0] = (double)ssum;
-      d[1] = (double)ssq;
-    }
-  }
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Winograd F(2x2, 3x3) over (z, y): the same kernel with the second transform applied to the A operand at load time
-// (see "second Winograd dimension" below).  The LDS halo is the z-transformed one of conv_wino_kernel, unchanged.
+// planes, and the tap loop reads "plane" as "xi".  The output transform is lane-local (a lane's accumulators of the four
+// xi belong to the same voxels).  Arithmetic: fp32 throughout; F(2,3) adds one rounding of an add before and after the
+// products (measured against float64: same error as the direct form).
+//
+// In height: this kernel applies the second transform to the A operand at load time (see "second Winograd dimension"
+// below), 48 pseudo-taps per 2 x 2 outputs.  The fused 1x1x1 skip connection (centre tap) becomes the 4 pseudo-taps
+// xi_z, xi_y in {1, 2} with weights +-w/4.
 // ---------------------------------------------------------------------------------------------
 // NWN: waves along Cout.  4: the workgroup covers 64 output channels, every wave both MFMA tiles of the plane pair;
 // 2 (32-channel convolutions, e.g. the output conv): waves 0,1 take tile 0 and waves 2,3 tile 1 of the same 32 channels.
@@ -2750,259 +2433,241 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
+const char* conv_kernel_name(ConvKernel k) {
+  switch (k) {
+    case ConvKernel::Gather: return "conv_igemm_kernel";
+    case ConvKernel::Halo: return "conv_halo_kernel";
+    case ConvKernel::RowTile: return "conv_small_kernel";
+    case ConvKernel::Wino2: return "conv_wino2_kernel";
+    case ConvKernel::Bf16Wide: return "conv_bf16t_kernel";
+    case ConvKernel::Wino3: return "conv_wino3_kernel";
+    case ConvKernel::Stream1x1: return "conv1x1_stream_kernel";
+    case ConvKernel::Bf16Persistent: return "conv_bf16p_kernel";
+    case ConvKernel::S2Bf16: return "conv_s2_bf16_kernel";
+    case ConvKernel::Qkv: return "conv1x1_qkv_bf16_kernel";
+    case ConvKernel::Bf16Stream1x1: return "conv1x1_bf16_stream_kernel";
+  }
+  return "?";
+}
+
+// workgroups per CU the row-tile kernel's split-K aims at
+constexpr int SM_SPLIT_WGS_PER_CU = 2;
+// the bf16 wide-tile kernel also runs on under-filled levels (split over 16-channel chunks) once the K extent is long
+// enough to pay for the partials - measured at 128^3: from 192 input channels (main + fused skip) it beats the 64/128-voxel
+// halo kernel (32^3 .. 8^3 levels together 1.96 -> 1.7 ms), below that it loses
+constexpr int BF16T_LONG_K = 192;
+// workgroups per CU its split-K aims at: two on the 32^3 level and above, ONE below it and for raw-input launches
+// (measured at 128^3, profiles/r06_bf16t_split_target.txt: the 16^3 / 8^3 launches 43.6 -> 39.0, 41.5 -> 36.4,
+// 41.2 -> 35.9 us with half the partial sums to write and reduce; the 32^3 launches the other way round, 59.8 vs 66.4;
+// the raw-input Upsample convolution at 32^3 un-split lands on the persistent form: 126.7 -> 91.5 us)
+constexpr int BF16T_SPLIT_WGS_PER_CU_TOP = 2;
+constexpr int BF16T_SPLIT_WGS_PER_CU = 1;
+
+struct KSplit {
+  int n, cps;  // splits, chunks per split
+};
+// split-K over `chunks` chunks: `want` splits, at most `max_split` (<= chunks), the chunks dealt evenly (the last split
+// may get fewer)
+KSplit ksplit(int64_t want, int max_split, int chunks) {
+  const int cps = (int)cdiv(chunks, want < max_split ? want : max_split);
+  return {(int)cdiv(chunks, cps), cps};
+}
+
+KSplit bf16t_split(const ConvParams& p, int64_t t8, int ncc16, int num_cus) {
+  const int64_t tgt = (int64_t)num_cus * (p.OD >= 32 && p.coef ? BF16T_SPLIT_WGS_PER_CU_TOP : BF16T_SPLIT_WGS_PER_CU);
+  return ksplit(t8 < tgt ? cdiv(tgt, t8) : 1, ncc16, ncc16);
+}
+
+// F(2x2x2, 3x3x3) form: ONE persistent 4-wave workgroup per CU walks (tile, 64-Cout block, split) items, so the chip is
+// full from num_cus items on; split-K only up to that
+KSplit wino3_split(int64_t t3, int ncc, int num_cus) { return ksplit(t3 < num_cus ? cdiv(num_cus, t3) : 1, ncc, ncc); }
+
 }  // namespace
 
 size_t conv_plan(ConvParams& p, int num_cus) {
   const int Cin = p.C0 + p.C1;
   const int ncc = (Cin + BK - 1) / BK;
   const int nchunks = p.ksz * p.ksz * p.ksz * ncc;
+  const int nsk = p.skip_w ? (int)cdiv(p.skip_C0 + p.skip_C1, BK) : 0;  // fused skip chunks (one tap each)
+  const int ncc16 = (Cin + 15) / 16;                                    // the wide-tile kernels' 16-channel chunks
+  const int nsk16 = p.skip_w ? (p.skip_C0 + p.skip_C1 + 15) / 16 : 0;
   const int64_t M = (int64_t)p.N * p.OD * p.OH * p.OW;
   const int bn = p.Cout >= 64 ? 64 : 32;
   const int64_t tiles = cdiv(M, BM) * cdiv(p.Cout, bn);
-  int nsplit = 1;
+  const int64_t t8 = (M / 512) * cdiv(p.Cout, bn);  // wide-tile kernels: 8^3 tiles x Cout slices
+  const int64_t t3 = (M / 128) * (p.Cout / 64);     // F(2x2x2) form: 2 x 8 x 8 tiles x 64-Cout blocks
   const int64_t target = 2 * (int64_t)num_cus;
   const int64_t src_vox = (int64_t)p.ID * p.IH * p.IW;  // the halo kernel addresses a source sample with 32-bit byte offsets
   const int cmax = p.C0 > p.C1 ? p.C0 : p.C1;
   const int skmax = p.skip_C0 > p.skip_C1 ? p.skip_C0 : p.skip_C1;
   const bool fits32 = src_vox * (cmax > skmax ? cmax : skmax) * 4 < ((int64_t)1 << 32) &&
                       (int64_t)p.OD * p.OH * p.OW * p.Cout * 4 < ((int64_t)1 << 32);  // (the wide-tile epilogue: output sample too)
-  p.mode = (p.ksz == 3 && p.stride == 1 && p.pad == 1 && (p.OD % 2) == 0 && (p.OH % 8) == 0 && (p.OW % 8) == 0 &&  // (TZ=1 tiles need no z divisibility)
-            p.ID == p.OD && p.IH == p.OH && p.IW == p.OW && ((p.C0 + p.C1) % 16) == 0 && fits32)
-               ? 1
-               : 0;
-  // the qkv convolution of an AttentionBlock, fused with the operand packing of the bf16 attention (the planner offers it by
-  // setting qkv_q; HOLO_CONV_QKV_FUSED=0 keeps the row-tile kernel + attn_pack_kernel)
-  if (p.qkv_q) {
-    const char* eq = getenv("HOLO_CONV_QKV_FUSED");
-    if (!(eq && eq[0] == '0') && conv1x1_qkv_bf16_supported(p)) {
-      p.mode = 5;
-      p.nsplit = 1;
-      p.chunks_per_split = ncc;
-      conv1x1_qkv_bf16_plan(p, num_cus);
-      if (getenv("HOLO_DEBUG_PLAN"))
-        fprintf(stderr, "[plan] qkv conv %d->%d, T %d: fused with the attention's operand packing, %d rows x %d slices per workgroup\n", Cin,
-                p.Cout, p.qkv_T, p.qkv_rows, p.qkv_sb);
-      return 0;
+  const bool halo = p.ksz == 3 && p.stride == 1 && p.pad == 1 && (p.OD % 2) == 0 && (p.OH % 8) == 0 && (p.OW % 8) == 0 &&  // (TZ=1 tiles need no z divisibility)
+                    p.ID == p.OD && p.IH == p.OH && p.IW == p.OW && (Cin % 16) == 0 && fits32;
+  // the (z,y) Winograd form of 64-channel output blocks, where its weights were prepared
+  const bool wino2_wide = p.w_wino2 && p.bf16 == 0 && p.Cout >= 64 && (p.Cout % 64) == 0 && (!p.skip_w || p.skip_w_wino2);
+  // the halo forms' tile depth: 128-voxel tiles, or on an under-filled chip 64-voxel tiles that double the workgroups before
+  // resorting to split-K.  Exact-fp32 launches whose Winograd weights exist keep the 128-voxel tile on under-filled levels
+  // too: the Winograd kernels do 4/9 (8/27) of the MFMAs per voxel, which buys more than the doubled workgroup count of
+  // 64-voxel tiles; the chip is filled by split-K over the channel chunks instead.  HOLO_CONV_WINO_SMALL=0 turns that off,
+  // HOLO_CONV_FORCE_TZ2=1 (tests) takes 128-voxel tiles (hence the Winograd kernels) on small grids
+  const bool wino_small = env_int("HOLO_CONV_WINO_SMALL", 1) != 0 && wino2_wide && ncc >= 2;
+  const int tz = tiles < target && env_int("HOLO_CONV_FORCE_TZ2", 0) != 1 && !wino_small ? 1 : 2;
+
+  // ---- the kernel: the first of these whose conditions hold
+  const ConvKernel kernel = [&] {
+    // the qkv convolution of an AttentionBlock, fused with the operand packing of the bf16 attention (the planner offers it by
+    // setting qkv_q; HOLO_CONV_QKV_FUSED=0 keeps the row-tile kernel + attn_pack_kernel)
+    if (p.qkv_q) {
+      if (env_int("HOLO_CONV_QKV_FUSED", 1) != 0 && conv1x1_qkv_bf16_supported(p)) return ConvKernel::Qkv;
+      p.qkv_q = nullptr;  // (not this launch: the caller packs)
     }
-    p.qkv_q = nullptr;  // (not this launch: the caller packs)
-  }
-  // any other 1x1x1 convolution of a large grid on bf16 storage (the attention's proj_out): the same streaming GEMM with a plain
-  // output (HOLO_CONV1X1_BF16_STREAM=0 keeps the row-tile kernel)
-  {
-    const char* e5 = getenv("HOLO_CONV1X1_BF16_STREAM");
-    if (!(e5 && e5[0] == '0') && conv1x1_bf16_stream_supported(p)) {
-      p.mode = 6;
-      p.nsplit = 1;
-      p.chunks_per_split = ncc;
-      conv1x1_bf16_stream_plan(p, num_cus);
-      if (getenv("HOLO_DEBUG_PLAN"))
-        fprintf(stderr, "[plan] conv1 %d->%d @%d^3: bf16 streaming GEMM, %d rows x %d slices per workgroup\n", Cin, p.Cout, p.OD, p.qkv_rows,
-                p.qkv_sb);
-      return 0;
+    // any other 1x1x1 convolution of a large grid on bf16 storage (the attention's proj_out): the same streaming GEMM with a
+    // plain output (HOLO_CONV1X1_BF16_STREAM=0 keeps the row-tile kernel)
+    if (env_int("HOLO_CONV1X1_BF16_STREAM", 1) != 0 && conv1x1_bf16_stream_supported(p)) return ConvKernel::Bf16Stream1x1;
+    if (!halo) {
+      // a 1x1x1 convolution of raw input over a LARGE grid (a ResBlock's skip_connection on the 64^3 level): the streaming
+      // GEMM (HOLO_CONV1X1_STREAM_MIN_M=<rows>: development knob, default 131 072 rows; 0 = off)
+      const int64_t min_m = env_int("HOLO_CONV1X1_STREAM_MIN_M", 131072);
+      if (min_m > 0 && M >= min_m && p.ksz == 1 && p.stride == 1 && !p.ups && !p.coef && !p.residual && !p.skip_w && p.bf16 == 0 &&
+          !p.in_bf16 && !p.out_bf16 && (p.Cout % 64) == 0 && (Cin % 32) == 0 && Cin >= 32 && Cin <= 256 &&
+          (!p.src1 || (p.C0 % 32) == 0) && (M % 16) == 0 && p.ID == p.OD && p.IH == p.OH && p.IW == p.OW)
+        return ConvKernel::Stream1x1;
+      // the stride-2 convolution of a Downsample block in the bf16 storage mode, where its 128-voxel tiles give the chip at
+      // least a workgroup per four CUs (128^3 net: 128^3 -> 64^3 540 -> ~100 us, and the two levels below; deeper the row-tile
+      // kernel's split-K fills the chip better).  HOLO_CONV_S2T=0 keeps the row-tile kernel, =1 takes this one wherever it is
+      // defined (tests)
+      const int64_t s2t = env_int("HOLO_CONV_S2T", -1);
+      if (s2t != 0 && conv_s2_bf16_supported(p) && ((M / 128) * (p.Cout / 64) >= num_cus / 4 || s2t == 1))
+        return ConvKernel::S2Bf16;
+      // 1x1x1, strided and deepest-level convs: row-tile kernel (also for the 32^3 stride-2 convolution with its 32 768 rows:
+      // the per-tap gather kernel takes 118 us there, this one 95)
+      return p.Cout >= 64 ? ConvKernel::RowTile : ConvKernel::Gather;
     }
-  }
-  // a 1x1x1 convolution of raw input over a LARGE grid (a ResBlock's skip_connection on the 64^3 level): the streaming GEMM
-  // (HOLO_CONV1X1_STREAM_MIN_M=<rows>: development knob, default 131 072 rows; 0 = off)
-  {
-    const char* e1 = getenv("HOLO_CONV1X1_STREAM_MIN_M");
-    const int64_t min_m = e1 ? atoll(e1) : 131072;
-    if (p.mode == 0 && min_m > 0 && M >= min_m && p.ksz == 1 && p.stride == 1 && !p.ups && !p.coef && !p.residual && !p.skip_w &&
-        p.bf16 == 0 && !p.in_bf16 && !p.out_bf16 && (p.Cout % 64) == 0 && (Cin % 32) == 0 && Cin >= 32 && Cin <= 256 &&
-        (!p.src1 || (p.C0 % 32) == 0) && (M % 16) == 0 && p.ID == p.OD && p.IH == p.OH && p.IW == p.OW) {
-      p.mode = 3;
-      p.nsplit = 1;
-      p.chunks_per_split = ncc;
-      return 0;
-    }
-  }
-  // the stride-2 convolution of a Downsample block in the bf16 storage mode, where its 128-voxel tiles give the chip at least
-  // a workgroup per four CUs (128^3 net: 128^3 -> 64^3 540 -> ~100 us, and the two levels below; deeper the row-tile kernel's
-  // split-K fills the chip better).  HOLO_CONV_S2T=0 keeps the row-tile kernel, =1 takes this one wherever it is defined (tests)
-  {
-    const char* es = getenv("HOLO_CONV_S2T");
-    const int64_t wgs = (M / 128) * (p.Cout / 64);
-    if (p.mode == 0 && !(es && es[0] == '0') && conv_s2_bf16_supported(p) && (wgs >= num_cus / 4 || (es && es[0] == '1'))) {
-      p.mode = 4;
-      p.nsplit = 1;
-      p.chunks_per_split = Cin / 16;
-      if (getenv("HOLO_DEBUG_PLAN"))
-        fprintf(stderr, "[plan] conv %d->%d @%d^3 stride 2: bf16 halo kernel, %lld workgroups\n", Cin, p.Cout, p.OD, (long long)wgs);
-      return 0;
-    }
-  }
-  // 1x1x1, strided and deepest-level convs: row-tile kernel (also for the 32^3 stride-2 convolution with its 32 768 rows: the
-  // per-tap gather kernel takes 118 us there, this one 95)
-  if (p.mode == 0 && p.Cout >= 64) {
-    p.mode = 2;
-    const int64_t t2 = cdiv(M, SM_ROWS) * cdiv(p.Cout, 64);
-    const char* st = getenv("HOLO_SMALL_SPLIT_TARGET");  // development knob: workgroups per CU the split-K aims at (default 2)
-    const int64_t tgt = (st && atoi(st) > 0 ? atoi(st) : 2) * (int64_t)num_cus;
-    nsplit = t2 < tgt ? (int)cdiv(tgt, t2) : 1;
-    // (a fused 1x1x1 skip: its chunks follow the (tap, chunk) list; stride 1 and no upsampling there: conv_launch)
-    const int nall = nchunks + (p.skip_w ? (int)cdiv(p.skip_C0 + p.skip_C1, BK) : 0);
-    int max_split = nall / SG;  // a split below one full staging group only adds a reduce launch
-    if (max_split < 1) max_split = 1;
-    if (nsplit > max_split) nsplit = max_split;
-    int cps = (int)cdiv(nall, nsplit);
-    nsplit = (int)cdiv(nall, cps);
-    p.nsplit = nsplit;
-    p.chunks_per_split = cps;
-    return nsplit > 1 ? (size_t)nsplit * M * p.Cout * sizeof(float) : 0;
-  }
-  p.bf16t = 0;
-  p.bf16p = 0;
-  if (p.mode == 1 && p.bf16 == 1 && p.in_bf16 && p.w_bft && (!p.skip_w || p.skip_w_bft) && (p.OD % 8) == 0 && (p.OH % 8) == 0 && (p.OW % 8) == 0 && (p.Cout % 32) == 0 &&
-      (p.C0 % 8) == 0 && (p.skip_C0 % 8) == 0 && ((p.skip_C0 + p.skip_C1) % 8) == 0 && (p.Cout >= 64 || !p.skip_w)) {
-    // bf16 wide-tile kernel (8^3 voxels x 64 | 32 output channels per workgroup): where it fills the chip without
-    // split-K, and on the under-filled levels (split over 16-channel chunks) once the K extent is long enough to pay for
-    // the partials - measured at 128^3: from 192 input channels (main + fused skip) it beats the 64/128-voxel halo
-    // kernel (32^3 .. 8^3 levels together 1.96 -> 1.7 ms), below that it loses.  HOLO_CONV_BF16T=0 disables it, =1
-    // forces it everywhere (tests)
-    const char* e = getenv("HOLO_CONV_BF16T");
-    const int64_t t8 = (M / 512) * cdiv(p.Cout, bn);
-    const char* lk = getenv("HOLO_CONV_BF16T_LONGK");  // development knob: channel threshold of the rule below (0 = off)
-    const int lk_min = lk ? atoi(lk) : 192;
-    const bool long_k = lk_min > 0 && Cin + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0) >= lk_min;
-    if (!(e && e[0] == '0') && (t8 >= target || long_k || (e && e[0] == '1'))) {
-      const int ncc16 = (Cin + 15) / 16;
-      const int nsk16 = p.skip_w ? (p.skip_C0 + p.skip_C1 + 15) / 16 : 0;
-      {
-        // workgroups per CU the split-K aims at: two on the 32^3 level and above, ONE below it and for raw-input launches
-        // (measured at 128^3, profiles/r06_bf16t_split_target.txt: the 16^3 / 8^3 launches 43.6 -> 39.0, 41.5 -> 36.4,
-        // 41.2 -> 35.9 us with half the partial sums to write and reduce; the 32^3 launches the other way round, 59.8 vs 66.4;
-        // the raw-input Upsample convolution at 32^3 un-split lands on the persistent form: 126.7 -> 91.5 us).
-        // HOLO_BF16T_SPLIT_TARGET=<n>: development knob
-        const char* st = getenv("HOLO_BF16T_SPLIT_TARGET");
-        const int64_t tgt = st && atoi(st) > 0 ? atoi(st) * (int64_t)num_cus : ((p.OD >= 32 && p.coef) ? target : (int64_t)num_cus);
-        if (t8 < tgt) {
-          nsplit = (int)cdiv(tgt, t8);
-          if (nsplit > ncc16) nsplit = ncc16;
-        }
-      }
-      const int cps = (int)cdiv(ncc16, nsplit);
-      nsplit = (int)cdiv(ncc16, cps);
-      p.bf16t = 1;
-      p.tz = 8;
-      p.wino = 0;
-      p.nsplit = nsplit;
-      p.chunks_per_split = cps;
-      p.skip_chunks_per_split = (int)cdiv(nsk16, nsplit);
-      p.grid_x = (int)(M / 512);
+    // bf16 wide-tile kernel (8^3 voxels x 64 | 32 output channels per workgroup): where it fills the chip without split-K,
+    // and on the under-filled levels once the K extent is long (BF16T_LONG_K).  HOLO_CONV_BF16T=0 disables it, =1 forces it
+    // everywhere (tests)
+    const int64_t bt = env_int("HOLO_CONV_BF16T", -1);
+    if (p.bf16 == 1 && p.in_bf16 && p.w_bft && (!p.skip_w || p.skip_w_bft) && (p.OD % 8) == 0 && (p.OH % 8) == 0 &&
+        (p.OW % 8) == 0 && (p.Cout % 32) == 0 && (p.C0 % 8) == 0 && (p.skip_C0 % 8) == 0 && ((p.skip_C0 + p.skip_C1) % 8) == 0 &&
+        (p.Cout >= 64 || !p.skip_w) && bt != 0 &&
+        (t8 >= target || Cin + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0) >= BF16T_LONG_K || bt == 1)) {
       // the filled levels (every CU gets whole tiles without split-K): the persistent wave-specialised form
       // (kernels_conv_bf16p.hip) - by default only for launches that stage their input RAW (no GroupNorm / SiLU on load: the
       // input convolution, the Upsample convolutions): there its producer waves keep up with the consumers (tools/bf16p_probe:
       // 128^3 32 -> 64 282 vs 293 us); with the activation arithmetic they do not yet (540 vs 479 us) and conv_bf16t_kernel
       // stays.  HOLO_CONV_BF16P=0 keeps conv_bf16t_kernel everywhere, =2 takes the persistent form for activated input too,
       // =1 forces it onto every wide-tile launch, without split-K (tests: small grids)
-      {
-        const char* ep = getenv("HOLO_CONV_BF16P");
-        const bool force = ep && ep[0] == '1';
-        const bool any_input = force || (ep && ep[0] == '2');
-        const int wgs = num_cus & ~7;
-        if (!(ep && ep[0] == '0') && (any_input || !p.coef) && ((nsplit == 1 && wgs >= 8 && t8 >= wgs) || force) &&
-            (p.C1 == 0 || (p.C0 % 16) == 0) &&  // (a 16-channel chunk / a 32-channel skip step lies in ONE source)
-            (!p.skip_w || (((p.skip_C0 + p.skip_C1) % 32) == 0 && (p.skip_C1 == 0 || (p.skip_C0 % 32) == 0))) &&
-            (int64_t)p.ID * p.IH * p.IW < ((int64_t)1 << 24)) {  // (24-bit voxel indices in the producers' address arithmetic)
-          p.bf16p = 1;
-          p.nsplit = nsplit = 1;
-          p.chunks_per_split = ncc16;
-          p.skip_chunks_per_split = nsk16;
-          const int64_t wcap = wgs >= 8 ? wgs : 8;
-          int64_t g = t8 < wcap ? ((t8 + 7) & ~(int64_t)7) : wcap;
-          const char* eg = getenv("HOLO_CONV_BF16P_WGS");  // test knob: at most this many persistent workgroups
-          if (eg && atoi(eg) > 0 && atoi(eg) < g) g = atoi(eg);
-          p.grid_x = (int)(g < 8 && !eg ? 8 : g);
-        }
-      }
-      if (getenv("HOLO_DEBUG_PLAN"))
-        fprintf(stderr, "[plan] conv %d->%d @%d^3: bf16 wide-tile kernel%s, %d tiles x %d slices, split-K %d%s\n", Cin, p.Cout,
-                p.OD, p.bf16p ? " (persistent, wave-specialised)" : "", (int)(M / 512), (int)cdiv(p.Cout, bn), nsplit,
-                p.skip_w ? ", fused skip" : "");
-      return nsplit > 1 ? (size_t)nsplit * M * p.Cout * sizeof(float) : 0;
+      const int64_t bp = env_int("HOLO_CONV_BF16P", -1);
+      const int wgs = num_cus & ~7;
+      if (bp != 0 && (bp == 1 || bp == 2 || !p.coef) &&
+          ((bf16t_split(p, t8, ncc16, num_cus).n == 1 && wgs >= 8 && t8 >= wgs) || bp == 1) &&
+          (p.C1 == 0 || (p.C0 % 16) == 0) &&  // (a 16-channel chunk / a 32-channel skip step lies in ONE source)
+          (!p.skip_w || (((p.skip_C0 + p.skip_C1) % 32) == 0 && (p.skip_C1 == 0 || (p.skip_C0 % 32) == 0))) &&
+          src_vox < ((int64_t)1 << 24))  // (24-bit voxel indices in the producers' address arithmetic)
+        return ConvKernel::Bf16Persistent;
+      return ConvKernel::Bf16Wide;
+    }
+    // F(2x2x2, 3x3x3) form (kernels_conv3.hip) from HOLO_CONV_WINO3_MIN_ITEMS work items on (default num_cus / 2: the (z,y)
+    // form needs 2 workgroups per CU).  HOLO_CONV_WINO3=0 disables it
+    if (tz == 2 && env_int("HOLO_CONV_WINO3", 1) != 0 && p.w_wino3 && p.bf16 == 0 && !p.in_bf16 && !p.out_bf16 && p.Cout >= 64 &&
+        (p.Cout % 64) == 0 && (!p.skip_w || p.skip_w_wino3) && (p.OH % 8) == 0 && (p.OW % 8) == 0 && (p.OD % 2) == 0 &&
+        (!p.coef || p.act) &&  // (its staging applies the affine and SiLU together)
+        (int64_t)p.N * src_vox * (cmax > skmax ? cmax : skmax) * 4 < ((int64_t)1 << 32) &&  // (buffer addressing of whole tensors)
+        (!p.skip_w || ((p.skip_C0 % 16) == 0 && (p.skip_C1 % 4) == 0)) &&
+        t3 * wino3_split(t3, ncc, num_cus).n >= env_int("HOLO_CONV_WINO3_MIN_ITEMS", num_cus / 2))
+      return ConvKernel::Wino3;
+    // exact-fp32 128-voxel tiles: the (z,y) Winograd form when its weights were prepared (32-channel convolutions: two wave rows)
+    if (tz == 2 && (wino2_wide || (p.w_wino2 && p.bf16 == 0 && p.Cout == 32 && !p.skip_w))) return ConvKernel::Wino2;
+    return ConvKernel::Halo;
+  }();
+  p.kernel = kernel;
+
+  // ---- its geometry
+  switch (kernel) {
+    case ConvKernel::Qkv:
+    case ConvKernel::Bf16Stream1x1:
+    case ConvKernel::Stream1x1:
+      p.nsplit = 1;
+      p.chunks_per_split = ncc;
+      if (kernel == ConvKernel::Qkv) conv1x1_qkv_bf16_plan(p, num_cus);
+      if (kernel == ConvKernel::Bf16Stream1x1) conv1x1_bf16_stream_plan(p, num_cus);
+      break;
+    case ConvKernel::S2Bf16:
+      p.nsplit = 1;
+      p.chunks_per_split = Cin / 16;
+      break;
+    case ConvKernel::RowTile: {
+      // (a fused 1x1x1 skip: its chunks follow the (tap, chunk) list; stride 1 and no upsampling there: conv_launch)
+      const int64_t t2 = cdiv(M, SM_ROWS) * cdiv(p.Cout, 64);
+      const int64_t tgt = SM_SPLIT_WGS_PER_CU * (int64_t)num_cus;
+      const int nall = nchunks + nsk;
+      const int max_split = nall / SG > 1 ? nall / SG : 1;  // a split below one full staging group only adds a reduce launch
+      const KSplit s = ksplit(t2 < tgt ? cdiv(tgt, t2) : 1, max_split, nall);
+      p.nsplit = s.n;
+      p.chunks_per_split = s.cps;
+      break;
+    }
+    case ConvKernel::Gather: {
+      const int max_split = nchunks / 4 > 1 ? nchunks / 4 : 1;  // keep >= 4 chunks per block
+      const KSplit s = ksplit(tiles < target ? cdiv(target, tiles) : 1, max_split, nchunks);
+      p.nsplit = s.n;
+      p.chunks_per_split = s.cps;
+      break;
+    }
+    case ConvKernel::Bf16Wide: {
+      const KSplit s = bf16t_split(p, t8, ncc16, num_cus);
+      p.tz = 8;
+      p.nsplit = s.n;
+      p.chunks_per_split = s.cps;
+      p.skip_chunks_per_split = (int)cdiv(nsk16, s.n);
+      p.grid_x = (int)(M / 512);
+      break;
+    }
+    case ConvKernel::Bf16Persistent: {  // no split-K: grid_x persistent workgroups, a multiple of 8 up to the CUs' multiple of 8
+      const int64_t wcap = (num_cus & ~7) >= 8 ? (num_cus & ~7) : 8;
+      int64_t g = t8 < wcap ? ((t8 + 7) & ~(int64_t)7) : wcap;
+      const int64_t max_wgs = env_int("HOLO_CONV_BF16P_WGS", 0);  // test knob: at most this many persistent workgroups
+      if (max_wgs > 0 && max_wgs < g) g = max_wgs;
+      p.tz = 8;
+      p.nsplit = 1;
+      p.chunks_per_split = ncc16;
+      p.skip_chunks_per_split = nsk16;
+      p.grid_x = (int)g;
+      break;
+    }
+    case ConvKernel::Wino3: {
+      const KSplit s = wino3_split(t3, ncc, num_cus);
+      const int64_t items = t3 * s.n;
+      p.tz = 2;
+      p.nsplit = s.n;
+      p.chunks_per_split = s.cps;
+      p.skip_chunks_per_split = (int)cdiv(nsk, s.n);
+      // every workgroup gets the same number of items when the list allows it (the last round is then full)
+      p.grid_x = (int)cdiv(items, cdiv(items, num_cus));
+      break;
+    }
+    case ConvKernel::Halo:
+    case ConvKernel::Wino2: {  // split over 32-channel chunks (each split walks all 27 taps)
+      const int64_t htiles = tz == 2 ? tiles : (M / 64) * cdiv(p.Cout, bn);
+      const KSplit s = ksplit(htiles < target ? cdiv(target, htiles) : 1, ncc, ncc);
+      p.tz = tz;
+      p.nsplit = s.n;
+      p.chunks_per_split = s.cps;
+      p.skip_chunks_per_split = (int)cdiv(nsk, s.n);
+      // One workgroup per tile.  (The kernel can also walk several tiles per workgroup - grid_x < tiles - with the
+      // next tile's halo prefetched under the last tap; measured on MI355X that is no faster than letting the
+      // dispatcher refill the slots, which also balances the load dynamically: tools/conv_timeline.cpp.)
+      p.grid_x = (int)(M / (64 * tz));
+      break;
     }
   }
-  if (p.mode == 1) {  // halo kernel: split over 32-channel chunks (each split walks all 27 taps)
-    p.tz = 2;
-    int64_t htiles = tiles;
-    const char* f2 = getenv("HOLO_CONV_FORCE_TZ2");  // test knob: 128-voxel tiles (hence the Winograd-in-depth kernel) on small grids
-    const bool force_tz2 = f2 && f2[0] == '1';
-    // exact-fp32 launches whose Winograd weights exist keep the 128-voxel tile on under-filled levels too: the Winograd
-    // kernels do 4/9 (2/3) of the MFMAs per voxel, which buys more than the doubled workgroup count of 64-voxel tiles;
-    // the chip is filled by split-K over the channel chunks instead
-    const char* ws = getenv("HOLO_CONV_WINO_SMALL");
-    const bool wino_small = !(ws && ws[0] == '0') && p.w_wino && p.bf16 == 0 && p.Cout >= 64 && (p.Cout % 64) == 0 &&
-                            (!p.skip_w || p.skip_w_wino) && ncc >= 2;
-    if (tiles < target && !force_tz2 && !wino_small) {  // under-filled chip: 64-voxel tiles double the workgroups before resorting to split-K
-      p.tz = 1;
-      htiles = (M / 64) * cdiv(p.Cout, bn);
-    }
-    const int nsk = p.skip_w ? (p.skip_C0 + p.skip_C1 + BK - 1) / BK : 0;  // fused skip chunks (one tap each)
-    if (htiles < target) {
-      nsplit = (int)cdiv(target, htiles);
-      if (nsplit > ncc) nsplit = ncc;
-    }
-    int cps = (int)cdiv(ncc, nsplit);
-    nsplit = (int)cdiv(ncc, cps);
-    p.nsplit = nsplit;
-    p.chunks_per_split = cps;
-    p.skip_chunks_per_split = (int)cdiv(nsk, nsplit);
-    // One workgroup per tile.  (The kernel can also walk several tiles per workgroup - grid_x < tiles - with the
-    // next tile's halo prefetched under the last tap; measured on MI355X that is no faster than letting the
-    // dispatcher refill the slots, which also balances the load dynamically: tools/conv_timeline.cpp.)
-    p.grid_x = (int)(M / (64 * p.tz));
-    // exact-fp32 128-voxel tiles: the Winograd-in-depth form (2/3 of the MFMAs) when its weights were prepared
-    p.wino = (p.tz == 2 && p.w_wino && p.bf16 == 0 && p.Cout >= 64 && (p.Cout % 64) == 0 && (!p.skip_w || p.skip_w_wino)) ? 1 : 0;
-    if (p.wino && p.w_wino2 && (!p.skip_w || p.skip_w_wino2)) p.wino = 2;  // both depth and height in Winograd form
-    if (p.tz == 2 && p.w_wino2 && p.bf16 == 0 && p.Cout == 32 && !p.skip_w) p.wino = 2;  // 32-channel (z,y) form, two wave rows
-    // F(2x2x2, 3x3x3) form (kernels_conv3.hip): ONE persistent 4-wave workgroup per CU walks (tile, 64-Cout block, split)
-    // items, so the chip is full from num_cus items on (the (z,y) form needs 2 workgroups per CU); split-K only up to that.
-    // HOLO_CONV_WINO3=0 disables it, HOLO_CONV_WINO3_MIN_ITEMS=<n> moves the threshold (default num_cus / 2)
-    {
-      const char* e3 = getenv("HOLO_CONV_WINO3");
-      const char* m3 = getenv("HOLO_CONV_WINO3_MIN_ITEMS");
-      const int64_t t3 = (M / 128) * (p.Cout / 64);
-      const int64_t min_items = m3 ? atoi(m3) : num_cus / 2;
-      if (!(e3 && e3[0] == '0') && p.tz == 2 && p.w_wino3 && p.bf16 == 0 && !p.in_bf16 && !p.out_bf16 && p.Cout >= 64 &&
-          (p.Cout % 64) == 0 && (!p.skip_w || p.skip_w_wino3) && (p.OH % 8) == 0 && (p.OW % 8) == 0 && (p.OD % 2) == 0 &&
-          (!p.coef || p.act) &&  // (its staging applies the affine and SiLU together)
-          (int64_t)p.N * src_vox * (cmax > skmax ? cmax : skmax) * 4 < ((int64_t)1 << 32) &&  // (buffer addressing of whole tensors)
-          (!p.skip_w || ((p.skip_C0 % 16) == 0 && (p.skip_C1 % 4) == 0))) {
-        int ns3 = 1;
-        if (t3 < num_cus) {
-          ns3 = (int)cdiv(num_cus, t3);
-          if (ns3 > ncc) ns3 = ncc;
-        }
-        const int cps3 = (int)cdiv(ncc, ns3);
-        ns3 = (int)cdiv(ncc, cps3);
-        if (t3 * ns3 >= min_items) {
-          p.wino = 3;
-          p.nsplit = ns3;
-          p.chunks_per_split = cps3;
-          p.skip_chunks_per_split = (int)cdiv(nsk, ns3);
-          const int64_t items = t3 * ns3;
-          // every workgroup gets the same number of items when the list allows it (the last round is then full)
-          const int64_t rounds = cdiv(items, num_cus);
-          p.grid_x = (int)cdiv(items, rounds);
-          if (getenv("HOLO_DEBUG_PLAN"))
-            fprintf(stderr, "[plan] conv %d->%d @%d^3: F(2x2x2) Winograd kernel, %lld items on %d workgroups, split-K %d%s\n", Cin,
-                    p.Cout, p.OD, (long long)items, p.grid_x, ns3, p.skip_w ? ", fused skip" : "");
-          return ns3 > 1 ? (size_t)ns3 * M * p.Cout * sizeof(float) : 0;
-        }
-      }
-    }
-    return nsplit > 1 ? (size_t)nsplit * M * p.Cout * sizeof(float) : 0;
-  }
-  if (tiles < target) {
-    nsplit = (int)cdiv(target, tiles);
-    int max_split = nchunks / 4;  // keep >= 4 chunks per block
-    if (max_split < 1) max_split = 1;
-    if (nsplit > max_split) nsplit = max_split;
-  }
-  int cps = (int)cdiv(nchunks, nsplit);
-  nsplit = (int)cdiv(nchunks, cps);
-  p.nsplit = nsplit;
-  p.chunks_per_split = cps;
-  return nsplit > 1 ? (size_t)nsplit * M * p.Cout * sizeof(float) : 0;
+  const size_t scratch = p.nsplit > 1 ? (size_t)p.nsplit * M * p.Cout * sizeof(float) : 0;
+  if (getenv("HOLO_DEBUG_PLAN"))
+    fprintf(stderr, "[plan] conv %d->%d k%d s%d @%d^3 batch %d%s: %s, tz %d, split-K %d x %d chunks (skip %d), grid_x %d, qkv %d rows x %d slices, scratch %zu bytes\n",
+            Cin, p.Cout, p.ksz, p.stride, p.OD, p.N, p.skip_w ? " +skip" : "", conv_kernel_name(kernel), p.tz, p.nsplit,
+            p.chunks_per_split, p.skip_chunks_per_split, p.grid_x, p.qkv_rows, p.qkv_sb, scratch);
+  return scratch;
 }
 
 // Number of GroupNorm-statistics slabs per sample the launch of `p` writes into p.stats (0 = this launch cannot
@@ -3014,13 +2679,25 @@ int conv_stats_slabs(const ConvParams& p) {
     gn_stats_geometry(p.Cout < 1024 ? p.Cout : 1024, V, &B, &vpb);
     return B;
   }
-  if (p.mode == 1 && p.bf16t) return (int)(V / 512);  // wide-tile bf16 kernel: one slab per tile
-  if (p.mode == 1 && p.bf16 == 2 && p.w_bf && p.Cout >= 64 && !p.skip_w) return (int)(V / 32);  // bf16x3 kernel: per half 8x8 slab
-  if (p.mode == 1) return (int)(V / (64 * p.tz)) * (p.Cout >= 64 ? 1 : 2);
-  if (p.mode == 2 && V % SM_ROWS == 0) return (int)(V / SM_ROWS);
-  if (p.mode == 4) return (int)(V / 128);  // stride-2 bf16 halo kernel: one slab per 2 x 8 x 8 tile
-  if (p.mode == 6) return conv1x1_bf16_stream_slabs(p);  // bf16 streaming 1x1x1 kernel: one slab per workgroup row block
-  return 0;
+  switch (p.kernel) {
+    case ConvKernel::Bf16Wide:
+    case ConvKernel::Bf16Persistent:
+      return (int)(V / 512);  // one slab per tile
+    case ConvKernel::Halo:
+      if (p.bf16 == 2 && p.w_bf && p.Cout >= 64 && !p.skip_w) return (int)(V / 32);  // bf16x3 kernel: per half 8x8 slab
+      [[fallthrough]];
+    case ConvKernel::Wino2:
+    case ConvKernel::Wino3:
+      return (int)(V / (64 * p.tz)) * (p.Cout >= 64 ? 1 : 2);
+    case ConvKernel::RowTile:
+      return V % SM_ROWS == 0 ? (int)(V / SM_ROWS) : 0;
+    case ConvKernel::S2Bf16:
+      return (int)(V / 128);  // one slab per 2 x 8 x 8 tile
+    case ConvKernel::Bf16Stream1x1:
+      return conv1x1_bf16_stream_slabs(p);  // one slab per workgroup row block
+    default:
+      return 0;
+  }
 }
 
 double conv_flops(const ConvParams& p) {
@@ -3028,16 +2705,14 @@ double conv_flops(const ConvParams& p) {
   return 2.0 * M * p.Cout * ((double)(p.C0 + p.C1) * p.ksz * p.ksz * p.ksz + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0));
 }
 
-// multiply-adds actually issued to the matrix pipe (x2): the Winograd-in-depth kernel spends 36 pseudo-taps where the
-// direct form spends 54 (two output planes), and 2 instead of 2 x 1 for the fused skip
+// multiply-adds actually issued to the matrix pipe (x2): the Winograd kernels spend 64 pseudo-taps per 2 x 2 x 2 outputs
+// (F(2x2x2)) or 48 per 2 x 2 outputs ((z,y) form) where the direct form spends 27 per output; the fused skip costs the
+// same in all forms (F(2x2x2): accumulated directly; (z,y): 4 pseudo-taps per 4 outputs)
 double conv_exec_flops(const ConvParams& p) {
-  if (!p.wino) return conv_flops(p);
+  const double taps = p.kernel == ConvKernel::Wino3 ? 8.0 : p.kernel == ConvKernel::Wino2 ? 12.0 : 0.0;
+  if (taps == 0.0) return conv_flops(p);
   const double M = (double)p.N * p.OD * p.OH * p.OW;
-  if (p.wino == 3)  // 64 pseudo-taps per 2 x 2 x 2 outputs; the fused skip is accumulated directly (1 per output)
-    return 2.0 * M * p.Cout * ((double)(p.C0 + p.C1) * 8.0 + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0));
-  if (p.wino == 2)  // 48 pseudo-taps per 2 x 2 outputs, the fused skip 4 pseudo-taps per 4 outputs
-    return 2.0 * M * p.Cout * ((double)(p.C0 + p.C1) * 12.0 + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0));
-  return 2.0 * M * p.Cout * ((double)(p.C0 + p.C1) * 18.0 + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0));
+  return 2.0 * M * p.Cout * ((double)(p.C0 + p.C1) * taps + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0));
 }
 
 int conv_launch(const ConvParams& p, void* stream) {
@@ -3052,65 +2727,38 @@ int conv_launch(const ConvParams& p, void* stream) {
   }
   const int64_t M = (int64_t)p.N * p.OD * p.OH * p.OW;
   const bool wide = p.Cout >= 64;
+  const bool sk = p.skip_w != nullptr;
   const int bn = wide ? 64 : 32;
-  dim3 grid((unsigned)cdiv(M, BM), (unsigned)cdiv(p.Cout, bn), (unsigned)p.nsplit);
   dim3 block(256);
-  if (p.mode == 1) {
-    dim3 hgrid((unsigned)p.grid_x, (unsigned)cdiv(p.Cout, bn), (unsigned)p.nsplit);
-    const bool sk = p.skip_w != nullptr;
-    if (p.bf16t && p.bf16p) {
-      if (conv_bf16p_launch(p, stream)) return -1;
-    } else if (p.bf16t) {
-#define HOLO_BF16T(NT_, SK_) HOLO_LAUNCH((conv_bf16t_kernel<NT_, SK_, true>), hgrid, block, stream, p)
-      if (!p.in_bf16 || (p.residual && !p.res_bf16)) {
-        set_error("conv_launch: the wide-tile bf16 kernel runs on bf16 activation storage");
+  dim3 hgrid((unsigned)p.grid_x, (unsigned)cdiv(p.Cout, bn), (unsigned)p.nsplit);  // the halo forms
+  switch (p.kernel) {
+    case ConvKernel::Gather: {
+      dim3 grid((unsigned)cdiv(M, BM), (unsigned)cdiv(p.Cout, bn), (unsigned)p.nsplit);
+      if (wide) {
+        HOLO_LAUNCH(conv_igemm_kernel<2>, grid, block, stream, p);
+      } else {
+        HOLO_LAUNCH(conv_igemm_kernel<1>, grid, block, stream, p);
+      }
+      break;
+    }
+    case ConvKernel::Halo: {
+      if (p.bf16 == 2 && p.w_bf && wide && !sk) {  // the bf16x3 form
+        if (p.tz == 2) {
+          HOLO_LAUNCH(conv_halo_split_kernel<2>, hgrid, dim3(512), stream, p);
+        } else {
+          HOLO_LAUNCH(conv_halo_split_kernel<1>, hgrid, block, stream, p);
+        }
+        break;
+      }
+      const bool bf = p.bf16 == 1 && p.w_bf && (!sk || p.skip_w_bf);
+      if ((p.in_bf16 != 0) != bf || (p.residual && (p.res_bf16 != 0) != bf)) {
+        set_error("conv_launch: the bf16 halo kernel and bf16 activation storage go together");
         return -1;
       }
-      if (!wide) {
-        HOLO_BF16T(1, false);
-      } else if (sk) {
-        HOLO_BF16T(2, true);
-      } else {
-        const char* sv = getenv("HOLO_BF16T_SCHED");  // development knob: 0 = operand requests in a clump between the taps
-        if (sv && sv[0] == '0') {
-          HOLO_LAUNCH((conv_bf16t_kernel<2, false, true, 0>), hgrid, block, stream, p);
-        } else {
-          HOLO_BF16T(2, false);
-        }
+      if (!wide && sk) {
+        set_error("conv_launch: fused skip needs Cout >= 64");
+        return -1;
       }
-#undef HOLO_BF16T
-    } else if (p.wino == 3) {
-      if (conv_wino3_launch(p, stream)) return -1;
-    } else if (p.wino == 2) {
-      if (!wide) {
-        HOLO_LAUNCH((conv_wino2_kernel<false, 2>), hgrid, block, stream, p);
-      } else if (sk) {
-        HOLO_LAUNCH((conv_wino2_kernel<true, 4>), hgrid, block, stream, p);
-      } else {
-        HOLO_LAUNCH((conv_wino2_kernel<false, 4>), hgrid, block, stream, p);
-      }
-    } else if (p.wino) {
-      if (sk) {
-        HOLO_LAUNCH(conv_wino_kernel<true>, hgrid, block, stream, p);
-      } else {
-        HOLO_LAUNCH(conv_wino_kernel<false>, hgrid, block, stream, p);
-      }
-    } else if (p.bf16 == 2 && p.w_bf && wide && !sk) {
-      if (p.tz == 2) {
-        HOLO_LAUNCH(conv_halo_split_kernel<2>, hgrid, dim3(512), stream, p);
-      } else {
-        HOLO_LAUNCH(conv_halo_split_kernel<1>, hgrid, block, stream, p);
-      }
-    } else {
-    const bool bf = p.bf16 == 1 && p.w_bf && (!sk || p.skip_w_bf);
-    if ((p.in_bf16 != 0) != bf || (p.residual && (p.res_bf16 != 0) != bf)) {
-      set_error("conv_launch: the bf16 halo kernel and bf16 activation storage go together");
-      return -1;
-    }
-    if (!wide && sk) {
-      set_error("conv_launch: fused skip needs Cout >= 64");
-      return -1;
-    }
 #define HOLO_HALO(NWN_, TZ_, SK_)                                                                 \
   do {                                                                                            \
     if (bf) {                                                                                     \
@@ -3119,69 +2767,104 @@ int conv_launch(const ConvParams& p, void* stream) {
       HOLO_LAUNCH((conv_halo_kernel<NWN_, TZ_, SK_, false>), hgrid, block, stream, p);            \
     }                                                                                             \
   } while (0)
-    if (wide && p.tz == 2 && sk) {
-      HOLO_HALO(4, 2, true);
-    } else if (wide && p.tz == 2) {
-      HOLO_HALO(4, 2, false);
-    } else if (wide && sk) {
-      HOLO_HALO(4, 1, true);
-    } else if (wide) {
-      HOLO_HALO(4, 1, false);
-    } else if (p.tz == 2) {
-      HOLO_HALO(2, 2, false);
-    } else {
-      HOLO_HALO(2, 1, false);
-    }
+      if (wide && p.tz == 2 && sk) {
+        HOLO_HALO(4, 2, true);
+      } else if (wide && p.tz == 2) {
+        HOLO_HALO(4, 2, false);
+      } else if (wide && sk) {
+        HOLO_HALO(4, 1, true);
+      } else if (wide) {
+        HOLO_HALO(4, 1, false);
+      } else if (p.tz == 2) {
+        HOLO_HALO(2, 2, false);
+      } else {
+        HOLO_HALO(2, 1, false);
+      }
 #undef HOLO_HALO
+      break;
     }
-  } else if (p.mode == 4) {
-    if (conv_s2_bf16_launch(p, stream)) return -1;
-  } else if (p.mode == 5) {
-    if (conv1x1_qkv_bf16_launch(p, stream)) return -1;
-  } else if (p.mode == 6) {
-    if (conv1x1_bf16_stream_launch(p, stream)) return -1;
-  } else if (p.mode == 3) {
-    if (p.stats || p.residual || p.coef || p.nsplit != 1) {
-      set_error("conv_launch: the streaming 1x1x1 kernel takes raw input and produces no statistics");
-      return -1;
-    }
-    // two workgroups per CU, every wave walks 16-row tiles with a stride of the whole grid
-    int64_t wgs = cdiv(M >> 4, 4 * 4);  // >= 4 tiles per wave
-    if (wgs > 512) wgs = 512;
-    if (wgs < 1) wgs = 1;
-    dim3 g3((unsigned)wgs, (unsigned)(p.Cout / 64));
-    switch (Cin / 32) {
-      case 1: HOLO_LAUNCH(conv1x1_stream_kernel<1>, g3, block, stream, p); break;
-      case 2: HOLO_LAUNCH(conv1x1_stream_kernel<2>, g3, block, stream, p); break;
-      case 3: HOLO_LAUNCH(conv1x1_stream_kernel<3>, g3, block, stream, p); break;
-      case 4: HOLO_LAUNCH(conv1x1_stream_kernel<4>, g3, block, stream, p); break;
-      case 5: HOLO_LAUNCH(conv1x1_stream_kernel<5>, g3, block, stream, p); break;
-      case 6: HOLO_LAUNCH(conv1x1_stream_kernel<6>, g3, block, stream, p); break;
-      case 7: HOLO_LAUNCH(conv1x1_stream_kernel<7>, g3, block, stream, p); break;
-      case 8: HOLO_LAUNCH(conv1x1_stream_kernel<8>, g3, block, stream, p); break;
-      default:
-        set_error("conv_launch: streaming 1x1x1 kernel: %d input channels", Cin);
+    case ConvKernel::RowTile: {
+      if (M >= ((int64_t)1 << 31)) {
+        set_error("conv_launch: the row-tile kernel indexes output voxels in 32 bits (M = %lld)", (long long)M);
         return -1;
+      }
+      if (sk && (p.stride != 1 || p.ups || p.ID != p.OD || (p.bf16 == 1 && p.w_bf && !p.skip_w_bf))) {
+        set_error("conv_launch: the row-tile kernel fuses a skip connection at stride 1 without upsampling only");
+        return -1;
+      }
+      dim3 sgrid((unsigned)cdiv(M, SM_ROWS), (unsigned)cdiv(p.Cout, 64), (unsigned)p.nsplit);
+      if (p.bf16 == 1 && p.w_bf) {  // bf16 compute mode
+        HOLO_LAUNCH(conv_small_kernel<true>, sgrid, block, stream, p);
+      } else {
+        HOLO_LAUNCH(conv_small_kernel<false>, sgrid, block, stream, p);
+      }
+      break;
     }
-  } else if (p.mode == 2) {
-    if (M >= ((int64_t)1 << 31)) {
-      set_error("conv_launch: the row-tile kernel indexes output voxels in 32 bits (M = %lld)", (long long)M);
+    case ConvKernel::Wino2:
+      if (!wide) {
+        HOLO_LAUNCH((conv_wino2_kernel<false, 2>), hgrid, block, stream, p);
+      } else if (sk) {
+        HOLO_LAUNCH((conv_wino2_kernel<true, 4>), hgrid, block, stream, p);
+      } else {
+        HOLO_LAUNCH((conv_wino2_kernel<false, 4>), hgrid, block, stream, p);
+      }
+      break;
+    case ConvKernel::Bf16Wide:
+      if (!p.in_bf16 || (p.residual && !p.res_bf16)) {
+        set_error("conv_launch: the wide-tile bf16 kernel runs on bf16 activation storage");
+        return -1;
+      }
+      if (!wide) {
+        HOLO_LAUNCH((conv_bf16t_kernel<1, false, true>), hgrid, block, stream, p);
+      } else if (sk) {
+        HOLO_LAUNCH((conv_bf16t_kernel<2, true, true>), hgrid, block, stream, p);
+      } else {
+        HOLO_LAUNCH((conv_bf16t_kernel<2, false, true>), hgrid, block, stream, p);
+      }
+      break;
+    case ConvKernel::Wino3:
+      if (conv_wino3_launch(p, stream)) return -1;
+      break;
+    case ConvKernel::Stream1x1: {
+      if (p.stats || p.residual || p.coef || p.nsplit != 1) {
+        set_error("conv_launch: the streaming 1x1x1 kernel takes raw input and produces no statistics");
+        return -1;
+      }
+      // two workgroups per CU, every wave walks 16-row tiles with a stride of the whole grid
+      int64_t wgs = cdiv(M >> 4, 4 * 4);  // >= 4 tiles per wave
+      if (wgs > 512) wgs = 512;
+      if (wgs < 1) wgs = 1;
+      dim3 g3((unsigned)wgs, (unsigned)(p.Cout / 64));
+      switch (Cin / 32) {
+        case 1: HOLO_LAUNCH(conv1x1_stream_kernel<1>, g3, block, stream, p); break;
+        case 2: HOLO_LAUNCH(conv1x1_stream_kernel<2>, g3, block, stream, p); break;
+        case 3: HOLO_LAUNCH(conv1x1_stream_kernel<3>, g3, block, stream, p); break;
+        case 4: HOLO_LAUNCH(conv1x1_stream_kernel<4>, g3, block, stream, p); break;
+        case 5: HOLO_LAUNCH(conv1x1_stream_kernel<5>, g3, block, stream, p); break;
+        case 6: HOLO_LAUNCH(conv1x1_stream_kernel<6>, g3, block, stream, p); break;
+        case 7: HOLO_LAUNCH(conv1x1_stream_kernel<7>, g3, block, stream, p); break;
+        case 8: HOLO_LAUNCH(conv1x1_stream_kernel<8>, g3, block, stream, p); break;
+        default:
+          set_error("conv_launch: streaming 1x1x1 kernel: %d input channels", Cin);
+          return -1;
+      }
+      break;
+    }
+    case ConvKernel::Bf16Persistent:
+      if (conv_bf16p_launch(p, stream)) return -1;
+      break;
+    case ConvKernel::S2Bf16:
+      if (conv_s2_bf16_launch(p, stream)) return -1;
+      break;
+    case ConvKernel::Qkv:
+      if (conv1x1_qkv_bf16_launch(p, stream)) return -1;
+      break;
+    case ConvKernel::Bf16Stream1x1:
+      if (conv1x1_bf16_stream_launch(p, stream)) return -1;
+      break;
+    default:
+      set_error("conv_launch: unknown kernel %d", (int)p.kernel);
       return -1;
-    }
-    if (p.skip_w && (p.stride != 1 || p.ups || p.ID != p.OD || (p.bf16 == 1 && p.w_bf && !p.skip_w_bf))) {
-      set_error("conv_launch: the row-tile kernel fuses a skip connection at stride 1 without upsampling only");
-      return -1;
-    }
-    dim3 sgrid((unsigned)cdiv(M, SM_ROWS), (unsigned)cdiv(p.Cout, 64), (unsigned)p.nsplit);
-    if (p.bf16 == 1 && p.w_bf) {  // bf16 compute mode
-      HOLO_LAUNCH(conv_small_kernel<true>, sgrid, block, stream, p);
-    } else {
-      HOLO_LAUNCH(conv_small_kernel<false>, sgrid, block, stream, p);
-    }
-  } else if (wide) {
-    HOLO_LAUNCH(conv_igemm_kernel<2>, grid, block, stream, p);
-  } else {
-    HOLO_LAUNCH(conv_igemm_kernel<1>, grid, block, stream, p);
   }
   if (p.nsplit > 1) {
     const int64_t MC = M * p.Cout;

@@ -766,7 +766,7 @@ int repack_conv_weight_wino3_launch(const float* w, float* out, int Cout, int Ci
 
 #endif  // the library copy
 
-// p.wino == 3 (conv_plan): p.grid_x persistent workgroups
+// ConvKernel::Wino3 (conv_plan): p.grid_x persistent workgroups
 int W3_ENTRY(const ConvParams& p, void* stream) {
   if (!p.w_wino3 || (p.skip_w && !p.skip_w_wino3) || (p.OD & 1) || (p.OH & 7) || (p.OW & 7) || (p.Cout & 63) ||
       (p.coef && !p.act)) {

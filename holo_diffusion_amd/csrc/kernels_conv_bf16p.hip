@@ -639,7 +639,7 @@ __global__ __launch_bounds__(512, 2) void conv_bf16p_kernel(ConvParams p) {
         if (tap + 1 < 27) load_a(A[(tap + 1) & 1], tap + 1, hb);
         if (tap + 2 < 27) load_b(B[(tap + 2) % 3], tap + 2);
         mfma_tap(A[tap & 1], B[tap % 3]);
-        {  // one operand read behind each MFMA (conv_bf16t_kernel's SCHED = 2)
+        {  // one operand read behind each MFMA (as in conv_bf16t_kernel)
 #pragma unroll
           for (int i = 0; i < 4 + NT; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);

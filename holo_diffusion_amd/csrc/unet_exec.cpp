@@ -71,8 +71,7 @@ struct ParamSlot {
   ParamKind kind;
   float* priv;  // private (repacked) device copy
   uint16_t* priv_bf = nullptr;  // conv weights: bf16 (RNE) copy packed for v_mfma_f32_16x16x32_bf16
-  float* priv_wino = nullptr;   // conv weights of the wide top levels: Winograd-in-depth pseudo-taps (conv_wino_kernel)
-  float* priv_wino2 = nullptr;  // ... and the (z,y) Winograd pseudo-taps (conv_wino2_kernel)
+  float* priv_wino2 = nullptr;  // conv weights of the wide top levels: (z,y) Winograd pseudo-taps (conv_wino2_kernel)
   float* priv_wino3 = nullptr;  // ... and the F(2x2x2, 3x3x3) pseudo-taps (conv_wino3_kernel)
   bool set;
 };
@@ -179,11 +178,10 @@ struct HoloUnet {
   uint16_t* pstore_bf = nullptr;                       // bf16 copies of the conv weights
   std::map<const float*, const uint16_t*> bf_of;       // fp32 private copy -> bf16 copy
   std::map<const float*, const uint16_t*> bft_of;      // fp32 private copy -> bf16 copy packed for the wide-tile kernel
-  float* pstore_wino = nullptr;                        // Winograd-in-depth copies (36 / 2 pseudo-taps)
-  std::map<const float*, const float*> wino_of;        // fp32 private copy -> Winograd copy
+  float* pstore_wino = nullptr;                        // Winograd copies of the conv weights
   std::map<const float*, const float*> wino2_of;       // fp32 private copy -> (z,y) Winograd copy
   std::map<const float*, const float*> wino3_of;       // fp32 private copy -> F(2x2x2, 3x3x3) Winograd copy
-  std::map<std::string, float*> dgrad_wino, dgrad_wino2, dgrad_wino3;  // Winograd copies of the transposed (dgrad) weights
+  std::map<std::string, float*> dgrad_wino2, dgrad_wino3;  // Winograd copies of the transposed (dgrad) weights
   // holo_unet_set_compute_dtype: 0 exact fp32 MFMA; 1 bf16: activations stored as bf16 in HBM, bf16 products with fp32
   // accumulation in the 3x3x3 convolutions and the long-sequence attention, fp32 GroupNorm statistics; 2 bf16x3 split
   // (fp32 storage, fp32-accurate)
@@ -508,9 +506,7 @@ struct Planner {
       p.w_bft = itt == u->bft_of.end() ? nullptr : itt->second;
       p.bf16 = u->compute_mode;
     }
-    if (u->compute_mode == 0) {  // exact fp32: the Winograd-in-depth kernel where conv_plan finds 128-voxel tiles
-      auto it = u->wino_of.find(w);
-      p.w_wino = it == u->wino_of.end() ? nullptr : it->second;
+    if (u->compute_mode == 0) {  // exact fp32: the Winograd kernels where conv_plan finds 128-voxel tiles
       auto it2 = u->wino2_of.find(w);
       p.w_wino2 = it2 == u->wino2_of.end() ? nullptr : it2->second;
       auto it3 = u->wino3_of.find(w);
@@ -534,8 +530,6 @@ struct Planner {
         p.skip_w_bft = itt == u->bft_of.end() ? nullptr : itt->second;
       }
       if (u->compute_mode == 0) {
-        auto it = u->wino_of.find(skip_w);
-        p.skip_w_wino = it == u->wino_of.end() ? nullptr : it->second;
         auto it2 = u->wino2_of.find(skip_w);
         p.skip_w_wino2 = it2 == u->wino2_of.end() ? nullptr : it2->second;
         auto it3 = u->wino3_of.find(skip_w);
@@ -696,7 +690,7 @@ struct Planner {
               offer_pack ? &qp : nullptr);
     if (flash) {
       Op op = fop;
-      op.i2 = ops.back().kind == OP_CONV && ops.back().conv.mode == 5 ? 1 : 0;  // operands already packed
+      op.i2 = ops.back().kind == OP_CONV && ops.back().conv.kernel == ConvKernel::Qkv ? 1 : 0;  // operands already packed
       if (getenv("HOLO_DEBUG_PLAN"))
         fprintf(stderr, "[plan] attention %s: T=%lld C=%d heads=%d -> %s flash kernel\n", p.c_str(), (long long)T, C, H,
                 op.i0 == 2 ? "bf16" : "fp32");
@@ -1520,31 +1514,25 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
         cb += 4 * ((priv_numel(s) + 63) & ~(int64_t)63);
       }
   }
-  {  // Winograd-in-depth copies for the convolutions that can land on 128-voxel tiles: the wide top levels
-     // (a 3x3x3 conv of <= 256 channels: 36 pseudo-taps; a ResBlock's 1x1x1 skip connection: 2 pseudo-taps)
-    const char* we = getenv("HOLO_CONV_WINO");
-    const bool enable = !(we && we[0] == '0');
-    auto wino_numel = [](const ParamSlot& s) -> int64_t {
+  {  // Winograd copies for the convolutions that can land on 128-voxel tiles: the wide top levels (a 3x3x3 conv of
+     // <= 256 channels: 48 (z,y) pseudo-taps; a ResBlock's 1x1x1 skip connection: 4).  HOLO_CONV_WINO=0: none
+    const bool enable = env_int("HOLO_CONV_WINO", 1) != 0;
+    auto wino2_numel = [&](const ParamSlot& s) -> int64_t {
       const bool c3 = s.kind == P_CONV3;
       const bool sk = s.kind == P_CONV1 && s.name.find("skip_connection") != std::string::npos;
       // (the levels with 8-divisible planes: up to 256 output channels, up to 768 input channels with the skip concat)
-      if (!(c3 || sk) || s.shape[0] > 256 || s.shape[1] > 768 || (s.shape[0] % 64 && !(c3 && s.shape[0] == 32))) return 0;
-      return (int64_t)(c3 ? 36 : 2) * pad_cout((int)s.shape[0]) * pad_cin((int)s.shape[1]);
+      if (!enable || !(c3 || sk) || s.shape[0] > 256 || s.shape[1] > 768 || (s.shape[0] % 64 && !(c3 && s.shape[0] == 32))) return 0;
+      return (int64_t)(c3 ? 48 : 4) * pad_cout((int)s.shape[0]) * pad_cin((int)s.shape[1]);
     };
-    const bool enable2 = enable && !(we && we[0] == '1');  // HOLO_CONV_WINO=1: depth only; default: both forms prepared
-    auto wino2_numel = [&](const ParamSlot& s) -> int64_t { return enable2 ? wino_numel(s) / (s.kind == P_CONV3 ? 36 : 2) * (s.kind == P_CONV3 ? 48 : 4) : 0; };
     // F(2x2x2, 3x3x3) copies (conv_wino3_kernel, 64 pseudo-taps / 8 signed skip copies): the levels whose workgroup list
     // can fill the chip - up to 256 output channels (64^3 .. 8^3 in the released nets); HOLO_CONV_WINO3=0: none
-    const char* w3e = getenv("HOLO_CONV_WINO3");
-    const bool enable3 = enable2 && !(w3e && w3e[0] == '0');
+    const bool enable3 = env_int("HOLO_CONV_WINO3", 1) != 0;
     auto wino3_numel = [&](const ParamSlot& s) -> int64_t {
-      if (!enable3 || wino_numel(s) == 0 || s.shape[0] % 64 || s.shape[0] > 256 || s.shape[1] > 768) return 0;
+      if (!enable3 || wino2_numel(s) == 0 || s.shape[0] % 64 || s.shape[0] > 256 || s.shape[1] > 768) return 0;
       return conv_wino3_weight_floats(pad_cout((int)s.shape[0]), pad_cin((int)s.shape[1]), s.kind == P_CONV3 ? 27 : 1);
     };
     int64_t tw = 0;
-    if (enable)
-      for (auto& s : u->params)
-        tw += ((wino_numel(s) + 63) & ~(int64_t)63) + ((wino2_numel(s) + 63) & ~(int64_t)63) + ((wino3_numel(s) + 63) & ~(int64_t)63);
+    for (auto& s : u->params) tw += ((wino2_numel(s) + 63) & ~(int64_t)63) + ((wino3_numel(s) + 63) & ~(int64_t)63);
     if (tw > 0) {
       if (hipMalloc((void**)&u->pstore_wino, (size_t)tw * sizeof(float)) != hipSuccess) {
         set_error("holo_unet_create: hipMalloc of %lld Winograd weights failed", (long long)tw);
@@ -1555,17 +1543,11 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
       }
       float* cw = u->pstore_wino;
       for (auto& s : u->params) {
-        const int64_t nw = wino_numel(s);
-        if (nw == 0) continue;
-        s.priv_wino = cw;
-        u->wino_of[s.priv] = cw;
-        cw += (nw + 63) & ~(int64_t)63;
         const int64_t nw2 = wino2_numel(s);
-        if (nw2) {
-          s.priv_wino2 = cw;
-          u->wino2_of[s.priv] = cw;
-          cw += (nw2 + 63) & ~(int64_t)63;
-        }
+        if (nw2 == 0) continue;
+        s.priv_wino2 = cw;
+        u->wino2_of[s.priv] = cw;
+        cw += (nw2 + 63) & ~(int64_t)63;
         const int64_t nw3 = wino3_numel(s);
         if (nw3) {
           s.priv_wino3 = cw;
@@ -1595,8 +1577,6 @@ int holo_unet_destroy(HoloUnet* net) {
   if (net->pstore_bf) (void)hipFree(net->pstore_bf);
   if (net->pstore_wino) (void)hipFree(net->pstore_wino);
   for (auto& kv : net->dgrad_w)
-    if (kv.second) (void)hipFree(kv.second);
-  for (auto& kv : net->dgrad_wino)
     if (kv.second) (void)hipFree(kv.second);
   for (auto& kv : net->dgrad_wino3)
     if (kv.second) (void)hipFree(kv.second);
@@ -1656,16 +1636,10 @@ int holo_unet_set_param(HoloUnet* net, const char* name, const void* dev_ptr, in
                                         s.kind == P_CONV3 ? 27 : 1, pad_cout((int)s.shape[0]), pad_cin((int)s.shape[1]),
                                         stream);
     if (rc) return rc;
-    if (s.priv_wino) {
-      rc = repack_conv_weight_wino_launch((const float*)dev_ptr, s.priv_wino, (int)s.shape[0], (int)s.shape[1],
-                                          s.kind == P_CONV3 ? 27 : 1, pad_cout((int)s.shape[0]),
-                                          pad_cin((int)s.shape[1]), stream);
-      if (rc) return rc;
-    }
     if (s.priv_wino2) {
-      rc = repack_conv_weight_wino_launch((const float*)dev_ptr, s.priv_wino2, (int)s.shape[0], (int)s.shape[1],
-                                          s.kind == P_CONV3 ? 27 : 1, pad_cout((int)s.shape[0]),
-                                          pad_cin((int)s.shape[1]), stream, 2);
+      rc = repack_conv_weight_wino2_launch((const float*)dev_ptr, s.priv_wino2, (int)s.shape[0], (int)s.shape[1],
+                                           s.kind == P_CONV3 ? 27 : 1, pad_cout((int)s.shape[0]),
+                                           pad_cin((int)s.shape[1]), stream);
       if (rc) return rc;
     }
     if (s.priv_wino3) {
@@ -1892,8 +1866,8 @@ int holo_unet_time_ops(HoloUnet* net, int batch, const float* x, const int64_t* 
       t.ms = ms / iters;
       if (op.kind == OP_CONV) {
         const ConvParams& c = op.conv;
-        t.kernel = c.mode == 6 ? 11 : c.mode == 5 ? 10 : c.mode == 4 ? 9 : c.mode == 3 ? 7 : (c.bf16t && c.bf16p) ? 8 : c.bf16t ? 5 : c.wino == 3 ? 6 : c.wino == 2 ? 4 : c.wino ? 3 : c.mode;
-        t.tile_depth = c.mode == 1 ? c.tz : 0;
+        t.kernel = (int)c.kernel;
+        t.tile_depth = c.tz;  // (0 off the halo forms)
         t.fused_skip = c.skip_w ? 1 : 0;
         t.nsplit = c.nsplit;
         t.cin = c.C0 + c.C1;
@@ -1961,27 +1935,21 @@ int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_
   if (flip_transpose_weight_launch((const float*)dev_ptr, net->dgrad_tmp, Co, Ci, T, stream)) return HOLO_E_INVALID;
   if (repack_conv_weight_launch(net->dgrad_tmp, dst, Ci, Co, T, pad_cout(Ci), pad_cin(Co), stream)) return HOLO_E_INVALID;
   // Winograd copies of the transposed convolution (the dgrad of a wide-level 3x3x3 conv runs on conv_wino2_kernel like
-  // the forward conv: 36 + 48 pseudo-taps, same eligibility as holo_unet_create's except that the transposed conv's output
+  // the forward conv: 48 pseudo-taps, same eligibility as holo_unet_create's except that the transposed conv's output
   // channels are the forward conv's INPUT channels, up to 768 with the skip concat)
-  static const char* we = getenv("HOLO_CONV_WINO");
-  const bool wino_on = !(we && (we[0] == '0' || we[0] == '1'));
+  static const bool wino_on = env_int("HOLO_CONV_WINO", 1) != 0;
   if (wino_on && net->compute_mode == 0 && T == 27 && (Ci % 64) == 0 && Ci <= 768 && Co <= 768) {
-    const size_t per_tap = (size_t)pad_cout(Ci) * pad_cin(Co);
-    float*& w1 = net->dgrad_wino[key];
     float*& w2 = net->dgrad_wino2[key];
-    if (!w1 || !w2) {  // a plan sized before these copies existed chose other kernels (and scratch sizes)
+    if (!w2) {  // a plan sized before these copies existed chose other kernels (and scratch sizes)
       net->tws_cache.clear();
       net->tplan_batch = -1;
+      HIP_TRY(hipMalloc((void**)&w2, 48 * (size_t)pad_cout(Ci) * pad_cin(Co) * sizeof(float)));
     }
-    if (!w1) HIP_TRY(hipMalloc((void**)&w1, 36 * per_tap * sizeof(float)));
-    if (!w2) HIP_TRY(hipMalloc((void**)&w2, 48 * per_tap * sizeof(float)));
-    if (repack_conv_weight_wino_launch(net->dgrad_tmp, w1, Ci, Co, 27, pad_cout(Ci), pad_cin(Co), stream, 1)) return HOLO_E_INVALID;
-    if (repack_conv_weight_wino_launch(net->dgrad_tmp, w2, Ci, Co, 27, pad_cout(Ci), pad_cin(Co), stream, 2)) return HOLO_E_INVALID;
-    net->wino_of[dst] = w1;
+    if (repack_conv_weight_wino2_launch(net->dgrad_tmp, w2, Ci, Co, 27, pad_cout(Ci), pad_cin(Co), stream)) return HOLO_E_INVALID;
     net->wino2_of[dst] = w2;
     // ... and on conv_wino3_kernel where the forward convolutions do (transposed: output channels = the forward's inputs)
-    static const char* w3e = getenv("HOLO_CONV_WINO3");
-    if (!(w3e && w3e[0] == '0') && Ci <= 256 && Co <= 768) {
+    static const bool wino3_on = env_int("HOLO_CONV_WINO3", 1) != 0;
+    if (wino3_on && Ci <= 256 && Co <= 768) {
       float*& w3 = net->dgrad_wino3[key];
       if (!w3) {
         net->tws_cache.clear();

@@ -446,8 +446,8 @@ int holo_unet_time_convs(HoloUnet* net, int batch, void* workspace, size_t works
  * `iters` back-to-back launches between two events on `stream`), in execution order.
  *   op     : 0 memset, 1 layout-in, 2 time-embed, 3 emb linears, 4 GroupNorm stats, 5 GroupNorm finalize,
  *            6 conv, 7 GEMM, 8 softmax, 9 flash attention, 10 layout-out
- *   conv ops: kernel 0 = per-tap gather kernel, 1 = LDS voxel-halo kernel, 2 = small-M weight-streaming kernel, 3 / 4 / 6 = the
- *            Winograd forms (depth / depth + height / all three axes), 5 = bf16 wide-tile kernel, 7 = streaming 1x1x1 kernel,
+ *   conv ops: kernel 0 = per-tap gather kernel, 1 = LDS voxel-halo kernel, 2 = small-M weight-streaming kernel, 4 / 6 = the
+ *            Winograd forms (depth + height / all three axes; 3, the depth-only form, is retired), 5 = bf16 wide-tile kernel, 7 = streaming 1x1x1 kernel,
  *            8 = bf16 wide-tile kernel in its persistent wave-specialised form, 9 = stride-2 bf16 halo kernel,
  *            10 = qkv convolution fused with the bf16 attention's operand packing, 11 = streaming 1x1x1 convolution on bf16 storage;
  *            tile_depth / fused_skip / nsplit describe the variant (they select the template instantiation that

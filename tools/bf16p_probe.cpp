@@ -152,15 +152,15 @@ int main(int argc, char** argv) {
     setenv("HOLO_CONV_BF16P", "0", 1);
     ConvParams qt = p;
     conv_plan(qt, 256);
-    if (!qt.bf16t || qt.bf16p || qt.nsplit != 1) {
-      printf("   planner: bf16t %d bf16p %d nsplit %d - skipped\n", qt.bf16t, qt.bf16p, qt.nsplit);
+    if (qt.kernel != ConvKernel::Bf16Wide || qt.nsplit != 1) {
+      printf("   planner: kernel %d nsplit %d - skipped\n", (int)qt.kernel, qt.nsplit);
       continue;
     }
     time_fn("conv_bf16t_kernel (2 workgroups per CU)", conv_launch, qt);
     setenv("HOLO_CONV_BF16P", "1", 1);
     ConvParams qp = p;
     conv_plan(qp, 256);
-    if (!qp.bf16p) {
+    if (qp.kernel != ConvKernel::Bf16Persistent) {
       printf("   planner did not choose the persistent form\n");
       continue;
     }

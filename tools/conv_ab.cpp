@@ -104,7 +104,7 @@ int main(int argc, char** argv) {
     p.stride = 1, p.pad = 1, p.ksz = 3;
     p.Cout = Cout, p.CoutP = CoutP, p.CinP = CinP;
     p.w = dev_random((size_t)27 * CinP * CoutP, 0.1f);
-    p.w_wino = p.w_wino2 = dev_random((size_t)48 * CinP * CoutP, 0.1f);
+    p.w_wino2 = dev_random((size_t)48 * CinP * CoutP, 0.1f);
     p.w_wino3 = dev_random((size_t)conv_wino3_weight_floats(CoutP, CinP, 27), 0.1f);
     CK(hipMalloc((void**)&p.out, V * Cout * 4));
     if (s.act) {
@@ -129,7 +129,7 @@ int main(int argc, char** argv) {
       p.skip_C0 = p.skip_C1 = 64;
       p.skip_CinP = 128;
       p.skip_w = dev_random((size_t)128 * CoutP, 0.1f);
-      p.skip_w_wino = p.skip_w_wino2 = dev_random((size_t)4 * 128 * CoutP, 0.1f);
+      p.skip_w_wino2 = dev_random((size_t)4 * 128 * CoutP, 0.1f);
       p.skip_w_wino3 = dev_random((size_t)conv_wino3_weight_floats(CoutP, 128, 1), 0.1f);
       p.skip_bias = dev_random(Cout, 1.f);
     }
@@ -140,8 +140,8 @@ int main(int argc, char** argv) {
       ConvParams q = p;
       const size_t sb = conv_plan(q, 256);
       if (sb) CK(hipMalloc((void**)&q.partial, sb));
-      if (q.wino != form) {
-        printf("   form %d: planner chose wino=%d\n", form, q.wino);
+      if (q.kernel != (form == 3 ? ConvKernel::Wino3 : ConvKernel::Wino2)) {
+        printf("   form %d: planner chose kernel %d\n", form, (int)q.kernel);
         continue;
       }
       // ~50 ms of the same launches first: the clocks of a short burst are 5 - 10 % below the sustained ones (a variant timed

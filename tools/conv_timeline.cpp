@@ -35,7 +35,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&w2, (size_t)48 * CinP * CoutP * 4));
     std::vector<float> hw2((size_t)48 * CinP * CoutP); for (auto& x : hw2) x = (rand() % 2001 - 1000) * 1e-4f;
     CK(hipMemcpy(w2, hw2.data(), hw2.size() * 4, hipMemcpyHostToDevice));
-    p.w_wino = w2; p.w_wino2 = w2;
+    p.w_wino2 = w2;
   }
   const int act = argc > 7 ? atoi(argv[7]) : 0;
   if (act) {
@@ -66,7 +66,7 @@ int main(int argc, char** argv) {
   const int ntile = (int)(V / (64 * p.tz));
   const int ny = (Cout + 63) / 64;
   CK(hipMalloc(&dbg, (size_t)ntile * ny * 64)); CK(hipMemset(dbg, 0, (size_t)ntile * ny * 64));
-  printf("mode %d tz %d nsplit %d grid_x %d tiles %d\n", p.mode, p.tz, p.nsplit, p.grid_x, ntile);
+  printf("kernel %d tz %d nsplit %d grid_x %d tiles %d\n", (int)p.kernel, p.tz, p.nsplit, p.grid_x, ntile);
   for (int i = 0; i < 3; ++i) conv_launch(p, nullptr);
   CK(hipDeviceSynchronize());
   p.dbg = dbg;
@@ -87,7 +87,7 @@ int main(int argc, char** argv) {
   const double n = ntile * ny, tick = 0.01;  // us per 100 MHz tick
   printf("event ms %.4f  span(first start..last end) %.2f us\n", ms, (t1 - t0) * tick);
   printf("per tile: prologue %.2f us  loops %.2f us  epilogue %.2f us  total %.2f us\n", pro / n * tick, loop / n * tick, epi / n * tick, (pro + loop + epi) / n * tick);
-  { double stg = 0; for (int i = 0; i < ntile * ny; ++i) stg += d[(size_t)i * 8 + 6]; printf("per tile: staging (issue -> barrier, all chunks) %.2f us [wino %d]\n", stg / n * tick, p.wino); }
+  { double stg = 0; for (int i = 0; i < ntile * ny; ++i) stg += d[(size_t)i * 8 + 6]; printf("per tile: staging (issue -> barrier, all chunks) %.2f us [kernel %d]\n", stg / n * tick, (int)p.kernel); }
   // occupancy of CU slots over time
   double busy = 0, gaps = 0; int ncu = 0; double firsts = 0, lasts = 0;
   for (auto& kv : per_cu) {

@@ -86,7 +86,7 @@ int main(int argc, char** argv) {
   p.Cout = Cout, p.w = w[0], p.CoutP = CoutP, p.CinP = CinP, p.out = out, p.coef = coef, p.act = 1, p.bias = bias;
   const size_t sb = conv_plan(p, 256);
   if (sb) CK(hipMalloc((void**)&p.partial, sb));
-  printf("%d^3 %d -> %d: mode %d, split-K %d x %d chunks, partials %.1f MB, weights %.1f MB\n", R, Cin, Cout, p.mode, p.nsplit,
+  printf("%d^3 %d -> %d: kernel %d, split-K %d x %d chunks, partials %.1f MB, weights %.1f MB\n", R, Cin, Cout, (int)p.kernel, p.nsplit,
          p.chunks_per_split, sb / 1e6, wfloats * 4 / 1e6);
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
