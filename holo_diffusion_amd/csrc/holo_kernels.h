@@ -35,6 +35,7 @@ enum class ConvKernel : int32_t {
   S2Bf16 = 9,          // stride-2 bf16 halo kernel (conv_s2_bf16_kernel, kernels_conv_s2.hip)
   Qkv = 10,            // qkv convolution fused with the attention's operand packing (conv1x1_qkv_bf16_kernel)
   Bf16Stream1x1 = 11,  // streaming 1x1x1 convolution on bf16 storage (conv1x1_bf16_stream_kernel)
+  Small1x1 = 12,       // exact-fp32 1x1x1 convolution of a small grid, K split over the waves (conv1x1_small_kernel)
 };
 
 struct ConvParams {
@@ -168,8 +169,15 @@ struct AttnParams {
   float* out;
   int N, T, C, H;
   float scale2;
+  // fp32 kernel: key splits (flash_attn_splits) and, when > 1, the workspace of their partials
+  // (flash_attn_workspace_bytes): part [nsplit][N][T][C] unnormalised O, part_ml [nsplit][N][H][T][2] (m, l)
+  int nsplit;
+  float* part;
+  float* part_ml;
 };
 bool flash_attn_supported(int T, int head_channels);
+int flash_attn_splits(int N, int T, int H, int num_cus);
+size_t flash_attn_workspace_bytes(const AttnParams& p);
 int flash_attn_launch(const AttnParams& p, void* stream);
 // bf16-product variant (shared K/V tiles in LDS, v_mfma_f32_16x16x32_bf16), for the opt-in bf16 mode
 // Second form of the bf16 attention (bf16 storage mode, long sequences): a pre-pass rewrites qkv once per call as

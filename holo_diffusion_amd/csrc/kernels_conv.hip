@@ -2321,6 +2321,129 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(ConvParams p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// 1x1x1 convolution of a SMALL grid in exact fp32: an AttentionBlock's qkv (GroupNorm's affine on load, no SiLU) and
+// proj_out (+ bias + the block input as residual, GroupNorm statistics of the output for the next block) on the 16^3 and
+// 8^3 levels, M = 4096 / 512 rows.  The row-tile kernel ran these split-K (a reduce launch behind it, 11 - 13.5 us each,
+// matrix pipe busy 0.02): here the workgroup is ONE 16-row x 64-channel tile and its four waves split the K extent (the
+// 32-channel chunks i = wave, wave + 4, ...), so the grid is M/16 x Cout/64 workgroups and every wave's chain is at most
+// two chunks (64 MFMAs) deep.  Rows and weights come straight from global memory (the weights in the row-tile kernel's
+// packed layout, 1 KB per (chunk, 16-Cout slice, half): coalesced float4 per lane); the four partial tiles are summed
+// through LDS in wave order (deterministic), then wave w finishes the 16 output channels of slice w.  Products formed
+// transposed as in conv1x1_stream_kernel: a lane holds 4 consecutive output channels of one voxel (16-byte stores).
+// GroupNorm statistics: one slab per workgroup (16 voxels of one sample: V % 16 == 0), [n][V/16][Cout][2].
+// ---------------------------------------------------------------------------------------------
+template <int NCH>  // NCH = Cin / 32
+__global__ __launch_bounds__(256) void conv1x1_small_kernel(ConvParams p) {
+  constexpr int NCW = (NCH + 3) / 4;  // chunks per wave (at most)
+  __shared__ __attribute__((aligned(16))) float s_red[4 * 4 * 64 * 4];  // [wave][slice][lane][4]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lj = lane & 15, kq = lane >> 4;
+  const int Cin = NCH * 32;
+  const int64_t V = (int64_t)p.OD * p.OH * p.OW;
+  const int64_t m0 = (int64_t)blockIdx.x * 16;
+  const int n = (int)(m0 / V);
+  const int n0 = blockIdx.y * 64;
+  const int wnsl = p.CoutP >> 4;
+  // the wave's rows and weights, all requested before the first MFMA
+  float4 a[NCW][2], bw[NCW][2][4];
+#pragma unroll
+  for (int k = 0; k < NCW; ++k) {
+    const int i = wave + 4 * k;
+    if (i < NCH) {  // (uniform)
+      const float* r = p.src0 + (m0 + lj) * Cin + i * 32 + kq * 8;
+      a[k][0] = *reinterpret_cast<const float4*>(r);
+      a[k][1] = *reinterpret_cast<const float4*>(r + 4);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int sl = 0; sl < 4; ++sl)
+          bw[k][h][sl] = *reinterpret_cast<const float4*>(p.w + ((int64_t)i * wnsl + (n0 >> 4) + sl) * 512 + h * 256 + lane * 4);
+    }
+  }
+  f32x4 acc[4];
+#pragma unroll
+  for (int sl = 0; sl < 4; ++sl)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[sl][r] = 0.f;
+#pragma unroll
+  for (int k = 0; k < NCW; ++k) {
+    const int i = wave + 4 * k;
+    if (i < NCH) {
+      if (p.coef) {  // GroupNorm's affine (a, b) of the lane's 8 channels i*32 + kq*8 + (0..7)
+        const float4* cf = reinterpret_cast<const float4*>(p.coef + ((int64_t)n * Cin + i * 32 + kq * 8) * 2);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float4 c0 = cf[2 * h], c1 = cf[2 * h + 1];
+          float4& x = a[k][h];
+          x = make_float4(fmaf(x.x, c0.x, c0.y), fmaf(x.y, c0.z, c0.w), fmaf(x.z, c1.x, c1.y), fmaf(x.w, c1.z, c1.w));
+        }
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float4 x = a[k][h];
+#pragma unroll
+        for (int sl = 0; sl < 4; ++sl) acc[sl] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[k][h][sl].x, x.x, acc[sl], 0, 0, 0);
+#pragma unroll
+        for (int sl = 0; sl < 4; ++sl) acc[sl] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[k][h][sl].y, x.y, acc[sl], 0, 0, 0);
+#pragma unroll
+        for (int sl = 0; sl < 4; ++sl) acc[sl] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[k][h][sl].z, x.z, acc[sl], 0, 0, 0);
+#pragma unroll
+        for (int sl = 0; sl < 4; ++sl) acc[sl] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[k][h][sl].w, x.w, acc[sl], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int sl = 0; sl < 4; ++sl)
+    *reinterpret_cast<float4*>(s_red + ((wave * 4 + sl) * 64 + lane) * 4) = make_float4(acc[sl][0], acc[sl][1], acc[sl][2], acc[sl][3]);
+  __syncthreads();
+  // wave w: slice w = output channels n0 + 16 w + 4 kq + (0..3) of voxel m0 + lj
+  float4 v = *reinterpret_cast<const float4*>(s_red + ((0 * 4 + wave) * 64 + lane) * 4);
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const float4 t = *reinterpret_cast<const float4*>(s_red + ((w * 4 + wave) * 64 + lane) * 4);
+    v.x += t.x;
+    v.y += t.y;
+    v.z += t.z;
+    v.w += t.w;
+  }
+  const int co = n0 + wave * 16 + 4 * kq;
+  const int64_t o = (m0 + lj) * p.Cout + co;
+  if (p.bias) {
+    const float4 b = *reinterpret_cast<const float4*>(p.bias + co);
+    v.x += b.x;
+    v.y += b.y;
+    v.z += b.z;
+    v.w += b.w;
+  }
+  if (p.residual) {
+    const float4 r = *reinterpret_cast<const float4*>(p.residual + o);
+    v.x += r.x;
+    v.y += r.y;
+    v.z += r.z;
+    v.w += r.w;
+  }
+  *reinterpret_cast<float4*>(p.out + o) = v;
+  if (p.stats) {  // sums over the tile's 16 voxels (lanes lj of the same kq)
+    float s4[4] = {v.x, v.y, v.z, v.w}, q4[4] = {v.x * v.x, v.y * v.y, v.z * v.z, v.w * v.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int d = 1; d < 16; d <<= 1) {
+        s4[e] += __shfl_xor(s4[e], d);
+        q4[e] += __shfl_xor(q4[e], d);
+      }
+    if (lj == 0) {
+      const int64_t slabs = V / 16, slab = (m0 - (int64_t)n * V) / 16;
+      double* d = p.stats + (((int64_t)n * slabs + slab) * p.Cout + co) * 2;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        d[2 * e] = (double)s4[e];
+        d[2 * e + 1] = (double)q4[e];
+      }
+    }
+  }
+}
+
 // s = b + sum over the splits of partial[k][i .. i+3], in the fixed order both reduce kernels share
 __device__ __forceinline__ float4 splitk_sum4(const float* __restrict__ partial, int nsplit, int64_t MC, int64_t i, float4 b) {
   float4 s = b;
@@ -2446,6 +2569,7 @@ const char* conv_kernel_name(ConvKernel k) {
     case ConvKernel::S2Bf16: return "conv_s2_bf16_kernel";
     case ConvKernel::Qkv: return "conv1x1_qkv_bf16_kernel";
     case ConvKernel::Bf16Stream1x1: return "conv1x1_bf16_stream_kernel";
+    case ConvKernel::Small1x1: return "conv1x1_small_kernel";
   }
   return "?";
 }
@@ -2471,6 +2595,19 @@ struct KSplit {
 KSplit ksplit(int64_t want, int max_split, int chunks) {
   const int cps = (int)cdiv(chunks, want < max_split ? want : max_split);
   return {(int)cdiv(chunks, cps), cps};
+}
+
+// conv1x1_small_kernel: an exact-fp32 1x1x1 convolution of a small grid (16 .. 4096 voxels per sample, 32 .. 256 input
+// channels in 32-channel chunks, 64-channel output blocks, one source) whose input is normalised without an activation
+// (an AttentionBlock's qkv) or that adds a residual (its proj_out).  Raw-input 1x1x1 convolutions (ResBlock skips) keep
+// their kernels.
+bool conv1x1_small_supported(const ConvParams& p) {
+  const int Cin = p.C0 + p.C1;
+  const int64_t V = (int64_t)p.OD * p.OH * p.OW;
+  return p.ksz == 1 && p.stride == 1 && p.pad == 0 && !p.ups && p.bf16 == 0 && !p.in_bf16 && !p.out_bf16 && !p.res_bf16 &&
+         !p.skip_w && !p.src1 && p.C1 == 0 && !p.qkv_q && ((p.coef && !p.act) || p.residual) && (Cin % 32) == 0 &&
+         Cin >= 32 && Cin <= 256 && p.CinP == Cin && (p.Cout % 64) == 0 && p.CoutP == p.Cout && p.ID == p.OD &&
+         p.IH == p.OH && p.IW == p.OW && (V % 16) == 0 && V <= 4096 && (int64_t)p.N * V * (Cin > p.Cout ? Cin : p.Cout) < ((int64_t)1 << 31);
 }
 
 KSplit bf16t_split(const ConvParams& p, int64_t t8, int ncc16, int num_cus) {
@@ -2533,6 +2670,9 @@ size_t conv_plan(ConvParams& p, int num_cus) {
           !p.in_bf16 && !p.out_bf16 && (p.Cout % 64) == 0 && (Cin % 32) == 0 && Cin >= 32 && Cin <= 256 &&
           (!p.src1 || (p.C0 % 32) == 0) && (M % 16) == 0 && p.ID == p.OD && p.IH == p.OH && p.IW == p.OW)
         return ConvKernel::Stream1x1;
+      // an attention block's qkv / proj_out in exact fp32 (16^3, 8^3): one 16-row tile per workgroup, K split over its
+      // waves (HOLO_CONV1X1_SMALL=0 keeps the row-tile kernel)
+      if (env_int("HOLO_CONV1X1_SMALL", 1) != 0 && conv1x1_small_supported(p)) return ConvKernel::Small1x1;
       // the stride-2 convolution of a Downsample block in the bf16 storage mode, where its 128-voxel tiles give the chip at
       // least a workgroup per four CUs (128^3 net: 128^3 -> 64^3 540 -> ~100 us, and the two levels below; deeper the row-tile
       // kernel's split-K fills the chip better).  HOLO_CONV_S2T=0 keeps the row-tile kernel, =1 takes this one wherever it is
@@ -2588,6 +2728,7 @@ size_t conv_plan(ConvParams& p, int num_cus) {
     case ConvKernel::Qkv:
     case ConvKernel::Bf16Stream1x1:
     case ConvKernel::Stream1x1:
+    case ConvKernel::Small1x1:
       p.nsplit = 1;
       p.chunks_per_split = ncc;
       if (kernel == ConvKernel::Qkv) conv1x1_qkv_bf16_plan(p, num_cus);
@@ -2695,6 +2836,8 @@ int conv_stats_slabs(const ConvParams& p) {
       return (int)(V / 128);  // one slab per 2 x 8 x 8 tile
     case ConvKernel::Bf16Stream1x1:
       return conv1x1_bf16_stream_slabs(p);  // one slab per workgroup row block
+    case ConvKernel::Small1x1:
+      return (int)(V / 16);  // one slab per workgroup
     default:
       return 0;
   }
@@ -2846,6 +2989,27 @@ int conv_launch(const ConvParams& p, void* stream) {
         case 8: HOLO_LAUNCH(conv1x1_stream_kernel<8>, g3, block, stream, p); break;
         default:
           set_error("conv_launch: streaming 1x1x1 kernel: %d input channels", Cin);
+          return -1;
+      }
+      break;
+    }
+    case ConvKernel::Small1x1: {
+      if (!conv1x1_small_supported(p) || p.nsplit != 1) {
+        set_error("conv_launch: conv1x1_small_kernel: unsupported launch (%d -> %d channels, %d^3)", Cin, p.Cout, p.OD);
+        return -1;
+      }
+      dim3 g1((unsigned)(M / 16), (unsigned)(p.Cout / 64));
+      switch (Cin / 32) {
+        case 1: HOLO_LAUNCH(conv1x1_small_kernel<1>, g1, block, stream, p); break;
+        case 2: HOLO_LAUNCH(conv1x1_small_kernel<2>, g1, block, stream, p); break;
+        case 3: HOLO_LAUNCH(conv1x1_small_kernel<3>, g1, block, stream, p); break;
+        case 4: HOLO_LAUNCH(conv1x1_small_kernel<4>, g1, block, stream, p); break;
+        case 5: HOLO_LAUNCH(conv1x1_small_kernel<5>, g1, block, stream, p); break;
+        case 6: HOLO_LAUNCH(conv1x1_small_kernel<6>, g1, block, stream, p); break;
+        case 7: HOLO_LAUNCH(conv1x1_small_kernel<7>, g1, block, stream, p); break;
+        case 8: HOLO_LAUNCH(conv1x1_small_kernel<8>, g1, block, stream, p); break;
+        default:
+          set_error("conv_launch: conv1x1_small_kernel: %d input channels", Cin);
           return -1;
       }
       break;

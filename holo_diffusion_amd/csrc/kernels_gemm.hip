@@ -215,9 +215,14 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ s
 //   O^T[c][query] += V[key][c] * P^T[key][query]             A = V (global, one dword per k-step),
 //   B = the lane's P register r: k-step r pairs key kappa(r) (lane half 0) with kappa(r)+4 (half 1), which is
 //   exactly the MFMA k index, so P never leaves its registers.
-// Block = 4 waves = ONE tile of 32 queries of one (sample, head); the waves split the T keys in four
-// contiguous quarters (each streams its own K/V rows straight from L2, nothing is shared) and the four
-// partial (m, l, O) are merged through LDS at the end.  Grid = N * H * T/32 workgroups.
+// Block = 4 waves = ONE tile of 32 queries of one (sample, head); the waves split the block's keys in four
+// contiguous ranges (each streams its own K/V rows straight from L2, nothing is shared) and the four
+// partial (m, l, O) are merged through LDS at the end.  Grid = N * H * T/32 * nsplit workgroups.
+// Key split (p.nsplit > 1, short sequences): a query tile's 32-key tiles are dealt to 4 * nsplit waves of nsplit
+// workgroups (the first ones get one tile more when they do not divide evenly); every workgroup writes its merged
+// (m, l, unnormalised O) to p.part and flash_attn_merge_kernel combines the splits in split order (no atomics: the
+// result does not depend on the order the workgroups ran in).  At T = 512 with two heads the un-split grid is 32
+// workgroups, 4 key tiles per wave in series; split four ways every wave has one.
 // ---------------------------------------------------------------------------------------------
 template <int CHH>  // head channels / 2  (the two lane halves split the head channels = MFMA k index)
 __global__ __launch_bounds__(256, 1) void flash_attn_kernel(AttnParams p) {
@@ -233,6 +238,8 @@ __global__ __launch_bounds__(256, 1) void flash_attn_kernel(AttnParams p) {
   const int lh = lane >> 5;
   const int qtiles = p.T / 32;
   int b = blockIdx.x;
+  const int split = b % p.nsplit;
+  b /= p.nsplit;
   const int qt = b % qtiles;
   b /= qtiles;
   const int head = b % p.H;
@@ -263,9 +270,11 @@ __global__ __launch_bounds__(256, 1) void flash_attn_kernel(AttnParams p) {
     for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
 
-  const int keys_per_wave = p.T / 4;
-  const int kbeg = wave * keys_per_wave;
-  const int ntile = keys_per_wave / 32;
+  // this wave's key tiles [kt0, kt1) of the T/32 (4 * nsplit <= T/32: every wave gets at least one)
+  const int nslot = 4 * p.nsplit, slot = split * 4 + wave;
+  const int kt0 = (int)((int64_t)slot * qtiles / nslot), kt1 = (int)((int64_t)(slot + 1) * qtiles / nslot);
+  const int kbeg = kt0 * 32;
+  const int ntile = kt1 - kt0;
 
   float kreg[CHH];
   auto load_k = [&](int kt) {
@@ -343,7 +352,17 @@ __global__ __launch_bounds__(256, 1) void flash_attn_kernel(AttnParams p) {
       if (c < CH) s_o[(wave * CH + c) * 33 + li] = oacc[t][r];
     }
   __syncthreads();
-  float* out = p.out + ((int64_t)n * p.T + qt * 32) * p.C + head * CH;
+  const int64_t row0 = (int64_t)n * p.T + qt * 32;  // (token of the whole batch)
+  float* out = (p.nsplit > 1 ? p.part + (int64_t)split * p.N * p.T * p.C : p.out) + row0 * p.C + head * CH;
+  if (p.nsplit > 1 && tid < 32) {  // the split's (m, l) of query tid
+    const float m0 = s_m[tid], m1 = s_m[32 + tid], m2 = s_m[64 + tid], m3 = s_m[96 + tid];
+    const float M = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+    const float L = __expf(m0 - M) * s_l[tid] + __expf(m1 - M) * s_l[32 + tid] + __expf(m2 - M) * s_l[64 + tid] +
+                    __expf(m3 - M) * s_l[96 + tid];
+    float* ml = p.part_ml + (((int64_t)split * p.N * p.H + (int64_t)n * p.H + head) * p.T + qt * 32 + tid) * 2;
+    ml[0] = M;
+    ml[1] = L;
+  }
   for (int idx = tid; idx < 32 * CH; idx += 256) {
     const int c = idx % CH, q = idx / CH;
     const float m0 = s_m[q], m1 = s_m[32 + q], m2 = s_m[64 + q], m3 = s_m[96 + q];
@@ -352,8 +371,37 @@ __global__ __launch_bounds__(256, 1) void flash_attn_kernel(AttnParams p) {
     const float L = w0 * s_l[q] + w1 * s_l[32 + q] + w2 * s_l[64 + q] + w3 * s_l[96 + q];
     const float o = w0 * s_o[(0 * CH + c) * 33 + q] + w1 * s_o[(1 * CH + c) * 33 + q] +
                     w2 * s_o[(2 * CH + c) * 33 + q] + w3 * s_o[(3 * CH + c) * 33 + q];
-    out[(int64_t)q * p.C + c] = o / L;
+    out[(int64_t)q * p.C + c] = p.nsplit > 1 ? o : o / L;
   }
+}
+
+// out = sum_s w_s O_s / sum_s w_s L_s, w_s = exp(m_s - max m), over the key splits in split order.  One thread per 4
+// consecutive channels of a token (they lie in one head: head channels % 4 == 0).
+__global__ __launch_bounds__(256) void flash_attn_merge_kernel(AttnParams p) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // float4 of out [N][T][C]
+  const int64_t NTC = (int64_t)p.N * p.T * p.C;
+  if (i * 4 >= NTC) return;
+  const int c = (int)((i * 4) % p.C);
+  const int64_t tok = (i * 4) / p.C;  // n * T + t
+  const int n = (int)(tok / p.T), t = (int)(tok - (int64_t)n * p.T);
+  const int head = c / (p.C / p.H);
+  const int64_t NHT = (int64_t)p.N * p.H * p.T;
+  const float* ml = p.part_ml + (((int64_t)n * p.H + head) * p.T + t) * 2;
+  float M = -INFINITY;
+  for (int s = 0; s < p.nsplit; ++s) M = fmaxf(M, ml[s * NHT * 2]);
+  float L = 0.f;
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int s = 0; s < p.nsplit; ++s) {
+    const float w = __expf(ml[s * NHT * 2] - M);
+    L += w * ml[s * NHT * 2 + 1];
+    const float4 v = *reinterpret_cast<const float4*>(p.part + s * NTC + i * 4);
+    o.x += w * v.x;
+    o.y += w * v.y;
+    o.z += w * v.z;
+    o.w += w * v.w;
+  }
+  const float inv = 1.f / L;
+  *reinterpret_cast<float4*>(p.out + i * 4) = make_float4(o.x * inv, o.y * inv, o.z * inv, o.w * inv);
 }
 
 
@@ -372,13 +420,33 @@ int gemm_launch(const GemmParams& p, void* stream) {
 
 bool flash_attn_supported(int T, int ch) { return (T % 128) == 0 && (ch == 16 || ch == 32 || ch == 64 || ch == 128); }
 
+// Key splits: enough workgroups for one per CU, at most one key tile per wave.  Measured on MI355X (profiles/r07_attn_*):
+// T = 512, two heads of 128 channels: 32 workgroups -> 128 with four splits; at T = 4096 the un-split grid has 256
+// workgroups already.  HOLO_FLASH_SPLIT=<n> sets the split count (clamped to [1, T/128]; tests, A/B).
+int flash_attn_splits(int N, int T, int H, int num_cus) {
+  const int max_split = T / 128;
+  const int64_t base = (int64_t)N * H * (T / 32);
+  int64_t s = env_int("HOLO_FLASH_SPLIT", 0);
+  if (s <= 0) s = base < num_cus ? cdiv(num_cus, base) : 1;
+  return (int)(s < 1 ? 1 : s > max_split ? max_split : s);
+}
+
+size_t flash_attn_workspace_bytes(const AttnParams& p) {
+  if (p.nsplit <= 1) return 0;
+  return (size_t)p.nsplit * ((size_t)p.N * p.T * p.C + (size_t)p.N * p.H * p.T * 2) * sizeof(float);
+}
+
 int flash_attn_launch(const AttnParams& p, void* stream) {
   const int ch = p.C / p.H;
   if (!flash_attn_supported(p.T, ch)) {
     set_error("flash_attn: unsupported shape T=%d head channels=%d", p.T, ch);
     return -1;
   }
-  dim3 grid((unsigned)((int64_t)p.N * p.H * (p.T / 32)));
+  if (p.nsplit < 1 || 4 * p.nsplit > p.T / 32 || (p.nsplit > 1 && (!p.part || !p.part_ml))) {
+    set_error("flash_attn: %d key splits at T=%d (workspace %p)", p.nsplit, p.T, (void*)p.part);
+    return -1;
+  }
+  dim3 grid((unsigned)((int64_t)p.N * p.H * (p.T / 32) * p.nsplit));
   switch (ch) {
     case 16:
       HOLO_LAUNCH(flash_attn_kernel<8>, grid, dim3(256), stream, p);
@@ -393,6 +461,8 @@ int flash_attn_launch(const AttnParams& p, void* stream) {
       HOLO_LAUNCH(flash_attn_kernel<64>, grid, dim3(256), stream, p);
       break;
   }
+  if (p.nsplit > 1)
+    HOLO_LAUNCH(flash_attn_merge_kernel, dim3((unsigned)cdiv((int64_t)p.N * p.T * p.C / 4, 256)), dim3(256), stream, p);
   return 0;
 }
 

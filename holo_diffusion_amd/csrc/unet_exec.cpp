@@ -658,6 +658,9 @@ struct Planner {
       const double sc = 1.0 / sqrt(sqrt((double)ch));
       fop.attn.scale2 = (float)(sc * sc);
     }
+    fop.attn.nsplit = 1;
+    fop.attn.part = fop.attn.part_ml = nullptr;
+    size_t split_work = 0, split_bytes = 0;
     // bf16 mode, sequences of 1 024 tokens and more: the packed-operand bf16 kernel (it splits the key range to fill
     // the chip, so it also serves the shorter of them; below that the exact-fp32 kernel is as fast).
     // HOLO_BF16_FLASH_MIN_T lowers the threshold (tests).  (A first, shared-tile form of the bf16 kernel was removed in
@@ -682,6 +685,15 @@ struct Planner {
           qp.qkv_T = (int)T, qp.qkv_CH = ch, qp.qkv_H = H;
           offer_pack = true;
         }
+      } else {
+        // exact fp32: the key range split across workgroups where one per query tile leaves CUs empty
+        fop.attn.nsplit = flash_attn_splits(N, (int)T, H, u->ctx->num_cus);
+        split_bytes = flash_attn_workspace_bytes(fop.attn);
+        if (split_bytes) {
+          split_work = scratch_alloc(split_bytes);
+          fop.attn.part = ptr<float>(split_work);
+          fop.attn.part_ml = fop.attn.part + (size_t)fop.attn.nsplit * N * T * C;
+        }
       }
     }
     // (the attention internals - qkv and the attention output - stay fp32 in every mode)
@@ -692,8 +704,8 @@ struct Planner {
       Op op = fop;
       op.i2 = ops.back().kind == OP_CONV && ops.back().conv.kernel == ConvKernel::Qkv ? 1 : 0;  // operands already packed
       if (getenv("HOLO_DEBUG_PLAN"))
-        fprintf(stderr, "[plan] attention %s: T=%lld C=%d heads=%d -> %s flash kernel\n", p.c_str(), (long long)T, C, H,
-                op.i0 == 2 ? "bf16" : "fp32");
+        fprintf(stderr, "[plan] attention %s: T=%lld C=%d heads=%d -> %s flash kernel, %d key splits\n", p.c_str(),
+                (long long)T, C, H, op.i0 == 2 ? "bf16" : "fp32", op.i0 == 2 ? 1 : op.attn.nsplit);
       ops.push_back(op);
     } else {
       size_t S = scratch_alloc(s_bytes);
@@ -768,6 +780,7 @@ struct Planner {
     emit_conv(av, nullptr, R, 0, R, 1, 1, P(u, p + ".proj_out.weight"), P(u, p + ".proj_out.bias"), 0, false, 0,
               ptr<float>(x.off), ptr<float>(out.off), C, &out, nullptr, nullptr, nullptr, nullptr, /*in_f32=*/!a_is_bf16);
     if (v2_bytes) scratch_free(v2_work, v2_bytes);
+    if (split_bytes) scratch_free(split_work, split_bytes);
     scratch_free(qkv, qkv_bytes);
     scratch_free(a, a_bytes);
     if (tape) {

@@ -440,7 +440,8 @@ class SimpleUnet3D(Unet3DBase):
                 "softmax", "flash_attn", "layout_out")
     # (indexed by HoloOpTiming.kernel; id 3 is the retired depth-only Winograd form, which no plan reports)
     CONV_KERNELS = ("conv_igemm_kernel", "conv_halo_kernel", "conv_small_kernel", "conv_wino_kernel", "conv_wino2_kernel",
-                    "conv_bf16t_kernel", "conv_wino3_kernel", "conv1x1_stream_kernel", "conv_bf16p_kernel", "conv_s2_bf16_kernel", "conv1x1_qkv_bf16_kernel", "conv1x1_bf16_stream_kernel")
+                    "conv_bf16t_kernel", "conv_wino3_kernel", "conv1x1_stream_kernel", "conv_bf16p_kernel", "conv_s2_bf16_kernel", "conv1x1_qkv_bf16_kernel", "conv1x1_bf16_stream_kernel",
+                    "conv1x1_small_kernel")
 
     def time_ops(self, batch: int, iters: int, device: torch.device):
         """Per-op timing of one forward in execution order (hipEvents on the launch stream): list of dicts."""
