@@ -7,6 +7,7 @@
 //   time_embed timestep_embedding + time_embed MLP (nn.py:109-127, unet.py:645-650)
 //   rows_linear all ResBlock emb_layers Linear(SiLU(emb)) at once (unet.py:199-205,245)
 //   ddpm_step  clamp + posterior mean + noise (gaussian_diffusion.py:314-343,237-240,499-506)
+//   ddim_step  clamp + DDIM update (Equation 12) + noise, and its reverse (gaussian_diffusion.py:645-727)
 #include <stdlib.h>
 
 #include "holo_common.h"
@@ -510,6 +511,109 @@ __global__ __launch_bounds__(256) void ddpm_step_philox_kernel(const float* __re
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// DDIM update (gaussian_diffusion.py:645-727: ddim_sample, and ddim_reverse_sample with c4 = 0), float4 per thread,
+// grid = (blocks over per/4, batch).  Sample b reads its row coefs[b*8 + 0..4] = (sqrt_recip_alphas_cumprod[t],
+// sqrt_recipm1_alphas_cumprod[t], sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), [t != 0] * sigma), computed on the host in
+// float32 in the reference's order, so strided schedules and the reverse step need nothing else here.  Per element, in the
+// reference's order and each operation rounded (no fma contraction, see ddim_mean):
+//   eps = (c0*x - pred) / c1 ;  mean = pred*c2 + c3*eps ;  sample = mean + c4*noise
+// ---------------------------------------------------------------------------------------------
+// Plain operators under contract(off): hipcc's __fmul_rn / __fadd_rn are plain operators compiled with the header's default
+// fp-contract, so after inlining they fuse into fmas (that costs the bit-exactness the DDIM tests check)
+__device__ __forceinline__ float ddim_mean(float x, float m, float c0, float c1, float c2, float c3) {
+#pragma clang fp contract(off)
+  const float eps = (c0 * x - m) / c1;
+  return m * c2 + c3 * eps;
+}
+__device__ __forceinline__ float4 ddim_mean4(float4 x, float4 m, const float (&c)[5]) {
+  return make_float4(ddim_mean(x.x, m.x, c[0], c[1], c[2], c[3]), ddim_mean(x.y, m.y, c[0], c[1], c[2], c[3]),
+                     ddim_mean(x.z, m.z, c[0], c[1], c[2], c[3]), ddim_mean(x.w, m.w, c[0], c[1], c[2], c[3]));
+}
+__device__ __forceinline__ float4 clamp4(float4 m) {
+  return make_float4(fminf(fmaxf(m.x, -1.f), 1.f), fminf(fmaxf(m.y, -1.f), 1.f), fminf(fmaxf(m.z, -1.f), 1.f),
+                     fminf(fmaxf(m.w, -1.f), 1.f));
+}
+__device__ __forceinline__ float4 add_noise4(float4 s, float c4, float4 e) {
+#pragma clang fp contract(off)
+  return make_float4(s.x + c4 * e.x, s.y + c4 * e.y, s.z + c4 * e.z, s.w + c4 * e.w);
+}
+
+__global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict__ coefs, int64_t per,
+                                                        const float* __restrict__ x_t,
+                                                        const float* __restrict__ model_out,
+                                                        const float* __restrict__ noise, int clip,
+                                                        float* __restrict__ sample, float* __restrict__ pred) {
+  const int b = blockIdx.y;
+  float c[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) c[k] = holo_ld_sys(coefs + b * 8 + k);  // (a small table uploaded from the host: see holo_ld_sys)
+  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= per) return;
+  const int64_t o = (int64_t)b * per + i;
+  const float4 x = *reinterpret_cast<const float4*>(x_t + o);
+  float4 m = *reinterpret_cast<const float4*>(model_out + o);
+  if (clip) m = clamp4(m);
+  float4 s = ddim_mean4(x, m, c);
+  if (noise && c[4] != 0.f) s = add_noise4(s, c[4], *reinterpret_cast<const float4*>(noise + o));
+  *reinterpret_cast<float4*>(sample + o) = s;
+  if (pred) *reinterpret_cast<float4*>(pred + o) = m;
+}
+
+// The same update with the noise drawn in the kernel: the draw of ddpm_step_philox_kernel (same counter, key and logical
+// element numbering, NCDHW as there), so a DDIM step at timestep t draws the noise a DDPM step at t would.  Samples whose
+// c4 is 0 skip the draw unless noise_out asks for it.
+template <bool NCDHW>
+__global__ __launch_bounds__(256) void ddim_step_philox_kernel(const float* __restrict__ coefs, int64_t per,
+                                                               const float* __restrict__ x_t,
+                                                               const float* __restrict__ model_out, uint32_t seed_lo,
+                                                               uint32_t seed_hi, uint32_t offset, int clip,
+                                                               float* __restrict__ sample, float* __restrict__ pred,
+                                                               float* __restrict__ noise_out, int channels) {
+  const int b = blockIdx.y;
+  float c[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) c[k] = holo_ld_sys(coefs + b * 8 + k);
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid * 4 >= per) return;
+  int64_t qd = tid, o = (int64_t)b * per + tid * 4, es = 1;  // canonical quad, its first element, element stride
+  if (NCDHW) {
+    const int64_t V = per / channels;
+    const int64_t cq = tid / V, v = tid - cq * V;
+    qd = v * (channels >> 2) + cq;
+    o = (int64_t)b * per + cq * 4 * V + v;
+    es = V;
+  }
+  float4 x, m;
+  if (NCDHW) {
+    x = make_float4(x_t[o], x_t[o + es], x_t[o + 2 * es], x_t[o + 3 * es]);
+    m = make_float4(model_out[o], model_out[o + es], model_out[o + 2 * es], model_out[o + 3 * es]);
+  } else {
+    x = *reinterpret_cast<const float4*>(x_t + o);
+    m = *reinterpret_cast<const float4*>(model_out + o);
+  }
+  if (clip) m = clamp4(m);
+  float4 s = ddim_mean4(x, m, c);
+  float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
+  const bool draw = c[4] != 0.f || noise_out;
+  if (draw) {
+    uint32_t rnd[4];
+    philox4x32_10((uint32_t)qd, (uint32_t)((uint64_t)qd >> 32), (uint32_t)b, offset, seed_lo, seed_hi, rnd);
+    box_muller(rnd[0], rnd[1], e.x, e.y);
+    box_muller(rnd[2], rnd[3], e.z, e.w);
+    if (c[4] != 0.f) s = add_noise4(s, c[4], e);
+  }
+  if (NCDHW) {
+    sample[o] = s.x, sample[o + es] = s.y, sample[o + 2 * es] = s.z, sample[o + 3 * es] = s.w;
+    if (pred) pred[o] = m.x, pred[o + es] = m.y, pred[o + 2 * es] = m.z, pred[o + 3 * es] = m.w;
+    if (noise_out) noise_out[o] = e.x, noise_out[o + es] = e.y, noise_out[o + 2 * es] = e.z, noise_out[o + 3 * es] = e.w;
+  } else {
+    *reinterpret_cast<float4*>(sample + o) = s;
+    if (pred) *reinterpret_cast<float4*>(pred + o) = m;
+    if (noise_out) *reinterpret_cast<float4*>(noise_out + o) = e;
+  }
+}
+
 // copy of a SMALL caller-provided tensor (biases, GroupNorm affine parameters, ...) with system-scope loads (holo_ld_sys)
 __global__ __launch_bounds__(256) void copy_sys_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -735,6 +839,39 @@ int ddpm_step_philox_launch(const float* tables, int T, const int64_t* timesteps
                 (uint32_t)offset, clip, sample, pred_xstart, noise_out, ncdhw_channels);
   else
     HOLO_LAUNCH(ddpm_step_philox_kernel<false>, grid, dim3(256), stream, tables, T, timesteps, per, x_t, model_out, k0, k1,
+                (uint32_t)offset, clip, sample, pred_xstart, noise_out, 0);
+  return 0;
+}
+
+int ddim_step_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
+                     const float* noise, int clip, float* sample, float* pred_xstart, void* stream) {
+  if (per & 3) {
+    set_error("ddim_step: elems_per_sample must be a multiple of 4");
+    return -1;
+  }
+  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
+  HOLO_LAUNCH(ddim_step_kernel, grid, dim3(256), stream, coefs, per, x_t, model_out, noise, clip, sample, pred_xstart);
+  return 0;
+}
+
+int ddim_step_philox_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
+                            uint64_t seed, uint64_t offset, int clip, float* sample, float* pred_xstart, float* noise_out,
+                            int ncdhw_channels, void* stream) {
+  if (per & 3) {
+    set_error("ddim_step: elems_per_sample must be a multiple of 4");
+    return -1;
+  }
+  if (ncdhw_channels < 0 || (ncdhw_channels & 3) || (ncdhw_channels > 0 && per % ncdhw_channels)) {
+    set_error("ddim_step_philox: ncdhw_channels must be 0 (channels-last tensors) or a multiple of 4 that divides elems_per_sample");
+    return -1;
+  }
+  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);  // (as ddpm_step_philox)
+  if (ncdhw_channels)
+    HOLO_LAUNCH(ddim_step_philox_kernel<true>, grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
+                (uint32_t)offset, clip, sample, pred_xstart, noise_out, ncdhw_channels);
+  else
+    HOLO_LAUNCH(ddim_step_philox_kernel<false>, grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
                 (uint32_t)offset, clip, sample, pred_xstart, noise_out, 0);
   return 0;
 }

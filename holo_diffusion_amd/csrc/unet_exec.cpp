@@ -2145,6 +2145,34 @@ int holo_ddpm_step_philox(HoloCtx* ctx, const float* tables, int num_timesteps, 
   return rc ? HOLO_E_INVALID : 0;
 }
 
+// gaussian_diffusion.py:645-727 (ddim_sample / ddim_reverse_sample, the elementwise tail)
+int holo_ddim_step(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                   const float* model_out, const float* noise, int clip_denoised, float* sample, float* pred_xstart,
+                   void* stream) {
+  if (!coefs || !x_t || !model_out || !sample || batch < 1 || elems_per_sample < 4) {
+    set_error("holo_ddim_step: null/invalid argument");
+    return HOLO_E_INVALID;
+  }
+  (void)ctx;
+  int rc = ddim_step_launch(coefs, batch, elems_per_sample, x_t, model_out, noise, clip_denoised, sample, pred_xstart,
+                            stream);
+  return rc ? HOLO_E_INVALID : 0;
+}
+
+// gaussian_diffusion.py:645-693 with the noise of :685 drawn in the kernel
+int holo_ddim_step_philox(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                          const float* model_out, uint64_t seed, uint64_t stream_offset, int clip_denoised, float* sample,
+                          float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
+  if (!coefs || !x_t || !model_out || !sample || batch < 1 || elems_per_sample < 4) {
+    set_error("holo_ddim_step_philox: null/invalid argument");
+    return HOLO_E_INVALID;
+  }
+  (void)ctx;
+  int rc = ddim_step_philox_launch(coefs, batch, elems_per_sample, x_t, model_out, seed, stream_offset, clip_denoised,
+                                   sample, pred_xstart, noise_out, ncdhw_channels, stream);
+  return rc ? HOLO_E_INVALID : 0;
+}
+
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream) {
   (void)ctx;
   return tanh_launch(x, y, n, stream);

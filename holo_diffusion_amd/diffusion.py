@@ -11,12 +11,17 @@ gather time like ``_extract_into_tensor`` (:1046-1059).  The per-step elementwis
 (clamp, posterior mean, noise add; :314-343,237-240,499-506) is one fused HIP kernel
 (``holo_ddpm_step``) reading the coefficients by timestep index from a device table, so the
 sampling loop never synchronises with the host.
+
+DDIM (``ddim_sample``, ``ddim_reverse_sample``, ``ddim_sample_loop*``; gaussian_diffusion.py:645-815) runs on a second
+fused kernel (``holo_ddim_step``) that reads one float32 coefficient row per sample, built on the host in the reference's
+order; a chain's rows are uploaded once.  Build-side extensions: strided "ddimS" schedules (``ddim_steps``), explicit
+``timesteps`` and ``ddim_reverse_sample_loop`` (inversion x_0 -> x_T).
 """
 from __future__ import annotations
 
 import enum
 import warnings
-from typing import Callable, Dict, Iterator, Optional
+from typing import Callable, Dict, Iterator, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -43,6 +48,16 @@ def get_named_beta_schedule(name: str, num_steps: int, beta_start_unscaled: floa
         raise NotImplementedError(f"unknown/unsupported beta schedule: {name}")
     scale = 1000 / num_steps
     return np.linspace(scale * beta_start_unscaled, scale * beta_end_unscaled, num_steps, dtype=np.float64)
+
+
+def ddim_timesteps(num_timesteps: int, ddim_steps: int) -> List[int]:
+    """guided-diffusion's "ddimS" spacing (respace.py ``space_timesteps``): ``range(0, T, k)`` for the smallest stride k that
+    gives exactly S timesteps, in the descending order a sampling loop walks them."""
+    S = int(ddim_steps)
+    for k in range(1, max(num_timesteps, 2)):
+        if len(range(0, num_timesteps, k)) == S:
+            return list(range(0, num_timesteps, k))[::-1]
+    raise ValueError(f"cannot create exactly {S} DDIM steps out of {num_timesteps} timesteps with an integer stride")
 
 
 class UniformSampler:
@@ -309,6 +324,232 @@ class ImplicitronGaussianDiffusion(Configurable):
         if final is not None and not final.is_contiguous():
             final = final.contiguous()  # (the channels-last perf chain: one conversion at the end of the chain)
         return (final, samples) if return_all_samples else final
+
+    # ---- DDIM (gaussian_diffusion.py:645-815) ----------------------------------------------------
+    def ddim_schedule(self, ddim_steps: Optional[int] = None, timesteps: Optional[Sequence[int]] = None) -> List[int]:
+        """The timesteps a DDIM loop visits, descending: all T (None), guided-diffusion's "ddimS" spacing (``ddim_steps``),
+        or an explicit strictly decreasing list (``timesteps``)."""
+        T = self.num_timesteps
+        if timesteps is not None:
+            if ddim_steps is not None:
+                raise ValueError("give ddim_steps or timesteps, not both")
+            ts = [int(t) for t in timesteps]
+            if not ts or any(a <= b for a, b in zip(ts, ts[1:])) or ts[0] >= T or ts[-1] < 0:
+                raise ValueError(f"timesteps must be a non-empty strictly decreasing list in [0, {T}): {ts}")
+            return ts
+        if ddim_steps is None:
+            return list(range(T))[::-1]
+        return ddim_timesteps(T, ddim_steps)
+
+    def ddim_coefs(self, t: Sequence[int], t_other: Sequence[int], eta: float = 0.0, reverse: bool = False) -> torch.Tensor:
+        """(batch, 8) float32 rows of holo_ddim_step (include/holo_abi.h), on the host, in float32 with torch ops in the
+        reference's order (gaussian_diffusion.py:677-689, :717-724).  ``t_other`` is the timestep stepped to: t_prev for a
+        sampling step (< 0: past the end of the chain, abar = 1), t_next for a reverse step (>= T: abar = 0)."""
+        t = np.asarray(t, dtype=np.int64).reshape(-1)
+        t_other = np.asarray(t_other, dtype=np.int64).reshape(-1)
+        if t.shape != t_other.shape or (t < 0).any() or (t >= self.num_timesteps).any():
+            raise ValueError(f"invalid DDIM step timesteps {t.tolist()} -> {t_other.tolist()}")
+        ac = self.alphas_cumprod
+        f32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float64)).float()  # noqa: E731  (_extract_into_tensor's cast)
+        # float32 sqrt, correctly rounded: torch's CPU sqrt may go through a vector math library whose last bit depends on
+        # the host CPU, which would make the rows (and the sampled grids) differ between machines
+        sqrt = lambda a: torch.from_numpy(np.sqrt(a.numpy()))  # noqa: E731
+        row = torch.zeros((t.shape[0], 8), dtype=torch.float32)
+        row[:, 0] = f32(self.sqrt_recip_alphas_cumprod[t])
+        row[:, 1] = f32(self.sqrt_recipm1_alphas_cumprod[t])
+        if reverse:
+            assert eta == 0.0, "Reverse ODE only for deterministic path"
+            alpha_bar_next = f32(np.where(t_other < self.num_timesteps, ac[np.minimum(t_other, self.num_timesteps - 1)], 0.0))
+            row[:, 2] = sqrt(alpha_bar_next)
+            row[:, 3] = sqrt(1 - alpha_bar_next)
+            return row
+        alpha_bar = f32(ac[t])
+        alpha_bar_prev = f32(np.where(t_other >= 0, ac[np.maximum(t_other, 0)], 1.0))
+        sigma = eta * sqrt((1 - alpha_bar_prev) / (1 - alpha_bar)) * sqrt(1 - alpha_bar / alpha_bar_prev)
+        row[:, 2] = sqrt(alpha_bar_prev)
+        row[:, 3] = sqrt(1 - alpha_bar_prev - sigma ** 2)
+        row[:, 4] = torch.from_numpy(t != 0).float() * sigma
+        return row
+
+    def _ddim_step(self, x, model_output, coefs_dev, noise, clip_denoised, want_pred=True):
+        """holo_ddim_step: (sample, pred_xstart | None).  ``coefs_dev`` is the (batch, 8) row block on the device."""
+        runtime.require_device(x, "ImplicitronGaussianDiffusion")
+        L = runtime.lib()
+        dev = x.device
+        x = x.contiguous()
+        model_output = model_output.contiguous()
+        noise = noise.contiguous() if noise is not None else None
+        sample = torch.empty_like(x)
+        pred = torch.empty_like(x) if want_pred else None
+        _lib.check(L, L.holo_ddim_step(runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x),
+                                       runtime.ptr(model_output), runtime.ptr(noise) if noise is not None else None,
+                                       1 if clip_denoised else 0, runtime.ptr(sample),
+                                       runtime.ptr(pred) if want_pred else None, runtime.stream_ptr(dev)), "holo_ddim_step")
+        return sample, pred
+
+    def _ddim_step_device_noise(self, x, model_output, coefs_dev, timestep_index: int, clip_denoised, want_pred=True,
+                                want_noise=False, channels_last: bool = False):
+        """holo_ddim_step_philox: (sample, pred_xstart | None, noise | None), the draw of ``_step_device_noise`` at the same
+        (seed, stream, timestep)."""
+        runtime.require_device(x, "ImplicitronGaussianDiffusion")
+        L = runtime.lib()
+        dev = x.device
+        x = x.contiguous()
+        model_output = model_output.contiguous()
+        sample = torch.empty_like(x)
+        pred = torch.empty_like(x) if want_pred else None
+        noise = torch.empty_like(x) if want_noise else None
+        offset = (int(self.device_noise_stream) << 32) | (int(timestep_index) & 0xFFFFFFFF)
+        _lib.check(L, L.holo_ddim_step_philox(
+            runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x), runtime.ptr(model_output),
+            int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, offset, 1 if clip_denoised else 0, runtime.ptr(sample),
+            runtime.ptr(pred) if want_pred else None, runtime.ptr(noise) if want_noise else None,
+            0 if (channels_last or x.dim() < 3 or x.shape[1] % 4) else int(x.shape[1]), runtime.stream_ptr(dev)),
+            "holo_ddim_step_philox")
+        return sample, pred, noise
+
+    @staticmethod
+    def _per_sample(v, t: torch.Tensor) -> np.ndarray:
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        return np.broadcast_to(np.asarray(v, dtype=np.int64), (t.shape[0],)).copy()
+
+    def _model_output(self, model, x, t, denoised_fn, model_kwargs):
+        model_output = model(x, t, **(model_kwargs or {}))
+        if denoised_fn is not None:
+            model_output = denoised_fn(model_output)
+        return model_output
+
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0,
+                    t_prev=None, noise_sampler=None):
+        """One DDIM step t -> t_prev (default t - 1; < 0: the end of the chain).  The noise: ``noise_sampler(t, shape,
+        device)``, else the in-kernel draw with ``device_noise_seed``, else ``torch.randn_like``; none is drawn when every
+        sample's sigma is 0 (eta = 0, or t = 0)."""
+        if cond_fn is not None:
+            raise NotImplementedError("cond_fn guidance is not used by HoloDiffusion and is not supported")
+        t = t.to(device=x.device, dtype=torch.int64).contiguous()
+        t_host = t.cpu().numpy()
+        t_prev = t_host - 1 if t_prev is None else self._per_sample(t_prev, t)
+        coefs = self.ddim_coefs(t_host, t_prev, eta)
+        model_output = self._model_output(model, x, t, denoised_fn, model_kwargs)
+        coefs_dev = coefs.to(x.device)
+        if noise_sampler is None and self.device_noise_seed is not None:
+            sample, pred, _ = self._ddim_step_device_noise(x, model_output, coefs_dev, int(t_host[0]), clip_denoised)
+            return {"sample": sample, "pred_xstart": pred}
+        noise = None
+        if bool((coefs[:, 4] != 0).any()):
+            noise = noise_sampler(int(t_host[0]), x.shape, x.device) if noise_sampler is not None else torch.randn_like(x)
+        sample, pred = self._ddim_step(x, model_output, coefs_dev, noise, clip_denoised)
+        return {"sample": sample, "pred_xstart": pred}
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0,
+                            t_next=None):
+        """One reverse-ODE step t -> t_next (default t + 1; >= T: abar_next = 0)."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        t = t.to(device=x.device, dtype=torch.int64).contiguous()
+        t_host = t.cpu().numpy()
+        t_next = t_host + 1 if t_next is None else self._per_sample(t_next, t)
+        coefs = self.ddim_coefs(t_host, t_next, reverse=True)
+        model_output = self._model_output(model, x, t, denoised_fn, model_kwargs)
+        sample, pred = self._ddim_step(x, model_output, coefs.to(x.device), None, clip_denoised)
+        return {"sample": sample, "pred_xstart": pred}
+
+    def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                     model_kwargs=None, device=None, progress=False, eta=0.0, ddim_steps=None,
+                                     timesteps=None, noise_sampler=None, _materialize_every_step: bool = True
+                                     ) -> Iterator[dict]:
+        """DDIM over ``ddim_schedule(ddim_steps, timesteps)``.  Noise and the perf mode as ``p_sample_loop_progressive``:
+        with ``device_noise_seed`` the chain runs channels-last through ``holo_ddim_step_philox``.  The coefficient rows of
+        the whole chain are built on the host and uploaded once."""
+        if cond_fn is not None:
+            raise NotImplementedError("cond_fn guidance is not supported")
+        if device is None:
+            device = next(model.parameters()).device
+        assert isinstance(shape, (tuple, list))
+        if model_kwargs is None:
+            model_kwargs = {}
+        if noise is not None:
+            img = noise
+        elif noise_sampler is not None:
+            img = noise_sampler(self.num_timesteps, shape, device)
+        else:
+            img = torch.randn(*shape, device=device)
+        indices = self.ddim_schedule(ddim_steps, timesteps)
+        B = shape[0]
+        rows = torch.stack([self.ddim_coefs([t] * B, [t_prev] * B, eta)
+                            for t, t_prev in zip(indices, indices[1:] + [-1])])  # (steps, B, 8)
+        noisy = (rows[:, :, 4] != 0).any(dim=1).tolist()
+        # the chain's timesteps and coefficient rows are uploaded once: no per-step host->device traffic
+        coefs_all = rows.to(device)
+        ts_all = torch.tensor(indices, dtype=torch.int64, device=device)[:, None].expand(-1, B).contiguous()
+        it = range(len(indices))
+        if progress:
+            try:
+                from tqdm.auto import tqdm
+                it = tqdm(it)
+            except Exception:
+                pass
+        use_cl = (self.device_noise_seed is not None and noise_sampler is None and denoised_fn is None and not model_kwargs
+                  and hasattr(model, "forward_channels_last")
+                  and getattr(model, "in_channels", None) == shape[1] and img.is_cuda)
+        if use_cl:
+            as_ncdhw = (lambda a: a.permute(0, 4, 1, 2, 3).contiguous()) if _materialize_every_step else \
+                (lambda a: a.permute(0, 4, 1, 2, 3))
+            with torch.no_grad():
+                img_cl = img.float().permute(0, 2, 3, 4, 1).contiguous()
+                for k in it:
+                    out_cl = model.forward_channels_last(img_cl, ts_all[k])
+                    sample_cl, pred_cl, _ = self._ddim_step_device_noise(img_cl, out_cl, coefs_all[k], indices[k],
+                                                                         clip_denoised, channels_last=True)
+                    yield {"sample": as_ncdhw(sample_cl), "pred_xstart": as_ncdhw(pred_cl)}
+                    img_cl = sample_cl
+            return
+        with torch.no_grad():
+            for k in it:
+                t = ts_all[k]
+                model_output = self._model_output(model, img, t, denoised_fn, model_kwargs)
+                if noise_sampler is None and self.device_noise_seed is not None:
+                    sample, pred, _ = self._ddim_step_device_noise(img, model_output, coefs_all[k], indices[k],
+                                                                   clip_denoised)
+                else:
+                    eps = None
+                    if noisy[k]:
+                        eps = noise_sampler(indices[k], img.shape, img.device) if noise_sampler is not None else \
+                            torch.randn_like(img)
+                    sample, pred = self._ddim_step(img, model_output, coefs_all[k], eps, clip_denoised)
+                yield {"sample": sample, "pred_xstart": pred}
+                img = sample
+
+    def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                         model_kwargs=None, device=None, progress=False, eta=0.0, ddim_steps=None, timesteps=None,
+                         noise_sampler=None):
+        final = None
+        for sample in self.ddim_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                        denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                                        model_kwargs=model_kwargs, device=device, progress=progress,
+                                                        eta=eta, ddim_steps=ddim_steps, timesteps=timesteps,
+                                                        noise_sampler=noise_sampler, _materialize_every_step=False):
+            final = sample["sample"]
+        if final is not None and not final.is_contiguous():
+            final = final.contiguous()  # (the channels-last perf chain: one conversion at the end of the chain)
+        return final
+
+    def ddim_reverse_sample_loop(self, model, x0, ddim_steps=None, timesteps=None, clip_denoised=True, denoised_fn=None,
+                                 model_kwargs=None) -> torch.Tensor:
+        """DDIM inversion (build-side extension): the reverse ODE from x0 over the schedule of ``ddim_sample_loop`` walked in
+        ascending order; each step goes to the next kept timestep, the last one to abar = 0.  Returns x_T."""
+        indices = self.ddim_schedule(ddim_steps, timesteps)[::-1]
+        B = x0.shape[0]
+        rows = torch.stack([self.ddim_coefs([t] * B, [t_next] * B, reverse=True)
+                            for t, t_next in zip(indices, indices[1:] + [self.num_timesteps])])
+        coefs_all = rows.to(x0.device)
+        ts_all = torch.tensor(indices, dtype=torch.int64, device=x0.device)[:, None].expand(-1, B).contiguous()
+        img = x0
+        with torch.no_grad():
+            for k in range(len(indices)):
+                model_output = self._model_output(model, img, ts_all[k], denoised_fn, model_kwargs)
+                img, _ = self._ddim_step(img, model_output, coefs_all[k], None, clip_denoised, want_pred=False)
+        return img
 
     def training_losses(self, *args, **kwargs):
         raise NotImplementedError("training losses are outside the sampling hot path (SURVEY.md §8f)")

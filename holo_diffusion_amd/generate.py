@@ -380,7 +380,8 @@ def generate_samples_from_experiment(exp_dir: str, output_directory: Optional[st
                                      camera_elevation: float = -30.0 * (2 * math.pi / 360),
                                      progressive_sampling_steps_per_render: int = -1, save_frames: bool = True,
                                      device: Optional[torch.device] = None, load_fn=None,
-                                     device_noise: bool = False) -> Dict[str, torch.Tensor]:
+                                     device_noise: bool = False,
+                                     sampler_kwargs: Optional[dict] = None) -> Dict[str, torch.Tensor]:
     """``generate_samples(exp_dir=...)`` of the reference script (generate_samples.py:37-138) on the HIP path:
     experiment directory -> model (``checkpoint.load_experiment``) -> sharded sampling + fly-around renders.
 
@@ -402,7 +403,7 @@ def generate_samples_from_experiment(exp_dir: str, output_directory: Optional[st
     out = generate_samples(model, num_samples=num_samples, n_eval_cameras=n_eval_cameras, seed=seed, up=up,
                            camera_elevation=camera_elevation,
                            progressive_sampling_steps_per_render=progressive_sampling_steps_per_render, device=device,
-                           device_noise=device_noise)
+                           sampler_kwargs=sampler_kwargs, device_noise=device_noise)
     if save_frames and rank == 0:
         from .flyaround_output import export_flyaround_frames
         os.makedirs(output_directory, exist_ok=True)
@@ -425,7 +426,21 @@ CLI_DEFAULTS = dict(exp_dir="", output_directory=None, render_size=None, video_s
                     n_eval_cameras=25 * 3, num_samples=2, seed=3, trajectory_scale=1.3, up=CANONICAL_CO3D_UP_AXIS,
                     camera_elevation=-30.0 * (2 * math.pi / 360), progressive_sampling_steps_per_render=-1,
                     save_voxel_features=True,
-                    device_noise=False)  # (build-side extension: in-kernel Philox noise per denoising step, generate_samples)
+                    device_noise=False,  # (build-side extension: in-kernel Philox noise per denoising step, generate_samples)
+                    sampler="ddpm", ddim_steps=None, ddim_eta=0.0)  # (build-side extension: DDIM sampling, cli_sampler_kwargs)
+
+
+def cli_sampler_kwargs(cfg: Dict[str, object]) -> Optional[dict]:
+    """``sampler`` / ``ddim_steps`` / ``ddim_eta`` of the command line as the ``sampler_kwargs`` of ``generate_samples``:
+    None for the default DDPM loop, ``{"sampler": "ddim", "ddim_steps": S, "eta": eta}`` for DDIM."""
+    if cfg["sampler"] == "ddpm":
+        if cfg["ddim_steps"] is not None or float(cfg["ddim_eta"]) != 0.0:
+            raise SystemExit("generate: ddim_steps / ddim_eta need sampler=ddim")
+        return None
+    if cfg["sampler"] != "ddim":
+        raise SystemExit(f"generate: sampler must be 'ddpm' or 'ddim', not '{cfg['sampler']}'")
+    steps = cfg["ddim_steps"]
+    return {"sampler": "ddim", "ddim_steps": None if steps is None else int(steps), "eta": float(cfg["ddim_eta"])}
 
 
 def parse_cli(argv: Sequence[str]) -> Dict[str, object]:
@@ -443,6 +458,7 @@ def parse_cli(argv: Sequence[str]) -> Dict[str, object]:
         cfg[k] = val
     if cfg["render_size"] is not None:
         cfg["render_size"] = tuple(int(x) for x in cfg["render_size"])
+    cli_sampler_kwargs(cfg)  # (rejects an unknown sampler or DDIM keys without sampler=ddim)
     return cfg
 
 
@@ -481,7 +497,7 @@ def main(argv: Optional[Sequence[str]] = None, load_fn=None) -> int:
                 n_eval_cameras=int(cfg["n_eval_cameras"]), num_samples=int(cfg["num_samples"]), seed=int(cfg["seed"]),
                 up=tuple(cfg["up"]), camera_elevation=float(cfg["camera_elevation"]),
                 progressive_sampling_steps_per_render=int(cfg["progressive_sampling_steps_per_render"]), device=device,
-                load_fn=load_fn, device_noise=bool(cfg["device_noise"]))
+                load_fn=load_fn, device_noise=bool(cfg["device_noise"]), sampler_kwargs=cli_sampler_kwargs(cfg))
         if rank == 0:
             img = out["images_render"]
             print(f"generate: {int(cfg['num_samples'])} samples x {int(cfg['n_eval_cameras'])} frames "

@@ -128,10 +128,23 @@ class HoloDiffusionModel(ImplicitronModelBase, torch.nn.Module):
     def _shape(self):
         return (1, self.feature_size, self.resol, self.resol, self.resol)
 
-    def sample_random_voxel_features_progressive(self, **loop_kwargs):
+    def _sampler_loop_kwargs(self, sampler: str, ddim_steps, timesteps, eta, loop_kwargs: dict) -> dict:
+        """The sampler choice (build-side extension): "ddpm" - the reference's ancestral loop, unchanged - or "ddim"
+        (``ddim_sample_loop``, with ``ddim_steps`` / ``timesteps`` / ``eta``)."""
+        if sampler == "ddim":
+            return dict(loop_kwargs, ddim_steps=ddim_steps, timesteps=timesteps, eta=eta)
+        if sampler != "ddpm":
+            raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
+        if ddim_steps is not None or timesteps is not None or eta != 0.0:
+            raise ValueError("ddim_steps / timesteps / eta apply to sampler='ddim' only")
+        return loop_kwargs
+
+    def sample_random_voxel_features_progressive(self, sampler: str = "ddpm", ddim_steps: Optional[int] = None,
+                                                 timesteps=None, eta: float = 0.0, **loop_kwargs):
         assert self.net_3d_enabled and self.diffusion_enabled
-        for sample in self.diffusion.p_sample_loop_progressive(model=self.net_3d, shape=self._shape(),
-                                                               clip_denoised=True, progress=False, **loop_kwargs):
+        loop_kwargs = self._sampler_loop_kwargs(sampler, ddim_steps, timesteps, eta, loop_kwargs)
+        loop = self.diffusion.ddim_sample_loop_progressive if sampler == "ddim" else self.diffusion.p_sample_loop_progressive
+        for sample in loop(model=self.net_3d, shape=self._shape(), clip_denoised=True, progress=False, **loop_kwargs):
             s = sample["sample"]
             out = torch.empty_like(s)
             L = runtime.lib()
@@ -139,11 +152,20 @@ class HoloDiffusionModel(ImplicitronModelBase, torch.nn.Module):
                                       runtime.stream_ptr(s.device)), "holo_clip")
             yield out
 
-    def sample_random_voxel_features(self, **loop_kwargs) -> torch.Tensor:
+    def sample_random_voxel_features(self, sampler: str = "ddpm", ddim_steps: Optional[int] = None, timesteps=None,
+                                     eta: float = 0.0, **loop_kwargs) -> torch.Tensor:
         assert self.net_3d_enabled and self.diffusion_enabled
         logger.info("generating random voxel features through denoising diffusion ...")
-        return self.diffusion.p_sample_loop(model=self.net_3d, shape=self._shape(), clip_denoised=True,
-                                            progress=loop_kwargs.pop("progress", False), **loop_kwargs)
+        loop_kwargs = self._sampler_loop_kwargs(sampler, ddim_steps, timesteps, eta, loop_kwargs)
+        loop = self.diffusion.ddim_sample_loop if sampler == "ddim" else self.diffusion.p_sample_loop
+        return loop(model=self.net_3d, shape=self._shape(), clip_denoised=True,
+                    progress=loop_kwargs.pop("progress", False), **loop_kwargs)
+
+    def invert_voxel_features(self, voxel_features: torch.Tensor, ddim_steps: Optional[int] = None) -> torch.Tensor:
+        """DDIM inversion (build-side extension): the x_T from which ``sample_random_voxel_features(sampler="ddim",
+        ddim_steps=...)`` regenerates ``voxel_features`` (e.g. a grid from the encoder path)."""
+        assert self.net_3d_enabled and self.diffusion_enabled
+        return self.diffusion.ddim_reverse_sample_loop(self.net_3d, voxel_features, ddim_steps=ddim_steps)
 
     # ---- render (holo_diffusion_model.py:201-540, evaluation branch) ------------------------
     def _weights_epoch(self):

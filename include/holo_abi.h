@@ -190,6 +190,28 @@ int holo_ddpm_step_philox(HoloCtx* ctx, const float* tables, int num_timesteps, 
                           uint64_t stream_offset, int clip_denoised, float* sample, float* pred_xstart, float* noise_out,
                           int ncdhw_channels, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DDIM step.  Replaces the elementwise tail of GaussianDiffusion.ddim_sample and ddim_reverse_sample:
+ *   gaussian_diffusion.py:677-693 (eps from pred_xstart, sigma, Equation 12, noise add) and :717-727 (reversed)
+ *   coefs    : (batch, 8) fp32 on the device, one row per sample, computed on the host in float32 in the reference's
+ *              order: {sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t], sqrt(abar_prev),
+ *              sqrt(1 - abar_prev - sigma^2), [t != 0] * sigma, 0, 0, 0}; the reverse step puts abar_next in place of
+ *              abar_prev and 0 in slot 4.  abar_prev / abar_next may come from any (strided) schedule.
+ *   pred = clip ? clamp(model_out, -1, 1) : model_out ;  eps = (c0*x_t - pred) / c1
+ *   sample = pred*c2 + c3*eps + c4*noise   (each operation rounded, no fma; noise read only if non-null and c4 != 0)
+ *   pred_xstart may be null (not written).
+ * ------------------------------------------------------------------------------------------ */
+int holo_ddim_step(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                   const float* model_out, const float* noise, int clip_denoised, float* sample, float* pred_xstart,
+                   void* stream);
+
+/* The same step with the noise drawn inside the kernel (gaussian_diffusion.py:685 `th.randn_like(x)`): exactly the draw of
+ * holo_ddpm_step_philox for the same (seed, stream_offset, sample, logical element), so a DDIM step at timestep t draws
+ * what a DDPM step at t would; ncdhw_channels as there.  pred_xstart and noise_out may be null (not written). */
+int holo_ddim_step_philox(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                          const float* model_out, uint64_t seed, uint64_t stream_offset, int clip_denoised, float* sample,
+                          float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
+
 /* Elementwise helpers on the path: torch.tanh (holo_diffusion_model.py:425) and
  * torch.clip(x,-1,1) (holo_diffusion_model.py:186). */
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream);
