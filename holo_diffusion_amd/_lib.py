@@ -90,6 +90,7 @@ SIGNATURES = {
     "holo_unet_param_info": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_int, _i64p, C.POINTER(C.c_int)]),
     "holo_unet_set_param": (C.c_int, [_vp, C.c_char_p, _vp, C.c_int, C.c_int, _i64p, _vp]),
     "holo_unet_set_compute_dtype": (C.c_int, [_vp, C.c_int]),
+    "holo_unet_set_batch_invariant": (C.c_int, [_vp, C.c_int]),
     "holo_unet_workspace_bytes": (C.c_size_t, [_vp, C.c_int]),
     "holo_unet_forward": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "holo_unet_forward_cl": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
@@ -110,6 +111,10 @@ SIGNATURES = {
     "holo_ddim_step": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "holo_ddim_step_philox": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int, _vp, _vp,
                                         _vp, C.c_int, _vp]),
+    "holo_ddpm_step_philox_rows": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_uint64, _vp, C.c_uint32,
+                                             C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    "holo_ddim_step_philox_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_int,
+                                             _vp, _vp, _vp, C.c_int, _vp]),
     "holo_tanh": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
     "holo_clip": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_float, C.c_int64, _vp]),
     "holo_renderer_create": (C.c_int, [_vp, C.POINTER(HoloRenderCfg), C.POINTER(_vp)]),

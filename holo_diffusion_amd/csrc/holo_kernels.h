@@ -135,7 +135,10 @@ int conv_wino3_launch(const ConvParams& p, void* stream);
 int conv_bf16p_launch(const ConvParams& p, void* stream);
 
 // Picks split-K so that the grid fills the chip; returns bytes of `partial` scratch needed (0 if none).
-size_t conv_plan(ConvParams& p, int num_cus);
+// plan_n > 0: every choice (kernel, tile depth, split-K) is made as for a launch of plan_n samples, and only the grid and the
+// scratch are sized for p.N - with plan_n = 1 each sample of a batch is computed as at batch 1 (the batch-invariant plan of
+// holo_unet_set_batch_invariant).  0: choices for p.N.
+size_t conv_plan(ConvParams& p, int num_cus, int plan_n = 0);
 int conv_launch(const ConvParams& p, void* stream);
 int conv_stats_slabs(const ConvParams& p);
 double conv_flops(const ConvParams& p);       // algorithmic (the reference's multiply-adds x 2)
@@ -236,6 +239,14 @@ int ddim_step_launch(const float* coefs, int batch, int64_t per, const float* x_
 int ddim_step_philox_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
                             uint64_t seed, uint64_t offset, int clip, float* sample, float* pred_xstart, float* noise_out,
                             int ncdhw_channels, void* stream);
+// the Philox steps with one stream per row (holo_ddpm_step_philox_rows / holo_ddim_step_philox_rows, include/holo_abi.h)
+int ddpm_step_philox_rows_launch(const float* tables, int T, const int64_t* timesteps, int batch, int64_t per,
+                                 const float* x_t, const float* model_out, uint64_t seed, const uint32_t* row_streams,
+                                 uint32_t timestep_index, int clip, float* sample, float* pred_xstart, float* noise_out,
+                                 int ncdhw_channels, void* stream);
+int ddim_step_philox_rows_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
+                                 uint64_t seed, const uint32_t* row_streams, uint32_t timestep_index, int clip,
+                                 float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
 int tanh_launch(const float* x, float* y, int64_t n, void* stream);
 // dst = src for a SMALL caller-provided tensor, read with system-scope loads (holo_ld_sys, holo_common.h)
 int copy_sys_launch(const float* src, float* dst, int64_t n, void* stream);

@@ -2621,7 +2621,7 @@ KSplit wino3_split(int64_t t3, int ncc, int num_cus) { return ksplit(t3 < num_cu
 
 }  // namespace
 
-size_t conv_plan(ConvParams& p, int num_cus) {
+size_t conv_plan(ConvParams& p, int num_cus, int plan_n) {
   const int Cin = p.C0 + p.C1;
   const int ncc = (Cin + BK - 1) / BK;
   const int nchunks = p.ksz * p.ksz * p.ksz * ncc;
@@ -2629,10 +2629,13 @@ size_t conv_plan(ConvParams& p, int num_cus) {
   const int ncc16 = (Cin + 15) / 16;                                    // the wide-tile kernels' 16-channel chunks
   const int nsk16 = p.skip_w ? (p.skip_C0 + p.skip_C1 + 15) / 16 : 0;
   const int64_t M = (int64_t)p.N * p.OD * p.OH * p.OW;
+  // the rows the choices are made for (plan_n samples); M (all samples) sizes the grids and the scratch.  (The addressing
+  // limits below stay on p.N: a batch past them takes another kernel - the batch-invariant planner checks for that.)
+  const int64_t Mc = (int64_t)(plan_n > 0 ? plan_n : p.N) * p.OD * p.OH * p.OW;
   const int bn = p.Cout >= 64 ? 64 : 32;
-  const int64_t tiles = cdiv(M, BM) * cdiv(p.Cout, bn);
-  const int64_t t8 = (M / 512) * cdiv(p.Cout, bn);  // wide-tile kernels: 8^3 tiles x Cout slices
-  const int64_t t3 = (M / 128) * (p.Cout / 64);     // F(2x2x2) form: 2 x 8 x 8 tiles x 64-Cout blocks
+  const int64_t tiles = cdiv(Mc, BM) * cdiv(p.Cout, bn);
+  const int64_t t8 = (Mc / 512) * cdiv(p.Cout, bn);  // wide-tile kernels: 8^3 tiles x Cout slices
+  const int64_t t3 = (Mc / 128) * (p.Cout / 64);     // F(2x2x2) form: 2 x 8 x 8 tiles x 64-Cout blocks
   const int64_t target = 2 * (int64_t)num_cus;
   const int64_t src_vox = (int64_t)p.ID * p.IH * p.IW;  // the halo kernel addresses a source sample with 32-bit byte offsets
   const int cmax = p.C0 > p.C1 ? p.C0 : p.C1;
@@ -2666,9 +2669,9 @@ size_t conv_plan(ConvParams& p, int num_cus) {
       // a 1x1x1 convolution of raw input over a LARGE grid (a ResBlock's skip_connection on the 64^3 level): the streaming
       // GEMM (HOLO_CONV1X1_STREAM_MIN_M=<rows>: development knob, default 131 072 rows; 0 = off)
       const int64_t min_m = env_int("HOLO_CONV1X1_STREAM_MIN_M", 131072);
-      if (min_m > 0 && M >= min_m && p.ksz == 1 && p.stride == 1 && !p.ups && !p.coef && !p.residual && !p.skip_w && p.bf16 == 0 &&
+      if (min_m > 0 && Mc >= min_m && p.ksz == 1 && p.stride == 1 && !p.ups && !p.coef && !p.residual && !p.skip_w && p.bf16 == 0 &&
           !p.in_bf16 && !p.out_bf16 && (p.Cout % 64) == 0 && (Cin % 32) == 0 && Cin >= 32 && Cin <= 256 &&
-          (!p.src1 || (p.C0 % 32) == 0) && (M % 16) == 0 && p.ID == p.OD && p.IH == p.OH && p.IW == p.OW)
+          (!p.src1 || (p.C0 % 32) == 0) && (Mc % 16) == 0 && p.ID == p.OD && p.IH == p.OH && p.IW == p.OW)
         return ConvKernel::Stream1x1;
       // an attention block's qkv / proj_out in exact fp32 (16^3, 8^3): one 16-row tile per workgroup, K split over its
       // waves (HOLO_CONV1X1_SMALL=0 keeps the row-tile kernel)
@@ -2678,7 +2681,7 @@ size_t conv_plan(ConvParams& p, int num_cus) {
       // kernel's split-K fills the chip better).  HOLO_CONV_S2T=0 keeps the row-tile kernel, =1 takes this one wherever it is
       // defined (tests)
       const int64_t s2t = env_int("HOLO_CONV_S2T", -1);
-      if (s2t != 0 && conv_s2_bf16_supported(p) && ((M / 128) * (p.Cout / 64) >= num_cus / 4 || s2t == 1))
+      if (s2t != 0 && conv_s2_bf16_supported(p) && ((Mc / 128) * (p.Cout / 64) >= num_cus / 4 || s2t == 1))
         return ConvKernel::S2Bf16;
       // 1x1x1, strided and deepest-level convs: row-tile kernel (also for the 32^3 stride-2 convolution with its 32 768 rows:
       // the per-tap gather kernel takes 118 us there, this one 95)
@@ -2740,7 +2743,7 @@ size_t conv_plan(ConvParams& p, int num_cus) {
       break;
     case ConvKernel::RowTile: {
       // (a fused 1x1x1 skip: its chunks follow the (tap, chunk) list; stride 1 and no upsampling there: conv_launch)
-      const int64_t t2 = cdiv(M, SM_ROWS) * cdiv(p.Cout, 64);
+      const int64_t t2 = cdiv(Mc, SM_ROWS) * cdiv(p.Cout, 64);
       const int64_t tgt = SM_SPLIT_WGS_PER_CU * (int64_t)num_cus;
       const int nall = nchunks + nsk;
       const int max_split = nall / SG > 1 ? nall / SG : 1;  // a split below one full staging group only adds a reduce launch
@@ -2767,7 +2770,8 @@ size_t conv_plan(ConvParams& p, int num_cus) {
     }
     case ConvKernel::Bf16Persistent: {  // no split-K: grid_x persistent workgroups, a multiple of 8 up to the CUs' multiple of 8
       const int64_t wcap = (num_cus & ~7) >= 8 ? (num_cus & ~7) : 8;
-      int64_t g = t8 < wcap ? ((t8 + 7) & ~(int64_t)7) : wcap;
+      const int64_t t8a = (M / 512) * cdiv(p.Cout, bn);  // (the tiles of all samples)
+      int64_t g = t8a < wcap ? ((t8a + 7) & ~(int64_t)7) : wcap;
       const int64_t max_wgs = env_int("HOLO_CONV_BF16P_WGS", 0);  // test knob: at most this many persistent workgroups
       if (max_wgs > 0 && max_wgs < g) g = max_wgs;
       p.tz = 8;
@@ -2779,7 +2783,7 @@ size_t conv_plan(ConvParams& p, int num_cus) {
     }
     case ConvKernel::Wino3: {
       const KSplit s = wino3_split(t3, ncc, num_cus);
-      const int64_t items = t3 * s.n;
+      const int64_t items = (M / 128) * (p.Cout / 64) * s.n;
       p.tz = 2;
       p.nsplit = s.n;
       p.chunks_per_split = s.cps;
@@ -2790,7 +2794,7 @@ size_t conv_plan(ConvParams& p, int num_cus) {
     }
     case ConvKernel::Halo:
     case ConvKernel::Wino2: {  // split over 32-channel chunks (each split walks all 27 taps)
-      const int64_t htiles = tz == 2 ? tiles : (M / 64) * cdiv(p.Cout, bn);
+      const int64_t htiles = tz == 2 ? tiles : (Mc / 64) * cdiv(p.Cout, bn);
       const KSplit s = ksplit(htiles < target ? cdiv(target, htiles) : 1, ncc, ncc);
       p.tz = tz;
       p.nsplit = s.n;

@@ -448,15 +448,20 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, fl
   z1 = r * sn;
 }
 
-template <bool NCDHW>
+// ROWS (holo_ddpm_step_philox_rows): row b draws what a batch-1 launch draws for stream row_streams[b] - counter slot 2 is 0
+// and the key's high word is seed_hi ^ row_streams[b] - so a chain's noise does not depend on the row it runs in.
+template <bool NCDHW, bool ROWS = false>
 __global__ __launch_bounds__(256) void ddpm_step_philox_kernel(const float* __restrict__ tables, int T,
                                                                const int64_t* __restrict__ timesteps, int64_t per,
                                                                const float* __restrict__ x_t,
                                                                const float* __restrict__ model_out, uint32_t seed_lo,
                                                                uint32_t seed_hi, uint32_t offset, int clip,
                                                                float* __restrict__ sample, float* __restrict__ pred,
-                                                               float* __restrict__ noise_out, int channels) {
+                                                               float* __restrict__ noise_out, int channels,
+                                                               const uint32_t* __restrict__ row_streams) {
   const int b = blockIdx.y;
+  const uint32_t slot = ROWS ? 0u : (uint32_t)b;
+  const uint32_t key_hi = ROWS ? seed_hi ^ holo_ld_sys(row_streams + b) : seed_hi;  // (a small table from the host)
   int64_t tt = holo_ld_sys(timesteps + b);
   if (tt < 0) tt = 0;
   if (tt >= T) tt = T - 1;
@@ -485,7 +490,7 @@ __global__ __launch_bounds__(256) void ddpm_step_philox_kernel(const float* __re
     m = *reinterpret_cast<const float4*>(model_out + o);
   }
   uint32_t rnd[4];
-  philox4x32_10((uint32_t)qd, (uint32_t)((uint64_t)qd >> 32), (uint32_t)b, offset, seed_lo, seed_hi, rnd);
+  philox4x32_10((uint32_t)qd, (uint32_t)((uint64_t)qd >> 32), slot, offset, seed_lo, key_hi, rnd);
   float4 e;
   box_muller(rnd[0], rnd[1], e.x, e.y);
   box_muller(rnd[2], rnd[3], e.z, e.w);
@@ -562,14 +567,15 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict_
 
 // The same update with the noise drawn in the kernel: the draw of ddpm_step_philox_kernel (same counter, key and logical
 // element numbering, NCDHW as there), so a DDIM step at timestep t draws the noise a DDPM step at t would.  Samples whose
-// c4 is 0 skip the draw unless noise_out asks for it.
-template <bool NCDHW>
+// c4 is 0 skip the draw unless noise_out asks for it.  ROWS: per-row streams, as ddpm_step_philox_kernel.
+template <bool NCDHW, bool ROWS = false>
 __global__ __launch_bounds__(256) void ddim_step_philox_kernel(const float* __restrict__ coefs, int64_t per,
                                                                const float* __restrict__ x_t,
                                                                const float* __restrict__ model_out, uint32_t seed_lo,
                                                                uint32_t seed_hi, uint32_t offset, int clip,
                                                                float* __restrict__ sample, float* __restrict__ pred,
-                                                               float* __restrict__ noise_out, int channels) {
+                                                               float* __restrict__ noise_out, int channels,
+                                                               const uint32_t* __restrict__ row_streams) {
   const int b = blockIdx.y;
   float c[5];
 #pragma unroll
@@ -597,8 +603,9 @@ __global__ __launch_bounds__(256) void ddim_step_philox_kernel(const float* __re
   float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
   const bool draw = c[4] != 0.f || noise_out;
   if (draw) {
+    const uint32_t key_hi = ROWS ? seed_hi ^ holo_ld_sys(row_streams + b) : seed_hi;
     uint32_t rnd[4];
-    philox4x32_10((uint32_t)qd, (uint32_t)((uint64_t)qd >> 32), (uint32_t)b, offset, seed_lo, seed_hi, rnd);
+    philox4x32_10((uint32_t)qd, (uint32_t)((uint64_t)qd >> 32), ROWS ? 0u : (uint32_t)b, offset, seed_lo, key_hi, rnd);
     box_muller(rnd[0], rnd[1], e.x, e.y);
     box_muller(rnd[2], rnd[3], e.z, e.w);
     if (c[4] != 0.f) s = add_noise4(s, c[4], e);
@@ -836,10 +843,33 @@ int ddpm_step_philox_launch(const float* tables, int T, const int64_t* timesteps
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);
   if (ncdhw_channels)
     HOLO_LAUNCH(ddpm_step_philox_kernel<true>, grid, dim3(256), stream, tables, T, timesteps, per, x_t, model_out, k0, k1,
-                (uint32_t)offset, clip, sample, pred_xstart, noise_out, ncdhw_channels);
+                (uint32_t)offset, clip, sample, pred_xstart, noise_out, ncdhw_channels, nullptr);
   else
     HOLO_LAUNCH(ddpm_step_philox_kernel<false>, grid, dim3(256), stream, tables, T, timesteps, per, x_t, model_out, k0, k1,
-                (uint32_t)offset, clip, sample, pred_xstart, noise_out, 0);
+                (uint32_t)offset, clip, sample, pred_xstart, noise_out, 0, nullptr);
+  return 0;
+}
+
+int ddpm_step_philox_rows_launch(const float* tables, int T, const int64_t* timesteps, int batch, int64_t per,
+                                 const float* x_t, const float* model_out, uint64_t seed, const uint32_t* row_streams,
+                                 uint32_t timestep_index, int clip, float* sample, float* pred_xstart, float* noise_out,
+                                 int ncdhw_channels, void* stream) {
+  if (per & 3) {
+    set_error("ddpm_step: elems_per_sample must be a multiple of 4");
+    return -1;
+  }
+  if (ncdhw_channels < 0 || (ncdhw_channels & 3) || (ncdhw_channels > 0 && per % ncdhw_channels)) {
+    set_error("ddpm_step_philox_rows: ncdhw_channels must be 0 (channels-last tensors) or a multiple of 4 that divides elems_per_sample");
+    return -1;
+  }
+  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);  // (the kernel folds each row's stream into k1)
+  if (ncdhw_channels)
+    HOLO_LAUNCH((ddpm_step_philox_kernel<true, true>), grid, dim3(256), stream, tables, T, timesteps, per, x_t, model_out, k0,
+                k1, timestep_index, clip, sample, pred_xstart, noise_out, ncdhw_channels, row_streams);
+  else
+    HOLO_LAUNCH((ddpm_step_philox_kernel<false, true>), grid, dim3(256), stream, tables, T, timesteps, per, x_t, model_out, k0,
+                k1, timestep_index, clip, sample, pred_xstart, noise_out, 0, row_streams);
   return 0;
 }
 
@@ -869,10 +899,32 @@ int ddim_step_philox_launch(const float* coefs, int batch, int64_t per, const fl
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);  // (as ddpm_step_philox)
   if (ncdhw_channels)
     HOLO_LAUNCH(ddim_step_philox_kernel<true>, grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
-                (uint32_t)offset, clip, sample, pred_xstart, noise_out, ncdhw_channels);
+                (uint32_t)offset, clip, sample, pred_xstart, noise_out, ncdhw_channels, nullptr);
   else
     HOLO_LAUNCH(ddim_step_philox_kernel<false>, grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
-                (uint32_t)offset, clip, sample, pred_xstart, noise_out, 0);
+                (uint32_t)offset, clip, sample, pred_xstart, noise_out, 0, nullptr);
+  return 0;
+}
+
+int ddim_step_philox_rows_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
+                                 uint64_t seed, const uint32_t* row_streams, uint32_t timestep_index, int clip,
+                                 float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
+  if (per & 3) {
+    set_error("ddim_step: elems_per_sample must be a multiple of 4");
+    return -1;
+  }
+  if (ncdhw_channels < 0 || (ncdhw_channels & 3) || (ncdhw_channels > 0 && per % ncdhw_channels)) {
+    set_error("ddim_step_philox_rows: ncdhw_channels must be 0 (channels-last tensors) or a multiple of 4 that divides elems_per_sample");
+    return -1;
+  }
+  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);  // (as ddpm_step_philox_rows)
+  if (ncdhw_channels)
+    HOLO_LAUNCH((ddim_step_philox_kernel<true, true>), grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
+                timestep_index, clip, sample, pred_xstart, noise_out, ncdhw_channels, row_streams);
+  else
+    HOLO_LAUNCH((ddim_step_philox_kernel<false, true>), grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
+                timestep_index, clip, sample, pred_xstart, noise_out, 0, row_streams);
   return 0;
 }
 

@@ -186,6 +186,9 @@ struct HoloUnet {
   // accumulation in the 3x3x3 convolutions and the long-sequence attention, fp32 GroupNorm statistics; 2 bf16x3 split
   // (fp32 storage, fp32-accurate)
   int compute_mode = 0;
+  // holo_unet_set_batch_invariant: the forward plan makes every geometry choice for ONE sample and launches it over the
+  // batch, so row b of a batched forward is bit-identical to the batch-1 forward of that row (exact-fp32 mode only)
+  bool batch_invariant = false;
   // concatenated emb_layers
   int emb_rows = 0;
   std::map<std::string, int> emb_row_off;  // resblock prefix -> first row
@@ -198,7 +201,7 @@ struct HoloUnet {
   std::vector<Op> ops;
   size_t ws_need = 0;
   std::map<std::string, Act> block_outputs;
-  std::map<int, size_t> ws_cache;
+  std::map<std::pair<int, bool>, size_t> ws_cache;  // (batch, batch_invariant) -> workspace bytes
   // ---- training (holo_unet_backward): weights of the transposed convolutions, packed like the forward ones
   // ([Cin][Cout] flipped taps for the stride-1 convs; [tap][Cout][Cin] for the stride-2 Downsample convs), supplied by
   // holo_unet_set_dgrad_weight; the training plan (forward with every intermediate kept + backward op list)
@@ -385,6 +388,7 @@ struct Planner {
   std::vector<Op>& ops;
   std::vector<Tape>* tape = nullptr;  // training forward: every layer is recorded, nothing is released
   size_t last_mom = 0;                // moments buffer of the last emit_finalize (training)
+  std::string err;                    // a batch-invariant plan that cannot be kept (ensure_plan reports it)
 
   Planner(HoloUnet* u_, int N_, void* ws, std::vector<Op>& ops_) : u(u_), N(N_), base((char*)ws), ops(ops_) {
     // generous fixed regions for the small buffers
@@ -401,6 +405,8 @@ struct Planner {
   }
   int64_t vox(int R) const { return (int64_t)R * R * R; }
   bool bfs() const { return u->compute_mode == 1; }  // bf16 storage of the activations
+  // the sample count the geometry choices are made for: one in a batch-invariant forward (the training plan keeps its own)
+  int plan_n() const { return u->batch_invariant && !tape ? 1 : N; }
 
   Act new_act(int C, int R, bool f32 = false) {
     Act a;
@@ -538,7 +544,18 @@ struct Planner {
       p.skip_CinP = pad_cin(p.skip_C0 + p.skip_C1);
       p.skip_bias = skip_bias;
     }
-    size_t sb = conv_plan(p, u->ctx->num_cus);
+    ConvParams one = p;
+    size_t sb = conv_plan(p, u->ctx->num_cus, plan_n());
+    if (plan_n() != N) {  // the batch-invariant plan: the launch must compute each sample as the batch-1 launch does
+      one.N = 1;
+      conv_plan(one, u->ctx->num_cus);
+      if (err.empty() && (one.kernel != p.kernel || one.tz != p.tz || one.nsplit != p.nsplit ||
+                          one.chunks_per_split != p.chunks_per_split || one.skip_chunks_per_split != p.skip_chunks_per_split))
+        err = "batch-invariant plan: at batch " + std::to_string(N) + " the " + std::to_string(p.C0 + p.C1) + " -> " +
+              std::to_string(p.Cout) + " convolution at " + std::to_string(p.OD) + "^3 cannot keep its batch-1 choice (kernel " +
+              std::to_string((int)one.kernel) + ", split-K " + std::to_string(one.nsplit) + " -> kernel " +
+              std::to_string((int)p.kernel) + ", split-K " + std::to_string(p.nsplit) + "; an addressing limit of the batch)";
+    }
     size_t so = 0;
     if (sb) {
       so = scratch_alloc(sb);
@@ -687,7 +704,7 @@ struct Planner {
         }
       } else {
         // exact fp32: the key range split across workgroups where one per query tile leaves CUs empty
-        fop.attn.nsplit = flash_attn_splits(N, (int)T, H, u->ctx->num_cus);
+        fop.attn.nsplit = flash_attn_splits(plan_n(), (int)T, H, u->ctx->num_cus);
         split_bytes = flash_attn_workspace_bytes(fop.attn);
         if (split_bytes) {
           split_work = scratch_alloc(split_bytes);
@@ -1379,8 +1396,17 @@ int ensure_plan(HoloUnet* u, int batch, void* ws) {
       set_error("holo_unet_forward: parameter '%s' has not been set", s.name.c_str());
       return HOLO_E_STATE;
     }
+  if (u->batch_invariant && u->compute_mode != 0) {  // (both setters refuse this; a guard for the plan itself)
+    set_error("holo_unet_forward: the batch-invariant plan is exact-fp32 only");
+    return HOLO_E_UNSUPPORTED;
+  }
   Planner pl(u, batch, ws, u->ops);
   pl.build();
+  if (!pl.err.empty()) {
+    u->ops.clear();
+    set_error("holo_unet_forward: %s", pl.err.c_str());
+    return HOLO_E_UNSUPPORTED;
+  }
   if (!pl.regions_ok()) {
     set_error("internal: small-buffer regions overflow");
     return HOLO_E_INVALID;
@@ -1675,6 +1701,11 @@ int holo_unet_set_compute_dtype(HoloUnet* net, int dtype) {
     return HOLO_E_INVALID;
   }
   const int mode = dtype == HOLO_DTYPE_BF16 ? 1 : dtype == HOLO_DTYPE_F32_BF16X3 ? 2 : 0;
+  if (mode != 0 && net->batch_invariant) {
+    set_error("holo_unet_set_compute_dtype: the batch-invariant plan is exact-fp32 only; turn it off first "
+              "(holo_unet_set_batch_invariant(net, 0))");
+    return HOLO_E_UNSUPPORTED;
+  }
   if (mode != net->compute_mode) {
     net->compute_mode = mode;
     net->plan_batch = -1;   // re-plan: the conv ops carry the choice
@@ -1683,15 +1714,37 @@ int holo_unet_set_compute_dtype(HoloUnet* net, int dtype) {
   return 0;
 }
 
+int holo_unet_set_batch_invariant(HoloUnet* net, int on) {
+  if (!net) {
+    set_error("holo_unet_set_batch_invariant: null net");
+    return HOLO_E_INVALID;
+  }
+  // Exact fp32 only.  The bf16 modes are refused rather than half supported: their plans pick kernels (the persistent
+  // bf16 convolution, the streaming bf16 1x1x1 GEMMs, the packed bf16 attention) whose geometry helpers size their
+  // work per launch, and no test pins the rows of those modes.
+  if (on && net->compute_mode != 0) {
+    set_error("holo_unet_set_batch_invariant: batch-invariant plans are exact-fp32 only (compute dtype HOLO_DTYPE_F32); "
+              "the bf16 and bf16x3 modes are not supported");
+    return HOLO_E_UNSUPPORTED;
+  }
+  if ((on != 0) != net->batch_invariant) {
+    net->batch_invariant = on != 0;
+    net->plan_batch = -1;  // re-plan: the conv ops carry the choices (ws_cache is keyed on the flag)
+    net->ops.clear();
+  }
+  return 0;
+}
+
 size_t holo_unet_workspace_bytes(HoloUnet* net, int batch) {
   if (!net || batch < 1) return 0;
-  auto it = net->ws_cache.find(batch);
+  const std::pair<int, bool> key(batch, net->batch_invariant);
+  auto it = net->ws_cache.find(key);
   if (it != net->ws_cache.end()) return it->second;
   std::vector<Op> tmp;
   Planner pl(net, batch, nullptr, tmp);
   pl.build();
   size_t b = pl.total_bytes();
-  net->ws_cache[batch] = b;
+  net->ws_cache[key] = b;
   // the sizing pass overwrote block_outputs with null-based offsets; force a re-plan
   net->plan_batch = -1;
   net->ops.clear();
@@ -2145,6 +2198,21 @@ int holo_ddpm_step_philox(HoloCtx* ctx, const float* tables, int num_timesteps, 
   return rc ? HOLO_E_INVALID : 0;
 }
 
+int holo_ddpm_step_philox_rows(HoloCtx* ctx, const float* tables, int num_timesteps, const int64_t* timesteps, int batch,
+                               int64_t elems_per_sample, const float* x_t, const float* model_out, uint64_t seed,
+                               const uint32_t* row_streams, uint32_t timestep_index, int clip_denoised, float* sample,
+                               float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
+  if (!tables || !timesteps || !x_t || !model_out || !row_streams || !sample || batch < 1) {
+    set_error("holo_ddpm_step_philox_rows: null/invalid argument");
+    return HOLO_E_INVALID;
+  }
+  (void)ctx;
+  int rc = ddpm_step_philox_rows_launch(tables, num_timesteps, timesteps, batch, elems_per_sample, x_t, model_out, seed,
+                                        row_streams, timestep_index, clip_denoised, sample, pred_xstart, noise_out,
+                                        ncdhw_channels, stream);
+  return rc ? HOLO_E_INVALID : 0;
+}
+
 // gaussian_diffusion.py:645-727 (ddim_sample / ddim_reverse_sample, the elementwise tail)
 int holo_ddim_step(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
                    const float* model_out, const float* noise, int clip_denoised, float* sample, float* pred_xstart,
@@ -2170,6 +2238,20 @@ int holo_ddim_step_philox(HoloCtx* ctx, const float* coefs, int batch, int64_t e
   (void)ctx;
   int rc = ddim_step_philox_launch(coefs, batch, elems_per_sample, x_t, model_out, seed, stream_offset, clip_denoised,
                                    sample, pred_xstart, noise_out, ncdhw_channels, stream);
+  return rc ? HOLO_E_INVALID : 0;
+}
+
+int holo_ddim_step_philox_rows(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                               const float* model_out, uint64_t seed, const uint32_t* row_streams, uint32_t timestep_index,
+                               int clip_denoised, float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels,
+                               void* stream) {
+  if (!coefs || !x_t || !model_out || !row_streams || !sample || batch < 1 || elems_per_sample < 4) {
+    set_error("holo_ddim_step_philox_rows: null/invalid argument");
+    return HOLO_E_INVALID;
+  }
+  (void)ctx;
+  int rc = ddim_step_philox_rows_launch(coefs, batch, elems_per_sample, x_t, model_out, seed, row_streams, timestep_index,
+                                        clip_denoised, sample, pred_xstart, noise_out, ncdhw_channels, stream);
   return rc ? HOLO_E_INVALID : 0;
 }
 

@@ -88,7 +88,9 @@ class ImplicitronGaussianDiffusion(Configurable):
     # ``p_sample_loop*`` draw the noise inside the step kernel (``holo_ddpm_step_philox``: Philox4x32-10 keyed on this
     # seed, counter = (element, sample, timestep); no randn launch, the noise never crosses HBM).  Statistically
     # equivalent to, not bit-equal with, torch's generator; the initial x_T still comes from torch.  ``device_noise_stream``
-    # separates chains that share a seed (generate.py passes the sample index).
+    # separates chains that share a seed (generate.py passes the sample index).  A sequence of ints: one stream per batch
+    # row (batched chains, ``holo_*_step_philox_rows``) - row b draws what a batch-1 chain of stream ``device_noise_stream[b]``
+    # draws, whatever batch and row it runs in.
     device_noise_seed: Optional[int] = None
     device_noise_stream: int = 0
 
@@ -171,6 +173,25 @@ class ImplicitronGaussianDiffusion(Configurable):
                                        runtime.ptr(pred), runtime.stream_ptr(dev)), "holo_ddpm_step")
         return sample, pred
 
+    def _row_streams(self, batch: int, device: torch.device) -> Optional[torch.Tensor]:
+        """``device_noise_stream`` as a (batch,) uint32 table on ``device`` (held as int32) when it is a sequence - the per-row
+        streams of the ``_rows`` step kernels, uploaded once per (streams, device) -, None for a plain int."""
+        s = self.device_noise_stream
+        if isinstance(s, (int, np.integer)):
+            return None
+        ids = tuple(int(v) for v in s)
+        if len(ids) != batch:
+            raise ValueError(f"device_noise_stream has {len(ids)} streams for a batch of {batch}")
+        if any(v < 0 or v > 0xFFFFFFFF for v in ids):
+            raise ValueError(f"device_noise_stream: stream ids must be in [0, 2^32): {ids}")
+        key = (ids, str(device))
+        cache = self.__dict__.setdefault("_row_stream_tables", {})
+        t = cache.get(key)
+        if t is None:
+            cache.clear()
+            t = cache[key] = torch.from_numpy(np.asarray(ids, dtype=np.uint32).view(np.int32)).to(device)
+        return t
+
     def _step_device_noise(self, x, t, model_output, timestep_index: int, clip_denoised, want_pred=True, want_noise=False,
                            channels_last: bool = False):
         """The step with in-kernel Philox noise (perf mode): (sample, pred_xstart | None, noise | None).  A draw is keyed on the
@@ -185,15 +206,23 @@ class ImplicitronGaussianDiffusion(Configurable):
         sample = torch.empty_like(x)
         pred = torch.empty_like(x) if want_pred else None
         noise = torch.empty_like(x) if want_noise else None
+        ncdhw = 0 if (channels_last or x.dim() < 3 or x.shape[1] % 4) else int(x.shape[1])
+        rows = self._row_streams(x.shape[0], dev)
+        if rows is not None:  # one stream per row: each row draws its batch-1 chain's noise
+            _lib.check(L, L.holo_ddpm_step_philox_rows(
+                runtime.ctx(dev), runtime.ptr(self._tables_on(dev)), self.num_timesteps, runtime.ptr(t), x.shape[0],
+                x[0].numel(), runtime.ptr(x), runtime.ptr(model_output), int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF,
+                runtime.ptr(rows), int(timestep_index) & 0xFFFFFFFF, 1 if clip_denoised else 0, runtime.ptr(sample),
+                runtime.ptr(pred) if want_pred else None, runtime.ptr(noise) if want_noise else None, ncdhw,
+                runtime.stream_ptr(dev)), "holo_ddpm_step_philox_rows")
+            return sample, pred, noise
         # stream offset: (chain id, timestep) - distinct for every step of every chain that shares the seed
         offset = (int(self.device_noise_stream) << 32) | (int(timestep_index) & 0xFFFFFFFF)
         _lib.check(L, L.holo_ddpm_step_philox(
             runtime.ctx(dev), runtime.ptr(self._tables_on(dev)), self.num_timesteps, runtime.ptr(t), x.shape[0], x[0].numel(),
             runtime.ptr(x), runtime.ptr(model_output), int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, offset,
             1 if clip_denoised else 0, runtime.ptr(sample), runtime.ptr(pred) if want_pred else None,
-            runtime.ptr(noise) if want_noise else None,
-            0 if (channels_last or x.dim() < 3 or x.shape[1] % 4) else int(x.shape[1]), runtime.stream_ptr(dev)),
-            "holo_ddpm_step_philox")
+            runtime.ptr(noise) if want_noise else None, ncdhw, runtime.stream_ptr(dev)), "holo_ddpm_step_philox")
         return sample, pred, noise
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
@@ -399,13 +428,21 @@ class ImplicitronGaussianDiffusion(Configurable):
         sample = torch.empty_like(x)
         pred = torch.empty_like(x) if want_pred else None
         noise = torch.empty_like(x) if want_noise else None
+        ncdhw = 0 if (channels_last or x.dim() < 3 or x.shape[1] % 4) else int(x.shape[1])
+        rows = self._row_streams(x.shape[0], dev)
+        if rows is not None:
+            _lib.check(L, L.holo_ddim_step_philox_rows(
+                runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x), runtime.ptr(model_output),
+                int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, runtime.ptr(rows), int(timestep_index) & 0xFFFFFFFF,
+                1 if clip_denoised else 0, runtime.ptr(sample), runtime.ptr(pred) if want_pred else None,
+                runtime.ptr(noise) if want_noise else None, ncdhw, runtime.stream_ptr(dev)), "holo_ddim_step_philox_rows")
+            return sample, pred, noise
         offset = (int(self.device_noise_stream) << 32) | (int(timestep_index) & 0xFFFFFFFF)
         _lib.check(L, L.holo_ddim_step_philox(
             runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x), runtime.ptr(model_output),
             int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, offset, 1 if clip_denoised else 0, runtime.ptr(sample),
-            runtime.ptr(pred) if want_pred else None, runtime.ptr(noise) if want_noise else None,
-            0 if (channels_last or x.dim() < 3 or x.shape[1] % 4) else int(x.shape[1]), runtime.stream_ptr(dev)),
-            "holo_ddim_step_philox")
+            runtime.ptr(pred) if want_pred else None, runtime.ptr(noise) if want_noise else None, ncdhw,
+            runtime.stream_ptr(dev)), "holo_ddim_step_philox")
         return sample, pred, noise
 
     @staticmethod

@@ -32,6 +32,15 @@ def shard_indices(num_items: int, rank: int, world_size: int) -> List[int]:
     return list(range(rank, num_items, world_size))
 
 
+def chain_groups(indices: Sequence[int], chains_per_gpu: int) -> List[List[int]]:
+    """A rank's samples in groups of ``chains_per_gpu`` chains sampled together (the last group may be shorter)."""
+    B = int(chains_per_gpu)
+    if B < 1:
+        raise ValueError(f"chains_per_gpu must be >= 1, got {chains_per_gpu}")
+    idx = list(indices)
+    return [idx[k:k + B] for k in range(0, len(idx), B)]
+
+
 def dist_info() -> Tuple[int, int]:
     if dist.is_available() and dist.is_initialized():
         return dist.get_rank(), dist.get_world_size()
@@ -333,11 +342,25 @@ def generate_samples(model, num_samples: int = 2, n_eval_cameras: int = 25 * 3, 
                      camera_elevation: float = -30.0 * (2 * math.pi / 360),
                      progressive_sampling_steps_per_render: int = -1, device: Optional[torch.device] = None,
                      gather: bool = True, sampler_kwargs: Optional[dict] = None,
-                     device_noise: bool = False) -> Dict[str, torch.Tensor]:
+                     device_noise: bool = False, chains_per_gpu: int = 1) -> Dict[str, torch.Tensor]:
     """Sharded counterpart of generate_samples.py:105-138.  Every rank renders its own samples; with
     ``gather`` all ranks end up with the frames of all samples.  ``device_noise`` (build-side extension, default off): the
     per-step noise of every chain is drawn inside the step kernel (``ImplicitronGaussianDiffusion.device_noise_seed`` =
-    ``seed``, stream = sample index) instead of by ``torch.randn_like``; x_T still comes from the per-sample torch seed."""
+    ``seed``, stream = sample index) instead of by ``torch.randn_like``; x_T still comes from the per-sample torch seed.
+
+    ``chains_per_gpu`` (build-side extension, default 1): a rank samples its chains in groups of this many, one UNet call
+    per step for the group, with the denoiser in batch-invariant mode (``SimpleUnet3D.set_batch_invariant``).  Sample ``i``
+    stays the sample of ``seed + i`` whatever the group size: its x_T and, in the torch-noise mode, its step noise come from
+    its own generator seeded ``seed + i``; with ``device_noise`` its rows draw Philox stream ``i``.  Not with progressive
+    rendering."""
+    if chains_per_gpu > 1 and progressive_sampling_steps_per_render > 0:
+        raise ValueError("generate_samples: chains_per_gpu > 1 needs progressive_sampling_steps_per_render <= 0 "
+                         "(a progressive fly-around renders one chain while it is being sampled)")
+    chains_per_gpu = int(chains_per_gpu)
+    if chains_per_gpu < 1:
+        raise ValueError(f"generate_samples: chains_per_gpu must be >= 1, got {chains_per_gpu}")
+    if chains_per_gpu > 1 and not hasattr(getattr(model, "net_3d", None), "set_batch_invariant"):
+        raise ValueError("generate_samples: chains_per_gpu > 1 needs a denoiser with batch-invariant plans (SimpleUnet3D)")
     rank, world = dist_info()
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -350,20 +373,36 @@ def generate_samples(model, num_samples: int = 2, n_eval_cameras: int = 25 * 3, 
     perf_noise = device_noise and diffusion is not None and hasattr(diffusion, "device_noise_seed")
     # (the caller's sampler settings come back whatever happens: a later p_sample on this model must not silently stay in
     # the Philox mode with the last sample's stream)
-    saved = (diffusion.device_noise_seed, diffusion.device_noise_stream) if perf_noise else None
+    keep = perf_noise or (chains_per_gpu > 1 and hasattr(diffusion, "device_noise_seed"))
+    saved = (diffusion.device_noise_seed, diffusion.device_noise_stream) if keep else None
+    net = getattr(model, "net_3d", None)
+    saved_inv = net.batch_invariant if chains_per_gpu > 1 else None
     try:
-        for i in mine:
-            torch.manual_seed(seed + i)  # per-sample seed
-            if perf_noise:
-                diffusion.device_noise_seed, diffusion.device_noise_stream = int(seed), int(i)
-            out = render_flyaround(model, n_flyaround_poses=n_eval_cameras, up=up, camera_elevation=camera_elevation,
-                                   device=device,
-                                   progressive_sampling_steps_per_render=progressive_sampling_steps_per_render,
-                                   sampler_kwargs=sampler_kwargs)
-            local_img[i], local_dep[i], local_msk[i] = out["images_render"], out["depths_render"], out["masks_render"]
+        if chains_per_gpu == 1:
+            for i in mine:
+                torch.manual_seed(seed + i)  # per-sample seed
+                if perf_noise:
+                    diffusion.device_noise_seed, diffusion.device_noise_stream = int(seed), int(i)
+                out = render_flyaround(model, n_flyaround_poses=n_eval_cameras, up=up, camera_elevation=camera_elevation,
+                                       device=device,
+                                       progressive_sampling_steps_per_render=progressive_sampling_steps_per_render,
+                                       sampler_kwargs=sampler_kwargs)
+                local_img[i], local_dep[i], local_msk[i] = out["images_render"], out["depths_render"], out["masks_render"]
+        else:
+            net.set_batch_invariant(True)  # row b of every UNet call = the batch-1 call of its chain
+            groups = chain_groups(mine, chains_per_gpu)
+            for group in groups:
+                vf = _sample_chain_group(model, group, seed, device, perf_noise, sampler_kwargs)
+                for b, i in enumerate(group):
+                    out = render_flyaround(model, n_flyaround_poses=n_eval_cameras, up=up,
+                                           camera_elevation=camera_elevation, device=device,
+                                           voxel_features=vf[b:b + 1])
+                    local_img[i], local_dep[i], local_msk[i] = out["images_render"], out["depths_render"], out["masks_render"]
     finally:
-        if perf_noise:
+        if saved is not None:
             diffusion.device_noise_seed, diffusion.device_noise_stream = saved
+        if saved_inv is not None:
+            net.set_batch_invariant(saved_inv)
     if not gather:
         return {"images_render": local_img, "depths_render": local_dep, "masks_render": local_msk}
     return {
@@ -371,6 +410,26 @@ def generate_samples(model, num_samples: int = 2, n_eval_cameras: int = 25 * 3, 
         "depths_render": gather_frames(local_dep, num_samples, (n_eval_cameras, 1, H, W), device),
         "masks_render": gather_frames(local_msk, num_samples, (n_eval_cameras, 1, H, W), device),
     }
+
+
+def _sample_chain_group(model, group: Sequence[int], seed: int, device: torch.device, perf_noise: bool,
+                        sampler_kwargs: Optional[dict]) -> torch.Tensor:
+    """The chains ``group`` (sample indices) in one batched sampling loop: (len(group), C, R, R, R), row b bit-equal to the
+    batch-1 chain of sample ``group[b]`` (see ``generate_samples``)."""
+    gens = [torch.Generator(device=device).manual_seed(seed + i) for i in group]  # = torch.manual_seed(seed + i) per chain
+    row_shape = model._shape(1)
+    x_T = torch.cat([torch.randn(row_shape, generator=g, device=device) for g in gens])
+    kwargs = dict(sampler_kwargs or {})
+    diffusion = model.diffusion
+    if perf_noise:
+        diffusion.device_noise_seed, diffusion.device_noise_stream = int(seed), [int(i) for i in group]
+    elif getattr(diffusion, "device_noise_seed", None) is not None:  # the caller's own Philox stream, in every chain
+        diffusion.device_noise_stream = [int(diffusion.device_noise_stream)] * len(group)
+    else:
+        # each row's step noise from its chain's generator: the randn_like sequence of the batch-1 chain
+        kwargs["noise_sampler"] = lambda t, shape, dev: torch.cat(
+            [torch.randn((1,) + tuple(shape[1:]), generator=g, device=dev) for g in gens])
+    return model.sample_random_voxel_features(batch_size=len(group), noise=x_T, **kwargs)
 
 
 def generate_samples_from_experiment(exp_dir: str, output_directory: Optional[str] = None,
@@ -381,7 +440,8 @@ def generate_samples_from_experiment(exp_dir: str, output_directory: Optional[st
                                      progressive_sampling_steps_per_render: int = -1, save_frames: bool = True,
                                      device: Optional[torch.device] = None, load_fn=None,
                                      device_noise: bool = False,
-                                     sampler_kwargs: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+                                     sampler_kwargs: Optional[dict] = None,
+                                     chains_per_gpu: int = 1) -> Dict[str, torch.Tensor]:
     """``generate_samples(exp_dir=...)`` of the reference script (generate_samples.py:37-138) on the HIP path:
     experiment directory -> model (``checkpoint.load_experiment``) -> sharded sampling + fly-around renders.
 
@@ -403,7 +463,7 @@ def generate_samples_from_experiment(exp_dir: str, output_directory: Optional[st
     out = generate_samples(model, num_samples=num_samples, n_eval_cameras=n_eval_cameras, seed=seed, up=up,
                            camera_elevation=camera_elevation,
                            progressive_sampling_steps_per_render=progressive_sampling_steps_per_render, device=device,
-                           sampler_kwargs=sampler_kwargs, device_noise=device_noise)
+                           sampler_kwargs=sampler_kwargs, device_noise=device_noise, chains_per_gpu=chains_per_gpu)
     if save_frames and rank == 0:
         from .flyaround_output import export_flyaround_frames
         os.makedirs(output_directory, exist_ok=True)
@@ -427,7 +487,8 @@ CLI_DEFAULTS = dict(exp_dir="", output_directory=None, render_size=None, video_s
                     camera_elevation=-30.0 * (2 * math.pi / 360), progressive_sampling_steps_per_render=-1,
                     save_voxel_features=True,
                     device_noise=False,  # (build-side extension: in-kernel Philox noise per denoising step, generate_samples)
-                    sampler="ddpm", ddim_steps=None, ddim_eta=0.0)  # (build-side extension: DDIM sampling, cli_sampler_kwargs)
+                    sampler="ddpm", ddim_steps=None, ddim_eta=0.0,  # (build-side extension: DDIM sampling, cli_sampler_kwargs)
+                    chains_per_gpu=1)  # (build-side extension: chains sampled together per UNet call, generate_samples)
 
 
 def cli_sampler_kwargs(cfg: Dict[str, object]) -> Optional[dict]:
@@ -459,6 +520,9 @@ def parse_cli(argv: Sequence[str]) -> Dict[str, object]:
     if cfg["render_size"] is not None:
         cfg["render_size"] = tuple(int(x) for x in cfg["render_size"])
     cli_sampler_kwargs(cfg)  # (rejects an unknown sampler or DDIM keys without sampler=ddim)
+    B = cfg["chains_per_gpu"]
+    if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+        raise SystemExit(f"generate: chains_per_gpu must be an integer >= 1, not {B!r}")
     return cfg
 
 
@@ -497,7 +561,8 @@ def main(argv: Optional[Sequence[str]] = None, load_fn=None) -> int:
                 n_eval_cameras=int(cfg["n_eval_cameras"]), num_samples=int(cfg["num_samples"]), seed=int(cfg["seed"]),
                 up=tuple(cfg["up"]), camera_elevation=float(cfg["camera_elevation"]),
                 progressive_sampling_steps_per_render=int(cfg["progressive_sampling_steps_per_render"]), device=device,
-                load_fn=load_fn, device_noise=bool(cfg["device_noise"]), sampler_kwargs=cli_sampler_kwargs(cfg))
+                load_fn=load_fn, device_noise=bool(cfg["device_noise"]), sampler_kwargs=cli_sampler_kwargs(cfg),
+                chains_per_gpu=int(cfg["chains_per_gpu"]))
         if rank == 0:
             img = out["images_render"]
             print(f"generate: {int(cfg['num_samples'])} samples x {int(cfg['n_eval_cameras'])} frames "

@@ -125,8 +125,8 @@ class HoloDiffusionModel(ImplicitronModelBase, torch.nn.Module):
         return torch.nn.ModuleList([if_ for _ in range(self.num_passes)])
 
     # ---- sampling (holo_diffusion_model.py:173-199) -----------------------------------------
-    def _shape(self):
-        return (1, self.feature_size, self.resol, self.resol, self.resol)
+    def _shape(self, batch_size: int = 1):
+        return (int(batch_size), self.feature_size, self.resol, self.resol, self.resol)
 
     def _sampler_loop_kwargs(self, sampler: str, ddim_steps, timesteps, eta, loop_kwargs: dict) -> dict:
         """The sampler choice (build-side extension): "ddpm" - the reference's ancestral loop, unchanged - or "ddim"
@@ -140,11 +140,13 @@ class HoloDiffusionModel(ImplicitronModelBase, torch.nn.Module):
         return loop_kwargs
 
     def sample_random_voxel_features_progressive(self, sampler: str = "ddpm", ddim_steps: Optional[int] = None,
-                                                 timesteps=None, eta: float = 0.0, **loop_kwargs):
+                                                 timesteps=None, eta: float = 0.0, batch_size: int = 1, **loop_kwargs):
+        """``batch_size`` (build-side extension): chains sampled together, one per batch row."""
         assert self.net_3d_enabled and self.diffusion_enabled
         loop_kwargs = self._sampler_loop_kwargs(sampler, ddim_steps, timesteps, eta, loop_kwargs)
         loop = self.diffusion.ddim_sample_loop_progressive if sampler == "ddim" else self.diffusion.p_sample_loop_progressive
-        for sample in loop(model=self.net_3d, shape=self._shape(), clip_denoised=True, progress=False, **loop_kwargs):
+        for sample in loop(model=self.net_3d, shape=self._shape(batch_size), clip_denoised=True, progress=False,
+                           **loop_kwargs):
             s = sample["sample"]
             out = torch.empty_like(s)
             L = runtime.lib()
@@ -153,12 +155,13 @@ class HoloDiffusionModel(ImplicitronModelBase, torch.nn.Module):
             yield out
 
     def sample_random_voxel_features(self, sampler: str = "ddpm", ddim_steps: Optional[int] = None, timesteps=None,
-                                     eta: float = 0.0, **loop_kwargs) -> torch.Tensor:
+                                     eta: float = 0.0, batch_size: int = 1, **loop_kwargs) -> torch.Tensor:
+        """``batch_size`` (build-side extension): chains sampled together, one per batch row."""
         assert self.net_3d_enabled and self.diffusion_enabled
         logger.info("generating random voxel features through denoising diffusion ...")
         loop_kwargs = self._sampler_loop_kwargs(sampler, ddim_steps, timesteps, eta, loop_kwargs)
         loop = self.diffusion.ddim_sample_loop if sampler == "ddim" else self.diffusion.p_sample_loop
-        return loop(model=self.net_3d, shape=self._shape(), clip_denoised=True,
+        return loop(model=self.net_3d, shape=self._shape(batch_size), clip_denoised=True,
                     progress=loop_kwargs.pop("progress", False), **loop_kwargs)
 
     def invert_voxel_features(self, voxel_features: torch.Tensor, ddim_steps: Optional[int] = None) -> torch.Tensor:

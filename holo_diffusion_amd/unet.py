@@ -199,7 +199,12 @@ class SimpleUnet3D(Unet3DBase):
         if code is None:
             raise _lib.HoloError("SimpleUnet3D.compute_dtype must be 'f32', 'bf16' or 'f32_bf16x3' "
                                  f"(got {self.compute_dtype!r})")
+        inv = 1 if self.batch_invariant else 0
+        if not inv:  # (off before a mode change: the library refuses a bf16 mode while the flag is on)
+            _lib.check(L, L.holo_unet_set_batch_invariant(self._handle, 0), "holo_unet_set_batch_invariant")
         _lib.check(L, L.holo_unet_set_compute_dtype(self._handle, code), "holo_unet_set_compute_dtype")
+        if inv:
+            _lib.check(L, L.holo_unet_set_batch_invariant(self._handle, 1), "holo_unet_set_batch_invariant")
         sd = dict(self._net.named_parameters())
         versions = self._poll_parameter_versions(sd)
         if self._dirty:
@@ -218,6 +223,25 @@ class SimpleUnet3D(Unet3DBase):
             self._dirty = False
             self.__dict__["_param_versions"] = versions
         return self._handle
+
+    @property
+    def batch_invariant(self) -> bool:
+        return bool(self.__dict__.get("_batch_invariant", False))
+
+    def set_batch_invariant(self, on: bool = True) -> "SimpleUnet3D":
+        """Batch-invariant forward plans (build-side extension, off by default; ``holo_unet_set_batch_invariant``): every
+        geometry choice of the plan is made for one sample, so row b of a batched forward is bit-identical to the batch-1
+        forward of that row - the mode of batched sampling chains.  Exact fp32 only: raises ``HoloError`` for
+        ``compute_dtype`` "bf16" / "f32_bf16x3" (the library refuses those modes with HOLO_E_UNSUPPORTED)."""
+        on = bool(on)
+        if on and self.compute_dtype != "f32":
+            raise _lib.HoloError(f"SimpleUnet3D.set_batch_invariant: batch-invariant plans are exact-fp32 only "
+                                 f"(compute_dtype 'f32'), not {self.compute_dtype!r}")
+        self.__dict__["_batch_invariant"] = on
+        if self._handle is not None:
+            L = runtime.lib()
+            _lib.check(L, L.holo_unet_set_batch_invariant(self._handle, 1 if on else 0), "holo_unet_set_batch_invariant")
+        return self
 
     def __del__(self):
         try:

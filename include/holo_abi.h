@@ -110,6 +110,16 @@ int holo_unet_set_param(HoloUnet* net, const char* name, const void* dev_ptr, in
  * May be called at any time; takes effect at the next forward. */
 int holo_unet_set_compute_dtype(HoloUnet* net, int dtype);
 
+/* Batch-invariant forward plans (off by default).  With on != 0, every geometry choice of the forward plan - the
+ * convolution kernel, its tile depth and split-K, the attention's key splits - is made for ONE sample and launched over the
+ * batch (scratch, statistics and grids are still sized for the batch), so row b of a holo_unet_forward /
+ * holo_unet_forward_cl at any batch is bit-identical to the batch-1 forward of that row.  For batched sampling chains
+ * whose samples must not depend on the batch they run in.  Exact fp32 only: HOLO_E_UNSUPPORTED in the bf16 and bf16x3
+ * modes (and holo_unet_set_compute_dtype refuses those modes while the flag is on).  A forward whose batch is too large to
+ * keep a batch-1 choice (a kernel's addressing limit) fails with HOLO_E_UNSUPPORTED.  The training entries keep their own
+ * plans.  Takes effect at the next forward. */
+int holo_unet_set_batch_invariant(HoloUnet* net, int on);
+
 size_t holo_unet_workspace_bytes(HoloUnet* net, int batch);
 
 /* y = UNetModel.forward(x, timesteps)  (unet.py:800-837).
@@ -190,6 +200,16 @@ int holo_ddpm_step_philox(HoloCtx* ctx, const float* tables, int num_timesteps, 
                           uint64_t stream_offset, int clip_denoised, float* sample, float* pred_xstart, float* noise_out,
                           int ncdhw_channels, void* stream);
 
+/* The same step with one Philox stream per row (batched chains): row b draws exactly what a batch-1
+ * holo_ddpm_step_philox launch on that row draws with stream_offset = (row_streams[b] << 32) | timestep_index - counter
+ * (q low, q high, 0, timestep_index), key (seed low, seed high ^ row_streams[b]) - so a chain's noise does not depend on
+ * the batch it runs in or its row.  row_streams: (batch,) uint32 on the device.  Layouts, pred_xstart and noise_out as
+ * holo_ddpm_step_philox. */
+int holo_ddpm_step_philox_rows(HoloCtx* ctx, const float* tables, int num_timesteps, const int64_t* timesteps, int batch,
+                               int64_t elems_per_sample, const float* x_t, const float* model_out, uint64_t seed,
+                               const uint32_t* row_streams, uint32_t timestep_index, int clip_denoised, float* sample,
+                               float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * DDIM step.  Replaces the elementwise tail of GaussianDiffusion.ddim_sample and ddim_reverse_sample:
  *   gaussian_diffusion.py:677-693 (eps from pred_xstart, sigma, Equation 12, noise add) and :717-727 (reversed)
@@ -211,6 +231,13 @@ int holo_ddim_step(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_pe
 int holo_ddim_step_philox(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
                           const float* model_out, uint64_t seed, uint64_t stream_offset, int clip_denoised, float* sample,
                           float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
+
+/* holo_ddim_step_philox with one Philox stream per row: row b draws what holo_ddpm_step_philox_rows draws for it (the
+ * batch-1 draw of stream row_streams[b] at timestep_index). */
+int holo_ddim_step_philox_rows(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                               const float* model_out, uint64_t seed, const uint32_t* row_streams, uint32_t timestep_index,
+                               int clip_denoised, float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels,
+                               void* stream);
 
 /* Elementwise helpers on the path: torch.tanh (holo_diffusion_model.py:425) and
  * torch.clip(x,-1,1) (holo_diffusion_model.py:186). */
