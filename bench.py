@@ -11,6 +11,11 @@ barrier + synchronize on both sides; with N>1 every rank (one process per GPU, l
 runs its own independent chain (weak scaling, no data-path collective) and the MAX time over ranks is used.
 The render leg (frames of the same grid) is timed the same way and reported in the same JSON line.
 
+A plain run does only what that line's headline needs: set-up, the W + K denoise steps, the render leg, --dump-outputs and
+the line.  `--full` adds everything else the benchmark measures, each leg run as before: the other noise path, the render
+leg at other call shapes and with normals, the roofline below, the opt-in arithmetic modes, the side workloads, the
+multi-GPU exchanges and the CPU baseline.  Their fields are null in the line of a plain run.
+
   roofline      the dominant kernel (the 64^3-level LDS voxel-halo conv3d), every launch of one UNet forward timed
                 with hipEvents on the launch stream (holo_unet_time_ops): algorithmic FLOPs / average launch
                 time vs the 157.3 TFLOP/s fp32 MFMA peak; `traffic` = HBM bytes per launch from the committed PMC
@@ -392,9 +397,9 @@ def main():
                     help="timed 400x400 frames in the render leg: one render call of a whole fly-around (render_flyaround's "
                          "default n_flyaround_poses = 40, flyaround.py:50; generate_samples.py uses 75)")
     ap.add_argument("--flyaround-frames", type=int, default=8,
-                    help="frame count of the SECONDARY render leg (0 = skip; the profiling scripts skip it so that every "
-                         "render dispatch of a profile has --frames frames).  8 = the call size round 1 reported: 40 000 "
-                         "wave tiles on 3 072 resident waves are 13.02 rounds, i.e. 7 % lost to the last round")
+                    help="with --full: frame count of the SECONDARY render leg (0 = skip; the profiling scripts skip it so that "
+                         "every render dispatch of a profile has --frames frames).  8 = the call size round 1 reported: 40 000 "
+                         "wave tiles on 3 072 resident waves are 13.02 rounds, i.e. 7 %% lost to the last round")
     ap.add_argument("--image-size", type=int, default=400)
     ap.add_argument("--workload", choices=["north", "small", "donut128"], default="north",
                     help="north = BASELINE configs[1] (the reported line); small / donut128 = configs[0] / [4] grid "
@@ -404,12 +409,19 @@ def main():
                          "the 3x3x3 convolutions (side measurement for the bf16 configurations)")
     ap.add_argument("--noise", choices=["device", "torch"], default="device",
                     help="per-step noise of the timed chain: device = drawn inside the step kernel (holo_ddpm_step_philox, the "
-                         "perf mode); torch = torch.randn_like + holo_ddpm_step (the reference's draw; also timed as a side figure)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the 128^3 bf16 side workload (BASELINE configs[4] size)")
-    ap.add_argument("--no-opt-in", action="store_true", help="skip the side measurements of the opt-in arithmetic modes")
+                         "perf mode); torch = torch.randn_like + holo_ddpm_step (the reference's draw; also timed as a side figure "
+                         "with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the reported line: the other noise path, the render leg at other "
+                         "call shapes and with normals, the roofline, the opt-in modes, the side workloads, the multi-GPU "
+                         "exchanges and the CPU baseline (their fields are null without it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side workloads (turntable, 128^3 bf16, "
+                                                           "batched chains, training step)")
+    ap.add_argument("--no-opt-in", action="store_true",
+                    help="with --full: skip the side measurements of the opt-in arithmetic modes")
     ap.add_argument("--dry-run", action="store_true", help="launch plumbing only (rendezvous + reductions), no kernels")
-    ap.add_argument("--conv-iters", type=int, default=3)
+    ap.add_argument("--conv-iters", type=int, default=3, help="with --full: timed forwards per op of the roofline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
                          "(float32, rank 0): denoise_sample (the chain's sample after the last timed step) and images_render / "
@@ -492,18 +504,20 @@ def main():
     steps_per_s = world * K / dt
     # the other noise path over the same K timesteps (side figure, this rank only)
     other_mode = "torch" if args.noise == "device" else "device"
-    with torch.no_grad():
-        xo = torch.randn(*shape, device=device)
-        if other_mode == "device" and cl_chain:
-            xo = xo.permute(0, 2, 3, 4, 1).contiguous()
-        for k in range(min(3, Wm)):
-            xo = one_step(xo, k, other_mode)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for k in range(Wm, Wm + K):
-            xo = one_step(xo, k, other_mode)
-        torch.cuda.synchronize()
-        steps_per_s_other = K / (time.perf_counter() - t0)
+    steps_per_s_other = None
+    if args.full:
+        with torch.no_grad():
+            xo = torch.randn(*shape, device=device)
+            if other_mode == "device" and cl_chain:
+                xo = xo.permute(0, 2, 3, 4, 1).contiguous()
+            for k in range(min(3, Wm)):
+                xo = one_step(xo, k, other_mode)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for k in range(Wm, Wm + K):
+                xo = one_step(xo, k, other_mode)
+            torch.cuda.synchronize()
+            steps_per_s_other = K / (time.perf_counter() - t0)
     per_rank_steps_per_s = [K / dt_own]
     if world > 1:  # every rank's own rate, gathered for the line rank 0 prints
         tr = torch.tensor([K / dt_own], dtype=torch.float64, device=device)
@@ -537,7 +551,7 @@ def main():
     # the same leg at a second call size (default: the 8-frame call round 1 reported): a secondary figure
     F40 = args.flyaround_frames
     rays_per_s_40, dtr40 = None, None
-    if F40 > 0:
+    if args.full and F40 > 0:
         cams40 = hda.get_simple_360_camera_trajectory(2 * math.pi, max(F40, 2), -30.0 * (2 * math.pi / 360), 10,
                                                       (0.0, -1.0, 0.0), 3.2).to(device)[list(range(F40))]
         with torch.no_grad():
@@ -552,38 +566,41 @@ def main():
     # the reference's call shape: one render call PER CAMERA (flyaround.py:247-253 loops over the cameras), same grid, the
     # t = 0 refinement cached as above
     n1 = min(F, 8)
-    with torch.no_grad():
-        singles = [cams[[i]] for i in range(n1)]
-        model.render_views(vf, singles[0])
-        barrier_sync(world)
-        t0 = time.perf_counter()
-        for c1 in singles:
-            model.render_views(vf, c1)
-        barrier_sync(world)
-        dts = max_over_ranks(time.perf_counter() - t0, world, device)
-    rays_per_s_single = world * n1 * H * W / dts
+    rays_per_s_single, dts = None, None
+    if args.full:
+        with torch.no_grad():
+            singles = [cams[[i]] for i in range(n1)]
+            model.render_views(vf, singles[0])
+            barrier_sync(world)
+            t0 = time.perf_counter()
+            for c1 in singles:
+                model.render_views(vf, c1)
+            barrier_sync(world)
+            dts = max_over_ranks(time.perf_counter() - t0, world, device)
+        rays_per_s_single = world * n1 * H * W / dts
 
     # the same call with rendered normals (the released YAMLs' render_normals: true): normals of both passes composited
     # inside render2_kernel<.., NRM> (density scalar field + octahedral normals in LDS)
     rays_per_s_nrm = None
-    try:
-        fn0 = model._implicit_functions[0]._fn
-        fn0.render_normals = True
-        with torch.no_grad():
-            model.render_views(vf, cams_f)
-            barrier_sync(world)
-            t0 = time.perf_counter()
-            outn = model.render_views(vf, cams_f)
-            barrier_sync(world)
-            dtn = max_over_ranks(time.perf_counter() - t0, world, device)
-        assert "normals_render" in outn and torch.isfinite(outn["normals_render"]).all()
-        rays_per_s_nrm = world * F * H * W / dtn
-    finally:
-        model._implicit_functions[0]._fn.render_normals = False
+    if args.full:
+        try:
+            fn0 = model._implicit_functions[0]._fn
+            fn0.render_normals = True
+            with torch.no_grad():
+                model.render_views(vf, cams_f)
+                barrier_sync(world)
+                t0 = time.perf_counter()
+                outn = model.render_views(vf, cams_f)
+                barrier_sync(world)
+                dtn = max_over_ranks(time.perf_counter() - t0, world, device)
+            assert "normals_render" in outn and torch.isfinite(outn["normals_render"]).all()
+            rays_per_s_nrm = world * F * H * W / dtn
+        finally:
+            model._implicit_functions[0]._fn.render_normals = False
 
     # ---------------- roofline of the dominant kernel, hipEvents on the launch stream (holo_unet_time_ops)
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         all_ops = net.time_ops(1, args.conv_iters, device)
         ops = [o for o in all_ops if o["op"] == "conv" and o["ksz"] == 3]
         HALO = ("conv_halo_kernel", "conv_wino_kernel", "conv_wino2_kernel", "conv_bf16t_kernel", "conv_wino3_kernel",
@@ -717,7 +734,7 @@ def main():
                   "sum", round(sum(v[1] for v in by_op.values()), 3), file=sys.stderr)
     # ---------------- side measurements (N=1 only, never the reported value): the opt-in matrix-core modes
     alt = None
-    if world == 1 and args.compute_dtype == "f32" and args.workload == "north" and not args.no_opt_in:
+    if args.full and world == 1 and args.compute_dtype == "f32" and args.workload == "north" and not args.no_opt_in:
         alt = {}
         for mode in ("f32_bf16x3", "bf16"):
             net.compute_dtype = mode
@@ -762,7 +779,7 @@ def main():
     # ---------------- side workload (N=1 only): BASELINE configs[4] donut.yaml size, 128^3x32 in the bf16 storage mode,
     # same weights (the UNet's parameters do not depend on the grid size): 3 warm + 5 timed DDPM steps
     side = None
-    if world == 1 and args.workload == "north" and args.compute_dtype == "f32" and not args.no_side:
+    if args.full and world == 1 and args.workload == "north" and args.compute_dtype == "f32" and not args.no_side:
         side = {"teddybear_turntable30": side_teddybear_turntable(model, device),
                 "donut128_bf16": side_donut128(usd, device), "batched_chains_f32": side_batched_chains(net, diff, w, device),
                 "training_step_f32": side_training_step(net, w, device)}
@@ -771,7 +788,7 @@ def main():
     # Every rank contributes the frames of its own sample (the timed render call's output); timed separately from the
     # render leg so that `rays_per_sec` stays the compute figure.
     gather = None
-    if world > 1:
+    if args.full and world > 1:
         from holo_diffusion_amd.generate import gather_frames
         frames = torch.cat([out["images_render"], out["depths_render"], out["masks_render"]], dim=1)  # (F,5,H,W)
         shape5 = tuple(frames.shape)
@@ -794,7 +811,7 @@ def main():
     # (generate.render_views_sharded: broadcast of the 33.5 MB grid from rank 0, cameras k mod N per rank in one render call,
     # one all_gather per output) against the same turntable rendered by rank 0 alone
     sharded = None
-    if world > 1 and args.workload == "north":
+    if args.full and world > 1 and args.workload == "north":
         from holo_diffusion_amd.generate import render_views_sharded
         cams30 = hda_cams(30, device)
         with torch.no_grad():
@@ -822,7 +839,7 @@ def main():
     # (165 M fp32 = 0.66 GB at the north-star size) in 64 MB buckets over RCCL / xGMI (holo_diffusion_amd/ddp.py); synthetic
     # gradients of the real parameter shapes, timed apart from the denoise and render legs
     grad_exchange = None
-    if world > 1 and args.workload == "north":
+    if args.full and world > 1 and args.workload == "north":
         from holo_diffusion_amd.ddp import DEFAULT_BUCKET_BYTES, allreduce_gradients, plan_buckets
         gsd = {k: torch.full(tuple(v.shape), float(rank + 1), device=device) for k, v in usd.items()}
         nb = sum(v.numel() for v in gsd.values()) * 4
@@ -845,7 +862,7 @@ def main():
         torch.cuda.empty_cache()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(w, usd, msd)
 
     if world > 1:
@@ -881,7 +898,7 @@ def main():
                               "attention), f32 GroupNorm statistics, f32 network input/output",
                       "f32_bf16x3": "f32 operands split into 3 bf16 terms, 6 bf16 MFMAs per product, f32 accumulate "
                                     "(3x3x3 convs); f32 elsewhere"}[args.compute_dtype],
-            "data": "synthetic",
+            "data": "synthetic", "full": args.full,
             "config": {"workload": ({"north": "apple.yaml single-sample DDPM, 64^3x32 grid, 1 MI355X per chain; ",
                                      "small": "32^3x16 plumbing grid; ",
                                      "donut128": f"128^3x32 grid (donut.yaml size), compute_dtype={args.compute_dtype}; "}[args.workload])
@@ -889,9 +906,9 @@ def main():
                        "parallelism": f"{world} independent chains (sample sharding), no data-path collective"},
             "rays_per_sec": rays_per_s, "ms_per_frame": 1e3 * dtr / F, "frames": F,
             "rays_per_sec_with_normals": rays_per_s_nrm,
-            "rays_per_sec_single_frame_calls": rays_per_s_single, "ms_per_single_frame_call": 1e3 * dts / n1,
-            "rays_per_sec_second_call_size": rays_per_s_40, "second_call_frames": F40,
-            "ms_per_frame_second_call_size": (1e3 * dtr40 / F40) if F40 > 0 else None,
+            "rays_per_sec_single_frame_calls": rays_per_s_single, "ms_per_single_frame_call": (1e3 * dts / n1) if dts else None,
+            "rays_per_sec_second_call_size": rays_per_s_40, "second_call_frames": F40 if args.full else None,
+            "ms_per_frame_second_call_size": (1e3 * dtr40 / F40) if dtr40 else None,
             "unet_tflops": FLOPS_PER_STEP[w["resol"]] * steps_per_s / world / 1e12,
             "unet_workspace_bytes": net.workspace_bytes(1, device),
             "roofline": roof,

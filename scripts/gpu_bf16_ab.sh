@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 echo "== bf16 parity tests (the persistent form is the default on the filled levels)"
 timeout 900 python -m pytest tests/test_gpu_unet.py tests/test_gpu_diffusion.py -m gpu -q -s --tb=short -p no:cacheprovider -k "bf16 or 128_cubed or donut" > $OUT/pytest_bf16.log 2>&1
 echo "pytest rc=$? | $(tail -1 $OUT/pytest_bf16.log)"; grep -E "^(FAILED|ERROR)" $OUT/pytest_bf16.log
-B="--no-cpu-baseline --steps 6 --warmup 2 --frames 8 --flyaround-frames 0"
+B="--full --no-cpu-baseline --steps 6 --warmup 2 --frames 8 --flyaround-frames 0"
 for mode in 0 on 2; do
   if [ "$mode" = "on" ]; then unset HOLO_CONV_BF16P; else export HOLO_CONV_BF16P=$mode; fi
   HOLO_DEBUG_PLAN=1 HOLO_BENCH_OPS=1 timeout 600 python bench.py $B --workload donut128 --compute-dtype bf16 > $OUT/donut128_bf16_p$mode.json 2> $OUT/donut128_bf16_p$mode.err

@@ -4,7 +4,8 @@ TAG=${1:-pmcs}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --steps 2 --warmup 1 --frames 8 --flyaround-frames 0 --workload donut128 --compute-dtype bf16 --conv-iters 1"
+REPO=$(cd "$(dirname "$0")/.." && pwd)
+CMD="python $REPO/bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --frames 8 --flyaround-frames 0 --workload donut128 --compute-dtype bf16 --conv-iters 1"
 run_pass () {
   name=$1; shift
   ( cd /tmp && timeout 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d /tmp/pmc_${TAG}_$name -o p -- $CMD > /dev/null 2> $GRAFT_REPO_ROOT/$OUT/pmc_$name.err ; echo "pass $name rc=$?" )

@@ -5,7 +5,7 @@ TAG=${1:-side}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="--no-cpu-baseline --steps 6 --warmup 2 --frames 8 --flyaround-frames 0"
+B="--full --no-cpu-baseline --steps 6 --warmup 2 --frames 8 --flyaround-frames 0"
 HOLO_BENCH_OPS=1 timeout 600 python bench.py $B --workload donut128 --compute-dtype bf16 > $OUT/donut128_bf16.json 2> $OUT/donut128_bf16.err; echo "bf16 rc=$?"
 grep "per-op totals" $OUT/donut128_bf16.err
 timeout 600 python bench.py $B --workload donut128 > $OUT/donut128.json 2> $OUT/donut128.err; echo "f32 rc=$?"

@@ -16,8 +16,8 @@ for pass in 1 2 3; do
 done
 grep -hE "loss.backward\(\) through|deterministic scatter|north-star perf-mode" $OUT/pytest_gpu_*.log >> $OUT/pytest_x3.txt
 tail -40 $OUT/pytest_gpu_1.log
-echo "== bench"; HOLO_DEBUG_PLAN=1 HOLO_BENCH_OPS=1 timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json
+echo "== bench"; HOLO_DEBUG_PLAN=1 HOLO_BENCH_OPS=1 timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json
 python scripts/ops_table.py $OUT/bench.err > $OUT/ops_table.txt 2>/dev/null
-B="--no-cpu-baseline --steps 6 --warmup 2 --frames 8 --flyaround-frames 0"
+B="--full --no-cpu-baseline --steps 6 --warmup 2 --frames 8 --flyaround-frames 0"
 HOLO_BENCH_OPS=1 timeout 600 python bench.py $B --workload donut128 --compute-dtype bf16 > $OUT/donut128_bf16.json 2> $OUT/donut128_bf16.err; echo "bf16 rc=$?"
 python scripts/ops_table.py $OUT/donut128_bf16.err > $OUT/donut128_bf16_ops.txt 2>/dev/null; head -80 $OUT/donut128_bf16_ops.txt

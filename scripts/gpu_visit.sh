@@ -5,6 +5,7 @@ TAG=${1:-v}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 rocminfo 2>/dev/null | grep -E "Marketing Name|gfx9|Compute Unit" | head -6 > $OUT/device.txt
 nproc >> $OUT/device.txt; lscpu | grep -E "Model name|Socket|Core|Thread" >> $OUT/device.txt
 echo "== smoke"; timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?" | tee -a $OUT/smoke.log; tail -2 $OUT/smoke.log
@@ -30,10 +31,10 @@ cat $OUT/render_probe.log
 echo "== probes: training step (forward + backward), view pooling forward / backward"
 timeout 200 python scripts/backward_probe.py 5 > $OUT/backward_probe.log 2>&1; tail -2 $OUT/backward_probe.log
 timeout 300 python scripts/viewpool_probe.py 16 64 > $OUT/viewpool_probe.log 2>&1; grep -E "view pooling|MLPMean" $OUT/viewpool_probe.log
-echo "== bench"; HOLO_DEBUG_PLAN=1 HOLO_BENCH_OPS=1 timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; grep -E "per-op totals|\[plan\]" $OUT/bench.err | head -3
+echo "== bench"; HOLO_DEBUG_PLAN=1 HOLO_BENCH_OPS=1 timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; grep -E "per-op totals|\[plan\]" $OUT/bench.err | head -3
 python scripts/ops_table.py $OUT/bench.err > $OUT/ops_table.txt 2>/dev/null
 echo "== rocprofv3 kernel trace of the bench command"
-( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o prof -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline > $GRAFT_REPO_ROOT/$OUT/rocprof_bench.json 2> $GRAFT_REPO_ROOT/$OUT/rocprof.err; echo "rocprof rc=$?" )
+( cd "$TMPDIR" && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$TMPDIR/prof_$TAG" -o prof -- python "$REPO/bench.py" --full --no-cpu-baseline > "$REPO/$OUT/rocprof_bench.json" 2> "$REPO/$OUT/rocprof.err"; echo "rocprof rc=$?" )
 for f in $(find /tmp/prof_$TAG -name "*kernel_stats.csv"); do cp $f $OUT/kernel_stats.csv; done
 for f in $(find /tmp/prof_$TAG -name "*kernel_trace.csv"); do
   python3 scripts/trace_by_grid.py "$f" "$OUT/kernel_trace_by_grid.csv"

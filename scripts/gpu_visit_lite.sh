@@ -15,5 +15,5 @@ fi
 echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log; tail -60 $OUT/pytest_gpu.log
 echo "== render probes"
 timeout 300 python scripts/render_probe.py 1 8 30 > $OUT/render_probe.log 2>&1; cat $OUT/render_probe.log
-echo "== bench"; HOLO_DEBUG_PLAN=1 HOLO_BENCH_OPS=1 timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; grep -E "per-op totals" $OUT/bench.err | head -3
+echo "== bench"; HOLO_DEBUG_PLAN=1 HOLO_BENCH_OPS=1 timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; grep -E "per-op totals" $OUT/bench.err | head -3
 python scripts/ops_table.py $OUT/bench.err > $OUT/ops_table.txt 2>/dev/null; head -60 $OUT/ops_table.txt
