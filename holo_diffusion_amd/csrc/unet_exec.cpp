@@ -13,6 +13,7 @@
 
 #include <functional>
 #include <map>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -51,7 +52,8 @@ using namespace holo;
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-enum BlockKind { B_CONV, B_RES, B_ATTN, B_DOWN, B_UP };
+// (B_HEAD, the output head GroupNorm + SiLU + conv, is not a block of the structure: only the training tape records it)
+enum BlockKind { B_CONV, B_RES, B_ATTN, B_DOWN, B_UP, B_HEAD };
 struct Block {
   BlockKind kind;
   std::string prefix;
@@ -64,17 +66,26 @@ enum ParamKind { P_PLAIN, P_CONV3, P_CONV1, P_EMB_W, P_EMB_B };
 // (64 when Cout >= 64, else 32), CinP a multiple of the 32-channel K chunk
 static inline int pad_cout(int c) { return c >= 64 ? (c + 63) / 64 * 64 : 32; }
 static inline int pad_cin(int c) { return (c + 31) / 32 * 32; }
+// every device copy of one convolution's weights (host-side bookkeeping; null = not prepared for this conv).
+// Planner::emit_conv copies the ones the compute mode uses into ConvParams, and conv_plan picks kernels from those.
+struct ConvWeights {
+  float* f32 = nullptr;     // repacked fp32 copy
+  uint16_t* bf = nullptr;   // bf16 (RNE) planes hi, mid, lo packed for v_mfma_f32_16x16x32_bf16
+  uint16_t* bft = nullptr;  // plane 3 of the same buffer: hi packed for the wide-tile kernel (conv_bf16t_kernel)
+  float* wino2 = nullptr;   // the wide top levels: (z,y) Winograd pseudo-taps (conv_wino2_kernel)
+  float* wino3 = nullptr;   // ... and the F(2x2x2, 3x3x3) pseudo-taps (conv_wino3_kernel)
+};
 struct ParamSlot {
   std::string name;
   std::vector<int64_t> shape;
   int64_t numel;
   ParamKind kind;
-  float* priv;  // private (repacked) device copy
-  uint16_t* priv_bf = nullptr;  // conv weights: bf16 (RNE) copy packed for v_mfma_f32_16x16x32_bf16
-  float* priv_wino2 = nullptr;  // conv weights of the wide top levels: (z,y) Winograd pseudo-taps (conv_wino2_kernel)
-  float* priv_wino3 = nullptr;  // ... and the F(2x2x2, 3x3x3) pseudo-taps (conv_wino3_kernel)
+  ConvWeights w;  // private device copies: f32 (repacked for a conv weight) of every parameter, the rest of conv weights only
   bool set;
 };
+static bool is_downsample_weight(const std::string& name) {  // Downsample: the stride-2 convolution
+  return name.size() > 10 && name.compare(name.size() - 10, 10, ".op.weight") == 0;
+}
 
 struct Arena {
   size_t top = 0, peak = 0;
@@ -130,8 +141,7 @@ struct Act {  // channels-last activation [N][R][R][R][C]
   int refs = 0;
 };
 
-struct Tape {  // one layer of the training forward (what its backward needs)
-  int kind = 0;  // BlockKind, or 100 = the output head (GroupNorm + SiLU + conv), 101 = input conv
+struct Tape {  // one layer of the training forward (what its backward needs); b.kind tells which
   Block b;
   Act x0, x1, h1, out;
   bool has_x1 = false;
@@ -141,26 +151,86 @@ struct Tape {  // one layer of the training forward (what its backward needs)
   bool has_skip = false;
 };
 
-enum OpKind { OP_MEMSET, OP_IN, OP_TEMB, OP_EMBLIN, OP_STATS, OP_FINAL, OP_CONV, OP_GEMM, OP_SOFTMAX, OP_FLASH, OP_OUT };
-struct Op {
-  OpKind kind;
-  ConvParams conv;
-  GemmParams gemm;
+// One launch of the forward.  The numbers are public (HoloOpTiming.op, SimpleUnet3D.OP_NAMES); 0 was a memset and stays reserved.
+enum OpKind { OP_IN = 1, OP_TEMB, OP_EMBLIN, OP_STATS, OP_FINAL, OP_CONV, OP_GEMM, OP_SOFTMAX, OP_FLASH, OP_OUT };
+// caller's NCDHW x -> the plan's channels-last input buffer, and that of the output -> caller's NCDHW y
+struct LayoutIn { float* dst; int C; int64_t V; int dst_bf16; };
+struct LayoutOut { const float* src; int C; int64_t V; };
+struct TimeEmbed {
+  const float *w1, *b1, *w2, *b2;
+  float *emb, *emb_silu;
+};
+struct EmbLinears {  // every ResBlock's emb_layers as one [emb_rows][ted] product
+  const float *emb_silu, *w, *b;
+  float* out;
+};
+struct GnStats {  // GroupNorm partial sums by a pass of their own (where the producing conv cannot write them)
+  const float* x;
+  double* part;
+  int C, x_bf16;
+  int64_t V;
+};
+struct GnFinalize {  // partial sums of the (virtual concat) input -> per-(sample, channel) affine, GroupNorm folded with FiLM
+  const double *part0, *part1;  // [N][B0][C0][2], [N][B1][C1][2] (part1 may be null)
+  int C0, B0, C1, B1;
+  int64_t V;
+  const float *gamma, *beta, *film;
+  int film_stride, film_cout;
+  float *coef, *moments;  // moments: (mean, rstd) kept for the backward in a training plan, else null
+};
+struct Softmax { float* S; int64_t rows; int cols; };  // in place
+struct Flash {
   AttnParams attn;
-  // generic
-  const float* f0 = nullptr;
-  const float* f1 = nullptr;
-  const float* f2 = nullptr;
-  const float* f3 = nullptr;
-  const float* f4 = nullptr;
-  float* o0 = nullptr;
-  float* o1 = nullptr;
-  const double* d0 = nullptr;
-  const double* d1 = nullptr;
-  double* dout = nullptr;
-  int i0 = 0, i1 = 0, i2 = 0, i3 = 0, i4 = 0, i5 = 0;
-  int64_t l0 = 0, l1 = 0;
+  int form;             // 0: exact-fp32 kernel; 2: packed-operand bf16 kernel
+  float* packed;        // form 2: scratch of the packed operands and split partials
+  int out_bf16;         // form 2: attn.out is bf16
+  int operands_packed;  // form 2: the qkv convolution wrote the packed operands itself
+};
+struct Op {  // trivially copyable: holo_unet_forward_cl patches copies of two of them
+  OpKind kind;
+  union {
+    LayoutIn in;
+    TimeEmbed temb;
+    EmbLinears emblin;
+    GnStats stats;
+    GnFinalize fin;
+    ConvParams conv;
+    GemmParams gemm;
+    Softmax softmax;
+    Flash flash;
+    LayoutOut out;
+  };
+};
+static Op make_op(OpKind kind) {
+  Op op;
+  memset(&op, 0, sizeof op);
+  op.kind = kind;
+  return op;
+}
+
+// A built forward plan.  Planner fills one; nothing else of it lives on the net.
+struct Plan {
+  int batch = -1;
+  void* ws = nullptr;  // workspace base it was built for (null: a sizing pass)
+  std::vector<Op> ops;
+  size_t bytes = 0;  // workspace it needs
+  std::map<std::string, Act> block_outputs;  // holo_unet_fetch_block
+  // holo_unet_forward_cl: the convolutions that read the plan's input buffer / write its output buffer, and why the
+  // entry cannot use this plan (null: it can)
+  int first_conv = -1, last_conv = -1;
+  const char* cl_refusal = nullptr;
+  bool built_for(int b, const void* w) const { return batch == b && ws == w && !ops.empty(); }
+  void invalidate() { *this = Plan(); }
+};
+// The training plan: the forward with every intermediate kept + the backward launches in execution order.
+struct TrainPlan {
+  Plan fwd;
+  std::vector<std::function<int(void*)>> bops;
+  std::vector<size_t> grad_off;  // per parameter: byte offset of its gradient in the workspace
+  size_t gy_off = 0, gx_off = 0;  // gradient of the output (laid out channels-last) / of the input
   size_t bytes = 0;
+  bool built_for(int b, const void* w) const { return fwd.built_for(b, w); }
+  void invalidate() { *this = TrainPlan(); }
 };
 
 }  // namespace
@@ -174,14 +244,9 @@ struct HoloUnet {
   int ted;
   std::vector<ParamSlot> params;
   std::map<std::string, int> pindex;
-  float* pstore = nullptr;  // one allocation for all private parameter copies
-  uint16_t* pstore_bf = nullptr;                       // bf16 copies of the conv weights
-  std::map<const float*, const uint16_t*> bf_of;       // fp32 private copy -> bf16 copy
-  std::map<const float*, const uint16_t*> bft_of;      // fp32 private copy -> bf16 copy packed for the wide-tile kernel
-  float* pstore_wino = nullptr;                        // Winograd copies of the conv weights
-  std::map<const float*, const float*> wino2_of;       // fp32 private copy -> (z,y) Winograd copy
-  std::map<const float*, const float*> wino3_of;       // fp32 private copy -> F(2x2x2, 3x3x3) Winograd copy
-  std::map<std::string, float*> dgrad_wino2, dgrad_wino3;  // Winograd copies of the transposed (dgrad) weights
+  float* pstore = nullptr;       // one allocation for all private parameter copies
+  uint16_t* pstore_bf = nullptr;  // bf16 copies of the conv weights
+  float* pstore_wino = nullptr;  // Winograd copies of the conv weights
   // holo_unet_set_compute_dtype: 0 exact fp32 MFMA; 1 bf16: activations stored as bf16 in HBM, bf16 products with fp32
   // accumulation in the 3x3x3 convolutions and the long-sequence attention, fp32 GroupNorm statistics; 2 bf16x3 split
   // (fp32 storage, fp32-accurate)
@@ -195,28 +260,17 @@ struct HoloUnet {
   float* emb_w = nullptr;                  // [emb_rows][ted]
   float* emb_b = nullptr;                  // [emb_rows]
   bool keep_intermediates = false;
-  // plan
-  int plan_batch = -1;
-  void* plan_ws = nullptr;
-  std::vector<Op> ops;
-  size_t ws_need = 0;
-  std::map<std::string, Act> block_outputs;
+  Plan plan;                                        // inference (holo_unet_forward, _forward_cl, _fetch_block, _time_*)
   std::map<std::pair<int, bool>, size_t> ws_cache;  // (batch, batch_invariant) -> workspace bytes
   // ---- training (holo_unet_backward): weights of the transposed convolutions, packed like the forward ones
-  // ([Cin][Cout] flipped taps for the stride-1 convs; [tap][Cout][Cin] for the stride-2 Downsample convs), supplied by
-  // holo_unet_set_dgrad_weight; the training plan (forward with every intermediate kept + backward op list)
-  std::map<std::string, float*> dgrad_w;
+  // ([Cin][Cout] flipped taps for the stride-1 convs; [tap][Cout][Cin] for the stride-2 Downsample convs, whose stride-1
+  // form lives under "<name>#s1"), supplied by holo_unet_set_dgrad_weight; this table owns every buffer it points to
+  std::map<std::string, ConvWeights> dgrad;
   float* dgrad_tmp = nullptr;
   size_t dgrad_tmp_floats = 0;
-  int tplan_batch = -1;
-  void* tplan_ws = nullptr;
-  std::vector<Op> tops;                                      // training forward
-  std::vector<std::function<int(void*)>> bops;               // backward, in execution order
-  std::vector<size_t> grad_off;                              // per parameter: byte offset of its gradient in the workspace
-  size_t tws_need = 0;
-  size_t gy_off = 0, gx_off = 0, y_off = 0;
-  const int64_t* t_dev = nullptr;                            // timesteps of the running call (time_embed backward)
-  bool tape_valid = false;                                    // holo_unet_forward_train ran and nothing has consumed its tape
+  TrainPlan tplan;
+  const int64_t* t_dev = nullptr;  // timesteps of the running call (time_embed backward)
+  bool tape_valid = false;         // holo_unet_forward_train ran and nothing has consumed its tape
   std::map<int, size_t> tws_cache;
 };
 
@@ -297,7 +351,6 @@ void add_param(HoloUnet* u, const std::string& name, std::vector<int64_t> shape,
   s.numel = 1;
   for (auto d : shape) s.numel *= d;
   s.kind = kind;
-  s.priv = nullptr;
   s.set = false;
   u->pindex[name] = (int)u->params.size();
   u->params.push_back(s);
@@ -354,6 +407,8 @@ void enumerate_params(HoloUnet* u) {
         add_param(u, p + ".conv.weight", {co, ci, 3, 3, 3}, P_CONV3);
         add_param(u, p + ".conv.bias", {co}, P_PLAIN);
         break;
+      case B_HEAD:
+        break;
     }
   };
   for (auto& l : u->inputs)
@@ -367,36 +422,107 @@ void enumerate_params(HoloUnet* u) {
   add_param(u, "out.2.bias", {c.out_channels}, P_PLAIN);
 }
 
-const float* P(HoloUnet* u, const std::string& name) {
+// the private copies of parameter `name`: P its fp32 copy, W the whole set of a convolution weight
+ConvWeights W(const HoloUnet* u, const std::string& name) {
   auto it = u->pindex.find(name);
-  if (it == u->pindex.end()) return nullptr;
-  return u->params[it->second].priv;
+  return it == u->pindex.end() ? ConvWeights() : u->params[it->second].w;
 }
+const float* P(const HoloUnet* u, const std::string& name) { return W(u, name).f32; }
 
 // ---------------------------------------------------------------------------------------------
 // plan builder
 // ---------------------------------------------------------------------------------------------
+// One convolution as its call site describes it: only what differs from a plain 3x3x3 stride-1 conv of x0 is set, by name.
+struct ConvDesc {
+  const Act* x0 = nullptr;
+  const Act* x1 = nullptr;  // second source of the virtual channel concat
+  int in_R = 0;             // logical input size (AFTER the upsampling when ups); 0: x0's
+  int ups = 0;
+  int out_R = 0;  // 0: the logical input size
+  int stride = 1, ksz = 3;
+  ConvWeights w;
+  const float* bias = nullptr;
+  std::optional<size_t> coef;  // workspace offset of the GroupNorm (+ FiLM) coefficients applied on load
+  int act = 0;                 // 1: SiLU after them
+  const float* residual = nullptr;
+  float* out = nullptr;
+  int Cout = 0;
+  Act* stats_of = nullptr;  // the output activation, when its GroupNorm statistics are wanted
+  struct {                  // 1x1x1 skip connection fused as extra K chunks (w.f32 null: none)
+    const Act* x0 = nullptr;
+    const Act* x1 = nullptr;
+    ConvWeights w;
+    const float* bias = nullptr;
+  } skip;
+  bool in_f32 = false, out_f32 = false;  // bf16 storage mode: this operand stays fp32
+  const ConvParams* qkv_pack = nullptr;  // an attention block's qkv convolution: where it may write the packed operands
+  int in_size() const { return in_R ? in_R : x0->R; }
+  int out_size() const { return out_R ? out_R : in_size(); }
+};
+
+// a workspace range seen as an activation (attention internals, gradients)
+static Act view(size_t off, int C, int R) {
+  Act a;
+  a.off = off;
+  a.C = C;
+  a.R = R;
+  return a;
+}
+
+// One operand of the attention GEMMs, batched over (sample, head), and the three layouts they come in
+struct AttnMat {
+  float* p;
+  int ld;
+  int64_t s0, s1;  // leading dimension; strides over samples / heads
+};
+struct AttnDims {
+  int N, H, C;
+  int64_t T;
+  int ch() const { return C / H; }
+  float scale2() const {
+    const double sc = 1.0 / sqrt(sqrt((double)ch()));
+    return (float)(sc * sc);
+  }
+  AttnMat qkv(float* base, int part) const { return AttnMat{base + part * ch(), 3 * C, T * 3 * C, 3 * ch()}; }  // q, k or v of [N][T][3C]
+  AttnMat scores(float* S) const { return AttnMat{S, (int)T, (int64_t)H * T * T, T * T}; }                     // [N][H][T][T]
+  AttnMat heads(float* a) const { return AttnMat{a, C, T * C, ch()}; }                                          // [N][T][C]
+};
+// C = alpha A B^T ([T][T] out of two [T][ch] operands), or with b_kmajor C = alpha A B ([T][ch] out of [T][T] and [T][ch])
+static GemmParams attn_gemm(const AttnDims& d, AttnMat A, AttnMat B, bool b_kmajor, AttnMat C, float alpha) {
+  GemmParams g;
+  memset(&g, 0, sizeof g);
+  g.A = A.p, g.lda = A.ld, g.sa0 = A.s0, g.sa1 = A.s1;
+  g.B = B.p, g.ldb = B.ld, g.sb0 = B.s0, g.sb1 = B.s1;
+  g.C = C.p, g.ldc = C.ld, g.sc0 = C.s0, g.sc1 = C.s1;
+  g.M = (int)d.T;
+  g.Nn = b_kmajor ? d.ch() : (int)d.T;
+  g.K = b_kmajor ? (int)d.T : d.ch();
+  g.nb0 = d.N;
+  g.nb1 = d.H;
+  g.b_kmajor = b_kmajor ? 1 : 0;
+  g.alpha = alpha;
+  return g;
+}
+
 struct Planner {
-  HoloUnet* u;
+  const HoloUnet* u;  // read only: everything a build produces goes into `plan`
   int N;
   char* base;  // workspace base (may be null for a sizing pass)
-  Arena arena;                // big activations, after the small regions
+  Plan& plan;
+  std::vector<Op>& ops;       // plan.ops
+  Arena arena;                // big activations, after the small region
   size_t small_top = 0;       // coef / emb buffers
-  size_t stats_top = 0;       // GroupNorm statistics (zeroed every forward)
-  size_t stats_cap, small_cap;
-  size_t stats_base, small_base, arena_base;
-  std::vector<Op>& ops;
+  size_t small_cap, arena_base;
   std::vector<Tape>* tape = nullptr;  // training forward: every layer is recorded, nothing is released
   size_t last_mom = 0;                // moments buffer of the last emit_finalize (training)
   std::string err;                    // a batch-invariant plan that cannot be kept (ensure_plan reports it)
+  size_t eml_off = 0, embs_off = 0;
+  Act x_in, y_out;
 
-  Planner(HoloUnet* u_, int N_, void* ws, std::vector<Op>& ops_) : u(u_), N(N_), base((char*)ws), ops(ops_) {
-    // generous fixed regions for the small buffers
-    stats_cap = 0;
+  Planner(const HoloUnet* u_, int N_, void* ws, Plan& plan_) : u(u_), N(N_), base((char*)ws), plan(plan_), ops(plan_.ops) {
+    // a generous fixed region for the small buffers
     small_cap = Arena::al((size_t)N * 8 * 1024 * 256 * 2 + (size_t)N * (u->emb_rows + 4 * u->ted) * 4 * 2 + 65536);
-    stats_base = 0;
-    small_base = stats_cap;
-    arena_base = stats_cap + small_cap;
+    arena_base = small_cap;
     arena.keep = u->keep_intermediates;
   }
   template <class T>
@@ -427,7 +553,7 @@ struct Planner {
     if (a.stats_bytes) arena.free(a.stats_off - arena_base, a.stats_bytes);
   }
   size_t small_alloc(size_t bytes) {
-    size_t off = small_base + small_top;
+    size_t off = small_top;
     small_top += Arena::al(bytes);
     return off;
   }
@@ -438,111 +564,109 @@ struct Planner {
     int B, vpb;
     gn_stats_geometry(a.C, vox(a.R), &B, &vpb);
     alloc_stats(a, B);
-    Op op;
-    op.kind = OP_STATS;
-    op.f0 = ptr<float>(a.off);
-    op.dout = ptr<double>(a.stats_off);
-    op.i0 = a.C;
-    op.i1 = bfs() ? 1 : 0;
-    op.l0 = vox(a.R);
+    Op op = make_op(OP_STATS);
+    op.stats.x = ptr<float>(a.off);
+    op.stats.part = ptr<double>(a.stats_off);
+    op.stats.C = a.C;
+    op.stats.V = vox(a.R);
+    op.stats.x_bf16 = bfs() ? 1 : 0;
     ops.push_back(op);
   }
-  // returns coef offset
-  size_t emit_finalize(const Act& x0, const Act* x1, const float* gamma, const float* beta, const float* film,
-                       int film_cout) {
+  // GroupNorm `norm` (its .weight / .bias) of [x0 | x1], folded with the FiLM rows when given; returns the coef offset
+  size_t emit_finalize(const Act& x0, const Act* x1, const std::string& norm, const float* film = nullptr, int film_cout = 0) {
     const int Cin = x0.C + (x1 ? x1->C : 0);
     size_t coef = small_alloc((size_t)N * Cin * 2 * sizeof(float));
-    Op op;
-    op.kind = OP_FINAL;
+    Op op = make_op(OP_FINAL);
+    GnFinalize& f = op.fin;
     if (tape) {
       last_mom = small_alloc((size_t)N * Cin * 2 * sizeof(float));
-      op.o1 = ptr<float>(last_mom);
+      f.moments = ptr<float>(last_mom);
     }
-    op.d0 = ptr<double>(x0.stats_off);
-    op.i0 = x0.C;
-    op.d1 = x1 ? ptr<double>(x1->stats_off) : nullptr;
-    op.i1 = x1 ? x1->C : 0;
-    op.i4 = x0.stats_B;
-    op.i5 = x1 ? x1->stats_B : 0;
-    op.l0 = vox(x0.R);
-    op.f0 = gamma;
-    op.f1 = beta;
-    op.f2 = film;
-    op.i2 = u->emb_rows;
-    op.i3 = film_cout;
-    op.o0 = ptr<float>(coef);
+    f.part0 = ptr<double>(x0.stats_off);
+    f.C0 = x0.C;
+    f.B0 = x0.stats_B;
+    f.part1 = x1 ? ptr<double>(x1->stats_off) : nullptr;
+    f.C1 = x1 ? x1->C : 0;
+    f.B1 = x1 ? x1->stats_B : 0;
+    f.V = vox(x0.R);
+    f.gamma = P(u, norm + ".weight");
+    f.beta = P(u, norm + ".bias");
+    f.film = film;
+    f.film_stride = u->emb_rows;
+    f.film_cout = film_cout;
+    f.coef = ptr<float>(coef);
     ops.push_back(op);
     return coef;
   }
-  void emit_conv(const Act& x0, const Act* x1, int in_R_logical, int ups, int out_R, int stride, int ksz,
-                 const float* w, const float* bias, size_t coef_off, bool has_coef, int act, const float* residual,
-                 float* out, int Cout, Act* stats_of = nullptr, const Act* skip0 = nullptr,
-                 const Act* skip1 = nullptr, const float* skip_w = nullptr, const float* skip_bias = nullptr,
-                 bool in_f32 = false, bool out_f32 = false, const ConvParams* qkv_pack = nullptr) {
-    Op op;
-    op.kind = OP_CONV;
+  Tape& record(const Block& b, const Act& x0, const Act& out) {  // training: a layer onto the tape
+    tape->emplace_back();
+    Tape& t = tape->back();
+    t.b = b;
+    t.x0 = x0;
+    t.out = out;
+    return t;
+  }
+  // the convolution `layer` (its .weight / .bias) of x into the activation `out`
+  ConvDesc conv_of(const std::string& layer, const Act& x, const Act& out) {
+    ConvDesc d;
+    d.x0 = &x;
+    d.w = W(u, layer + ".weight");
+    d.bias = P(u, layer + ".bias");
+    d.out = ptr<float>(out.off);
+    d.Cout = out.C;
+    return d;
+  }
+  void emit_conv(const ConvDesc& d) {
+    Op op = make_op(OP_CONV);
     ConvParams& p = op.conv;
-    memset(&p, 0, sizeof p);
-    if (qkv_pack) {  // (an attention block's qkv convolution: conv_plan may fuse the attention's operand packing into it)
-      p.qkv_q = qkv_pack->qkv_q, p.qkv_k = qkv_pack->qkv_k, p.qkv_vt = qkv_pack->qkv_vt;
-      p.qkv_scale = qkv_pack->qkv_scale, p.qkv_T = qkv_pack->qkv_T, p.qkv_CH = qkv_pack->qkv_CH, p.qkv_H = qkv_pack->qkv_H;
+    if (const ConvParams* q = d.qkv_pack) {  // (conv_plan may fuse the attention's operand packing into the launch)
+      p.qkv_q = q->qkv_q, p.qkv_k = q->qkv_k, p.qkv_vt = q->qkv_vt;
+      p.qkv_scale = q->qkv_scale, p.qkv_T = q->qkv_T, p.qkv_CH = q->qkv_CH, p.qkv_H = q->qkv_H;
     }
-    p.in_bf16 = bfs() && !in_f32;
+    p.in_bf16 = bfs() && !d.in_f32;
     p.res_bf16 = bfs();
-    p.out_bf16 = bfs() && !out_f32;
-    p.src0 = ptr<float>(x0.off);
-    p.src1 = x1 ? ptr<float>(x1->off) : nullptr;
-    p.C0 = x0.C;
-    p.C1 = x1 ? x1->C : 0;
+    p.out_bf16 = bfs() && !d.out_f32;
+    p.src0 = ptr<float>(d.x0->off);
+    p.src1 = d.x1 ? ptr<float>(d.x1->off) : nullptr;
+    p.C0 = d.x0->C;
+    p.C1 = d.x1 ? d.x1->C : 0;
     p.N = N;
-    p.ID = p.IH = p.IW = in_R_logical;
-    p.ups = ups;
-    p.OD = p.OH = p.OW = out_R;
-    p.stride = stride;
-    p.pad = ksz == 3 ? 1 : 0;
-    p.ksz = ksz;
-    p.Cout = Cout;
-    p.CoutP = pad_cout(Cout);
+    p.ID = p.IH = p.IW = d.in_size();
+    p.ups = d.ups;
+    p.OD = p.OH = p.OW = d.out_size();
+    p.stride = d.stride;
+    p.pad = d.ksz == 3 ? 1 : 0;
+    p.ksz = d.ksz;
+    p.Cout = d.Cout;
+    p.CoutP = pad_cout(d.Cout);
     p.CinP = pad_cin(p.C0 + p.C1);
-    p.w = w;
-    if (u->compute_mode) {  // halo-path launches multiply on the bf16 matrix cores (conv_launch checks the pointers)
-      auto it = u->bf_of.find(w);
-      p.w_bf = it == u->bf_of.end() ? nullptr : it->second;
-      auto itt = u->bft_of.find(w);
-      p.w_bft = itt == u->bft_of.end() ? nullptr : itt->second;
-      p.bf16 = u->compute_mode;
-    }
-    if (u->compute_mode == 0) {  // exact fp32: the Winograd kernels where conv_plan finds 128-voxel tiles
-      auto it2 = u->wino2_of.find(w);
-      p.w_wino2 = it2 == u->wino2_of.end() ? nullptr : it2->second;
-      auto it3 = u->wino3_of.find(w);
-      p.w_wino3 = it3 == u->wino3_of.end() ? nullptr : it3->second;
-    }
-    p.coef = has_coef ? ptr<float>(coef_off) : nullptr;
-    p.act = act;
-    p.bias = bias;
-    p.residual = residual;
-    p.out = out;
-    if (skip_w) {  // 1x1x1 skip connection fused as extra K chunks (halo kernel)
-      p.skip_src0 = ptr<float>(skip0->off);
-      p.skip_src1 = skip1 ? ptr<float>(skip1->off) : nullptr;
-      p.skip_C0 = skip0->C;
-      p.skip_C1 = skip1 ? skip1->C : 0;
-      p.skip_w = skip_w;
-      if (u->compute_mode) {
-        auto it = u->bf_of.find(skip_w);
-        p.skip_w_bf = it == u->bf_of.end() ? nullptr : it->second;
-        auto itt = u->bft_of.find(skip_w);
-        p.skip_w_bft = itt == u->bft_of.end() ? nullptr : itt->second;
-      }
-      if (u->compute_mode == 0) {
-        auto it2 = u->wino2_of.find(skip_w);
-        p.skip_w_wino2 = it2 == u->wino2_of.end() ? nullptr : it2->second;
-        auto it3 = u->wino3_of.find(skip_w);
-        p.skip_w_wino3 = it3 == u->wino3_of.end() ? nullptr : it3->second;
-      }
+    // conv_plan picks kernels from the weight pointers it finds, so which copies are handed over IS the compute mode:
+    // the bf16 ones off the exact mode (halo-path launches multiply on the bf16 matrix cores), the Winograd ones in it
+    // (where conv_plan finds 128-voxel tiles)
+    const bool bf = u->compute_mode != 0, wino = u->compute_mode == 0;
+    p.w = d.w.f32;
+    p.w_bf = bf ? d.w.bf : nullptr;
+    p.w_bft = bf ? d.w.bft : nullptr;
+    p.bf16 = u->compute_mode;
+    p.w_wino2 = wino ? d.w.wino2 : nullptr;
+    p.w_wino3 = wino ? d.w.wino3 : nullptr;
+    p.coef = d.coef ? ptr<float>(*d.coef) : nullptr;
+    p.act = d.act;
+    p.bias = d.bias;
+    p.residual = d.residual;
+    p.out = d.out;
+    if (d.skip.w.f32) {  // halo kernel
+      p.skip_src0 = ptr<float>(d.skip.x0->off);
+      p.skip_src1 = d.skip.x1 ? ptr<float>(d.skip.x1->off) : nullptr;
+      p.skip_C0 = d.skip.x0->C;
+      p.skip_C1 = d.skip.x1 ? d.skip.x1->C : 0;
+      p.skip_w = d.skip.w.f32;
+      p.skip_w_bf = bf ? d.skip.w.bf : nullptr;
+      p.skip_w_bft = bf ? d.skip.w.bft : nullptr;
+      p.skip_w_wino2 = wino ? d.skip.w.wino2 : nullptr;
+      p.skip_w_wino3 = wino ? d.skip.w.wino3 : nullptr;
       p.skip_CinP = pad_cin(p.skip_C0 + p.skip_C1);
-      p.skip_bias = skip_bias;
+      p.skip_bias = d.skip.bias;
     }
     ConvParams one = p;
     size_t sb = conv_plan(p, u->ctx->num_cus, plan_n());
@@ -563,10 +687,10 @@ struct Planner {
     }
     // GroupNorm statistics of the output: from the conv / split-K-reduce epilogue when the launch can
     // produce them, else by a separate pass over the output
-    const int slabs = stats_of ? conv_stats_slabs(p) : 0;
+    const int slabs = d.stats_of ? conv_stats_slabs(p) : 0;
     if (slabs > 0) {
-      alloc_stats(*stats_of, slabs);
-      p.stats = ptr<double>(stats_of->stats_off);
+      alloc_stats(*d.stats_of, slabs);
+      p.stats = ptr<double>(d.stats_of->stats_off);
     }
     // The split-K scratch is released only AFTER the statistics buffer has its place: the reduce kernel of this very
     // launch writes the statistics while other workgroups of it still read partial sums, so the two must not share memory.
@@ -575,23 +699,24 @@ struct Planner {
     // Stream order protects the scratch against every LATER launch.
     if (sb) scratch_free(so, sb);
     ops.push_back(op);
-    if (stats_of && slabs == 0) emit_stats(*stats_of);
+    if (d.stats_of && slabs == 0) emit_stats(*d.stats_of);
   }
 
   Act resblock(const Block& b, Act& x0, Act* x1) {
     const std::string& p = b.prefix;
     const int R = x0.R;
-    size_t coefA = emit_finalize(x0, x1, P(u, p + ".in_layers.0.weight"), P(u, p + ".in_layers.0.bias"), nullptr, 0);
+    size_t coefA = emit_finalize(x0, x1, p + ".in_layers.0");
     const size_t momA = last_mom;
     Act h1 = new_act(b.cout, R);
-    emit_conv(x0, x1, R, 0, R, 1, 3, P(u, p + ".in_layers.2.weight"), P(u, p + ".in_layers.2.bias"), coefA, true, 1,
-              nullptr, ptr<float>(h1.off), b.cout, &h1);
-    const float* film = ptr<float>(eml_off) + u->emb_row_off[p];
-    size_t coefB =
-        emit_finalize(h1, nullptr, P(u, p + ".out_layers.0.weight"), P(u, p + ".out_layers.0.bias"), film, b.cout);
+    ConvDesc c1 = conv_of(p + ".in_layers.2", x0, h1);
+    c1.x1 = x1;
+    c1.coef = coefA;
+    c1.act = 1;
+    c1.stats_of = &h1;
+    emit_conv(c1);
+    const float* film = ptr<float>(eml_off) + u->emb_row_off.at(p);
+    size_t coefB = emit_finalize(h1, nullptr, p + ".out_layers.0", film, b.cout);
     const size_t momB = last_mom;
-    Act s;
-    const float* residual;
     const bool has_skip = b.cin != b.cout;
     // the 1x1x1 skip conv rides inside the second 3x3x3 conv (halo kernel) wherever that kernel applies
     // (the bf16x3 kernel has no fused-skip variant: its skip connection runs as a separate fp32 1x1x1 conv)
@@ -599,8 +724,6 @@ struct Planner {
     //  mode; four launches + four reduces less at the 4^3 level of the north-star net)
     bool fuse_skip = has_skip && ((R % 8) == 0 || (u->compute_mode == 0 && R < 8)) && b.cout >= 64 && u->compute_mode != 2 &&
                      !getenv("HOLO_NO_SKIP_FUSION");
-    // development knob: from this grid size on the skip runs as its own 1x1x1 launch whose output is the second
-    // convolution's residual (A/B of the fused form on the wide levels)
     // From 64^3 on (exact-fp32 mode) the skip runs as its own streaming 1x1x1 launch (conv1x1_stream_kernel) whose output is the
     // second convolution's residual: measured on the north-star net, fused 305 us per launch against 208 (plain) + ~45.
     // HOLO_SKIP_FUSION_BELOW_R=<R>: development knob for the threshold (A/B of the two forms)
@@ -609,42 +732,41 @@ struct Planner {
       const int below = mr ? atoi(mr) : 64;
       if (fuse_skip && u->compute_mode == 0 && R >= below && (b.cin % 32) == 0 && b.cin <= 256 && (b.cout % 64) == 0) fuse_skip = false;
     }
+    Act s;
     if (has_skip && !fuse_skip) {
       s = new_act(b.cout, R);
-      emit_conv(x0, x1, R, 0, R, 1, 1, P(u, p + ".skip_connection.weight"), P(u, p + ".skip_connection.bias"), 0,
-                false, 0, nullptr, ptr<float>(s.off), b.cout);
-      residual = ptr<float>(s.off);
-    } else if (has_skip) {
-      residual = nullptr;
-    } else {
-      residual = ptr<float>(x0.off);
+      ConvDesc cs = conv_of(p + ".skip_connection", x0, s);
+      cs.x1 = x1;
+      cs.ksz = 1;
+      emit_conv(cs);
     }
     Act out = new_act(b.cout, R);
-    if (fuse_skip)
-      emit_conv(h1, nullptr, R, 0, R, 1, 3, P(u, p + ".out_layers.3.weight"), P(u, p + ".out_layers.3.bias"), coefB,
-                true, 1, nullptr, ptr<float>(out.off), b.cout, &out, &x0, x1, P(u, p + ".skip_connection.weight"),
-                P(u, p + ".skip_connection.bias"));
-    else
-      emit_conv(h1, nullptr, R, 0, R, 1, 3, P(u, p + ".out_layers.3.weight"), P(u, p + ".out_layers.3.bias"), coefB,
-                true, 1, residual, ptr<float>(out.off), b.cout, &out);
+    ConvDesc c2 = conv_of(p + ".out_layers.3", h1, out);
+    c2.coef = coefB;
+    c2.act = 1;
+    c2.stats_of = &out;
+    if (fuse_skip) {
+      c2.skip.x0 = &x0;
+      c2.skip.x1 = x1;
+      c2.skip.w = W(u, p + ".skip_connection.weight");
+      c2.skip.bias = P(u, p + ".skip_connection.bias");
+    } else {
+      c2.residual = ptr<float>(has_skip ? s.off : x0.off);
+    }
+    emit_conv(c2);
     release(h1);
     if (has_skip && !fuse_skip) release(s);
     if (tape) {
-      Tape t;
-      t.kind = B_RES;
-      t.b = b;
-      t.x0 = x0;
+      Tape& t = record(b, x0, out);
       t.has_x1 = x1 != nullptr;
       if (x1) t.x1 = *x1;
       t.h1 = h1;
-      t.out = out;
       t.coefA = coefA;
       t.coefB = coefB;
       t.momA = momA;
       t.momB = momB;
       t.film = film;
       t.has_skip = has_skip;
-      tape->push_back(t);
     }
     return out;
   }
@@ -653,7 +775,8 @@ struct Planner {
     const std::string& p = b.prefix;
     const int C = x.C, R = x.R, H = u->cfg.num_heads, ch = C / H;
     const int64_t T = vox(R);
-    size_t coef = emit_finalize(x, nullptr, P(u, p + ".norm.weight"), P(u, p + ".norm.bias"), nullptr, 0);
+    const AttnDims dims{N, H, C, T};
+    size_t coef = emit_finalize(x, nullptr, p + ".norm");
     const size_t momX = last_mom;
     const size_t qkv_bytes = (size_t)N * T * 3 * C * sizeof(float);
     const size_t s_bytes = (size_t)N * H * T * T * sizeof(float);
@@ -663,20 +786,16 @@ struct Planner {
     size_t v2_work = 0, v2_bytes = 0;
     bool a_is_bf16 = false;
     const bool flash = flash_attn_supported((int)T, ch) && !getenv("HOLO_NO_FLASH_ATTN");
-    Op fop;
-    fop.kind = OP_FLASH;
-    fop.attn.qkv = ptr<float>(qkv);
-    fop.attn.out = ptr<float>(a);
-    fop.attn.N = N;
-    fop.attn.T = (int)T;
-    fop.attn.C = C;
-    fop.attn.H = H;
-    {
-      const double sc = 1.0 / sqrt(sqrt((double)ch));
-      fop.attn.scale2 = (float)(sc * sc);
-    }
-    fop.attn.nsplit = 1;
-    fop.attn.part = fop.attn.part_ml = nullptr;
+    Op fop = make_op(OP_FLASH);
+    Flash& fl = fop.flash;
+    fl.attn.qkv = ptr<float>(qkv);
+    fl.attn.out = ptr<float>(a);
+    fl.attn.N = N;
+    fl.attn.T = (int)T;
+    fl.attn.C = C;
+    fl.attn.H = H;
+    fl.attn.scale2 = dims.scale2();
+    fl.attn.nsplit = 1;
     size_t split_work = 0, split_bytes = 0;
     // bf16 mode, sequences of 1 024 tokens and more: the packed-operand bf16 kernel (it splits the key range to fill
     // the chip, so it also serves the shorter of them; below that the exact-fp32 kernel is as fast).
@@ -688,172 +807,97 @@ struct Planner {
     if (flash) {
       const char* mt = getenv("HOLO_BF16_FLASH_MIN_T");
       const int64_t min_t = mt ? atoll(mt) : 1024;
-      fop.i0 = 0;
       if (u->compute_mode == 1 && T >= min_t && flash_attn_bf16v2_supported((int)T, ch)) {
         // packed bf16 operands (V transposed) in scratch, bf16 attention output
-        fop.i0 = 2;
-        v2_bytes = flash_attn_bf16v2_workspace_bytes(fop.attn, u->ctx->num_cus);
+        fl.form = 2;
+        v2_bytes = flash_attn_bf16v2_workspace_bytes(fl.attn, u->ctx->num_cus);
         v2_work = scratch_alloc(v2_bytes);
-        fop.o1 = ptr<float>(v2_work);
-        fop.i1 = 1;
+        fl.packed = ptr<float>(v2_work);
+        fl.out_bf16 = 1;
         a_is_bf16 = true;
         if (!tape && bfs()) {  // the qkv convolution may write the packed operands itself (the backward's tape keeps fp32 qkv)
-          flash_attn_bf16v2_operands(fop.attn, fop.o1, &qp.qkv_q, &qp.qkv_k, &qp.qkv_vt, &qp.qkv_scale);
+          flash_attn_bf16v2_operands(fl.attn, fl.packed, &qp.qkv_q, &qp.qkv_k, &qp.qkv_vt, &qp.qkv_scale);
           qp.qkv_T = (int)T, qp.qkv_CH = ch, qp.qkv_H = H;
           offer_pack = true;
         }
       } else {
         // exact fp32: the key range split across workgroups where one per query tile leaves CUs empty
-        fop.attn.nsplit = flash_attn_splits(plan_n(), (int)T, H, u->ctx->num_cus);
-        split_bytes = flash_attn_workspace_bytes(fop.attn);
+        fl.attn.nsplit = flash_attn_splits(plan_n(), (int)T, H, u->ctx->num_cus);
+        split_bytes = flash_attn_workspace_bytes(fl.attn);
         if (split_bytes) {
           split_work = scratch_alloc(split_bytes);
-          fop.attn.part = ptr<float>(split_work);
-          fop.attn.part_ml = fop.attn.part + (size_t)fop.attn.nsplit * N * T * C;
+          fl.attn.part = ptr<float>(split_work);
+          fl.attn.part_ml = fl.attn.part + (size_t)fl.attn.nsplit * N * T * C;
         }
       }
     }
     // (the attention internals - qkv and the attention output - stay fp32 in every mode)
-    emit_conv(x, nullptr, R, 0, R, 1, 1, P(u, p + ".qkv.weight"), P(u, p + ".qkv.bias"), coef, true, 0, nullptr,
-              ptr<float>(qkv), 3 * C, nullptr, nullptr, nullptr, nullptr, nullptr, false, /*out_f32=*/true,
-              offer_pack ? &qp : nullptr);
+    ConvDesc cq = conv_of(p + ".qkv", x, view(qkv, 3 * C, R));
+    cq.ksz = 1;
+    cq.coef = coef;
+    cq.out_f32 = true;
+    if (offer_pack) cq.qkv_pack = &qp;
+    emit_conv(cq);
     if (flash) {
-      Op op = fop;
-      op.i2 = ops.back().kind == OP_CONV && ops.back().conv.kernel == ConvKernel::Qkv ? 1 : 0;  // operands already packed
+      fl.operands_packed = ops.back().conv.kernel == ConvKernel::Qkv ? 1 : 0;
       if (getenv("HOLO_DEBUG_PLAN"))
         fprintf(stderr, "[plan] attention %s: T=%lld C=%d heads=%d -> %s flash kernel, %d key splits\n", p.c_str(),
-                (long long)T, C, H, op.i0 == 2 ? "bf16" : "fp32", op.i0 == 2 ? 1 : op.attn.nsplit);
-      ops.push_back(op);
-    } else {
+                (long long)T, C, H, fl.form == 2 ? "bf16" : "fp32", fl.form == 2 ? 1 : fl.attn.nsplit);
+      ops.push_back(fop);
+    } else {  // S = scale2 q k^T; softmax over its rows; a = S v
       size_t S = scratch_alloc(s_bytes);
-    {
-      Op op;
-      op.kind = OP_GEMM;
-      GemmParams& g = op.gemm;
-      memset(&g, 0, sizeof g);
-      g.A = ptr<float>(qkv);
-      g.B = ptr<float>(qkv) + ch;
-      g.C = ptr<float>(S);
-      g.M = (int)T;
-      g.Nn = (int)T;
-      g.K = ch;
-      g.lda = 3 * C;
-      g.ldb = 3 * C;
-      g.ldc = (int)T;
-      g.nb0 = N;
-      g.nb1 = H;
-      g.sa0 = T * 3 * C;
-      g.sa1 = 3 * ch;
-      g.sb0 = T * 3 * C;
-      g.sb1 = 3 * ch;
-      g.sc0 = (int64_t)H * T * T;
-      g.sc1 = T * T;
-      g.b_kmajor = 0;
-      const double sc = 1.0 / sqrt(sqrt((double)ch));
-      g.alpha = (float)(sc * sc);
+      float* qkvp = ptr<float>(qkv);
+      Op op = make_op(OP_GEMM);
+      op.gemm = attn_gemm(dims, dims.qkv(qkvp, 0), dims.qkv(qkvp, 1), false, dims.scores(ptr<float>(S)), dims.scale2());
       ops.push_back(op);
-    }
-    {
-      Op op;
-      op.kind = OP_SOFTMAX;
-      op.o0 = ptr<float>(S);
-      op.l0 = (int64_t)N * H * T;
-      op.i0 = (int)T;
+      Op sm = make_op(OP_SOFTMAX);
+      sm.softmax.S = ptr<float>(S);
+      sm.softmax.rows = (int64_t)N * H * T;
+      sm.softmax.cols = (int)T;
+      ops.push_back(sm);
+      op.gemm = attn_gemm(dims, dims.scores(ptr<float>(S)), dims.qkv(qkvp, 2), true, dims.heads(ptr<float>(a)), 1.0f);
       ops.push_back(op);
-    }
-    {
-      Op op;
-      op.kind = OP_GEMM;
-      GemmParams& g = op.gemm;
-      memset(&g, 0, sizeof g);
-      g.A = ptr<float>(S);
-      g.B = ptr<float>(qkv) + 2 * ch;
-      g.C = ptr<float>(a);
-      g.M = (int)T;
-      g.Nn = ch;
-      g.K = (int)T;
-      g.lda = (int)T;
-      g.ldb = 3 * C;
-      g.ldc = C;
-      g.nb0 = N;
-      g.nb1 = H;
-      g.sa0 = (int64_t)H * T * T;
-      g.sa1 = T * T;
-      g.sb0 = T * 3 * C;
-      g.sb1 = 3 * ch;
-      g.sc0 = T * C;
-      g.sc1 = ch;
-      g.b_kmajor = 1;
-      g.alpha = 1.0f;
-      ops.push_back(op);
-    }
       scratch_free(S, s_bytes);
     }
     Act out = new_act(C, R);
-    Act av;  // view of `a` as an activation for the 1x1 conv
-    av.off = a;
-    av.C = C;
-    av.R = R;
-    emit_conv(av, nullptr, R, 0, R, 1, 1, P(u, p + ".proj_out.weight"), P(u, p + ".proj_out.bias"), 0, false, 0,
-              ptr<float>(x.off), ptr<float>(out.off), C, &out, nullptr, nullptr, nullptr, nullptr, /*in_f32=*/!a_is_bf16);
+    const Act av = view(a, C, R);  // `a` as an activation for the 1x1 conv
+    ConvDesc cp = conv_of(p + ".proj_out", av, out);
+    cp.ksz = 1;
+    cp.residual = ptr<float>(x.off);
+    cp.stats_of = &out;
+    cp.in_f32 = !a_is_bf16;
+    emit_conv(cp);
     if (v2_bytes) scratch_free(v2_work, v2_bytes);
     if (split_bytes) scratch_free(split_work, split_bytes);
     scratch_free(qkv, qkv_bytes);
     scratch_free(a, a_bytes);
     if (tape) {
-      Tape t;
-      t.kind = B_ATTN;
-      t.b = b;
-      t.x0 = x;
-      t.out = out;
+      Tape& t = record(b, x, out);
       t.coefA = coef;
       t.momA = momX;
       t.qkv = qkv;
       t.a = a;
-      tape->push_back(t);
     }
     return out;
   }
-
-  size_t eml_off = 0, embs_off = 0;
-  Act x_in, y_out;
 
   // runs a TimestepEmbedSequential; consumes (releases) the input activation(s)
   Act run_layers(const std::vector<Block>& layers, Act h, Act* skip, bool release_h) {
     bool first = true;
     for (const Block& b : layers) {
       Act out;
-      Act* x1 = first ? skip : nullptr;
-      switch (b.kind) {
-        case B_CONV:
-          out = new_act(b.cout, h.R);
-          emit_conv(h, nullptr, h.R, 0, h.R, 1, 3, P(u, b.prefix + ".weight"), P(u, b.prefix + ".bias"), 0, false, 0,
-                    nullptr, ptr<float>(out.off), b.cout, &out);
-          break;
-        case B_RES:
-          out = resblock(b, h, x1);
-          break;
-        case B_ATTN:
-          out = attention(b, h);
-          break;
-        case B_DOWN:
-          out = new_act(b.cout, h.R / 2);
-          emit_conv(h, nullptr, h.R, 0, h.R / 2, 2, 3, P(u, b.prefix + ".op.weight"), P(u, b.prefix + ".op.bias"), 0,
-                    false, 0, nullptr, ptr<float>(out.off), b.cout, &out);
-          break;
-        case B_UP:
-          out = new_act(b.cout, h.R * 2);
-          emit_conv(h, nullptr, h.R * 2, 1, h.R * 2, 1, 3, P(u, b.prefix + ".conv.weight"),
-                    P(u, b.prefix + ".conv.bias"), 0, false, 0, nullptr, ptr<float>(out.off), b.cout, &out);
-          break;
-      }
-      if (tape && (b.kind == B_CONV || b.kind == B_DOWN || b.kind == B_UP)) {
-        Tape t;
-        t.kind = b.kind;
-        t.b = b;
-        t.x0 = h;
-        t.out = out;
-        tape->push_back(t);
+      if (b.kind == B_RES) {
+        out = resblock(b, h, first ? skip : nullptr);
+      } else if (b.kind == B_ATTN) {
+        out = attention(b, h);
+      } else {  // a bare convolution: input conv, Downsample (stride 2), Upsample (nearest x2 on load)
+        out = new_act(b.cout, b.kind == B_DOWN ? h.R / 2 : b.kind == B_UP ? h.R * 2 : h.R);
+        ConvDesc d = conv_of(b.prefix + (b.kind == B_DOWN ? ".op" : b.kind == B_UP ? ".conv" : ""), h, out);
+        if (b.kind == B_DOWN) d.out_R = out.R, d.stride = 2;
+        if (b.kind == B_UP) d.in_R = out.R, d.ups = 1;
+        d.stats_of = &out;
+        emit_conv(d);
+        if (tape) record(b, h, out);
       }
       if (!first || release_h) release(h);
       if (first && skip) release(*skip);
@@ -866,42 +910,38 @@ struct Planner {
   void build() {
     const HoloUnetCfg& c = u->cfg;
     const int R = c.image_size;
-    ops.clear();
-    u->block_outputs.clear();
+    plan.invalidate();
     // time embedding
     size_t emb = small_alloc((size_t)N * u->ted * 4);
     size_t embs = small_alloc((size_t)N * u->ted * 4);
     eml_off = small_alloc((size_t)N * u->emb_rows * 4);
     embs_off = embs;
     {
-      Op op;
-      op.kind = OP_TEMB;
-      op.f0 = P(u, "time_embed.0.weight");
-      op.f1 = P(u, "time_embed.0.bias");
-      op.f2 = P(u, "time_embed.2.weight");
-      op.f3 = P(u, "time_embed.2.bias");
-      op.o0 = ptr<float>(emb);
-      op.o1 = ptr<float>(embs);
+      Op op = make_op(OP_TEMB);
+      op.temb.w1 = P(u, "time_embed.0.weight");
+      op.temb.b1 = P(u, "time_embed.0.bias");
+      op.temb.w2 = P(u, "time_embed.2.weight");
+      op.temb.b2 = P(u, "time_embed.2.bias");
+      op.temb.emb = ptr<float>(emb);
+      op.temb.emb_silu = ptr<float>(embs);
       ops.push_back(op);
     }
     {
-      Op op;
-      op.kind = OP_EMBLIN;
-      op.f0 = ptr<float>(embs);
-      op.f1 = u->emb_w;
-      op.f2 = u->emb_b;
-      op.o0 = ptr<float>(eml_off);
+      Op op = make_op(OP_EMBLIN);
+      op.emblin.emb_silu = ptr<float>(embs);
+      op.emblin.w = u->emb_w;
+      op.emblin.b = u->emb_b;
+      op.emblin.out = ptr<float>(eml_off);
       ops.push_back(op);
     }
     Act x = new_act(c.in_channels, R);
     x_in = x;
     {
-      Op op;
-      op.kind = OP_IN;
-      op.o0 = ptr<float>(x.off);
-      op.i0 = c.in_channels;
-      op.i1 = bfs() ? 1 : 0;
-      op.l0 = vox(R);
+      Op op = make_op(OP_IN);
+      op.in.dst = ptr<float>(x.off);
+      op.in.C = c.in_channels;
+      op.in.V = vox(R);
+      op.in.dst_bf16 = bfs() ? 1 : 0;
       ops.push_back(op);
     }
     std::vector<Act> hs;
@@ -912,40 +952,37 @@ struct Planner {
       h = run_layers(u->inputs[i], h, nullptr, /*release_h=*/i == 0);
       hs.push_back(h);
       snprintf(tag, sizeof tag, "input_blocks.%d", (int)i);
-      u->block_outputs[tag] = h;
+      plan.block_outputs[tag] = h;
     }
     // middle: h == hs.back(); keep it alive for the skip connection
     h = run_layers(u->middle, h, nullptr, false);
-    u->block_outputs["middle_block"] = h;
+    plan.block_outputs["middle_block"] = h;
     for (size_t i = 0; i < u->outputs.size(); ++i) {
       Act skip = hs.back();
       hs.pop_back();
       h = run_layers(u->outputs[i], h, &skip, true);
       snprintf(tag, sizeof tag, "output_blocks.%d", (int)i);
-      u->block_outputs[tag] = h;
+      plan.block_outputs[tag] = h;
     }
-    size_t coef = emit_finalize(h, nullptr, P(u, "out.0.weight"), P(u, "out.0.bias"), nullptr, 0);
+    size_t coef = emit_finalize(h, nullptr, "out.0");
     Act y = new_act(c.out_channels, R, /*f32=*/true);  // the network output stays fp32
     if (tape) {
-      Tape t;
-      t.kind = 100;
-      t.b = Block{B_CONV, "out", u->final_ch, c.out_channels};
-      t.x0 = h;
-      t.out = y;
+      Tape& t = record(Block{B_HEAD, "out", u->final_ch, c.out_channels}, h, y);
       t.coefA = coef;
       t.momA = last_mom;
-      tape->push_back(t);
     }
-    emit_conv(h, nullptr, R, 0, R, 1, 3, P(u, "out.2.weight"), P(u, "out.2.bias"), coef, true, 1, nullptr,
-              ptr<float>(y.off), c.out_channels, nullptr, nullptr, nullptr, nullptr, nullptr, false, /*out_f32=*/true);
+    ConvDesc head = conv_of("out.2", h, y);
+    head.coef = coef;
+    head.act = 1;
+    head.out_f32 = true;
+    emit_conv(head);
     y_out = y;
     release(h);
     {
-      Op op;
-      op.kind = OP_OUT;
-      op.f0 = ptr<float>(y.off);
-      op.i0 = c.out_channels;
-      op.l0 = vox(R);
+      Op op = make_op(OP_OUT);
+      op.out.src = ptr<float>(y.off);
+      op.out.C = c.out_channels;
+      op.out.V = vox(R);
       ops.push_back(op);
     }
     release(y);
@@ -960,9 +997,37 @@ struct Planner {
       fprintf(stderr, "[plan] batch %d: %zu ops | %d convs, %d of them split-K (+ a reduce launch) | %d gn_finalize launches\n", N, ops.size(),
               n_conv, n_split, n_fin);
     }
+    find_cl_ends();
+    plan.batch = N;
+    plan.ws = base;
+    plan.bytes = arena_base + arena.peak;
   }
-  size_t total_bytes() const { return arena_base + arena.peak; }
-  bool regions_ok() const { return stats_top <= stats_cap && small_top <= small_cap; }
+  // holo_unet_forward_cl points every convolution that reads the plan's input buffer or writes its output buffer at the
+  // caller's channels-last tensors instead (by POSITION in the op list, not by address: the arena hands the input
+  // buffer's memory to later activations).  Which two those are, and whether they can, is a property of the plan.
+  void find_cl_ends() {
+    const float* in_buf = nullptr;
+    const float* out_buf = nullptr;
+    int first = -1, last = -1;
+    for (size_t i = 0; i < ops.size(); ++i) {
+      const Op& op = ops[i];
+      if (op.kind == OP_IN) in_buf = op.in.dst;
+      if (op.kind == OP_OUT) out_buf = op.out.src;
+      if (op.kind == OP_CONV) {
+        if (first < 0 && in_buf) first = (int)i;
+        last = (int)i;
+      }
+    }
+    plan.first_conv = first;
+    plan.last_conv = last;
+    if (first < 0 || !in_buf || !out_buf || ops[first].conv.src0 != in_buf || ops[first].conv.src1 ||
+        ops[last].conv.out != out_buf || ops[last].conv.nsplit != 1 || ops[first].conv.nsplit != 1 || first == last) {
+      plan.cl_refusal = "holo_unet_forward_cl: this plan's first / last convolution cannot take the caller's tensors";
+    } else if (bfs() && (ops[last].conv.out_bf16 || !ops[first].conv.in_bf16)) {
+      plan.cl_refusal = "holo_unet_forward_cl: unexpected storage types at the ends of the bf16 plan";
+    }
+  }
+  bool regions_ok() const { return small_top <= small_cap; }
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -976,16 +1041,16 @@ struct Planner {
 // identity branches of ResBlock / AttentionBlock).  Parameter gradients live in the workspace in the reference's layouts.
 // ---------------------------------------------------------------------------------------------
 struct TrainPlanner {
-  HoloUnet* u;
+  const HoloUnet* u;  // read only: everything a build produces goes into `tp`
   int N;
+  TrainPlan& tp;
   Planner pl;
   std::vector<Tape> tape;
-  std::vector<std::function<int(void*)>>& bops;
+  std::vector<std::function<int(void*)>>& bops;      // tp.bops
   std::map<size_t, std::pair<size_t, bool>> grads;  // activation offset -> (gradient offset, already written)
   std::string err;
 
-  TrainPlanner(HoloUnet* u_, int N_, void* ws, std::vector<Op>& fops, std::vector<std::function<int(void*)>>& b)
-      : u(u_), N(N_), pl(u_, N_, ws, fops), bops(b) {
+  TrainPlanner(const HoloUnet* u_, int N_, void* ws, TrainPlan& tp_) : u(u_), N(N_), tp(tp_), pl(u_, N_, ws, tp_.fwd), bops(tp_.bops) {
     pl.arena.keep = true;
     pl.tape = &tape;
   }
@@ -1020,67 +1085,105 @@ struct TrainPlanner {
   }
   float* pgrad(const std::string& name) {
     auto it = u->pindex.find(name);
-    return it == u->pindex.end() ? nullptr : reinterpret_cast<float*>(pl.base + u->grad_off[it->second]);
+    return it == u->pindex.end() ? nullptr : reinterpret_cast<float*>(pl.base + tp.grad_off[it->second]);
   }
-  const float* dgw(const std::string& name) {
-    auto it = u->dgrad_w.find(name);
-    if (it == u->dgrad_w.end()) {
-      err = "holo_unet_backward: call holo_unet_set_dgrad_weight for '" + name + "' first";
-      return nullptr;
-    }
-    return it->second;
+  // The transposed weights under `name`, or null.  A sizing pass (no workspace base) launches nothing and must not fail
+  // on weights that were not supplied yet, so there every convolution weight counts as present, and so does the stride-1
+  // form "<name>#s1" of a Downsample weight whose two leading dims are multiples of 4 (the one holo_unet_set_dgrad_weight
+  // creates); they count as plain fp32 copies, without Winograd forms.
+  const ConvWeights* find_dgw(const std::string& name) {
+    auto it = u->dgrad.find(name);
+    if (it != u->dgrad.end()) return &it->second;
+    if (pl.base) return nullptr;
+    const bool s1 = name.size() > 3 && name.compare(name.size() - 3, 3, "#s1") == 0;
+    auto pi = u->pindex.find(s1 ? name.substr(0, name.size() - 3) : name);
+    if (pi == u->pindex.end()) return nullptr;
+    const ParamSlot& s = u->params[pi->second];
+    if (s.kind != P_CONV3 && s.kind != P_CONV1) return nullptr;
+    if (s1 && (!is_downsample_weight(s.name) || (s.shape[0] & 3) || (s.shape[1] & 3))) return nullptr;
+    static float never_read;
+    static const ConvWeights assumed{&never_read};
+    return &assumed;
+  }
+  const ConvWeights* dgw(const std::string& name) {
+    const ConvWeights* w = find_dgw(name);
+    if (!w) err = "holo_unet_backward: call holo_unet_set_dgrad_weight for '" + name + "' first";
+    return w;
   }
 
   // dgrad of a stride-1 conv (3x3x3 pad 1 or 1x1x1): out[M][cin] = conv(gy[M][cout], flipped weights)
   void emit_dgrad(size_t gy_off, int cout, int R, const std::string& wname, int cin, int ksz, size_t out_off,
                   bool accumulate = false) {
-    const float* w = dgw(wname);
+    const ConvWeights* w = dgw(wname);
     if (!w) return;
-    Act g;
-    g.off = gy_off;
-    g.C = cout;
-    g.R = R;
-    pl.emit_conv(g, nullptr, R, 0, R, 1, ksz, w, nullptr, 0, false, 0, accumulate ? ptr<float>(out_off) : nullptr,
-                 ptr<float>(out_off), cin);
-    Op op = pl.ops.back();
+    const Act g = view(gy_off, cout, R);
+    ConvDesc d;
+    d.x0 = &g;
+    d.ksz = ksz;
+    d.w = *w;
+    d.residual = accumulate ? ptr<float>(out_off) : nullptr;
+    d.out = ptr<float>(out_off);
+    d.Cout = cin;
+    pl.emit_conv(d);
+    const ConvParams cp = pl.ops.back().conv;
     pl.ops.pop_back();
-    ConvParams cp = op.conv;
     bops.push_back([cp](void* st) { return conv_launch(cp, st); });
   }
-  void emit_wgrad(size_t gy_off, int cout, const Act& x0, const Act* x1, int in_R, int ups, int out_R, int stride, int ksz,
-                  size_t coef, bool has_coef, int act, const std::string& wname, const std::string& bname) {
+  // wgrad of the forward convolution `f` (sources, geometry, coefficients on load, Cout) into the gradients of
+  // `layer`.weight / .bias
+  void emit_wgrad(size_t gy_off, const ConvDesc& f, const std::string& layer) {
     const float* gy = ptr<float>(gy_off);
+    const int cout = f.Cout;
     WgradParams w;
     memset(&w, 0, sizeof w);
     w.gy = gy;
-    w.src0 = ptr<float>(x0.off);
-    w.src1 = x1 ? ptr<float>(x1->off) : nullptr;
-    w.C0 = x0.C;
-    w.C1 = x1 ? x1->C : 0;
+    w.src0 = ptr<float>(f.x0->off);
+    w.src1 = f.x1 ? ptr<float>(f.x1->off) : nullptr;
+    w.C0 = f.x0->C;
+    w.C1 = f.x1 ? f.x1->C : 0;
     w.N = N;
-    w.ID = w.IH = w.IW = in_R;
-    w.ups = ups;
-    w.OD = w.OH = w.OW = out_R;
-    w.stride = stride;
-    w.pad = ksz == 3 ? 1 : 0;
-    w.ksz = ksz;
-    w.ntaps = ksz == 3 ? 27 : 1;
+    w.ID = w.IH = w.IW = f.in_size();
+    w.ups = f.ups;
+    w.OD = w.OH = w.OW = f.out_size();
+    w.stride = f.stride;
+    w.pad = f.ksz == 3 ? 1 : 0;
+    w.ksz = f.ksz;
+    w.ntaps = f.ksz == 3 ? 27 : 1;
     w.Cout = cout;
-    w.coef = has_coef ? ptr<float>(coef) : nullptr;
-    w.act = act;
+    w.coef = f.coef ? ptr<float>(*f.coef) : nullptr;
+    w.act = f.act;
     const size_t pb = wgrad_partial_bytes(w, u->ctx->num_cus);
     w.partial = ptr<float>(alloc(pb));
-    float* dw = pgrad(wname);
-    float* db = pgrad(bname);
+    float* dw = pgrad(layer + ".weight");
+    float* db = pgrad(layer + ".bias");
     double* cs = ptr<double>(alloc(colsum_scratch_bytes(cout)));
     const int ncu = u->ctx->num_cus;
-    const int64_t M = (int64_t)N * vox(out_R);
+    const int64_t M = (int64_t)N * vox(f.out_size());
     bops.push_back([w, dw, ncu](void* st) { return conv_wgrad_launch(w, dw, 0, ncu, st); });
     bops.push_back([gy, M, cout, cs, db](void* st) { return colsum_launch(gy, M, cout, cs, db, 0, st); });
   }
-  // GroupNorm (+FiLM) (+SiLU) backward of the (virtual concat) input of a conv: ga [M][Cin] -> gradients of x0 / x1
-  void emit_gn_bwd(const Act& x0, const Act* x1, size_t ga_off, size_t coef, size_t mom, const std::string& gname,
-                   const std::string& bname, const float* film, int film_cout, float* dfilm, int act) {
+  // the forward convolution of `cout` channels out of [x0 | x1], as emit_wgrad wants it
+  static ConvDesc fwd_conv(const Act& x0, const Act* x1, int cout) {
+    ConvDesc f;
+    f.x0 = &x0;
+    f.x1 = x1;
+    f.Cout = cout;
+    return f;
+  }
+  struct FilmGrad {  // a FiLM-modulated GroupNorm: the rows it was modulated with, and where their gradient goes
+    const float* film;
+    int cout;
+    float* dfilm;
+  };
+  // Backward of the stride-1 convolution `layer` = f(act(norm([x0 | x1]))) from the gradient of its output at gy_off:
+  // dgrad into a scratch ga [M][Cin], wgrad, then GroupNorm `norm` (+FiLM) (+SiLU) backward: ga -> gradients of x0 / x1
+  void bwd_norm_conv(size_t gy_off, const ConvDesc& f, const std::string& layer, const std::string& norm, size_t mom,
+                     const FilmGrad* film = nullptr) {
+    const Act &x0 = *f.x0, *x1 = f.x1;
+    const int Cin = x0.C + (x1 ? x1->C : 0);
+    const size_t ga = alloc((size_t)N * vox(x0.R) * Cin * sizeof(float));
+    emit_dgrad(gy_off, f.Cout, x0.R, layer + ".weight", Cin, f.ksz, ga);
+    emit_wgrad(gy_off, f, layer);
     GnBwdParams g;
     memset(&g, 0, sizeof g);
     g.x0 = ptr<float>(x0.off);
@@ -1089,20 +1192,20 @@ struct TrainPlanner {
     g.C1 = x1 ? x1->C : 0;
     g.N = N;
     g.V = vox(x0.R);
-    g.ga = ptr<float>(ga_off);
-    g.coef = ptr<float>(coef);
+    g.ga = ptr<float>(ga);
+    g.coef = ptr<float>(*f.coef);
     g.mom = ptr<float>(mom);
-    g.gamma = P(u, gname);
-    g.beta = P(u, bname);
-    g.film = film;
+    g.gamma = P(u, norm + ".weight");
+    g.beta = P(u, norm + ".bias");
+    g.film = film ? film->film : nullptr;
     g.film_stride = u->emb_rows;
-    g.film_cout = film_cout;
-    g.act = act;
+    g.film_cout = film ? film->cout : 0;
+    g.act = f.act;
     g.part = ptr<double>(alloc(gn_bwd_scratch_bytes(g)));
-    g.grp = ptr<float>(alloc((size_t)N * (g.C0 + g.C1) * 2 * sizeof(float)));
-    g.dgamma = pgrad(gname);
-    g.dbeta = pgrad(bname);
-    g.dfilm = dfilm;
+    g.grp = ptr<float>(alloc((size_t)N * Cin * 2 * sizeof(float)));
+    g.dgamma = pgrad(norm + ".weight");
+    g.dbeta = pgrad(norm + ".bias");
+    g.dfilm = film ? film->dfilm : nullptr;
     g.gx0 = ptr<float>(grad_of(x0, &g.acc0));
     if (x1) g.gx1 = ptr<float>(grad_of(*x1, &g.acc1));
     bops.push_back([g](void* st) { return gn_bwd_launch(g, st); });
@@ -1116,19 +1219,18 @@ struct TrainPlanner {
     if (gout == NONE) return;
     const Act* x1 = t.has_x1 ? &t.x1 : nullptr;
     // second conv: out = skip(x) + conv2(silu(film(gn2(h1))))
-    const size_t ga2 = alloc((size_t)M * cout * sizeof(float));
-    emit_dgrad(gout, cout, R, p + ".out_layers.3.weight", cout, 3, ga2);
-    emit_wgrad(gout, cout, t.h1, nullptr, R, 0, R, 1, 3, t.coefB, true, 1, p + ".out_layers.3.weight", p + ".out_layers.3.bias");
-    const int row = u->emb_row_off[p];
-    emit_gn_bwd(t.h1, nullptr, ga2, t.coefB, t.momB, p + ".out_layers.0.weight", p + ".out_layers.0.bias", t.film, cout,
-                dfilm_base + row, 1);
+    ConvDesc c2 = fwd_conv(t.h1, nullptr, cout);
+    c2.coef = t.coefB;
+    c2.act = 1;
+    const FilmGrad fg{t.film, cout, dfilm_base + u->emb_row_off.at(p)};
+    bwd_norm_conv(gout, c2, p + ".out_layers.3", p + ".out_layers.0", t.momB, &fg);
     const size_t gh1 = grad_ready(t.h1);
     if (gh1 == NONE) return;
     // first conv: h1 = conv1(silu(gn1([x0 | x1])))
-    const size_t ga1 = alloc((size_t)M * cin * sizeof(float));
-    emit_dgrad(gh1, cout, R, p + ".in_layers.2.weight", cin, 3, ga1);
-    emit_wgrad(gh1, cout, t.x0, x1, R, 0, R, 1, 3, t.coefA, true, 1, p + ".in_layers.2.weight", p + ".in_layers.2.bias");
-    emit_gn_bwd(t.x0, x1, ga1, t.coefA, t.momA, p + ".in_layers.0.weight", p + ".in_layers.0.bias", nullptr, 0, nullptr, 1);
+    ConvDesc c1 = fwd_conv(t.x0, x1, cout);
+    c1.coef = t.coefA;
+    c1.act = 1;
+    bwd_norm_conv(gh1, c1, p + ".in_layers.2", p + ".in_layers.0", t.momA);
     // skip connection: identity, or a 1x1x1 conv of the raw input
     int a0 = 0, a1 = 0;
     float* gx0 = ptr<float>(grad_of(t.x0, &a0));
@@ -1141,7 +1243,9 @@ struct TrainPlanner {
       const size_t gso = alloc((size_t)M * cin * sizeof(float));
       const float* gs = ptr<float>(gso);
       emit_dgrad(gout, cout, R, p + ".skip_connection.weight", cin, 1, gso);
-      emit_wgrad(gout, cout, t.x0, x1, R, 0, R, 1, 1, 0, false, 0, p + ".skip_connection.weight", p + ".skip_connection.bias");
+      ConvDesc cs = fwd_conv(t.x0, x1, cout);
+      cs.ksz = 1;
+      emit_wgrad(gout, cs, p + ".skip_connection");
       if (x1) {
         const int C0 = t.x0.C, C1 = t.x1.C;
         bops.push_back([gs, gx0, gx1, M, C0, C1, a0, a1](void* st) { return split_cat_launch(gs, gx0, gx1, M, C0, C1, a0, a1, st); });
@@ -1154,8 +1258,9 @@ struct TrainPlanner {
 
   void bwd_attn(const Tape& t) {
     const std::string& p = t.b.prefix;
-    const int C = t.x0.C, R = t.x0.R, H = u->cfg.num_heads, ch = C / H;
+    const int C = t.x0.C, R = t.x0.R, H = u->cfg.num_heads;
     const int64_t T = vox(R), M = (int64_t)N * T;
+    const AttnDims dims{N, H, C, T};
     const size_t gout = grad_ready(t.out);
     if (gout == NONE) return;
     int ax = 0;
@@ -1166,14 +1271,13 @@ struct TrainPlanner {
       bops.push_back([gx, goutp, n, ax](void* st) { return add_launch(gx, goutp, n, ax, st); });
     }
     // proj_out (1x1 over the attention output a)
-    Act av;
-    av.off = t.a;
-    av.C = C;
-    av.R = R;
+    const Act av = view(t.a, C, R);
     const size_t ga_off = alloc((size_t)M * C * sizeof(float));
     float* ga = ptr<float>(ga_off);
     emit_dgrad(gout, C, R, p + ".proj_out.weight", C, 1, ga_off);
-    emit_wgrad(gout, C, av, nullptr, R, 0, R, 1, 1, 0, false, 0, p + ".proj_out.weight", p + ".proj_out.bias");
+    ConvDesc cp = fwd_conv(av, nullptr, C);
+    cp.ksz = 1;
+    emit_wgrad(gout, cp, p + ".proj_out");
     // attention core: P = softmax(s2 q k^T); dP = ga v^T; dS = P (dP - rowsum(dP P)); dv = P^T ga; dq = s2 dS k; dk = s2 dS^T q
     const size_t sb = (size_t)N * H * T * T * sizeof(float);
     float* Pm = ptr<float>(alloc(sb));
@@ -1181,90 +1285,59 @@ struct TrainPlanner {
     float* Tm = ptr<float>(alloc(sb));
     const size_t gqkv_off = alloc((size_t)M * 3 * C * sizeof(float));
     float* gqkv = ptr<float>(gqkv_off);
-    const float* qkv = ptr<float>(t.qkv);
-    const double sc = 1.0 / sqrt(sqrt((double)ch));
-    const float s2 = (float)(sc * sc);
-    auto gemm = [&](const float* A, int lda, int64_t sa0, int64_t sa1, const float* B, int ldb, int64_t sb0, int64_t sb1,
-                    int kmajor, float* Cc, int ldc, int64_t sc0, int64_t sc1, int Mm, int Nn, int K, float alpha) {
-      GemmParams g;
-      memset(&g, 0, sizeof g);
-      g.A = A;
-      g.B = B;
-      g.C = Cc;
-      g.M = Mm;
-      g.Nn = Nn;
-      g.K = K;
-      g.lda = lda;
-      g.ldb = ldb;
-      g.ldc = ldc;
-      g.nb0 = N;
-      g.nb1 = H;
-      g.sa0 = sa0;
-      g.sa1 = sa1;
-      g.sb0 = sb0;
-      g.sb1 = sb1;
-      g.sc0 = sc0;
-      g.sc1 = sc1;
-      g.b_kmajor = kmajor;
-      g.alpha = alpha;
+    float* qkv = ptr<float>(t.qkv);
+    const float s2 = dims.scale2();
+    auto gemm = [&](AttnMat A, AttnMat B, bool b_kmajor, AttnMat Cc, float alpha) {
+      const GemmParams g = attn_gemm(dims, A, B, b_kmajor, Cc, alpha);
       bops.push_back([g](void* st) { return gemm_launch(g, st); });
     };
-    const int64_t TT = T * T, q3 = T * 3 * C;
-    const int Ti = (int)T;
-    gemm(qkv, 3 * C, q3, 3 * ch, qkv + ch, 3 * C, q3, 3 * ch, 0, Pm, Ti, (int64_t)H * TT, TT, Ti, Ti, ch, s2);
-    {
-      const int64_t rows = (int64_t)N * H * T;
-      bops.push_back([Pm, rows, Ti](void* st) { return softmax_rows_launch(Pm, rows, Ti, st); });
-    }
-    gemm(ga, C, T * C, ch, qkv + 2 * ch, 3 * C, q3, 3 * ch, 0, dS, Ti, (int64_t)H * TT, TT, Ti, Ti, ch, 1.0f);
-    {
-      const int64_t rows = (int64_t)N * H * T;
-      bops.push_back([Pm, dS, rows, Ti](void* st) { return attn_ds_launch(Pm, dS, rows, Ti, st); });
-    }
-    const int NH = N * H;
+    const int Ti = (int)T, NH = N * H;
+    const int64_t rows = (int64_t)NH * T;
+    gemm(dims.qkv(qkv, 0), dims.qkv(qkv, 1), false, dims.scores(Pm), s2);
+    bops.push_back([Pm, rows, Ti](void* st) { return softmax_rows_launch(Pm, rows, Ti, st); });
+    gemm(dims.heads(ga), dims.qkv(qkv, 2), false, dims.scores(dS), 1.0f);
+    bops.push_back([Pm, dS, rows, Ti](void* st) { return attn_ds_launch(Pm, dS, rows, Ti, st); });
     bops.push_back([Pm, Tm, NH, Ti](void* st) { return transpose_launch(Pm, Tm, NH, Ti, st); });
-    gemm(Tm, Ti, (int64_t)H * TT, TT, ga, C, T * C, ch, 1, gqkv + 2 * ch, 3 * C, q3, 3 * ch, Ti, ch, Ti, 1.0f);           // dv
-    gemm(dS, Ti, (int64_t)H * TT, TT, qkv + ch, 3 * C, q3, 3 * ch, 1, gqkv, 3 * C, q3, 3 * ch, Ti, ch, Ti, s2);           // dq
+    gemm(dims.scores(Tm), dims.heads(ga), true, dims.qkv(gqkv, 2), 1.0f);  // dv
+    gemm(dims.scores(dS), dims.qkv(qkv, 1), true, dims.qkv(gqkv, 0), s2);    // dq
     bops.push_back([dS, Tm, NH, Ti](void* st) { return transpose_launch(dS, Tm, NH, Ti, st); });
-    gemm(Tm, Ti, (int64_t)H * TT, TT, qkv, 3 * C, q3, 3 * ch, 1, gqkv + ch, 3 * C, q3, 3 * ch, Ti, ch, Ti, s2);            // dk
+    gemm(dims.scores(Tm), dims.qkv(qkv, 0), true, dims.qkv(gqkv, 1), s2);  // dk
     // qkv conv (1x1, C -> 3C, GroupNorm applied on load, no activation)
-    const size_t gxn = alloc((size_t)M * C * sizeof(float));
-    emit_dgrad(gqkv_off, 3 * C, R, p + ".qkv.weight", C, 1, gxn);
-    emit_wgrad(gqkv_off, 3 * C, t.x0, nullptr, R, 0, R, 1, 1, t.coefA, true, 0, p + ".qkv.weight", p + ".qkv.bias");
-    emit_gn_bwd(t.x0, nullptr, gxn, t.coefA, t.momA, p + ".norm.weight", p + ".norm.bias", nullptr, 0, nullptr, 0);
+    ConvDesc cq = fwd_conv(t.x0, nullptr, 3 * C);
+    cq.ksz = 1;
+    cq.coef = t.coefA;
+    bwd_norm_conv(gqkv_off, cq, p + ".qkv", p + ".norm", t.momA);
   }
 
   void bwd_conv(const Tape& t) {  // input conv / Downsample / Upsample / output head
-    const int cin = t.b.cin, cout = t.b.cout, Ri = t.x0.R, Ro = t.out.R;
+    const BlockKind kind = t.b.kind;
+    const int cin = t.b.cin, cout = t.b.cout, Ri = t.x0.R, Ro = t.out.R, Nn = N;
     const size_t gout = grad_ready(t.out);
     if (gout == NONE) return;
-    if (t.kind == 100) {  // y = conv(silu(gn(h)))
-      const int64_t M = (int64_t)N * vox(Ri);
-      const size_t ga = alloc((size_t)M * cin * sizeof(float));
-      emit_dgrad(gout, cout, Ri, "out.2.weight", cin, 3, ga);
-      emit_wgrad(gout, cout, t.x0, nullptr, Ri, 0, Ri, 1, 3, t.coefA, true, 1, "out.2.weight", "out.2.bias");
-      emit_gn_bwd(t.x0, nullptr, ga, t.coefA, t.momA, "out.0.weight", "out.0.bias", nullptr, 0, nullptr, 1);
+    ConvDesc f = fwd_conv(t.x0, nullptr, cout);
+    if (kind == B_HEAD) {  // y = conv(silu(gn(h)))
+      f.coef = t.coefA;
+      f.act = 1;
+      bwd_norm_conv(gout, f, "out.2", "out.0", t.momA);
       return;
     }
     int ax = 0;
     const size_t gx_off = grad_of(t.x0, &ax);
     float* gx = ptr<float>(gx_off);
     const float* goutp = ptr<float>(gout);
-    const std::string wn = t.b.prefix + (t.kind == B_DOWN ? ".op.weight" : t.kind == B_UP ? ".conv.weight" : ".weight");
-    const std::string bn = t.b.prefix + (t.kind == B_DOWN ? ".op.bias" : t.kind == B_UP ? ".conv.bias" : ".bias");
-    if (t.kind == B_CONV) {
+    const std::string layer = t.b.prefix + (kind == B_DOWN ? ".op" : kind == B_UP ? ".conv" : "");
+    const std::string wn = layer + ".weight";
+    if (kind == B_CONV) {
       if (ax) {
         err = "internal: the input conv's source already has a gradient";
         return;
       }
       emit_dgrad(gout, cout, Ri, wn, cin, 3, gx_off);
-      emit_wgrad(gout, cout, t.x0, nullptr, Ri, 0, Ro, 1, 3, 0, false, 0, wn, bn);
-    } else if (t.kind == B_DOWN) {
-      const float* wt = dgw(wn);
+    } else if (kind == B_DOWN) {
+      const ConvWeights* wt = dgw(wn);
       if (!wt) return;
-      const int Nn = N;
       const char* zi = getenv("HOLO_DGRAD_S2_DIRECT");  // development / test knob: 1 = conv_dgrad_s2_kernel everywhere
-      if (!(zi && zi[0] == '1') && u->dgrad_w.count(wn + "#s1") && Ri == 2 * Ro && (Ri % 8) == 0) {
+      if (!(zi && zi[0] == '1') && find_dgw(wn + "#s1") && Ri == 2 * Ro && (Ri % 8) == 0) {
         // zero insertion + the stride-1 transposed convolution on the forward's conv kernels (8x the multiply-adds, on the
         // Winograd kernels: 0.24 instead of 1.35 ms at 64^3 <- 32^3)
         const size_t gz_off = alloc((size_t)N * vox(Ri) * cout * sizeof(float));
@@ -1272,36 +1345,40 @@ struct TrainPlanner {
         bops.push_back([goutp, gz, Nn, Ro, cout](void* st) { return zero_insert2_launch(goutp, gz, Nn, Ro, cout, st); });
         emit_dgrad(gz_off, cout, Ri, wn + "#s1", cin, 3, gx_off, ax != 0);
       } else {
-        bops.push_back([goutp, wt, gx, Nn, Ri, Ro, cin, cout, ax](void* st) {
-          return conv_dgrad_s2_launch(goutp, wt, gx, Nn, Ri, Ro, cin, cout, ax, st);
+        const float* wtp = wt->f32;
+        bops.push_back([goutp, wtp, gx, Nn, Ri, Ro, cin, cout, ax](void* st) {
+          return conv_dgrad_s2_launch(goutp, wtp, gx, Nn, Ri, Ro, cin, cout, ax, st);
         });
       }
-      emit_wgrad(gout, cout, t.x0, nullptr, Ri, 0, Ro, 2, 3, 0, false, 0, wn, bn);
+      f.out_R = Ro;
+      f.stride = 2;
     } else {  // B_UP: conv at the fine size of the nearest-upsampled input
       const int64_t Mf = (int64_t)N * vox(Ro);
       const size_t gup_off = alloc((size_t)Mf * cin * sizeof(float));
       float* gup = ptr<float>(gup_off);
       emit_dgrad(gout, cout, Ro, wn, cin, 3, gup_off);
-      const int Nn = N;
       bops.push_back([gup, gx, Nn, Ri, cin, ax](void* st) { return sumpool2_launch(gup, gx, Nn, Ri, cin, ax, st); });
-      emit_wgrad(gout, cout, t.x0, nullptr, Ro, 1, Ro, 1, 3, 0, false, 0, wn, bn);
+      f.in_R = Ro;
+      f.ups = 1;
     }
+    emit_wgrad(gout, f, layer);
   }
 
   int build() {
     const HoloUnetCfg& c = u->cfg;
+    tp.invalidate();
     pl.build();
     // parameter gradients: one region in the reference's layouts; emb_layers rows alias the concatenated matrix
-    u->grad_off.assign(u->params.size(), 0);
+    tp.grad_off.assign(u->params.size(), 0);
     const size_t gembw = alloc((size_t)u->emb_rows * u->ted * sizeof(float));
     const size_t gembb = alloc((size_t)u->emb_rows * sizeof(float));
     for (size_t i = 0; i < u->params.size(); ++i) {
       const ParamSlot& s = u->params[i];
       if (s.kind == P_EMB_W || s.kind == P_EMB_B) {
-        const int row = u->emb_row_off[s.name.substr(0, s.name.rfind(".emb_layers"))];
-        u->grad_off[i] = s.kind == P_EMB_W ? gembw + (size_t)row * u->ted * sizeof(float) : gembb + (size_t)row * sizeof(float);
+        const int row = u->emb_row_off.at(s.name.substr(0, s.name.rfind(".emb_layers")));
+        tp.grad_off[i] = s.kind == P_EMB_W ? gembw + (size_t)row * u->ted * sizeof(float) : gembb + (size_t)row * sizeof(float);
       } else {
-        u->grad_off[i] = alloc((size_t)s.numel * sizeof(float));
+        tp.grad_off[i] = alloc((size_t)s.numel * sizeof(float));
       }
     }
     // the gradient of the output arrives NCDHW and is laid out channels-last as the gradient of y
@@ -1309,15 +1386,14 @@ struct TrainPlanner {
     const int64_t V = vox(R);
     const size_t gy = alloc((size_t)N * V * c.out_channels * sizeof(float));
     grads[pl.y_out.off] = std::make_pair(gy, true);
-    u->gy_off = gy;
-    u->y_off = pl.y_out.off;
+    tp.gy_off = gy;
     const size_t dfilm = alloc((size_t)N * u->emb_rows * sizeof(float));
     float* dfilm_base = ptr<float>(dfilm);
     for (int i = (int)tape.size() - 1; i >= 0 && err.empty(); --i) {
       const Tape& t = tape[i];
-      if (t.kind == B_RES)
+      if (t.b.kind == B_RES)
         bwd_res(t, dfilm_base);
-      else if (t.kind == B_ATTN)
+      else if (t.b.kind == B_ATTN)
         bwd_attn(t);
       else
         bwd_conv(t);
@@ -1337,7 +1413,7 @@ struct TrainPlanner {
       bops.push_back([dfilm_base, embs, w, dw, db, gembs, Nn, rows, K](void* st) {
         return film_bwd_launch(dfilm_base, embs, w, dw, db, gembs, Nn, rows, K, st);
       });
-      HoloUnet* uu = u;
+      const HoloUnet* uu = u;  // (t_dev is the running call's)
       const int mc = c.model_channels;
       const float *w1 = P(u, "time_embed.0.weight"), *b1 = P(u, "time_embed.0.bias"), *w2 = P(u, "time_embed.2.weight"),
                   *b2 = P(u, "time_embed.2.bias");
@@ -1352,99 +1428,124 @@ struct TrainPlanner {
       set_error("internal: the network input has no gradient");
       return HOLO_E_STATE;
     }
-    u->gx_off = gi->second.first;
+    tp.gx_off = gi->second.first;
+    tp.bytes = tp.fwd.bytes = pl.arena_base + pl.arena.peak;  // (the backward's buffers grew the arena after pl.build())
     return 0;
   }
-  size_t total_bytes() const { return pl.total_bytes(); }
 };
 
-int ensure_train_plan(HoloUnet* u, int batch, void* ws) {
-  if (u->tplan_batch == batch && u->tplan_ws == ws && !u->tops.empty()) return 0;
-  if (u->compute_mode != 0) {
-    set_error("holo_unet_backward: the backward pass runs in the fp32 mode only");
-    return HOLO_E_UNSUPPORTED;
-  }
+bool params_set(const HoloUnet* u, const char* entry) {
   for (auto& s : u->params)
     if (!s.set) {
-      set_error("holo_unet_backward: parameter '%s' has not been set", s.name.c_str());
-      return HOLO_E_STATE;
+      set_error("%s: parameter '%s' has not been set", entry, s.name.c_str());
+      return false;
     }
-  u->tops.clear();
-  u->bops.clear();
-  TrainPlanner tp(u, batch, ws, u->tops, u->bops);
-  int rc = tp.build();
-  if (rc) {
-    u->tops.clear();
-    u->bops.clear();
-    return rc;
+  return true;
+}
+
+// the training plan of (batch, ws), rebuilt when either changed; `entry` names the caller in the workspace message
+int ensure_train_plan(HoloUnet* u, const char* entry, int batch, void* ws, size_t ws_bytes) {
+  if (!u->tplan.built_for(batch, ws)) {
+    if (u->compute_mode != 0) {
+      set_error("holo_unet_backward: the backward pass runs in the fp32 mode only");
+      return HOLO_E_UNSUPPORTED;
+    }
+    if (!params_set(u, "holo_unet_backward")) return HOLO_E_STATE;
+    TrainPlanner tp(u, batch, ws, u->tplan);
+    int rc = tp.build();
+    if (!rc && !tp.pl.regions_ok()) {
+      set_error("internal: small-buffer regions overflow");
+      rc = HOLO_E_INVALID;
+    }
+    if (rc) {
+      u->tplan.invalidate();
+      return rc;
+    }
   }
-  if (!tp.pl.regions_ok()) {
-    set_error("internal: small-buffer regions overflow");
-    return HOLO_E_INVALID;
+  if (ws_bytes < u->tplan.bytes) {
+    set_error("%s: workspace too small (%zu < %zu)", entry, ws_bytes, u->tplan.bytes);
+    u->tplan.invalidate();
+    return HOLO_E_WORKSPACE;
   }
-  u->tws_need = tp.total_bytes();
-  u->tplan_batch = batch;
-  u->tplan_ws = ws;
-  u->plan_batch = -1;  // block_outputs were rewritten
   return 0;
 }
 
 int ensure_plan(HoloUnet* u, int batch, void* ws) {
-  if (u->plan_batch == batch && u->plan_ws == ws && !u->ops.empty()) return 0;
-  for (auto& s : u->params)
-    if (!s.set) {
-      set_error("holo_unet_forward: parameter '%s' has not been set", s.name.c_str());
-      return HOLO_E_STATE;
-    }
+  if (u->plan.built_for(batch, ws)) return 0;
+  if (!params_set(u, "holo_unet_forward")) return HOLO_E_STATE;
   if (u->batch_invariant && u->compute_mode != 0) {  // (both setters refuse this; a guard for the plan itself)
     set_error("holo_unet_forward: the batch-invariant plan is exact-fp32 only");
     return HOLO_E_UNSUPPORTED;
   }
-  Planner pl(u, batch, ws, u->ops);
+  Planner pl(u, batch, ws, u->plan);
   pl.build();
+  int rc = 0;
   if (!pl.err.empty()) {
-    u->ops.clear();
     set_error("holo_unet_forward: %s", pl.err.c_str());
-    return HOLO_E_UNSUPPORTED;
-  }
-  if (!pl.regions_ok()) {
+    rc = HOLO_E_UNSUPPORTED;
+  } else if (!pl.regions_ok()) {
     set_error("internal: small-buffer regions overflow");
-    return HOLO_E_INVALID;
+    rc = HOLO_E_INVALID;
   }
-  u->ws_need = pl.total_bytes();
-  u->plan_batch = batch;
-  u->plan_ws = ws;
-  return 0;
+  if (rc) u->plan.invalidate();
+  return rc;
 }
 
-int run_op(HoloUnet* u, const Op& op, int N, const float* x, const int64_t* t, float* y, void* stream) {
+int run_op(const HoloUnet* u, const Op& op, int N, const float* x, const int64_t* t, float* y, void* stream) {
   switch (op.kind) {
-    case OP_MEMSET:
-      HIP_TRY(hipMemsetAsync(op.o0, 0, op.bytes, (hipStream_t)stream));
-      return 0;
     case OP_IN:
-      return ncdhw_to_ndhwc_launch(x, op.o0, N, op.i0, op.l0, 0, stream, op.i1);
+      return ncdhw_to_ndhwc_launch(x, op.in.dst, N, op.in.C, op.in.V, 0, stream, op.in.dst_bf16);
     case OP_TEMB:
-      return time_embed_launch(t, N, u->cfg.model_channels, u->ted, op.f0, op.f1, op.f2, op.f3, op.o0, op.o1, stream);
+      return time_embed_launch(t, N, u->cfg.model_channels, u->ted, op.temb.w1, op.temb.b1, op.temb.w2, op.temb.b2,
+                               op.temb.emb, op.temb.emb_silu, stream);
     case OP_EMBLIN:
-      return rows_linear_launch(op.f0, op.f1, op.f2, op.o0, N, u->emb_rows, u->ted, stream);
+      return rows_linear_launch(op.emblin.emb_silu, op.emblin.w, op.emblin.b, op.emblin.out, N, u->emb_rows, u->ted, stream);
     case OP_STATS:
-      return gn_stats_launch(op.f0, op.dout, N, op.i0, op.l0, stream, op.i1);
-    case OP_FINAL:
-      return gn_finalize_launch(op.d0, op.i0, op.i4, op.d1, op.i1, op.i5, N, op.l0, 32, 1e-5f, op.f0, op.f1, op.f2,
-                                op.i2, op.i3, op.o0, stream, op.o1);
+      return gn_stats_launch(op.stats.x, op.stats.part, N, op.stats.C, op.stats.V, stream, op.stats.x_bf16);
+    case OP_FINAL: {
+      const GnFinalize& f = op.fin;
+      return gn_finalize_launch(f.part0, f.C0, f.B0, f.part1, f.C1, f.B1, N, f.V, 32, 1e-5f, f.gamma, f.beta, f.film,
+                                f.film_stride, f.film_cout, f.coef, stream, f.moments);
+    }
     case OP_CONV:
       return conv_launch(op.conv, stream);
     case OP_GEMM:
       return gemm_launch(op.gemm, stream);
     case OP_SOFTMAX:
-      return softmax_rows_launch(op.o0, op.l0, op.i0, stream);
-    case OP_FLASH:
-      if (op.i0 == 2) return flash_attn_bf16v2_launch(op.attn, op.o1, op.i1, u->ctx->num_cus, stream, op.i2);
-      return flash_attn_launch(op.attn, stream);
+      return softmax_rows_launch(op.softmax.S, op.softmax.rows, op.softmax.cols, stream);
+    case OP_FLASH: {
+      const Flash& f = op.flash;
+      if (f.form == 2) return flash_attn_bf16v2_launch(f.attn, f.packed, f.out_bf16, u->ctx->num_cus, stream, f.operands_packed);
+      return flash_attn_launch(f.attn, stream);
+    }
     case OP_OUT:
-      return ndhwc_to_ncdhw_launch(op.f0, y, N, op.i0, op.l0, stream);
+      return ndhwc_to_ncdhw_launch(op.out.src, y, N, op.out.C, op.out.V, stream);
   }
+  return 0;
+}
+
+// the forward of a plan (inference or training) on the caller's tensors; y may be null where the caller does not want it
+int run_plan(const HoloUnet* u, const Plan& plan, const float* x, const int64_t* t, float* y, void* stream) {
+  for (const Op& op : plan.ops) {
+    if (op.kind == OP_OUT && !y) continue;
+    const int rc = run_op(u, op, plan.batch, x, t, y, stream);
+    if (rc) return rc < 0 ? rc : HOLO_E_INVALID;
+  }
+  return 0;
+}
+// the backward launches of a training plan whose taped forward has run on `workspace`
+int run_backward(const HoloUnet* u, const TrainPlan& tp, const float* grad_out, float* grad_x, void* workspace, void* stream) {
+  const HoloUnetCfg& c = u->cfg;
+  const int batch = tp.fwd.batch;
+  const int64_t V = (int64_t)c.image_size * c.image_size * c.image_size;
+  if (ncdhw_to_ndhwc_launch(grad_out, (float*)((char*)workspace + tp.gy_off), batch, c.out_channels, V, 0, stream))
+    return HOLO_E_INVALID;
+  for (auto& f : tp.bops) {
+    const int rc = f(stream);
+    if (rc) return rc < 0 ? rc : HOLO_E_INVALID;
+  }
+  if (grad_x && ndhwc_to_ncdhw_launch((const float*)((char*)workspace + tp.gx_off), grad_x, batch, c.in_channels, V, stream))
+    return HOLO_E_INVALID;
   return 0;
 }
 
@@ -1525,13 +1626,13 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
   total += (u->emb_rows + 63) & ~63;
   if (hipMalloc((void**)&u->pstore, (size_t)total * sizeof(float)) != hipSuccess) {
     set_error("holo_unet_create: hipMalloc of %lld parameter floats failed", (long long)total);
-    delete u;
+    holo_unet_destroy(u);
     return HOLO_E_HIP;
   }
   float* cur = u->pstore;
   for (auto& s : u->params)
     if (s.kind == P_PLAIN || s.kind == P_CONV3 || s.kind == P_CONV1) {
-      s.priv = cur;
+      s.w.f32 = cur;
       cur += (priv_numel(s) + 63) & ~(int64_t)63;
     }
   {  // bf16 copies of the conv weights (same padded element counts, 2 bytes each)
@@ -1540,16 +1641,14 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
       if (s.kind == P_CONV3 || s.kind == P_CONV1) tb += 4 * ((priv_numel(s) + 63) & ~(int64_t)63);  // hi, mid, lo planes + the 32x32x16 packing of hi
     if (hipMalloc((void**)&u->pstore_bf, (size_t)tb * sizeof(uint16_t)) != hipSuccess) {
       set_error("holo_unet_create: hipMalloc of %lld bf16 weights failed", (long long)tb);
-      (void)hipFree(u->pstore);
-      delete u;
+      holo_unet_destroy(u);
       return HOLO_E_HIP;
     }
     uint16_t* cb = u->pstore_bf;
     for (auto& s : u->params)
       if (s.kind == P_CONV3 || s.kind == P_CONV1) {
-        s.priv_bf = cb;
-        u->bf_of[s.priv] = cb;
-        u->bft_of[s.priv] = cb + 3 * priv_numel(s);  // plane 3 (the repack kernel lays the planes out back to back)
+        s.w.bf = cb;
+        s.w.bft = cb + 3 * priv_numel(s);  // plane 3 (the repack kernel lays the planes out back to back)
         cb += 4 * ((priv_numel(s) + 63) & ~(int64_t)63);
       }
   }
@@ -1575,22 +1674,18 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
     if (tw > 0) {
       if (hipMalloc((void**)&u->pstore_wino, (size_t)tw * sizeof(float)) != hipSuccess) {
         set_error("holo_unet_create: hipMalloc of %lld Winograd weights failed", (long long)tw);
-        (void)hipFree(u->pstore);
-        (void)hipFree(u->pstore_bf);
-        delete u;
+        holo_unet_destroy(u);
         return HOLO_E_HIP;
       }
       float* cw = u->pstore_wino;
       for (auto& s : u->params) {
         const int64_t nw2 = wino2_numel(s);
         if (nw2 == 0) continue;
-        s.priv_wino2 = cw;
-        u->wino2_of[s.priv] = cw;
+        s.w.wino2 = cw;
         cw += (nw2 + 63) & ~(int64_t)63;
         const int64_t nw3 = wino3_numel(s);
         if (nw3) {
-          s.priv_wino3 = cw;
-          u->wino3_of[s.priv] = cw;
+          s.w.wino3 = cw;
           cw += (nw3 + 63) & ~(int64_t)63;
         }
       }
@@ -1603,7 +1698,7 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
     if (s.kind == P_EMB_W || s.kind == P_EMB_B) {
       std::string prefix = s.name.substr(0, s.name.rfind(".emb_layers"));
       int row = u->emb_row_off[prefix];
-      s.priv = s.kind == P_EMB_W ? u->emb_w + (int64_t)row * u->ted : u->emb_b + row;
+      s.w.f32 = s.kind == P_EMB_W ? u->emb_w + (int64_t)row * u->ted : u->emb_b + row;
     }
   }
   *out = u;
@@ -1615,12 +1710,9 @@ int holo_unet_destroy(HoloUnet* net) {
   if (net->pstore) (void)hipFree(net->pstore);
   if (net->pstore_bf) (void)hipFree(net->pstore_bf);
   if (net->pstore_wino) (void)hipFree(net->pstore_wino);
-  for (auto& kv : net->dgrad_w)
-    if (kv.second) (void)hipFree(kv.second);
-  for (auto& kv : net->dgrad_wino3)
-    if (kv.second) (void)hipFree(kv.second);
-  for (auto& kv : net->dgrad_wino2)
-    if (kv.second) (void)hipFree(kv.second);
+  for (auto& kv : net->dgrad)
+    for (float* buf : {kv.second.f32, kv.second.wino2, kv.second.wino3})
+      if (buf) (void)hipFree(buf);
   if (net->dgrad_tmp) (void)hipFree(net->dgrad_tmp);
   delete net;
   return 0;
@@ -1667,29 +1759,16 @@ int holo_unet_set_param(HoloUnet* net, const char* name, const void* dev_ptr, in
     return HOLO_E_INVALID;
   }
   if (s.kind == P_CONV3 || s.kind == P_CONV1) {
-    int rc = repack_conv_weight_launch((const float*)dev_ptr, s.priv, (int)s.shape[0], (int)s.shape[1],
-                                       s.kind == P_CONV3 ? 27 : 1, pad_cout((int)s.shape[0]), pad_cin((int)s.shape[1]),
-                                       stream);
+    const float* src = (const float*)dev_ptr;
+    const int Co = (int)s.shape[0], Ci = (int)s.shape[1], taps = s.kind == P_CONV3 ? 27 : 1, CoP = pad_cout(Co), CiP = pad_cin(Ci);
+    int rc = repack_conv_weight_launch(src, s.w.f32, Co, Ci, taps, CoP, CiP, stream);
+    if (!rc) rc = repack_conv_weight_bf16_launch(src, s.w.bf, Co, Ci, taps, CoP, CiP, stream);
+    if (!rc && s.w.wino2) rc = repack_conv_weight_wino2_launch(src, s.w.wino2, Co, Ci, taps, CoP, CiP, stream);
+    if (!rc && s.w.wino3) rc = repack_conv_weight_wino3_launch(src, s.w.wino3, Co, Ci, taps, CoP, CiP, stream);
     if (rc) return rc;
-    rc = repack_conv_weight_bf16_launch((const float*)dev_ptr, s.priv_bf, (int)s.shape[0], (int)s.shape[1],
-                                        s.kind == P_CONV3 ? 27 : 1, pad_cout((int)s.shape[0]), pad_cin((int)s.shape[1]),
-                                        stream);
-    if (rc) return rc;
-    if (s.priv_wino2) {
-      rc = repack_conv_weight_wino2_launch((const float*)dev_ptr, s.priv_wino2, (int)s.shape[0], (int)s.shape[1],
-                                           s.kind == P_CONV3 ? 27 : 1, pad_cout((int)s.shape[0]),
-                                           pad_cin((int)s.shape[1]), stream);
-      if (rc) return rc;
-    }
-    if (s.priv_wino3) {
-      rc = repack_conv_weight_wino3_launch((const float*)dev_ptr, s.priv_wino3, (int)s.shape[0], (int)s.shape[1],
-                                           s.kind == P_CONV3 ? 27 : 1, pad_cout((int)s.shape[0]), pad_cin((int)s.shape[1]),
-                                           stream);
-      if (rc) return rc;
-    }
   } else {  // biases, GroupNorm parameters, Linear layers: a copy kernel with system-scope loads (holo_ld_sys) - like the
             // weight repack kernels, every ingestion of a caller-provided tensor reads it past the L2
-    if (copy_sys_launch((const float*)dev_ptr, s.priv, s.numel, stream)) return HOLO_E_INVALID;
+    if (copy_sys_launch((const float*)dev_ptr, s.w.f32, s.numel, stream)) return HOLO_E_INVALID;
   }
   s.set = true;
   return 0;
@@ -1708,8 +1787,8 @@ int holo_unet_set_compute_dtype(HoloUnet* net, int dtype) {
   }
   if (mode != net->compute_mode) {
     net->compute_mode = mode;
-    net->plan_batch = -1;   // re-plan: the conv ops carry the choice
-    net->ws_cache.clear();  // ... and the plan's workspace differs between modes (fused skips, statistics slabs)
+    net->plan.invalidate();  // re-plan: the conv ops carry the choice
+    net->ws_cache.clear();   // ... and the plan's workspace differs between modes (fused skips, statistics slabs)
   }
   return 0;
 }
@@ -1729,8 +1808,7 @@ int holo_unet_set_batch_invariant(HoloUnet* net, int on) {
   }
   if ((on != 0) != net->batch_invariant) {
     net->batch_invariant = on != 0;
-    net->plan_batch = -1;  // re-plan: the conv ops carry the choices (ws_cache is keyed on the flag)
-    net->ops.clear();
+    net->plan.invalidate();  // re-plan: the conv ops carry the choices (ws_cache is keyed on the flag)
   }
   return 0;
 }
@@ -1740,15 +1818,10 @@ size_t holo_unet_workspace_bytes(HoloUnet* net, int batch) {
   const std::pair<int, bool> key(batch, net->batch_invariant);
   auto it = net->ws_cache.find(key);
   if (it != net->ws_cache.end()) return it->second;
-  std::vector<Op> tmp;
-  Planner pl(net, batch, nullptr, tmp);
-  pl.build();
-  size_t b = pl.total_bytes();
-  net->ws_cache[key] = b;
-  // the sizing pass overwrote block_outputs with null-based offsets; force a re-plan
-  net->plan_batch = -1;
-  net->ops.clear();
-  return b;
+  Plan sizing;  // built on a null base and dropped
+  Planner(net, batch, nullptr, sizing).build();
+  net->ws_cache[key] = sizing.bytes;
+  return sizing.bytes;
 }
 
 int holo_unet_forward(HoloUnet* net, int batch, const float* x, const int64_t* timesteps, float* y, void* workspace,
@@ -1759,15 +1832,11 @@ int holo_unet_forward(HoloUnet* net, int batch, const float* x, const int64_t* t
   }
   int rc = ensure_plan(net, batch, workspace);
   if (rc) return rc;
-  if (workspace_bytes < net->ws_need) {
-    set_error("holo_unet_forward: workspace too small (%zu < %zu)", workspace_bytes, net->ws_need);
+  if (workspace_bytes < net->plan.bytes) {
+    set_error("holo_unet_forward: workspace too small (%zu < %zu)", workspace_bytes, net->plan.bytes);
     return HOLO_E_WORKSPACE;
   }
-  for (const Op& op : net->ops) {
-    rc = run_op(net, op, batch, x, timesteps, y, stream);
-    if (rc) return rc < 0 ? rc : HOLO_E_INVALID;
-  }
-  return 0;
+  return run_plan(net, net->plan, x, timesteps, y, stream);
 }
 
 int holo_unet_forward_cl(HoloUnet* net, int batch, const float* x_cl, const int64_t* timesteps, float* y_cl, void* workspace,
@@ -1776,49 +1845,31 @@ int holo_unet_forward_cl(HoloUnet* net, int batch, const float* x_cl, const int6
     set_error("holo_unet_forward_cl: null/invalid argument");
     return HOLO_E_INVALID;
   }
-  const bool bf16_storage = net->compute_mode == 1;  // the plan's input buffer is bf16: a cast replaces the layout pass
   int rc = ensure_plan(net, batch, workspace);
   if (rc) return rc;
-  if (workspace_bytes < net->ws_need) {
-    set_error("holo_unet_forward_cl: workspace too small (%zu < %zu)", workspace_bytes, net->ws_need);
+  const Plan& plan = net->plan;
+  if (workspace_bytes < plan.bytes) {
+    set_error("holo_unet_forward_cl: workspace too small (%zu < %zu)", workspace_bytes, plan.bytes);
     return HOLO_E_WORKSPACE;
   }
-  // the plan's own input / output buffers: every convolution that reads the one or writes the other is pointed at the
-  // caller's channels-last tensors instead, and the two layout passes are skipped
-  // (by POSITION in the op list, not by address: the arena hands the input buffer's memory to later activations)
-  const float* in_buf = nullptr;
-  const float* out_buf = nullptr;
-  int first_conv = -1, last_conv = -1;
-  for (size_t i = 0; i < net->ops.size(); ++i) {
-    const Op& op = net->ops[i];
-    if (op.kind == OP_IN) in_buf = op.o0;
-    if (op.kind == OP_OUT) out_buf = op.f0;
-    if (op.kind == OP_CONV) {
-      if (first_conv < 0 && in_buf) first_conv = (int)i;
-      last_conv = (int)i;
-    }
-  }
-  if (first_conv < 0 || !in_buf || !out_buf || net->ops[first_conv].conv.src0 != in_buf || net->ops[first_conv].conv.src1 ||
-      net->ops[last_conv].conv.out != out_buf || net->ops[last_conv].conv.nsplit != 1 || net->ops[first_conv].conv.nsplit != 1 ||
-      first_conv == last_conv) {
-    set_error("holo_unet_forward_cl: this plan's first / last convolution cannot take the caller's tensors");
+  if (plan.cl_refusal) {
+    set_error("%s", plan.cl_refusal);
     return HOLO_E_UNSUPPORTED;
   }
-  if (bf16_storage && (net->ops[last_conv].conv.out_bf16 || !net->ops[first_conv].conv.in_bf16)) {
-    set_error("holo_unet_forward_cl: unexpected storage types at the ends of the bf16 plan");
-    return HOLO_E_UNSUPPORTED;
-  }
-  for (size_t i = 0; i < net->ops.size(); ++i) {
-    const Op& op = net->ops[i];
+  // the first / last convolution (Planner::find_cl_ends) run on the caller's channels-last tensors instead of the plan's
+  // own input / output buffers, and the two layout passes are skipped
+  const bool bf16_storage = net->compute_mode == 1;  // the plan's input buffer is bf16: a cast replaces the layout pass
+  for (int i = 0; i < (int)plan.ops.size(); ++i) {
+    const Op& op = plan.ops[i];
     if (op.kind == OP_IN && bf16_storage) {  // fp32 channels-last -> the plan's bf16 channels-last input buffer
-      if (f32_to_bf16_launch(x_cl, op.o0, (int64_t)batch * op.i0 * op.l0, stream)) return HOLO_E_INVALID;
+      if (f32_to_bf16_launch(x_cl, op.in.dst, (int64_t)batch * op.in.C * op.in.V, stream)) return HOLO_E_INVALID;
       continue;
     }
     if (op.kind == OP_IN || op.kind == OP_OUT) continue;
-    if ((int)i == first_conv || (int)i == last_conv) {
+    if (i == plan.first_conv || i == plan.last_conv) {
       Op o2 = op;
-      if ((int)i == first_conv && !bf16_storage) o2.conv.src0 = x_cl;
-      if ((int)i == last_conv) o2.conv.out = y_cl;
+      if (i == plan.first_conv && !bf16_storage) o2.conv.src0 = x_cl;
+      if (i == plan.last_conv) o2.conv.out = y_cl;
       rc = run_op(net, o2, batch, x_cl, timesteps, y_cl, stream);
     } else {
       rc = run_op(net, op, batch, x_cl, timesteps, y_cl, stream);
@@ -1838,24 +1889,25 @@ int holo_unet_fetch_block(HoloUnet* net, const char* tag, float* dst, int64_t ds
     set_error("holo_unet_fetch_block: create the net with HOLO_KEEP_INTERMEDIATES=1");
     return HOLO_E_STATE;
   }
-  if (net->plan_ws != workspace || net->ops.empty()) {
+  const Plan& plan = net->plan;
+  if (plan.ws != workspace || plan.ops.empty()) {
     set_error("holo_unet_fetch_block: no forward has run on this workspace");
     return HOLO_E_STATE;
   }
-  auto it = net->block_outputs.find(tag);
-  if (it == net->block_outputs.end()) {
+  auto it = plan.block_outputs.find(tag);
+  if (it == plan.block_outputs.end()) {
     set_error("holo_unet_fetch_block: unknown tag '%s'", tag);
     return HOLO_E_INVALID;
   }
   const Act& a = it->second;
   const int64_t V = (int64_t)a.R * a.R * a.R;
-  const int64_t n = (int64_t)net->plan_batch * V * a.C;
+  const int64_t n = (int64_t)plan.batch * V * a.C;
   if (numel) *numel = n;
   if (dst_capacity < n) {
     set_error("holo_unet_fetch_block: destination too small");
     return HOLO_E_INVALID;
   }
-  return ndhwc_to_ncdhw_launch((const float*)((char*)workspace + a.off), dst, net->plan_batch, a.C, V, stream,
+  return ndhwc_to_ncdhw_launch((const float*)((char*)workspace + a.off), dst, plan.batch, a.C, V, stream,
                                net->compute_mode == 1 ? 1 : 0);
 }
 
@@ -1867,7 +1919,7 @@ int holo_unet_time_convs(HoloUnet* net, int batch, void* workspace, size_t works
   }
   int rc = ensure_plan(net, batch, workspace);
   if (rc) return rc;
-  if (workspace_bytes < net->ws_need) {
+  if (workspace_bytes < net->plan.bytes) {
     set_error("holo_unet_time_convs: workspace too small");
     return HOLO_E_WORKSPACE;
   }
@@ -1876,14 +1928,14 @@ int holo_unet_time_convs(HoloUnet* net, int batch, void* workspace, size_t works
   HIP_TRY(hipEventCreate(&e1));
   double flops = 0.0;
   int launches = 0;
-  for (const Op& op : net->ops)
+  for (const Op& op : net->plan.ops)
     if (op.kind == OP_CONV && op.conv.ksz == 3) {
       flops += conv_flops(op.conv);
       ++launches;
     }
   HIP_TRY(hipEventRecord(e0, (hipStream_t)stream));
   for (int it = 0; it < iters; ++it)
-    for (const Op& op : net->ops)
+    for (const Op& op : net->plan.ops)
       if (op.kind == OP_CONV && op.conv.ksz == 3) {
         rc = conv_launch(op.conv, stream);
         if (rc) return HOLO_E_INVALID;
@@ -1908,7 +1960,7 @@ int holo_unet_time_ops(HoloUnet* net, int batch, const float* x, const int64_t* 
   }
   int rc = ensure_plan(net, batch, workspace);
   if (rc) return rc;
-  if (workspace_bytes < net->ws_need) {
+  if (workspace_bytes < net->plan.bytes) {
     set_error("holo_unet_time_ops: workspace too small");
     return HOLO_E_WORKSPACE;
   }
@@ -1916,7 +1968,7 @@ int holo_unet_time_ops(HoloUnet* net, int batch, const float* x, const int64_t* 
   HIP_TRY(hipEventCreate(&e0));
   HIP_TRY(hipEventCreate(&e1));
   int n = 0;
-  for (const Op& op : net->ops) {
+  for (const Op& op : net->plan.ops) {
     rc = run_op(net, op, batch, x, timesteps, y, stream);  // untimed first touch (also keeps the data flow valid)
     if (rc) return HOLO_E_INVALID;
     if (n < cap) {
@@ -1945,9 +1997,10 @@ int holo_unet_time_ops(HoloUnet* net, int batch, const float* x, const int64_t* 
         t.flops = conv_flops(c);
         t.flops_executed = conv_exec_flops(c);
       } else if (op.kind == OP_FLASH) {
-        t.cin = t.cout = op.attn.C;
-        t.out_dim = op.attn.T;
-        t.flops = 4.0 * op.attn.N * (double)op.attn.T * op.attn.T * op.attn.C;
+        const AttnParams& at = op.flash.attn;
+        t.cin = t.cout = at.C;
+        t.out_dim = at.T;
+        t.flops = 4.0 * at.N * (double)at.T * at.T * at.C;
       } else if (op.kind == OP_GEMM) {
         t.cin = op.gemm.K;
         t.cout = op.gemm.Nn;
@@ -1977,18 +2030,19 @@ int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_
   const ParamSlot& s = net->params[it->second];
   const int Co = (int)s.shape[0], Ci = (int)s.shape[1], T = s.kind == P_CONV3 ? 27 : 1;
   const std::string nm(name);
-  const bool down = nm.size() > 10 && nm.compare(nm.size() - 10, 10, ".op.weight") == 0;  // Downsample: stride 2
+  const bool down = is_downsample_weight(nm);
   // transposed convolution: Cout' = Ci, Cin' = Co
   const size_t packed = down ? (size_t)T * Co * Ci : (size_t)T * pad_cout(Ci) * pad_cin(Co);
   if (down) {  // [tap][co][ci] for conv_dgrad_s2_kernel (the fallback), then the stride-1 form below under "<name>#s1":
                // the transposed stride-2 convolution runs as zero insertion + the stride-1 transposed convolution
-    float*& d2 = net->dgrad_w[nm];
+    float*& d2 = net->dgrad[nm].f32;
     if (!d2) HIP_TRY(hipMalloc((void**)&d2, packed * sizeof(float)));
     if (weight_tco_ci_launch((const float*)dev_ptr, d2, Co, Ci, T, stream)) return HOLO_E_INVALID;
     if ((Co & 3) || (Ci & 3)) return 0;
   }
   const std::string key = down ? nm + "#s1" : nm;
-  float*& dst = net->dgrad_w[key];
+  ConvWeights& dw = net->dgrad[key];
+  float*& dst = dw.f32;
   if (!dst) HIP_TRY(hipMalloc((void**)&dst, (size_t)T * pad_cout(Ci) * pad_cin(Co) * sizeof(float)));
   if (net->dgrad_tmp_floats < (size_t)s.numel) {
     if (net->dgrad_tmp) {
@@ -2005,25 +2059,23 @@ int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_
   // channels are the forward conv's INPUT channels, up to 768 with the skip concat)
   static const bool wino_on = env_int("HOLO_CONV_WINO", 1) != 0;
   if (wino_on && net->compute_mode == 0 && T == 27 && (Ci % 64) == 0 && Ci <= 768 && Co <= 768) {
-    float*& w2 = net->dgrad_wino2[key];
+    float*& w2 = dw.wino2;
     if (!w2) {  // a plan sized before these copies existed chose other kernels (and scratch sizes)
       net->tws_cache.clear();
-      net->tplan_batch = -1;
+      net->tplan.invalidate();
       HIP_TRY(hipMalloc((void**)&w2, 48 * (size_t)pad_cout(Ci) * pad_cin(Co) * sizeof(float)));
     }
     if (repack_conv_weight_wino2_launch(net->dgrad_tmp, w2, Ci, Co, 27, pad_cout(Ci), pad_cin(Co), stream)) return HOLO_E_INVALID;
-    net->wino2_of[dst] = w2;
     // ... and on conv_wino3_kernel where the forward convolutions do (transposed: output channels = the forward's inputs)
     static const bool wino3_on = env_int("HOLO_CONV_WINO3", 1) != 0;
     if (wino3_on && Ci <= 256 && Co <= 768) {
-      float*& w3 = net->dgrad_wino3[key];
+      float*& w3 = dw.wino3;
       if (!w3) {
         net->tws_cache.clear();
-        net->tplan_batch = -1;
+        net->tplan.invalidate();
         HIP_TRY(hipMalloc((void**)&w3, (size_t)conv_wino3_weight_floats(pad_cout(Ci), pad_cin(Co), 27) * sizeof(float)));
       }
       if (repack_conv_weight_wino3_launch(net->dgrad_tmp, w3, Ci, Co, 27, pad_cout(Ci), pad_cin(Co), stream)) return HOLO_E_INVALID;
-      net->wino3_of[dst] = w3;
     }
   }
   return 0;
@@ -2033,29 +2085,10 @@ size_t holo_unet_backward_workspace_bytes(HoloUnet* net, int batch) {
   if (!net || batch < 1) return 0;
   auto it = net->tws_cache.find(batch);
   if (it != net->tws_cache.end()) return it->second;
-  std::vector<Op> fo;
-  std::vector<std::function<int(void*)>> bo;
-  std::vector<size_t> keep = net->grad_off;
-  TrainPlanner tp(net, batch, nullptr, fo, bo);
-  // a sizing pass must not fail on missing transposed weights: it only allocates
-  std::map<std::string, float*> saved = net->dgrad_w;
-  for (auto& s : net->params)
-    if (s.kind == P_CONV3 || s.kind == P_CONV1) {
-      if (!net->dgrad_w.count(s.name)) net->dgrad_w[s.name] = (float*)(uintptr_t)256;
-      const bool down = s.name.size() > 10 && s.name.compare(s.name.size() - 10, 10, ".op.weight") == 0;
-      if (down && !(s.shape[0] & 3) && !(s.shape[1] & 3) && !net->dgrad_w.count(s.name + "#s1"))
-        net->dgrad_w[s.name + "#s1"] = (float*)(uintptr_t)256;
-    }
-  const int rc = tp.build();
-  net->dgrad_w = saved;
-  net->grad_off = keep;
-  if (rc) return 0;  // the message is in holo_last_error()
-  const size_t b = tp.total_bytes();
-  net->tws_cache[batch] = b;
-  net->tplan_batch = -1;
-  net->plan_batch = -1;
-  net->ops.clear();
-  return b;
+  TrainPlan sizing;  // built on a null base (TrainPlanner::find_dgw: no transposed weight is missed there) and dropped
+  if (TrainPlanner(net, batch, nullptr, sizing).build()) return 0;  // the message is in holo_last_error()
+  net->tws_cache[batch] = sizing.bytes;
+  return sizing.bytes;
 }
 
 // The two halves of holo_unet_backward as entries of their own (ABI 4): a caller whose cotangent depends on the output - the
@@ -2068,21 +2101,12 @@ int holo_unet_forward_train(HoloUnet* net, int batch, const float* x, const int6
     return HOLO_E_INVALID;
   }
   net->tape_valid = false;
-  int rc = ensure_train_plan(net, batch, workspace);
+  int rc = ensure_train_plan(net, "holo_unet_forward_train", batch, workspace, workspace_bytes);
   if (rc) return rc;
-  if (workspace_bytes < net->tws_need) {
-    set_error("holo_unet_forward_train: workspace too small (%zu < %zu)", workspace_bytes, net->tws_need);
-    net->tplan_batch = -1;
-    return HOLO_E_WORKSPACE;
-  }
   net->t_dev = timesteps;
-  for (const Op& op : net->tops) {
-    if (op.kind == OP_OUT && !y) continue;
-    rc = run_op(net, op, batch, x, timesteps, y, stream);
-    if (rc) return rc < 0 ? rc : HOLO_E_INVALID;
-  }
-  net->tape_valid = true;
-  return 0;
+  rc = run_plan(net, net->tplan.fwd, x, timesteps, y, stream);
+  net->tape_valid = rc == 0;
+  return rc;
 }
 
 int holo_unet_backward_taped(HoloUnet* net, int batch, const float* grad_out, float* grad_x, void* workspace, size_t workspace_bytes,
@@ -2091,24 +2115,12 @@ int holo_unet_backward_taped(HoloUnet* net, int batch, const float* grad_out, fl
     set_error("holo_unet_backward_taped: null/invalid argument");
     return HOLO_E_INVALID;
   }
-  if (!net->tape_valid || net->tplan_batch != batch || net->tplan_ws != workspace || workspace_bytes < net->tws_need) {
+  if (!net->tape_valid || !net->tplan.built_for(batch, workspace) || workspace_bytes < net->tplan.bytes) {
     set_error("holo_unet_backward_taped: no taped forward of this batch on this workspace (holo_unet_forward_train first)");
     return HOLO_E_STATE;
   }
   net->tape_valid = false;  // the backward consumes the tape (gradient buffers share its workspace)
-  int rc;
-  const HoloUnetCfg& c = net->cfg;
-  const int64_t V = (int64_t)c.image_size * c.image_size * c.image_size;
-  if (ncdhw_to_ndhwc_launch(grad_out, (float*)((char*)workspace + net->gy_off), batch, c.out_channels, V, 0, stream))
-    return HOLO_E_INVALID;
-  for (auto& f : net->bops) {
-    rc = f(stream);
-    if (rc) return rc < 0 ? rc : HOLO_E_INVALID;
-  }
-  if (grad_x &&
-      ndhwc_to_ncdhw_launch((const float*)((char*)workspace + net->gx_off), grad_x, batch, c.in_channels, V, stream))
-    return HOLO_E_INVALID;
-  return 0;
+  return run_backward(net, net->tplan, grad_out, grad_x, workspace, stream);
 }
 
 int holo_unet_backward(HoloUnet* net, int batch, const float* x, const int64_t* timesteps, const float* grad_out, float* y,
@@ -2118,33 +2130,11 @@ int holo_unet_backward(HoloUnet* net, int batch, const float* x, const int64_t* 
     return HOLO_E_INVALID;
   }
   net->tape_valid = false;
-  int rc = ensure_train_plan(net, batch, workspace);
+  int rc = ensure_train_plan(net, "holo_unet_backward", batch, workspace, workspace_bytes);
   if (rc) return rc;
-  if (workspace_bytes < net->tws_need) {
-    set_error("holo_unet_backward: workspace too small (%zu < %zu)", workspace_bytes, net->tws_need);
-    net->tplan_batch = -1;
-    return HOLO_E_WORKSPACE;
-  }
   net->t_dev = timesteps;
-  float ydummy;
-  (void)ydummy;
-  for (const Op& op : net->tops) {
-    if (op.kind == OP_OUT && !y) continue;
-    rc = run_op(net, op, batch, x, timesteps, y, stream);
-    if (rc) return rc < 0 ? rc : HOLO_E_INVALID;
-  }
-  const HoloUnetCfg& c = net->cfg;
-  const int64_t V = (int64_t)c.image_size * c.image_size * c.image_size;
-  if (ncdhw_to_ndhwc_launch(grad_out, (float*)((char*)workspace + net->gy_off), batch, c.out_channels, V, 0, stream))
-    return HOLO_E_INVALID;
-  for (auto& f : net->bops) {
-    rc = f(stream);
-    if (rc) return rc < 0 ? rc : HOLO_E_INVALID;
-  }
-  if (grad_x &&
-      ndhwc_to_ncdhw_launch((const float*)((char*)workspace + net->gx_off), grad_x, batch, c.in_channels, V, stream))
-    return HOLO_E_INVALID;
-  return 0;
+  rc = run_plan(net, net->tplan.fwd, x, timesteps, y, stream);
+  return rc ? rc : run_backward(net, net->tplan, grad_out, grad_x, workspace, stream);
 }
 
 int holo_unet_get_grad(HoloUnet* net, const char* name, float* dst, int64_t numel, const void* workspace, void* stream) {
@@ -2157,7 +2147,7 @@ int holo_unet_get_grad(HoloUnet* net, const char* name, float* dst, int64_t nume
     set_error("holo_unet_get_grad: unknown parameter '%s'", name);
     return HOLO_E_INVALID;
   }
-  if (net->tplan_ws != workspace || net->grad_off.size() != net->params.size()) {
+  if (net->tplan.fwd.ws != workspace || net->tplan.grad_off.size() != net->params.size()) {
     set_error("holo_unet_get_grad: no backward pass has run on this workspace");
     return HOLO_E_STATE;
   }
@@ -2166,7 +2156,7 @@ int holo_unet_get_grad(HoloUnet* net, const char* name, float* dst, int64_t nume
     set_error("holo_unet_get_grad: '%s' has %lld elements, not %lld", name, (long long)s.numel, (long long)numel);
     return HOLO_E_INVALID;
   }
-  HIP_TRY(hipMemcpyAsync(dst, (const char*)workspace + net->grad_off[it->second], (size_t)numel * sizeof(float),
+  HIP_TRY(hipMemcpyAsync(dst, (const char*)workspace + net->tplan.grad_off[it->second], (size_t)numel * sizeof(float),
                          hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }

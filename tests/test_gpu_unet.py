@@ -58,6 +58,21 @@ def test_tiny_unet_vs_reference_golden(gu, golden_dir):
         os.environ.pop("HOLO_KEEP_INTERMEDIATES", None)
 
 
+def test_fetch_block_after_workspace_size_queries(gu, golden_dir, monkeypatch):
+    """The workspace-size queries plan aside and leave the plan of the last forward alone: a block output reads the same,
+    bit for bit, after sizes that no cache holds yet were asked for (the forward at another batch, the training plan)."""
+    monkeypatch.setenv("HOLO_KEEP_INTERMEDIATES", "1")
+    ref = torch.from_numpy(np.load(os.path.join(golden_dir, "tiny_unet.npz"))["t500.middle_block"])
+    net, _ = gu.make_unet(TINY_CFG)
+    net(seeded_input(TINY_CFG, 7 + 500).to(gu.DEV), torch.tensor([500], device=gu.DEV))
+    before = net.fetch_block("middle_block", tuple(ref.shape)).clone()
+    assert gu.rel_err(before, ref) < TOL
+    assert net.workspace_bytes(3, gu.DEV) > 0
+    assert runtime.lib().holo_unet_backward_workspace_bytes(net._handle, 1) > 0
+    after = net.fetch_block("middle_block", tuple(ref.shape))
+    assert torch.equal(before, after)
+
+
 def test_tiny_unet_batch2(gu, golden_dir):
     g = np.load(os.path.join(golden_dir, "tiny_unet_b2.npz"))
     net, _ = gu.make_unet(TINY_CFG)
