@@ -172,6 +172,29 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
   }
 }
 
+// The same product for shapes the tiled kernel's 16-byte loads cannot take (a leading dimension or K that is no multiple
+// of 4: the T x T score matrix of an attention block at 3^3 = 27 or 5^3 = 125 tokens).  One thread per element of C, K in
+// series in fp32; these matrices are a few hundred rows, speed is not a concern.
+__global__ __launch_bounds__(256) void gemm_scalar_kernel(GemmParams p) {
+  const int bz = blockIdx.y;
+  const int b0 = bz / p.nb1, b1 = bz - b0 * p.nb1;
+  const float* A = p.A + b0 * p.sa0 + b1 * p.sa1;
+  const float* B = p.B + b0 * p.sb0 + b1 * p.sb1;
+  float* C = p.C + b0 * p.sc0 + b1 * p.sc1;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)p.M * p.Nn) return;
+  const int m = (int)(i / p.Nn), n = (int)(i - (int64_t)m * p.Nn);
+  const float* a = A + (int64_t)m * p.lda;
+  float s = 0.f;
+  if (p.b_kmajor) {
+    for (int k = 0; k < p.K; ++k) s = fmaf(a[k], B[(int64_t)k * p.ldb + n], s);
+  } else {
+    const float* b = B + (int64_t)n * p.ldb;
+    for (int k = 0; k < p.K; ++k) s = fmaf(a[k], b[k], s);
+  }
+  C[(int64_t)m * p.ldc + n] = p.alpha * s;
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
@@ -408,10 +431,14 @@ __global__ __launch_bounds__(256) void flash_attn_merge_kernel(AttnParams p) {
 }  // namespace
 
 int gemm_launch(const GemmParams& p, void* stream) {
-  if ((p.lda & 3) || (p.ldb & 3) || (p.K & 3) || (p.b_kmajor && (p.Nn & 3))) {
-    set_error("gemm_launch: leading dimensions / K must be multiples of 4 (lda=%d ldb=%d K=%d N=%d)", p.lda, p.ldb,
-              p.K, p.Nn);
+  if (p.M <= 0 || p.Nn <= 0 || p.K <= 0 || p.nb0 <= 0 || p.nb1 <= 0) {
+    set_error("gemm_launch: empty product (M=%d N=%d K=%d batch %d x %d)", p.M, p.Nn, p.K, p.nb0, p.nb1);
     return -1;
+  }
+  if ((p.lda & 3) || (p.ldb & 3) || (p.K & 3) || (p.b_kmajor && (p.Nn & 3))) {  // no 16-byte rows: the scalar form
+    dim3 grid((unsigned)cdiv((int64_t)p.M * p.Nn, 256), (unsigned)(p.nb0 * p.nb1));
+    HOLO_LAUNCH(gemm_scalar_kernel, grid, dim3(256), stream, p);
+    return 0;
   }
   dim3 grid((unsigned)cdiv(p.M, BM), (unsigned)cdiv(p.Nn, BN), (unsigned)(p.nb0 * p.nb1));
   HOLO_LAUNCH(gemm_kernel, grid, dim3(256), stream, p);

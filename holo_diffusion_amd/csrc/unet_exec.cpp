@@ -1020,8 +1020,10 @@ struct Planner {
     }
     plan.first_conv = first;
     plan.last_conv = last;
+    // (a split-K launch at either end is fine: its kernel reads src0 like an un-split one, and the reduce launch behind it
+    // writes `out` - the small and the non-tileable grids, whose 16- or 32-channel end convolutions are split to fill the chip)
     if (first < 0 || !in_buf || !out_buf || ops[first].conv.src0 != in_buf || ops[first].conv.src1 ||
-        ops[last].conv.out != out_buf || ops[last].conv.nsplit != 1 || ops[first].conv.nsplit != 1 || first == last) {
+        ops[last].conv.out != out_buf || first == last) {
       plan.cl_refusal = "holo_unet_forward_cl: this plan's first / last convolution cannot take the caller's tensors";
     } else if (bfs() && (ops[last].conv.out_bf16 || !ops[first].conv.in_bf16)) {
       plan.cl_refusal = "holo_unet_forward_cl: unexpected storage types at the ends of the bf16 plan";

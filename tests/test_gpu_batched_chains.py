@@ -18,7 +18,7 @@ from oracle.common import NORTH_CFG, TINY_CFG, np_noise, seeded_input  # noqa: E
 
 TINY_UNET = dict(model_channels=32, channel_mult=(1, 2), attention_resolutions=(1, 2))
 # 16^3: its 8^3 level runs split-K convolutions and a key-split attention (T = 512); 32 channels at both ends keep the first
-# and last convolution un-split at batch 1, as forward_channels_last needs
+# and last convolution un-split at batch 1 (split-K ends: forward_channels_last in test_gpu_unet_grid_sizes.py)
 MID_CFG = uo.UNetCfg(image_size=16, in_channels=32, out_channels=32, model_channels=32, num_res_blocks=1,
                      channel_mult=(1, 2), attention_resolutions=(2,), num_heads=2)
 STREAMS = [5, 0, 9]
