@@ -184,10 +184,4 @@ const char* get_error();
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// an integer knob from the environment (development and test settings of the planners): `dflt` when unset or empty
-static inline int64_t env_int(const char* name, int64_t dflt) {
-  const char* e = getenv(name);
-  return e && e[0] ? strtoll(e, nullptr, 10) : dflt;
-}
-
 }  // namespace holo

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "holo_knobs.h"
+
 // per-device context of the C ABI (holo_ctx_create)
 struct HoloCtx {
   int device;
@@ -137,8 +139,8 @@ int conv_bf16p_launch(const ConvParams& p, void* stream);
 // Picks split-K so that the grid fills the chip; returns bytes of `partial` scratch needed (0 if none).
 // plan_n > 0: every choice (kernel, tile depth, split-K) is made as for a launch of plan_n samples, and only the grid and the
 // scratch are sized for p.N - with plan_n = 1 each sample of a batch is computed as at batch 1 (the batch-invariant plan of
-// holo_unet_set_batch_invariant).  0: choices for p.N.
-size_t conv_plan(ConvParams& p, int num_cus, int plan_n = 0);
+// holo_unet_set_batch_invariant).  0: choices for p.N.  `k`: the caller's snapshot of the knobs (holo_knobs.h).
+size_t conv_plan(ConvParams& p, int num_cus, const Knobs& k, int plan_n = 0);
 int conv_launch(const ConvParams& p, void* stream);
 int conv_stats_slabs(const ConvParams& p);
 double conv_flops(const ConvParams& p);       // algorithmic (the reference's multiply-adds x 2)
@@ -179,7 +181,7 @@ struct AttnParams {
   float* part_ml;
 };
 bool flash_attn_supported(int T, int head_channels);
-int flash_attn_splits(int N, int T, int H, int num_cus);
+int flash_attn_splits(int N, int T, int H, int num_cus, const Knobs& k);
 size_t flash_attn_workspace_bytes(const AttnParams& p);
 int flash_attn_launch(const AttnParams& p, void* stream);
 // bf16-product variant (shared K/V tiles in LDS, v_mfma_f32_16x16x32_bf16), for the opt-in bf16 mode
@@ -188,11 +190,14 @@ int flash_attn_launch(const AttnParams& p, void* stream);
 // 64-key blocks, 64 queries per wave, v_mfma_f32_32x32x16_bf16, exp2-domain softmax; the key range is split across
 // workgroups (and recombined) when one workgroup per 256 queries would leave half of the chip's wave slots empty.
 // `work` (flash_attn_bf16v2_workspace_bytes) holds the packed operands and the split partials; out_bf16: `out` is bf16.
+// The plan decides ONCE how the key range is split (flash_attn_bf16v2_ksplit) and whether the LAZY pass runs before the exact
+// kernel (`lazy`; head channels 32 / 64 only); the workspace is sized and laid out from that same split count.
 bool flash_attn_bf16v2_supported(int T, int head_channels);
-size_t flash_attn_bf16v2_workspace_bytes(const AttnParams& p, int num_cus);
+int flash_attn_bf16v2_ksplit(const AttnParams& p, int num_cus, const Knobs& k);
+size_t flash_attn_bf16v2_workspace_bytes(const AttnParams& p, int ksplit);
 // packed != 0: the operands in `work` have been written already (the fused qkv convolution), the packing pre-pass is skipped;
 // flash_attn_bf16v2_operands: where they go and the scale folded into Q
-int flash_attn_bf16v2_launch(const AttnParams& p, void* work, int out_bf16, int num_cus, void* stream, int packed = 0);
+int flash_attn_bf16v2_launch(const AttnParams& p, void* work, int out_bf16, int ksplit, int lazy, void* stream, int packed = 0);
 void flash_attn_bf16v2_operands(const AttnParams& p, void* work, uint16_t** q, uint16_t** k, uint16_t** vt, float* qscale);
 
 // in-place row softmax over `rows` rows of length `cols` (unet.py:453, fp32)
@@ -219,9 +224,9 @@ int gn_finalize_launch(const double* part0, int C0, int B0, const double* part1,
 // moments (training forward): [N][C0 + C1][2] = (mean, rstd) of the channel's group, for the backward pass
 
 // emb = Linear2(SiLU(Linear1(timestep_embedding(t, mc))));  writes silu(emb) (all consumers apply SiLU first:
-// unet.py:199-205) and emb itself.
+// unet.py:199-205) and emb itself.  load_kind: the HOLO_DEBUG_TIMESTEP_LOAD of the plan (0 in production, see the kernel).
 int time_embed_launch(const int64_t* t, int N, int mc, int ted, const float* w1, const float* b1, const float* w2,
-                      const float* b2, float* emb, float* emb_silu, void* stream);
+                      const float* b2, float* emb, float* emb_silu, int load_kind, void* stream);
 
 // out[n][r] = bias[r] + sum_k W[r][k] * in[n][k]      (all ResBlock emb_layers concatenated)
 int rows_linear_launch(const float* in, const float* w, const float* bias, float* out, int N, int rows, int K,
@@ -479,7 +484,7 @@ struct ViewPoolBwdParams {
   long long* gfix[ViewPoolParams::MAX_FEATS];
   uint32_t* fix_max;  // [MAX_FEATS], zeroed
 };
-int view_pool_bwd_launch(const ViewPoolBwdParams& b, int n_wgs, void* stream);
+int view_pool_bwd_launch(const ViewPoolBwdParams& b, int n_wgs, const Knobs& k, void* stream);
 int nhwc_pad_to_nchw_launch(const float* in, float* out, int n, int C, int Cp, int64_t HW, void* stream);
 // deterministic mode: in (+)= value of the fixed-point image (binary point from *maxbits), the image zeroed again
 int fix_flush_launch(long long* fix, const uint32_t* maxbits, float* out, int64_t n, void* stream);
@@ -534,9 +539,14 @@ struct WgradParams {   // dW[co][ci][tap] = sum_m gy[m][co] act(coef . x)[m + ta
   int act;
   float* partial;      // [splits][Cout][Cin][ntaps] scratch (wgrad_partial_bytes)
 };
-int wgrad_splits(const WgradParams& p, int num_cus);
-size_t wgrad_partial_bytes(const WgradParams& p, int num_cus);
-int conv_wgrad_launch(const WgradParams& p, float* dw, int accumulate, int num_cus, void* stream);
+struct WgradPlan {  // what wgrad_plan chose for a WgradParams: the scratch is sized and the launch shaped from the same value
+  int rows;         // 1: the row-staged kernel (conv_wgrad_rows_kernel), 0: the tile kernel
+  int splits;       // slabs of rows, one partial each
+  int reduce_tile;  // row-staged kernel: the tile form of the reduce
+};
+WgradPlan wgrad_plan(const WgradParams& p, int num_cus, const Knobs& k);
+size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& g);
+int conv_wgrad_launch(const WgradParams& p, const WgradPlan& g, float* dw, int accumulate, void* stream);
 int flip_transpose_weight_launch(const float* in, float* out, int Co, int Ci, int T, void* stream);
 int weight_tco_ci_launch(const float* in, float* out, int Co, int Ci, int T, void* stream);
 size_t colsum_scratch_bytes(int C);
@@ -585,8 +595,9 @@ int implicit_dirs_launch(const ImplicitEvalParams& p, void* stream);
 int implicit_points_launch(const ImplicitEvalParams& p, void* stream);
 int implicit_normals_launch(const ImplicitEvalParams& p, float* normals, void* stream);  // uses grid_cl, pts, n_points, mlp
 int density_field_launch(const float* grid_cl, const float* w_dens, int C, int64_t nvox, float* out, void* stream);
-int render_launch(const RenderKernelParams& p, void* stream, int n_workgroups);
-int render_waves_per_wg(int C, int n_fine, int with_normals, int split3 = 0, int train = 0);
-int render_rays_per_tile(int C, int n_fine, int with_normals, int split3, int train);
+// (`k`: the renderer handle's snapshot of the knobs - the three must see the same one)
+int render_launch(const RenderKernelParams& p, const Knobs& k, void* stream, int n_workgroups);
+int render_waves_per_wg(const Knobs& k, int C, int n_fine, int with_normals, int split3 = 0, int train = 0);
+int render_rays_per_tile(const Knobs& k, int C, int n_fine, int with_normals, int split3, int train);
 
 }  // namespace holo

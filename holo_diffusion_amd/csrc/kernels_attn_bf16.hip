@@ -599,21 +599,18 @@ int flash_attn_bf16v2_lazy_launch(const void* attn_v2, int ch, unsigned grid, vo
 int flash_attn_bf16v2_lazy_launch(const void* attn_v2, int ch, unsigned grid, void* stream);  // (kernels_attn_bf16_lazy.hip)
 
 bool flash_attn_bf16v2_supported(int T, int ch) { return (T % 256) == 0 && (ch == 32 || ch == 64 || ch == 128); }
-static int attn_v2_ksplit(const AttnParams& p, int num_cus) {
+int flash_attn_bf16v2_ksplit(const AttnParams& p, int num_cus, const Knobs& k) {
   const int64_t wgs = (int64_t)p.N * p.H * (p.T / (p.C / p.H == 128 ? 128 : 256));
   int ks = 1;
   // two workgroups per CU for the kernels that run two waves per SIMD; the LAZY kernel (head channels 32 / 64) runs one
   const int per_cu = 2;
   while (wgs * ks < per_cu * (int64_t)num_cus && ks < 8 && (p.T / (ks * 2)) % 128 == 0) ks *= 2;  // (an even number of 64-key blocks per split: the LAZY loop takes two per trip)
-  if (const char* e = getenv("HOLO_FLASH_V2_KSPLIT")) {  // development knob
-    const int v = atoi(e);
-    if (v >= 1 && v <= 8 && (p.T / v) % 128 == 0) ks = v;
-  }
+  const int64_t v = k.flash_v2_ksplit;  // development knob
+  if (v >= 1 && v <= 8 && (p.T / v) % 128 == 0) ks = (int)v;
   return ks;
 }
-size_t flash_attn_bf16v2_workspace_bytes(const AttnParams& p, int num_cus) {
+size_t flash_attn_bf16v2_workspace_bytes(const AttnParams& p, int ks) {
   const size_t ntc = (size_t)p.N * p.T * p.C;
-  const int ks = attn_v2_ksplit(p, num_cus);
   size_t b = 3 * ntc * sizeof(uint16_t);
   if (ks > 1) b += (size_t)ks * ntc * sizeof(float) + (size_t)ks * p.N * p.H * p.T * 2 * sizeof(float);
   b += (size_t)p.N * p.H * ks * (p.T / 128) * sizeof(int);  // the LAZY kernel's redo flags, one per workgroup
@@ -626,10 +623,14 @@ void flash_attn_bf16v2_operands(const AttnParams& p, void* work, uint16_t** q, u
   *qscale = p.scale2 * 1.4426950408889634f;  // softmax in the exp2 domain
 }
 
-int flash_attn_bf16v2_launch(const AttnParams& p, void* work, int out_bf16, int num_cus, void* stream, int packed) {
+int flash_attn_bf16v2_launch(const AttnParams& p, void* work, int out_bf16, int ksplit, int lazy_pass, void* stream, int packed) {
   const int ch = p.C / p.H;
   if (!flash_attn_bf16v2_supported(p.T, ch)) {
     set_error("flash_attn_bf16v2: unsupported shape T=%d head channels=%d", p.T, ch);
+    return -1;
+  }
+  if (ksplit < 1 || ksplit > 8 || (p.T / ksplit) % 128 != 0) {  // (what flash_attn_bf16v2_ksplit can answer)
+    set_error("flash_attn_bf16v2: %d key splits at T=%d", ksplit, p.T);
     return -1;
   }
   const size_t ntc = (size_t)p.N * p.T * p.C;
@@ -640,7 +641,7 @@ int flash_attn_bf16v2_launch(const AttnParams& p, void* work, int out_bf16, int 
   a.vt = w16 + 2 * ntc;
   a.out = p.out;
   a.opart = reinterpret_cast<float*>(w16 + 3 * ntc);
-  a.ksplit = attn_v2_ksplit(p, num_cus);
+  a.ksplit = ksplit;
   a.ml = a.opart + (size_t)a.ksplit * ntc;
   a.redo = reinterpret_cast<int*>(a.ksplit > 1 ? a.ml + (size_t)a.ksplit * p.N * p.H * p.T * 2 : a.opart);
   a.N = p.N, a.T = p.T, a.C = p.C, a.H = p.H;
@@ -653,12 +654,12 @@ int flash_attn_bf16v2_launch(const AttnParams& p, void* work, int out_bf16, int 
     constexpr int CHC = decltype(chc)::value;
     if (!packed) HOLO_LAUNCH(attn_pack_kernel<CHC>, pgrid, dim3(256), stream, p.qkv, w16, w16 + ntc, w16 + 2 * ntc, p.T, p.C, p.H, qscale);
   };
-  const bool lazy = HOLO_ATTN_LAZY != 0 && ch != 128 && !getenv("HOLO_ATTN_EXACT");  // (development knob: the exact loop alone)
+  const bool lazy = HOLO_ATTN_LAZY != 0 && ch != 128 && lazy_pass;
   switch (ch) {
     case 32:
       pack(std::integral_constant<int, 32>{});
       if (lazy) {
-        flash_attn_bf16v2_lazy_launch(&a, 32, grid.x, stream);
+        if (flash_attn_bf16v2_lazy_launch(&a, 32, grid.x, stream)) return -1;
         HOLO_LAUNCH((flash_attn_bf16v2_kernel<32, 2, 2>), grid, dim3(256), stream, a);
       } else {
         HOLO_LAUNCH((flash_attn_bf16v2_kernel<32, 2, 0>), grid, dim3(256), stream, a);
@@ -667,7 +668,7 @@ int flash_attn_bf16v2_launch(const AttnParams& p, void* work, int out_bf16, int 
     case 64:
       pack(std::integral_constant<int, 64>{});
       if (lazy) {
-        flash_attn_bf16v2_lazy_launch(&a, 64, grid.x, stream);
+        if (flash_attn_bf16v2_lazy_launch(&a, 64, grid.x, stream)) return -1;
         HOLO_LAUNCH((flash_attn_bf16v2_kernel<64, 2, 2>), grid, dim3(256), stream, a);
       } else {
         HOLO_LAUNCH((flash_attn_bf16v2_kernel<64, 2, 0>), grid, dim3(256), stream, a);

@@ -905,46 +905,47 @@ int weight_tco_ci_launch(const float* in, float* out, int Co, int Ci, int T, voi
 }
 
 // the row-staged kernel serves the stride-1 3x3x3 convolutions of rows up to 64 voxels (HOLO_WGRAD_TILES=1: tile kernel)
-static bool wgrad_rows_ok(const WgradParams& p) {
-#ifndef HOLO_EMU
-  static const char* e = getenv("HOLO_WGRAD_TILES");
-  if (e && atoi(e) > 0) return false;
-#endif
+static bool wgrad_rows_ok(const WgradParams& p, const Knobs& k) {
+  if (k.wgrad_tiles > 0) return false;
   const int Cin = p.C0 + p.C1;
   return p.ksz == 3 && p.stride == 1 && p.pad == 1 && p.OW <= WR_MAXW && (p.OW & 1) == 0 && p.ID == p.OD && p.IH == p.OH &&
          p.IW == p.OW && (Cin & 3) == 0 && (p.Cout & 3) == 0 && (p.C0 & 3) == 0 && (p.C1 & 3) == 0 && (!p.src1 || (p.C0 & 31) == 0);
 }
-int wgrad_splits(const WgradParams& p, int num_cus) {
+WgradPlan wgrad_plan(const WgradParams& p, int num_cus, const Knobs& k) {
   const int Cin = p.C0 + p.C1;
   const int64_t nrows = (int64_t)p.N * p.OD * p.OH;
   const int ncu = num_cus > 0 ? num_cus : 256;
-  if (wgrad_rows_ok(p)) {  // workgroups per CU by LDS / registers (1 or 2); slabs of at least 8 rows keep the row ring useful
+  WgradPlan g;
+  g.rows = wgrad_rows_ok(p, k) ? 1 : 0;
+  // row-staged kernel: the tile form of the reduce from HOLO_WGRAD_REDUCE_TILE_MIN 64-element tiles on (development / test knob)
+  g.reduce_tile = g.rows && ((int64_t)p.Cout * Cin + 63) / 64 >= k.wgrad_reduce_tile_min && p.ntaps <= 28;
+  int64_t s;
+  if (g.rows) {  // workgroups per CU by LDS / registers (1 or 2); slabs of at least 8 rows keep the row ring useful
     const int64_t pairs = (int64_t)((p.Cout + 31) / 32) * ((Cin + 31) / 32);
-    int64_t s = ((p.OW > 32 ? 1 : 2) * (int64_t)ncu + pairs - 1) / pairs;
+    s = ((p.OW > 32 ? 1 : 2) * (int64_t)ncu + pairs - 1) / pairs;
     if (s > nrows / 8) s = nrows / 8;
-    if (s < 1) s = 1;
-    if (s > 64) s = 64;
-    return (int)s;
+  } else {
+    const int64_t tiles = (int64_t)((p.Cout + 31) / 32) * ((Cin + 31) / 32) * p.ntaps;
+    s = (8LL * ncu + tiles - 1) / tiles;  // ~8 workgroups per CU in flight over the launch
+    if (s > nrows / 4) s = nrows / 4;
   }
-  const int64_t tiles = (int64_t)((p.Cout + 31) / 32) * ((Cin + 31) / 32) * p.ntaps;
-  int64_t s = (8LL * ncu + tiles - 1) / tiles;  // ~8 workgroups per CU in flight over the launch
-  if (s > nrows / 4) s = nrows / 4;
   if (s < 1) s = 1;
   if (s > 64) s = 64;
-  return (int)s;
+  g.splits = (int)s;
+  return g;
 }
-size_t wgrad_partial_bytes(const WgradParams& p, int num_cus) {
-  return (size_t)wgrad_splits(p, num_cus) * p.Cout * (p.C0 + p.C1) * p.ntaps * sizeof(float);
+size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& g) {
+  return (size_t)g.splits * p.Cout * (p.C0 + p.C1) * p.ntaps * sizeof(float);
 }
 // dw: OIDHW [Cout][C0 + C1][ntaps]
-int conv_wgrad_launch(const WgradParams& p, float* dw, int accumulate, int num_cus, void* stream) {
+int conv_wgrad_launch(const WgradParams& p, const WgradPlan& g, float* dw, int accumulate, void* stream) {
   const int Cin = p.C0 + p.C1;
   if (p.src1 && (p.C0 & 31)) {
     set_error("conv_wgrad: the first source of a virtual concat must have a multiple of 32 channels");
     return -1;
   }
-  const int splits = wgrad_splits(p, num_cus);
-  if (wgrad_rows_ok(p)) {
+  const int splits = g.splits;
+  if (g.rows) {
     dim3 grid((unsigned)(((p.Cout + 31) / 32) * ((Cin + 31) / 32)), (unsigned)splits);
     if (p.OW > 32) {
       HOLO_LAUNCH((conv_wgrad_rows_kernel<64, 8>), grid, dim3(512), stream, p);
@@ -958,11 +959,9 @@ int conv_wgrad_launch(const WgradParams& p, float* dw, int accumulate, int num_c
     HOLO_LAUNCH(conv_wgrad_kernel, grid, dim3(256), stream, p);
   }
   const int64_t n = (int64_t)p.Cout * Cin * p.ntaps;
-  if (wgrad_rows_ok(p)) {
+  if (g.rows) {
     const int64_t tiles = ((int64_t)p.Cout * Cin + 63) / 64;
-    const char* rt = getenv("HOLO_WGRAD_REDUCE_TILE_MIN");  // development / test knob: tiles from which the tile form runs
-    const int64_t tmin = rt ? atoll(rt) : 1024;
-    if (tiles >= tmin && p.ntaps <= 28) {
+    if (g.reduce_tile) {
       HOLO_LAUNCH(wgrad_reduce_tile_kernel, dim3((unsigned)(tiles < 8192 ? tiles : 8192)), dim3(256), stream, p.partial, dw, p.Cout,
                   Cin, p.ntaps, splits, accumulate);
     } else {

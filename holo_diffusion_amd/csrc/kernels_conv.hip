@@ -2621,7 +2621,7 @@ KSplit wino3_split(int64_t t3, int ncc, int num_cus) { return ksplit(t3 < num_cu
 
 }  // namespace
 
-size_t conv_plan(ConvParams& p, int num_cus, int plan_n) {
+size_t conv_plan(ConvParams& p, int num_cus, const Knobs& k, int plan_n) {
   const int Cin = p.C0 + p.C1;
   const int ncc = (Cin + BK - 1) / BK;
   const int nchunks = p.ksz * p.ksz * p.ksz * ncc;
@@ -2651,36 +2651,36 @@ size_t conv_plan(ConvParams& p, int num_cus, int plan_n) {
   // too: the Winograd kernels do 4/9 (8/27) of the MFMAs per voxel, which buys more than the doubled workgroup count of
   // 64-voxel tiles; the chip is filled by split-K over the channel chunks instead.  HOLO_CONV_WINO_SMALL=0 turns that off,
   // HOLO_CONV_FORCE_TZ2=1 (tests) takes 128-voxel tiles (hence the Winograd kernels) on small grids
-  const bool wino_small = env_int("HOLO_CONV_WINO_SMALL", 1) != 0 && wino2_wide && ncc >= 2;
-  const int tz = tiles < target && env_int("HOLO_CONV_FORCE_TZ2", 0) != 1 && !wino_small ? 1 : 2;
+  const bool wino_small = k.conv_wino_small != 0 && wino2_wide && ncc >= 2;
+  const int tz = tiles < target && k.conv_force_tz2 != 1 && !wino_small ? 1 : 2;
 
   // ---- the kernel: the first of these whose conditions hold
   const ConvKernel kernel = [&] {
     // the qkv convolution of an AttentionBlock, fused with the operand packing of the bf16 attention (the planner offers it by
     // setting qkv_q; HOLO_CONV_QKV_FUSED=0 keeps the row-tile kernel + attn_pack_kernel)
     if (p.qkv_q) {
-      if (env_int("HOLO_CONV_QKV_FUSED", 1) != 0 && conv1x1_qkv_bf16_supported(p)) return ConvKernel::Qkv;
+      if (k.conv_qkv_fused != 0 && conv1x1_qkv_bf16_supported(p)) return ConvKernel::Qkv;
       p.qkv_q = nullptr;  // (not this launch: the caller packs)
     }
     // any other 1x1x1 convolution of a large grid on bf16 storage (the attention's proj_out): the same streaming GEMM with a
     // plain output (HOLO_CONV1X1_BF16_STREAM=0 keeps the row-tile kernel)
-    if (env_int("HOLO_CONV1X1_BF16_STREAM", 1) != 0 && conv1x1_bf16_stream_supported(p)) return ConvKernel::Bf16Stream1x1;
+    if (k.conv1x1_bf16_stream != 0 && conv1x1_bf16_stream_supported(p)) return ConvKernel::Bf16Stream1x1;
     if (!halo) {
       // a 1x1x1 convolution of raw input over a LARGE grid (a ResBlock's skip_connection on the 64^3 level): the streaming
       // GEMM (HOLO_CONV1X1_STREAM_MIN_M=<rows>: development knob, default 131 072 rows; 0 = off)
-      const int64_t min_m = env_int("HOLO_CONV1X1_STREAM_MIN_M", 131072);
+      const int64_t min_m = k.conv1x1_stream_min_m;
       if (min_m > 0 && Mc >= min_m && p.ksz == 1 && p.stride == 1 && !p.ups && !p.coef && !p.residual && !p.skip_w && p.bf16 == 0 &&
           !p.in_bf16 && !p.out_bf16 && (p.Cout % 64) == 0 && (Cin % 32) == 0 && Cin >= 32 && Cin <= 256 &&
           (!p.src1 || (p.C0 % 32) == 0) && (Mc % 16) == 0 && p.ID == p.OD && p.IH == p.OH && p.IW == p.OW)
         return ConvKernel::Stream1x1;
       // an attention block's qkv / proj_out in exact fp32 (16^3, 8^3): one 16-row tile per workgroup, K split over its
       // waves (HOLO_CONV1X1_SMALL=0 keeps the row-tile kernel)
-      if (env_int("HOLO_CONV1X1_SMALL", 1) != 0 && conv1x1_small_supported(p)) return ConvKernel::Small1x1;
+      if (k.conv1x1_small != 0 && conv1x1_small_supported(p)) return ConvKernel::Small1x1;
       // the stride-2 convolution of a Downsample block in the bf16 storage mode, where its 128-voxel tiles give the chip at
       // least a workgroup per four CUs (128^3 net: 128^3 -> 64^3 540 -> ~100 us, and the two levels below; deeper the row-tile
       // kernel's split-K fills the chip better).  HOLO_CONV_S2T=0 keeps the row-tile kernel, =1 takes this one wherever it is
       // defined (tests)
-      const int64_t s2t = env_int("HOLO_CONV_S2T", -1);
+      const int64_t s2t = k.conv_s2t;
       if (s2t != 0 && conv_s2_bf16_supported(p) && ((Mc / 128) * (p.Cout / 64) >= num_cus / 4 || s2t == 1))
         return ConvKernel::S2Bf16;
       // 1x1x1, strided and deepest-level convs: row-tile kernel (also for the 32^3 stride-2 convolution with its 32 768 rows:
@@ -2690,7 +2690,7 @@ size_t conv_plan(ConvParams& p, int num_cus, int plan_n) {
     // bf16 wide-tile kernel (8^3 voxels x 64 | 32 output channels per workgroup): where it fills the chip without split-K,
     // and on the under-filled levels once the K extent is long (BF16T_LONG_K).  HOLO_CONV_BF16T=0 disables it, =1 forces it
     // everywhere (tests)
-    const int64_t bt = env_int("HOLO_CONV_BF16T", -1);
+    const int64_t bt = k.conv_bf16t;
     if (p.bf16 == 1 && p.in_bf16 && p.w_bft && (!p.skip_w || p.skip_w_bft) && (p.OD % 8) == 0 && (p.OH % 8) == 0 &&
         (p.OW % 8) == 0 && (p.Cout % 32) == 0 && (p.C0 % 8) == 0 && (p.skip_C0 % 8) == 0 && ((p.skip_C0 + p.skip_C1) % 8) == 0 &&
         (p.Cout >= 64 || !p.skip_w) && bt != 0 &&
@@ -2701,7 +2701,7 @@ size_t conv_plan(ConvParams& p, int num_cus, int plan_n) {
       // 128^3 32 -> 64 282 vs 293 us); with the activation arithmetic they do not yet (540 vs 479 us) and conv_bf16t_kernel
       // stays.  HOLO_CONV_BF16P=0 keeps conv_bf16t_kernel everywhere, =2 takes the persistent form for activated input too,
       // =1 forces it onto every wide-tile launch, without split-K (tests: small grids)
-      const int64_t bp = env_int("HOLO_CONV_BF16P", -1);
+      const int64_t bp = k.conv_bf16p;
       const int wgs = num_cus & ~7;
       if (bp != 0 && (bp == 1 || bp == 2 || !p.coef) &&
           ((bf16t_split(p, t8, ncc16, num_cus).n == 1 && wgs >= 8 && t8 >= wgs) || bp == 1) &&
@@ -2713,12 +2713,12 @@ size_t conv_plan(ConvParams& p, int num_cus, int plan_n) {
     }
     // F(2x2x2, 3x3x3) form (kernels_conv3.hip) from HOLO_CONV_WINO3_MIN_ITEMS work items on (default num_cus / 2: the (z,y)
     // form needs 2 workgroups per CU).  HOLO_CONV_WINO3=0 disables it
-    if (tz == 2 && env_int("HOLO_CONV_WINO3", 1) != 0 && p.w_wino3 && p.bf16 == 0 && !p.in_bf16 && !p.out_bf16 && p.Cout >= 64 &&
+    if (tz == 2 && k.conv_wino3 != 0 && p.w_wino3 && p.bf16 == 0 && !p.in_bf16 && !p.out_bf16 && p.Cout >= 64 &&
         (p.Cout % 64) == 0 && (!p.skip_w || p.skip_w_wino3) && (p.OH % 8) == 0 && (p.OW % 8) == 0 && (p.OD % 2) == 0 &&
         (!p.coef || p.act) &&  // (its staging applies the affine and SiLU together)
         (int64_t)p.N * src_vox * (cmax > skmax ? cmax : skmax) * 4 < ((int64_t)1 << 32) &&  // (buffer addressing of whole tensors)
         (!p.skip_w || ((p.skip_C0 % 16) == 0 && (p.skip_C1 % 4) == 0)) &&
-        t3 * wino3_split(t3, ncc, num_cus).n >= env_int("HOLO_CONV_WINO3_MIN_ITEMS", num_cus / 2))
+        t3 * wino3_split(t3, ncc, num_cus).n >= (k.conv_wino3_min_items != KNOB_UNSET ? k.conv_wino3_min_items : num_cus / 2))
       return ConvKernel::Wino3;
     // exact-fp32 128-voxel tiles: the (z,y) Winograd form when its weights were prepared (32-channel convolutions: two wave rows)
     if (tz == 2 && (wino2_wide || (p.w_wino2 && p.bf16 == 0 && p.Cout == 32 && !p.skip_w))) return ConvKernel::Wino2;
@@ -2772,7 +2772,7 @@ size_t conv_plan(ConvParams& p, int num_cus, int plan_n) {
       const int64_t wcap = (num_cus & ~7) >= 8 ? (num_cus & ~7) : 8;
       const int64_t t8a = (M / 512) * cdiv(p.Cout, bn);  // (the tiles of all samples)
       int64_t g = t8a < wcap ? ((t8a + 7) & ~(int64_t)7) : wcap;
-      const int64_t max_wgs = env_int("HOLO_CONV_BF16P_WGS", 0);  // test knob: at most this many persistent workgroups
+      const int64_t max_wgs = k.conv_bf16p_wgs;  // test knob: at most this many persistent workgroups
       if (max_wgs > 0 && max_wgs < g) g = max_wgs;
       p.tz = 8;
       p.nsplit = 1;
@@ -2808,7 +2808,7 @@ size_t conv_plan(ConvParams& p, int num_cus, int plan_n) {
     }
   }
   const size_t scratch = p.nsplit > 1 ? (size_t)p.nsplit * M * p.Cout * sizeof(float) : 0;
-  if (getenv("HOLO_DEBUG_PLAN"))
+  if (k.debug_plan)
     fprintf(stderr, "[plan] conv %d->%d k%d s%d @%d^3 batch %d%s: %s, tz %d, split-K %d x %d chunks (skip %d), grid_x %d, qkv %d rows x %d slices, scratch %zu bytes\n",
             Cin, p.Cout, p.ksz, p.stride, p.OD, p.N, p.skip_w ? " +skip" : "", conv_kernel_name(kernel), p.tz, p.nsplit,
             p.chunks_per_split, p.skip_chunks_per_split, p.grid_x, p.qkv_rows, p.qkv_sb, scratch);

@@ -796,14 +796,12 @@ int gn_finalize_launch(const double* part0, int C0, int B0, const double* part1,
 }
 
 int time_embed_launch(const int64_t* t, int N, int mc, int ted, const float* w1, const float* b1, const float* w2,
-                      const float* b2, float* emb, float* emb_silu, void* stream) {
+                      const float* b2, float* emb, float* emb_silu, int load_kind, void* stream) {
   if (mc > 256 || ted > 1024) {
     set_error("time_embed: model_channels=%d too large", mc);
     return -1;
   }
-  const char* lk = getenv("HOLO_DEBUG_TIMESTEP_LOAD");  // development knob, see the kernel
-  HOLO_LAUNCH(time_embed_kernel, dim3((unsigned)N), dim3(256), stream, t, mc, ted, w1, b1, w2, b2, emb, emb_silu,
-              lk ? atoi(lk) : 0);
+  HOLO_LAUNCH(time_embed_kernel, dim3((unsigned)N), dim3(256), stream, t, mc, ted, w1, b1, w2, b2, emb, emb_silu, load_kind);
   return 0;
 }
 

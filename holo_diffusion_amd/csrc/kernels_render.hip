@@ -1447,32 +1447,21 @@ int bias_leaky_launch(float* y, const float* bias, int64_t rows, int cols, void*
 
 // waves per workgroup of render2_kernel at run time (HOLO_RENDER2_NW=8: development knob, the 8-wave form of the
 // 12-wave configurations)
-static int render2_waves_rt(int C, int n_fine, int with_normals = 0) {
+static int render2_waves_rt(const Knobs& k, int C, int n_fine, int with_normals = 0) {
   const int ch = C / 2;
-  (void)ch;
-  if (with_normals) {  // render2_waves<CH, 64, true>(); HOLO_RENDER2_NRM_NW=8: the two-waves-per-SIMD form (development knob)
-#ifndef HOLO_EMU
-    static const char* en = getenv("HOLO_RENDER2_NRM_NW");
-    if (en && atoi(en) == 8) return 8;
-    return 10;
-#else
-    return 8;
-#endif
-  }
-  int nw = n_fine <= 64 ? (ch <= 16 ? 12 : 8) : (ch <= 16 ? 8 : 4);
-#ifndef HOLO_EMU
-  static const char* e = getenv("HOLO_RENDER2_NW");
-  if (e && atoi(e) == 8 && nw == 12) nw = 8;
-#endif
-  return nw;
+  // render2_waves<CH, 64, true>(); HOLO_RENDER2_NRM_NW=8: the two-waves-per-SIMD form (development knob; what the
+  // emulation build always runs)
+  if (with_normals) return k.render2_nrm_nw == 8 || EMU_BUILD ? 8 : 10;
+  const int nw = n_fine <= 64 ? (ch <= 16 ? 12 : 8) : (ch <= 16 ? 8 : 4);
+  return k.render2_nw == 8 && nw == 12 ? 8 : nw;
 }
 
 template <int CH, bool SP>
-static int render_launch_t(const RenderKernelParams& p, void* stream, int n_wgs) {
+static int render_launch_t(const RenderKernelParams& p, const Knobs& k, void* stream, int n_wgs) {
   const bool nrm = p.nrm != nullptr || p.nrm_c != nullptr;
-  if (render_rays_per_tile(2 * CH, p.n_fine, nrm ? 1 : 0, SP ? 1 : 0, p.train.n_rays > 0 ? 1 : 0) == 4) {
+  if (render_rays_per_tile(k, 2 * CH, p.n_fine, nrm ? 1 : 0, SP ? 1 : 0, p.train.n_rays > 0 ? 1 : 0) == 4) {
     // the (ray, depth)-tiled kernel: exact fp32, with or without rendered normals
-    const int nw = render2_waves_rt(2 * CH, p.n_fine);
+    const int nw = render2_waves_rt(k, 2 * CH, p.n_fine);
 #define HOLO_R2(ZFV, TRV, NWV) HOLO_LAUNCH((render2_kernel<CH, ZFV, TRV, NWV>), dim3((unsigned)n_wgs), dim3(64 * NWV), stream, p)
     if (nrm) {
       if (p.train.n_rays > 0) {
@@ -1480,7 +1469,7 @@ static int render_launch_t(const RenderKernelParams& p, void* stream, int n_wgs)
         return -1;
       }
       if constexpr (CH <= 16) {
-        if (render2_waves_rt(2 * CH, p.n_fine, 1) == 10) {
+        if (render2_waves_rt(k, 2 * CH, p.n_fine, 1) == 10) {
           HOLO_LAUNCH((render2_kernel<CH, 64, false, 10, true>), dim3((unsigned)n_wgs), dim3(640), stream, p);
         } else {
           HOLO_LAUNCH((render2_kernel<CH, 64, false, 8, true>), dim3((unsigned)n_wgs), dim3(512), stream, p);
@@ -1521,22 +1510,18 @@ static int render_launch_t(const RenderKernelParams& p, void* stream, int n_wgs)
 
 // rays of one wave tile: 4 on the (ray, depth)-tiled kernel, 32 on the ray-per-column kernel (the bf16x3 split arithmetic
 // and - development knob HOLO_RENDER_V1=1 - everything)
-int render_rays_per_tile(int C, int n_fine, int with_normals, int split3, int train) {
+int render_rays_per_tile(const Knobs& k, int C, int n_fine, int with_normals, int split3, int train) {
   if (train) return 4;
   if (split3) return 32;
   // rendered normals: on the (ray, depth)-tiled kernel for the BASELINE / released shapes (round 5), else ray-per-column
   if (with_normals && (C > 32 || n_fine > 64)) return 32;
-#ifndef HOLO_EMU
-  static const bool v1 = getenv("HOLO_RENDER_V1") != nullptr;
-  if (v1) return 32;
-#endif
-  return 4;
+  return k.render_v1 ? 32 : 4;
 }
 
 // waves per workgroup of the persistent kernel for this configuration (the scratch has one slot per resident wave)
-int render_waves_per_wg(int C, int n_fine, int with_normals, int split3, int train) {
+int render_waves_per_wg(const Knobs& k, int C, int n_fine, int with_normals, int split3, int train) {
   const bool z64 = n_fine <= 64;
-  if (render_rays_per_tile(C, n_fine, with_normals, split3, train) == 4) return render2_waves_rt(C, n_fine, with_normals);
+  if (render_rays_per_tile(k, C, n_fine, with_normals, split3, train) == 4) return render2_waves_rt(k, C, n_fine, with_normals);
   if (C <= 32) {
     if (with_normals) return z64 ? render_waves<16, 64, true>() : render_waves<16, 128, true>();
     return z64 ? render_waves<16, 64, false>() : render_waves<16, 128, false>();
@@ -1553,7 +1538,7 @@ int density_field_launch(const float* grid_cl, const float* w_dens, int C, int64
   return 0;
 }
 
-int render_launch(const RenderKernelParams& p, void* stream, int n_wgs) {
+int render_launch(const RenderKernelParams& p, const Knobs& k, void* stream, int n_wgs) {
   if (p.mlp.Hd != HD) {
     set_error("render: dnet_hidden_dim must be %d (got %d)", HD, p.mlp.Hd);
     return -1;
@@ -1568,11 +1553,11 @@ int render_launch(const RenderKernelParams& p, void* stream, int n_wgs) {
   }
   switch (p.C) {
     case 16:
-      return render_launch_t<8, false>(p, stream, n_wgs);
+      return render_launch_t<8, false>(p, k, stream, n_wgs);
     case 32:
-      return p.split3 ? render_launch_t<16, true>(p, stream, n_wgs) : render_launch_t<16, false>(p, stream, n_wgs);
+      return p.split3 ? render_launch_t<16, true>(p, k, stream, n_wgs) : render_launch_t<16, false>(p, k, stream, n_wgs);
     case 64:
-      return render_launch_t<32, false>(p, stream, n_wgs);
+      return render_launch_t<32, false>(p, k, stream, n_wgs);
     default:
       set_error("render: the fused renderer is built for feature_size 16, 32 or 64 (got %d; 128 input features are "
                 "supported by the stand-alone implicit function only)", p.C);

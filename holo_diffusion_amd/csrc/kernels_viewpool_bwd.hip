@@ -1035,25 +1035,22 @@ __global__ __launch_bounds__(256) void mm_sum_partials_kernel(const float* __res
 
 }  // namespace
 
-int view_pool_bwd_launch(const ViewPoolBwdParams& b, int n_wgs, void* stream) {
+int view_pool_bwd_launch(const ViewPoolBwdParams& b, int n_wgs, const Knobs& k, void* stream) {
   if (b.fwd.F > VB_F || b.fwd.A > 512) {
     set_error("view_pool_backward: feature_size <= %d and <= 512 aggregated features (got %d, %d)", VB_F, b.fwd.F, b.fwd.A);
     return -1;
   }
   // (HOLO_VIEWPOOL_BWD_V1=1: the register-accumulating form on every call - the knob tests/test_viewpool.py flips per call)
-  const char* ev = getenv("HOLO_VIEWPOOL_BWD_V1");
-  const bool v1 = ev && ev[0] == '1';
+  const bool v1 = k.viewpool_bwd_v1;
   const bool fixed = b.want_feats && b.fix_max != nullptr;  // deterministic mode: measure the addends, then add in fixed point
   if (!v1 && b.fwd.A + 1 <= VB2_AMAX) {
     ViewPoolBwdParams q = b;
 #ifdef HOLO_DEV_PROBES  // timing probes of a development build only (-DHOLO_DEV_PROBES): they DROP gradients
-    const char* ep = getenv("HOLO_VIEWPOOL_BWD_PROBE");  // 0 no pass 2, 2 pass 2 without its atomics, 10 + k the atomics of map k alone
-    if (ep && q.want_feats) {
-      q.want_feats = atoi(ep);
+    if (k.viewpool_bwd_probe != KNOB_UNSET && q.want_feats) {  // 0 no pass 2, 2 pass 2 without its atomics, 10 + k the atomics of map k alone
+      q.want_feats = (int)k.viewpool_bwd_probe;
       fprintf(stderr, "[holo] HOLO_VIEWPOOL_BWD_PROBE=%d: feature-map gradients are INCOMPLETE (timing probe)\n", q.want_feats);
     }
-    const char* eo = getenv("HOLO_VIEWPOOL_BWD_OCC");  // 3 = the 166-register build (measured 6.3 vs 3.9 ms)
-    if (eo && eo[0] == '3' && !fixed) {
+    if (k.viewpool_bwd_occ && !fixed) {  // 3 = the 166-register build (measured 6.3 vs 3.9 ms)
       HOLO_LAUNCH((view_pool_bwd2_kernel<3, 0>), dim3((unsigned)n_wgs), dim3(256), stream, q);
     } else
 #endif

@@ -33,6 +33,7 @@ using namespace holo;
 struct HoloRenderer {
   HoloCtx* ctx;
   HoloRenderCfg cfg;
+  Knobs knobs;  // snapshot of holo_renderer_create (holo_knobs.h): the render family shapes the scratch and every launch
   std::map<std::string, std::vector<float>> host;        // raw parameters (host copies)
   std::map<std::string, std::vector<int64_t>> expected;  // expected shapes
   float* packed = nullptr;  // device: w_feat | b_feat | w_dens | w_rad | w_dir | u_rad | w_fnet [Fd][Hd] | b_fnet [Fd]
@@ -77,6 +78,7 @@ int holo_renderer_create(HoloCtx* ctx, const HoloRenderCfg* cfg, HoloRenderer** 
   HoloRenderer* r = new HoloRenderer;
   r->ctx = ctx;
   r->cfg = *cfg;
+  r->knobs = Knobs::from_env();
   const int64_t C = cfg->feature_size, Hd = cfg->dnet_hidden_dim, De = dir_emb(*cfg);
   r->expected["_density_net.mlp.0.0.weight"] = {Hd, C};
   r->expected["_density_net.mlp.0.0.bias"] = {Hd};
@@ -267,21 +269,18 @@ static size_t grid_cl_bytes(const HoloRenderer* r) {
 // (64 coarse samples x 32 rays x float4 = 32 KB; the same again for the normals).  The scratch therefore depends on the
 // chip and the configuration only - not on the number of cameras or the image size.
 static int render_workgroups(const HoloRenderer* r) {
-#ifndef HOLO_EMU
-  static const char* e = getenv("HOLO_RENDER_WGS");  // development knob
-  if (e && atoi(e) > 0) return atoi(e);
-#endif
+  if (r->knobs.render_wgs > 0) return (int)r->knobs.render_wgs;  // development knob
   return r->ctx->num_cus > 0 ? r->ctx->num_cus : 256;
 }
 static int split3_active(const HoloRenderer* r) { return (r->split3 && r->cfg.feature_size == 32) ? 1 : 0; }
 static size_t render_slots(const HoloRenderer* r, int with_normals) {
   return (size_t)render_workgroups(r) *
-         (size_t)render_waves_per_wg(r->cfg.feature_size, r->cfg.n_pts_fine, with_normals, split3_active(r), 0);
+         (size_t)render_waves_per_wg(r->knobs, r->cfg.feature_size, r->cfg.n_pts_fine, with_normals, split3_active(r), 0);
 }
 // scratch of the ray-per-column kernel (rendered normals / split arithmetic): one 32 KB slot per resident wave; the
 // (ray, depth)-tiled kernel keeps every per-ray value in LDS and needs none
 static size_t val_ws_bytes(const HoloRenderer* r, int with_normals) {
-  if (render_rays_per_tile(r->cfg.feature_size, r->cfg.n_pts_fine, with_normals, split3_active(r), 0) == 4) return 256;
+  if (render_rays_per_tile(r->knobs, r->cfg.feature_size, r->cfg.n_pts_fine, with_normals, split3_active(r), 0) == 4) return 256;
   return render_slots(r, with_normals) * 64 * 32 * 4 * sizeof(float);
 }
 
@@ -356,7 +355,7 @@ int holo_render(HoloRenderer* r, const float* grid, const HoloCamera* cameras, i
   const int H = c.image_height, Wd = c.image_width;
   const int64_t npix = (int64_t)H * Wd;
   float* dens_field = nullptr;
-  if (want_nrm && render_rays_per_tile(C, c.n_pts_fine, 1, split3_active(r), 0) == 4) {
+  if (want_nrm && render_rays_per_tile(r->knobs, C, c.n_pts_fine, 1, split3_active(r), 0) == 4) {
     MlpParams mp;
     fill_mlp(r, mp);
     dens_field = (float*)((char*)workspace + grid_cl_bytes(r) + val_ws_bytes(r, 1) * 2 + 256);
@@ -368,16 +367,10 @@ int holo_render(HoloRenderer* r, const float* grid, const HoloCamera* cameras, i
   const int G = (n_cameras + n_launches - 1) / n_launches;
   const int n_wgs_max = render_workgroups(r);
   const int sp3 = split3_active(r);
-  const int waves_per_wg = render_waves_per_wg(C, c.n_pts_fine, want_nrm ? 1 : 0, sp3, 0);
-  const int rays_per_tile = render_rays_per_tile(C, c.n_pts_fine, want_nrm ? 1 : 0, sp3, 0);
-#ifndef HOLO_EMU
-  static const bool timeline = getenv("HOLO_RENDER_TIMELINE") != nullptr;  // development probe (synchronises!)
-  static const char* xcd_env = getenv("HOLO_RENDER_XCD");
-  const int xcd = xcd_env ? atoi(xcd_env) : 8;
-#else
-  const bool timeline = false;
-  const int xcd = 2;
-#endif
+  const int waves_per_wg = render_waves_per_wg(r->knobs, C, c.n_pts_fine, want_nrm ? 1 : 0, sp3, 0);
+  const int rays_per_tile = render_rays_per_tile(r->knobs, C, c.n_pts_fine, want_nrm ? 1 : 0, sp3, 0);
+  const bool timeline = r->knobs.render_timeline;  // development probe (synchronises!)
+  const int xcd = r->knobs.render_xcd != KNOB_UNSET ? (int)r->knobs.render_xcd : EMU_BUILD ? 2 : 8;
   for (int c0 = 0; c0 < n_cameras; c0 += G) {
     const int ng = n_cameras - c0 < G ? n_cameras - c0 : G;
     RenderKernelParams p;
@@ -423,24 +416,14 @@ int holo_render(HoloRenderer* r, const float* grid, const HoloCamera* cameras, i
     int n_wgs = (int)((p.n_tiles + waves_per_wg - 1) / waves_per_wg);
     if (n_wgs > n_wgs_max) n_wgs = n_wgs_max;
     p.xcd = (xcd > 1 && n_wgs == n_wgs_max && n_wgs % xcd == 0) ? xcd : 1;
-#ifndef HOLO_EMU
-    static const bool static_tiles = getenv("HOLO_RENDER_STATIC_TILES") != nullptr;  // development knob
-#else
-    const bool static_tiles = false;
-#endif
-    if (rays_per_tile == 4 && !static_tiles) {  // dynamic tile hand-out: the counters live in the (otherwise unused) scratch area
+    if (rays_per_tile == 4 && !r->knobs.render_static_tiles) {  // dynamic tile hand-out: the counters live in the (otherwise unused) scratch area
       p.tile_ctr = (int*)p.val_ws;
       HIP_TRY(hipMemsetAsync(p.tile_ctr, 0, 8 * sizeof(int), (hipStream_t)stream));
       // the end of every XCD range in single-ray items: about two rounds of them on the range's resident waves
       // (HOLO_RENDER_TAIL=<quads per range>: development knob, 0 = off)
       const int ranges = p.xcd > 1 ? p.xcd : 1;
-      p.tail_quads = (n_wgs * waves_per_wg / ranges) / 2;
-#ifndef HOLO_EMU
-      static const char* tq = getenv("HOLO_RENDER_TAIL");
-      if (tq) p.tail_quads = atoi(tq);
-#else
-      p.tail_quads = 3;  // (the emulation's tiny frames: a few tail tiles in every test)
-#endif
+      p.tail_quads = EMU_BUILD ? 3 : (n_wgs * waves_per_wg / ranges) / 2;  // (the emulation's tiny frames: a few tail tiles in every test)
+      if (r->knobs.render_tail != KNOB_UNSET) p.tail_quads = (int)r->knobs.render_tail;
     }
     const int nslots = n_wgs * waves_per_wg;
 #ifndef HOLO_EMU
@@ -449,7 +432,7 @@ int holo_render(HoloRenderer* r, const float* grid, const HoloCamera* cameras, i
       HIP_TRY(hipMemsetAsync(p.dbg, 0, (size_t)nslots * 64, (hipStream_t)stream));
     }
 #endif
-    rc = render_launch(p, stream, n_wgs);
+    rc = render_launch(p, r->knobs, stream, n_wgs);
     if (rc) return HOLO_E_INVALID;
 #ifndef HOLO_EMU
     if (timeline) {
@@ -584,7 +567,7 @@ static int render_rays_impl(HoloRenderer* r, const float* grid_cl, const HoloCam
   const HoloRenderCfg& c = r->cfg;
   const int R = c.resol, C = c.feature_size;
   const int G = RenderKernelParams::MAX_CAMS;
-  const int waves_per_wg = render_waves_per_wg(C, c.n_pts_fine, 0, 0, 1);
+  const int waves_per_wg = render_waves_per_wg(r->knobs, C, c.n_pts_fine, 0, 0, 1);
   const int n_wgs_max = render_workgroups(r);
   const int64_t nm = (int64_t)c.n_pts_coarse + c.n_pts_fine;
   for (int c0 = 0; c0 < n_cameras; c0 += G) {
@@ -627,7 +610,7 @@ static int render_rays_impl(HoloRenderer* r, const float* grid_cl, const HoloCam
     int n_wgs = (int)((p.n_tiles + waves_per_wg - 1) / waves_per_wg);
     if (n_wgs > n_wgs_max) n_wgs = n_wgs_max;
     p.xcd = 1;
-    if (render_launch(p, stream, n_wgs)) return HOLO_E_INVALID;
+    if (render_launch(p, r->knobs, stream, n_wgs)) return HOLO_E_INVALID;
   }
   return 0;
 }

@@ -159,6 +159,7 @@ struct LayoutOut { const float* src; int C; int64_t V; };
 struct TimeEmbed {
   const float *w1, *b1, *w2, *b2;
   float *emb, *emb_silu;
+  int load_kind;  // HOLO_DEBUG_TIMESTEP_LOAD of the plan (0 in production)
 };
 struct EmbLinears {  // every ResBlock's emb_layers as one [emb_rows][ted] product
   const float *emb_silu, *w, *b;
@@ -185,6 +186,7 @@ struct Flash {
   float* packed;        // form 2: scratch of the packed operands and split partials
   int out_bf16;         // form 2: attn.out is bf16
   int operands_packed;  // form 2: the qkv convolution wrote the packed operands itself
+  int ksplit, lazy;     // form 2: key splits (`packed` is sized and laid out for them); the LAZY pass runs before the exact kernel
 };
 struct Op {  // trivially copyable: holo_unet_forward_cl patches copies of two of them
   OpKind kind;
@@ -259,7 +261,7 @@ struct HoloUnet {
   std::map<std::string, int> emb_row_off;  // resblock prefix -> first row
   float* emb_w = nullptr;                  // [emb_rows][ted]
   float* emb_b = nullptr;                  // [emb_rows]
-  bool keep_intermediates = false;
+  Knobs knobs;  // snapshot of holo_unet_create (holo_knobs.h): which weight copies exist, whether plans release activations
   Plan plan;                                        // inference (holo_unet_forward, _forward_cl, _fetch_block, _time_*)
   std::map<std::pair<int, bool>, size_t> ws_cache;  // (batch, batch_invariant) -> workspace bytes
   // ---- training (holo_unet_backward): weights of the transposed convolutions, packed like the forward ones
@@ -509,6 +511,7 @@ struct Planner {
   int N;
   char* base;  // workspace base (may be null for a sizing pass)
   Plan& plan;
+  const Knobs knobs = Knobs::from_env();  // THE snapshot of this build: nothing below or behind it reads the environment
   std::vector<Op>& ops;       // plan.ops
   Arena arena;                // big activations, after the small region
   size_t small_top = 0;       // coef / emb buffers
@@ -523,7 +526,7 @@ struct Planner {
     // a generous fixed region for the small buffers
     small_cap = Arena::al((size_t)N * 8 * 1024 * 256 * 2 + (size_t)N * (u->emb_rows + 4 * u->ted) * 4 * 2 + 65536);
     arena_base = small_cap;
-    arena.keep = u->keep_intermediates;
+    arena.keep = u->knobs.keep_intermediates;
   }
   template <class T>
   T* ptr(size_t off) {
@@ -669,10 +672,10 @@ struct Planner {
       p.skip_bias = d.skip.bias;
     }
     ConvParams one = p;
-    size_t sb = conv_plan(p, u->ctx->num_cus, plan_n());
+    size_t sb = conv_plan(p, u->ctx->num_cus, knobs, plan_n());
     if (plan_n() != N) {  // the batch-invariant plan: the launch must compute each sample as the batch-1 launch does
       one.N = 1;
-      conv_plan(one, u->ctx->num_cus);
+      conv_plan(one, u->ctx->num_cus, knobs);
       if (err.empty() && (one.kernel != p.kernel || one.tz != p.tz || one.nsplit != p.nsplit ||
                           one.chunks_per_split != p.chunks_per_split || one.skip_chunks_per_split != p.skip_chunks_per_split))
         err = "batch-invariant plan: at batch " + std::to_string(N) + " the " + std::to_string(p.C0 + p.C1) + " -> " +
@@ -723,15 +726,12 @@ struct Planner {
     // (below 8^3 the convolution runs on the row-tile kernel, which takes the skip's channels as extra K chunks: exact-fp32
     //  mode; four launches + four reduces less at the 4^3 level of the north-star net)
     bool fuse_skip = has_skip && ((R % 8) == 0 || (u->compute_mode == 0 && R < 8)) && b.cout >= 64 && u->compute_mode != 2 &&
-                     !getenv("HOLO_NO_SKIP_FUSION");
+                     !knobs.no_skip_fusion;
     // From 64^3 on (exact-fp32 mode) the skip runs as its own streaming 1x1x1 launch (conv1x1_stream_kernel) whose output is the
     // second convolution's residual: measured on the north-star net, fused 305 us per launch against 208 (plain) + ~45.
     // HOLO_SKIP_FUSION_BELOW_R=<R>: development knob for the threshold (A/B of the two forms)
-    {
-      const char* mr = getenv("HOLO_SKIP_FUSION_BELOW_R");
-      const int below = mr ? atoi(mr) : 64;
-      if (fuse_skip && u->compute_mode == 0 && R >= below && (b.cin % 32) == 0 && b.cin <= 256 && (b.cout % 64) == 0) fuse_skip = false;
-    }
+    if (fuse_skip && u->compute_mode == 0 && R >= knobs.skip_fusion_below_r && (b.cin % 32) == 0 && b.cin <= 256 && (b.cout % 64) == 0)
+      fuse_skip = false;
     Act s;
     if (has_skip && !fuse_skip) {
       s = new_act(b.cout, R);
@@ -785,7 +785,7 @@ struct Planner {
     size_t a = scratch_alloc(a_bytes);
     size_t v2_work = 0, v2_bytes = 0;
     bool a_is_bf16 = false;
-    const bool flash = flash_attn_supported((int)T, ch) && !getenv("HOLO_NO_FLASH_ATTN");
+    const bool flash = flash_attn_supported((int)T, ch) && !knobs.no_flash_attn;
     Op fop = make_op(OP_FLASH);
     Flash& fl = fop.flash;
     fl.attn.qkv = ptr<float>(qkv);
@@ -805,12 +805,12 @@ struct Planner {
     memset(&qp, 0, sizeof qp);
     bool offer_pack = false;
     if (flash) {
-      const char* mt = getenv("HOLO_BF16_FLASH_MIN_T");
-      const int64_t min_t = mt ? atoll(mt) : 1024;
-      if (u->compute_mode == 1 && T >= min_t && flash_attn_bf16v2_supported((int)T, ch)) {
+      if (u->compute_mode == 1 && T >= knobs.bf16_flash_min_t && flash_attn_bf16v2_supported((int)T, ch)) {
         // packed bf16 operands (V transposed) in scratch, bf16 attention output
         fl.form = 2;
-        v2_bytes = flash_attn_bf16v2_workspace_bytes(fl.attn, u->ctx->num_cus);
+        fl.ksplit = flash_attn_bf16v2_ksplit(fl.attn, u->ctx->num_cus, knobs);
+        fl.lazy = knobs.attn_exact ? 0 : 1;  // (HOLO_ATTN_EXACT: the exact loop alone)
+        v2_bytes = flash_attn_bf16v2_workspace_bytes(fl.attn, fl.ksplit);
         v2_work = scratch_alloc(v2_bytes);
         fl.packed = ptr<float>(v2_work);
         fl.out_bf16 = 1;
@@ -822,7 +822,7 @@ struct Planner {
         }
       } else {
         // exact fp32: the key range split across workgroups where one per query tile leaves CUs empty
-        fl.attn.nsplit = flash_attn_splits(plan_n(), (int)T, H, u->ctx->num_cus);
+        fl.attn.nsplit = flash_attn_splits(plan_n(), (int)T, H, u->ctx->num_cus, knobs);
         split_bytes = flash_attn_workspace_bytes(fl.attn);
         if (split_bytes) {
           split_work = scratch_alloc(split_bytes);
@@ -840,7 +840,7 @@ struct Planner {
     emit_conv(cq);
     if (flash) {
       fl.operands_packed = ops.back().conv.kernel == ConvKernel::Qkv ? 1 : 0;
-      if (getenv("HOLO_DEBUG_PLAN"))
+      if (knobs.debug_plan)
         fprintf(stderr, "[plan] attention %s: T=%lld C=%d heads=%d -> %s flash kernel, %d key splits\n", p.c_str(),
                 (long long)T, C, H, fl.form == 2 ? "bf16" : "fp32", fl.form == 2 ? 1 : fl.attn.nsplit);
       ops.push_back(fop);
@@ -924,6 +924,7 @@ struct Planner {
       op.temb.b2 = P(u, "time_embed.2.bias");
       op.temb.emb = ptr<float>(emb);
       op.temb.emb_silu = ptr<float>(embs);
+      op.temb.load_kind = (int)knobs.debug_timestep_load;
       ops.push_back(op);
     }
     {
@@ -986,7 +987,7 @@ struct Planner {
       ops.push_back(op);
     }
     release(y);
-    if (getenv("HOLO_DEBUG_PLAN")) {  // development: what the plan launches
+    if (knobs.debug_plan) {  // development: what the plan launches
       int n_fin = 0, n_conv = 0, n_split = 0;
       for (const Op& o : ops) {
         n_fin += o.kind == OP_FINAL;
@@ -1154,14 +1155,13 @@ struct TrainPlanner {
     w.Cout = cout;
     w.coef = f.coef ? ptr<float>(*f.coef) : nullptr;
     w.act = f.act;
-    const size_t pb = wgrad_partial_bytes(w, u->ctx->num_cus);
-    w.partial = ptr<float>(alloc(pb));
+    const WgradPlan wg = wgrad_plan(w, u->ctx->num_cus, pl.knobs);
+    w.partial = ptr<float>(alloc(wgrad_partial_bytes(w, wg)));
     float* dw = pgrad(layer + ".weight");
     float* db = pgrad(layer + ".bias");
     double* cs = ptr<double>(alloc(colsum_scratch_bytes(cout)));
-    const int ncu = u->ctx->num_cus;
     const int64_t M = (int64_t)N * vox(f.out_size());
-    bops.push_back([w, dw, ncu](void* st) { return conv_wgrad_launch(w, dw, 0, ncu, st); });
+    bops.push_back([w, wg, dw](void* st) { return conv_wgrad_launch(w, wg, dw, 0, st); });
     bops.push_back([gy, M, cout, cs, db](void* st) { return colsum_launch(gy, M, cout, cs, db, 0, st); });
   }
   // the forward convolution of `cout` channels out of [x0 | x1], as emit_wgrad wants it
@@ -1338,8 +1338,8 @@ struct TrainPlanner {
     } else if (kind == B_DOWN) {
       const ConvWeights* wt = dgw(wn);
       if (!wt) return;
-      const char* zi = getenv("HOLO_DGRAD_S2_DIRECT");  // development / test knob: 1 = conv_dgrad_s2_kernel everywhere
-      if (!(zi && zi[0] == '1') && find_dgw(wn + "#s1") && Ri == 2 * Ro && (Ri % 8) == 0) {
+      // (HOLO_DGRAD_S2_DIRECT=1, development / test knob: conv_dgrad_s2_kernel everywhere)
+      if (!pl.knobs.dgrad_s2_direct && find_dgw(wn + "#s1") && Ri == 2 * Ro && (Ri % 8) == 0) {
         // zero insertion + the stride-1 transposed convolution on the forward's conv kernels (8x the multiply-adds, on the
         // Winograd kernels: 0.24 instead of 1.35 ms at 64^3 <- 32^3)
         const size_t gz_off = alloc((size_t)N * vox(Ri) * cout * sizeof(float));
@@ -1499,7 +1499,7 @@ int run_op(const HoloUnet* u, const Op& op, int N, const float* x, const int64_t
       return ncdhw_to_ndhwc_launch(x, op.in.dst, N, op.in.C, op.in.V, 0, stream, op.in.dst_bf16);
     case OP_TEMB:
       return time_embed_launch(t, N, u->cfg.model_channels, u->ted, op.temb.w1, op.temb.b1, op.temb.w2, op.temb.b2,
-                               op.temb.emb, op.temb.emb_silu, stream);
+                               op.temb.emb, op.temb.emb_silu, op.temb.load_kind, stream);
     case OP_EMBLIN:
       return rows_linear_launch(op.emblin.emb_silu, op.emblin.w, op.emblin.b, op.emblin.out, N, u->emb_rows, u->ted, stream);
     case OP_STATS:
@@ -1517,7 +1517,7 @@ int run_op(const HoloUnet* u, const Op& op, int N, const float* x, const int64_t
       return softmax_rows_launch(op.softmax.S, op.softmax.rows, op.softmax.cols, stream);
     case OP_FLASH: {
       const Flash& f = op.flash;
-      if (f.form == 2) return flash_attn_bf16v2_launch(f.attn, f.packed, f.out_bf16, u->ctx->num_cus, stream, f.operands_packed);
+      if (f.form == 2) return flash_attn_bf16v2_launch(f.attn, f.packed, f.out_bf16, f.ksplit, f.lazy, stream, f.operands_packed);
       return flash_attn_launch(f.attn, stream);
     }
     case OP_OUT:
@@ -1572,10 +1572,8 @@ int holo_ctx_create(int device_id, HoloCtx** out) {
   HoloCtx* c = new HoloCtx;
   c->device = device_id;
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  if (const char* e = getenv("HOLO_NUM_CUS")) {  // test knob: planners size grids / split-K for this many CUs
-    const int v = atoi(e);
-    if (v > 0) c->num_cus = v;
-  }
+  // (HOLO_NUM_CUS, test knob: planners size grids / split-K for this many CUs - the one knob read here, holo_knobs.h)
+  if (const int64_t v = Knobs::from_env().num_cus) c->num_cus = (int)v;
   *out = c;
   return 0;
 }
@@ -1613,8 +1611,7 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
   u->cfg = *cfg;
   build_structure(u);
   enumerate_params(u);
-  const char* dbg = getenv("HOLO_KEEP_INTERMEDIATES");
-  u->keep_intermediates = dbg && dbg[0] == '1';
+  u->knobs = Knobs::from_env();
   // private parameter storage
   int64_t total = 0;
   auto priv_numel = [](const ParamSlot& s) -> int64_t {
@@ -1656,7 +1653,7 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
   }
   {  // Winograd copies for the convolutions that can land on 128-voxel tiles: the wide top levels (a 3x3x3 conv of
      // <= 256 channels: 48 (z,y) pseudo-taps; a ResBlock's 1x1x1 skip connection: 4).  HOLO_CONV_WINO=0: none
-    const bool enable = env_int("HOLO_CONV_WINO", 1) != 0;
+    const bool enable = u->knobs.conv_wino != 0;
     auto wino2_numel = [&](const ParamSlot& s) -> int64_t {
       const bool c3 = s.kind == P_CONV3;
       const bool sk = s.kind == P_CONV1 && s.name.find("skip_connection") != std::string::npos;
@@ -1666,7 +1663,7 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
     };
     // F(2x2x2, 3x3x3) copies (conv_wino3_kernel, 64 pseudo-taps / 8 signed skip copies): the levels whose workgroup list
     // can fill the chip - up to 256 output channels (64^3 .. 8^3 in the released nets); HOLO_CONV_WINO3=0: none
-    const bool enable3 = env_int("HOLO_CONV_WINO3", 1) != 0;
+    const bool enable3 = u->knobs.conv_wino3 != 0;
     auto wino3_numel = [&](const ParamSlot& s) -> int64_t {
       if (!enable3 || wino2_numel(s) == 0 || s.shape[0] % 64 || s.shape[0] > 256 || s.shape[1] > 768) return 0;
       return conv_wino3_weight_floats(pad_cout((int)s.shape[0]), pad_cin((int)s.shape[1]), s.kind == P_CONV3 ? 27 : 1);
@@ -1887,7 +1884,7 @@ int holo_unet_fetch_block(HoloUnet* net, const char* tag, float* dst, int64_t ds
     set_error("holo_unet_fetch_block: null argument");
     return HOLO_E_INVALID;
   }
-  if (!net->keep_intermediates) {
+  if (!net->knobs.keep_intermediates) {
     set_error("holo_unet_fetch_block: create the net with HOLO_KEEP_INTERMEDIATES=1");
     return HOLO_E_STATE;
   }
@@ -2059,8 +2056,7 @@ int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_
   // Winograd copies of the transposed convolution (the dgrad of a wide-level 3x3x3 conv runs on conv_wino2_kernel like
   // the forward conv: 48 pseudo-taps, same eligibility as holo_unet_create's except that the transposed conv's output
   // channels are the forward conv's INPUT channels, up to 768 with the skip concat)
-  static const bool wino_on = env_int("HOLO_CONV_WINO", 1) != 0;
-  if (wino_on && net->compute_mode == 0 && T == 27 && (Ci % 64) == 0 && Ci <= 768 && Co <= 768) {
+  if (net->knobs.conv_wino != 0 && net->compute_mode == 0 && T == 27 && (Ci % 64) == 0 && Ci <= 768 && Co <= 768) {
     float*& w2 = dw.wino2;
     if (!w2) {  // a plan sized before these copies existed chose other kernels (and scratch sizes)
       net->tws_cache.clear();
@@ -2069,8 +2065,7 @@ int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_
     }
     if (repack_conv_weight_wino2_launch(net->dgrad_tmp, w2, Ci, Co, 27, pad_cout(Ci), pad_cin(Co), stream)) return HOLO_E_INVALID;
     // ... and on conv_wino3_kernel where the forward convolutions do (transposed: output channels = the forward's inputs)
-    static const bool wino3_on = env_int("HOLO_CONV_WINO3", 1) != 0;
-    if (wino3_on && Ci <= 256 && Co <= 768) {
+    if (net->knobs.conv_wino3 != 0 && Ci <= 256 && Co <= 768) {
       float*& w3 = dw.wino3;
       if (!w3) {
         net->tws_cache.clear();

@@ -167,6 +167,7 @@ int holo_view_pool_backward(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const Holo
     set_error("holo_view_pool_backward: null argument");
     return HOLO_E_INVALID;
   }
+  const Knobs knobs = Knobs::from_env();  // per call: this entry has no handle (holo_knobs.h, CALL)
   ViewPoolBwdParams b;
   memset(&b, 0, sizeof b);
   char* ws;
@@ -207,7 +208,7 @@ int holo_view_pool_backward(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const Holo
       return HOLO_E_HIP;
     }
   }
-  if (view_pool_bwd_launch(b, n_wgs, stream)) return HOLO_E_UNSUPPORTED;
+  if (view_pool_bwd_launch(b, n_wgs, knobs, stream)) return HOLO_E_UNSUPPORTED;
   for (int k = 0; k < n_feats; ++k)
     if (b.gfeat[k]) {
       const ViewPoolParams::Feat& f = b.fwd.feat[k];
@@ -225,6 +226,7 @@ int holo_view_pool_backward(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const Holo
 struct HoloMlpMeanPooler {
   HoloCtx* ctx;
   HoloMlpMeanCfg cfg;
+  Knobs knobs;  // snapshot of holo_mlp_mean_create (holo_knobs.h): the backward's chunk layout, for its size query and its run
   std::map<std::string, std::vector<float>> host;
   std::map<std::string, std::vector<int64_t>> expected;
   int D = 0, E = 0, dp = 0, emb0 = 0;
@@ -264,6 +266,7 @@ int holo_mlp_mean_create(HoloCtx* ctx, const HoloMlpMeanCfg* cfg, HoloMlpMeanPoo
   HoloMlpMeanPooler* h = new HoloMlpMeanPooler;
   h->ctx = ctx;
   h->cfg = *cfg;
+  h->knobs = Knobs::from_env();
   int quad = 0;
   for (int k = 0; k < cfg->n_feats; ++k) {
     if (cfg->channels[k] < 1) {
@@ -527,12 +530,8 @@ static MmBwdLayout mm_bwd_layout(const HoloMlpMeanPooler* h, const HoloViewFeatu
   {
     const int64_t row_bytes = (int64_t)(2 * h->dp + 3 * 128 + 3 * ((F + 1 + 3) / 4 * 4)) * 4 * n_views;
     int64_t target = ((int64_t)4 << 30) / (row_bytes > 0 ? row_bytes : 1);
-#ifndef HOLO_EMU
-    const char* e = getenv("HOLO_MLP_MEAN_BWD_CHUNK");
-    if (e && atoll(e) > 0) target = atoll(e);
-#else
-    target = 2048;  // (the emulation's small grids: two chunks at 16^3)
-#endif
+    if (EMU_BUILD) target = 2048;  // (the emulation's small grids: two chunks at 16^3; the knob is not honoured there)
+    else if (h->knobs.mlp_mean_bwd_chunk > 0) target = h->knobs.mlp_mean_bwd_chunk;
     while (L.Pall / L.nchunks > target && (L.Pall % (2 * L.nchunks)) == 0) L.nchunks *= 2;
   }
   L.P = L.Pall / L.nchunks;

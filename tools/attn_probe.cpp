@@ -95,12 +95,14 @@ int main(int argc, char** argv) {
     p.qkv = d_qkv, p.out = d_out, p.N = 1, p.T = T, p.C = C, p.H = H;
     p.scale2 = 1.f / sqrtf((float)CH);
     void* work;
-    CK(hipMalloc(&work, flash_attn_bf16v2_workspace_bytes(p, num_cus)));
-    if (flash_attn_bf16v2_launch(p, work, 0, num_cus, nullptr) != 0) return 1;
+    const Knobs knobs = Knobs::from_env();
+    const int ks = flash_attn_bf16v2_ksplit(p, num_cus, knobs), lazy = knobs.attn_exact ? 0 : 1;
+    CK(hipMalloc(&work, flash_attn_bf16v2_workspace_bytes(p, ks)));
+    if (flash_attn_bf16v2_launch(p, work, 0, ks, lazy, nullptr) != 0) return 1;
     CK(hipDeviceSynchronize());
-    for (int i = 0; i < 3; ++i) flash_attn_bf16v2_launch(p, work, 0, num_cus, nullptr);
+    for (int i = 0; i < 3; ++i) flash_attn_bf16v2_launch(p, work, 0, ks, lazy, nullptr);
     CK(hipEventRecord(e0));
-    for (int i = 0; i < iters; ++i) flash_attn_bf16v2_launch(p, work, 0, num_cus, nullptr);
+    for (int i = 0; i < iters; ++i) flash_attn_bf16v2_launch(p, work, 0, ks, lazy, nullptr);
     CK(hipEventRecord(e1));
     CK(hipEventSynchronize(e1));
     float ms;

@@ -151,7 +151,7 @@ int main(int argc, char** argv) {
     };
     setenv("HOLO_CONV_BF16P", "0", 1);
     ConvParams qt = p;
-    conv_plan(qt, 256);
+    conv_plan(qt, 256, Knobs::from_env());
     if (qt.kernel != ConvKernel::Bf16Wide || qt.nsplit != 1) {
       printf("   planner: kernel %d nsplit %d - skipped\n", (int)qt.kernel, qt.nsplit);
       continue;
@@ -159,7 +159,7 @@ int main(int argc, char** argv) {
     time_fn("conv_bf16t_kernel (2 workgroups per CU)", conv_launch, qt);
     setenv("HOLO_CONV_BF16P", "1", 1);
     ConvParams qp = p;
-    conv_plan(qp, 256);
+    conv_plan(qp, 256, Knobs::from_env());
     if (qp.kernel != ConvKernel::Bf16Persistent) {
       printf("   planner did not choose the persistent form\n");
       continue;

@@ -138,7 +138,7 @@ int main(int argc, char** argv) {
       setenv("HOLO_CONV_WINO3", form == 3 ? "1" : "0", 1);
       setenv("HOLO_CONV_WINO3_MIN_ITEMS", "1", 1);
       ConvParams q = p;
-      const size_t sb = conv_plan(q, 256);
+      const size_t sb = conv_plan(q, 256, Knobs::from_env());
       if (sb) CK(hipMalloc((void**)&q.partial, sb));
       if (q.kernel != (form == 3 ? ConvKernel::Wino3 : ConvKernel::Wino2)) {
         printf("   form %d: planner chose kernel %d\n", form, (int)q.kernel);

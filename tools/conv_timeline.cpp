@@ -59,7 +59,7 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&stats, (size_t)(V / 64) * Cout * 2 * 8));
     p.residual = res; p.bias = bias; p.stats = stats;
   }
-  conv_plan(p, 256);
+  conv_plan(p, 256, Knobs::from_env());
   if (tzo > 0) { p.tz = tzo; p.grid_x = (int)(V / (64 * p.tz)); }
   (void)gx;  // (the persistent multi-tile form was removed from the kernel after these measurements; one tile per workgroup)
   p.stagger_ticks = stag * 100;

@@ -84,7 +84,7 @@ int main(int argc, char** argv) {
   ConvParams p{};
   p.src0 = src, p.C0 = Cin, p.N = 1, p.ID = p.IH = p.IW = p.OD = p.OH = p.OW = R, p.stride = 1, p.pad = 1, p.ksz = 3;
   p.Cout = Cout, p.w = w[0], p.CoutP = CoutP, p.CinP = CinP, p.out = out, p.coef = coef, p.act = 1, p.bias = bias;
-  const size_t sb = conv_plan(p, 256);
+  const size_t sb = conv_plan(p, 256, Knobs::from_env());
   if (sb) CK(hipMalloc((void**)&p.partial, sb));
   printf("%d^3 %d -> %d: kernel %d, split-K %d x %d chunks, partials %.1f MB, weights %.1f MB\n", R, Cin, Cout, (int)p.kernel, p.nsplit,
          p.chunks_per_split, sb / 1e6, wfloats * 4 / 1e6);
