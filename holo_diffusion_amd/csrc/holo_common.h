@@ -39,6 +39,8 @@ static inline T holo_ld_sys(const T* p) { return *p; }
 #define HOLO_MFMA16_ACC(acc, a, b) ((acc) = emu_mfma_f32_16x16x4f32((a), (b), (acc)))
 #define HOLO_MFMA16_ACC_FIRST(acc, a, b) ((acc) = emu_mfma_f32_16x16x4f32((a), (b), (acc)))
 #define HOLO_MFMA_DRAIN() ((void)0)
+#define HOLO_ACC_READ(dst, acc, r) ((dst) = (acc)[r])
+#define HOLO_MAD_U24(a, b, c) ((a) * (b) + (c))
 #define HOLO_SINK8(a, b, c, d, e, f, g, h) ((void)0)
 #define HOLO_PIN_V2(x) ((void)0)
 #define HOLO_ATOMIC_ADD_F32(ptr, v) atomicAdd((ptr), (v))
@@ -123,6 +125,11 @@ __device__ __forceinline__ T holo_ld_sys(const T* p) {
 #define HOLO_MFMA16_ACC_FIRST(acc, a, b) \
   asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b))
 #define HOLO_MFMA_DRAIN() asm volatile("s_nop 15" ::: "memory")
+// One accumulator register -> an arch VGPR, HERE: the allocator neither chooses the moment nor renames the tuple on the
+// way (after HOLO_MFMA_DRAIN(); `r` is a compile-time register index of the tuple).
+#define HOLO_ACC_READ(dst, acc, r) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(dst) : "a"((acc)[r]))
+// a * b + c on 24-bit unsigned factors: v_mad_u32_u24 (a full 32-bit multiply-add compiles to v_mad_u64_u32)
+#define HOLO_MAD_U24(a, b, c) (__umul24((a), (b)) + (c))
 // pins the computation of a register pair at this point of the program (an empty asm volatile that "modifies" it: asm
 // volatile statements keep their order, so the value is formed before the next asm MFMA)
 #define HOLO_PIN_V2(x) asm volatile("" : "+v"(x))

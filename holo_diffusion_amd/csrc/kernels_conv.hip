@@ -2717,6 +2717,9 @@ size_t conv_plan(ConvParams& p, int num_cus, const Knobs& k, int plan_n) {
         (p.Cout % 64) == 0 && (!p.skip_w || p.skip_w_wino3) && (p.OH % 8) == 0 && (p.OW % 8) == 0 && (p.OD % 2) == 0 &&
         (!p.coef || p.act) &&  // (its staging applies the affine and SiLU together)
         (int64_t)p.N * src_vox * (cmax > skmax ? cmax : skmax) * 4 < ((int64_t)1 << 32) &&  // (buffer addressing of whole tensors)
+        // (... and of what its epilogue writes and reads: out / residual, every split's partial sums, the statistics records)
+        (int64_t)wino3_split(t3, ncc, num_cus).n * Mc * p.Cout * 4 < ((int64_t)1 << 32) &&
+        (!p.stats || (Mc / 128) * p.Cout * 16 < ((int64_t)1 << 32)) &&
         (!p.skip_w || ((p.skip_C0 % 16) == 0 && (p.skip_C1 % 4) == 0)) &&
         t3 * wino3_split(t3, ncc, num_cus).n >= (k.conv_wino3_min_items != KNOB_UNSET ? k.conv_wino3_min_items : num_cus / 2))
       return ConvKernel::Wino3;

@@ -90,6 +90,16 @@ static inline w3_rsrc w3_make_rsrc(const void* p) { return w3_rsrc{reinterpret_c
 static inline w3q w3_bld(const w3_rsrc& r, unsigned voff, unsigned soff) {
   return w3_ld(reinterpret_cast<const float*>(r.base + (size_t)voff + (size_t)soff));
 }
+static inline float w3_bld1(const w3_rsrc& r, unsigned voff, unsigned soff) {
+  return *reinterpret_cast<const float*>(r.base + (size_t)voff + (size_t)soff);
+}
+static inline void w3_bst1(const w3_rsrc& r, unsigned voff, unsigned soff, float v) {
+  *reinterpret_cast<float*>(const_cast<char*>(r.base) + (size_t)voff + (size_t)soff) = v;
+}
+static inline void w3_bst_d2(const w3_rsrc& r, unsigned voff, unsigned soff, double a, double b) {
+  double* d = reinterpret_cast<double*>(const_cast<char*>(r.base) + (size_t)voff + (size_t)soff);
+  d[0] = a, d[1] = b;
+}
 #else
 typedef __amdgpu_buffer_rsrc_t w3_rsrc;
 typedef unsigned w3u4 __attribute__((ext_vector_type(4)));
@@ -99,6 +109,18 @@ __device__ __forceinline__ w3_rsrc w3_make_rsrc(const void* p) {
 __device__ __forceinline__ w3q w3_bld(w3_rsrc r, unsigned voff, unsigned soff) {
   const w3u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
   return w3q{f32x2{__uint_as_float(v.x), __uint_as_float(v.y)}, f32x2{__uint_as_float(v.z), __uint_as_float(v.w)}};
+}
+// the epilogue's side of the same addressing: one dword in / out, and a statistics record (two doubles, one 16-byte store)
+__device__ __forceinline__ float w3_bld1(w3_rsrc r, unsigned voff, unsigned soff) {
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+}
+__device__ __forceinline__ void w3_bst1(w3_rsrc r, unsigned voff, unsigned soff, float v) {
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, soff, 0);
+}
+__device__ __forceinline__ void w3_bst_d2(w3_rsrc r, unsigned voff, unsigned soff, double a, double b) {
+  const unsigned long long ua = __builtin_bit_cast(unsigned long long, a), ub = __builtin_bit_cast(unsigned long long, b);
+  const w3u4 v = {(unsigned)ua, (unsigned)(ua >> 32), (unsigned)ub, (unsigned)(ub >> 32)};
+  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0);
 }
 #endif
 __device__ __forceinline__ w3q w3_add(const w3q& a, const w3q& b) { return w3q{pk_add(a.lo, b.lo), pk_add(a.hi, b.hi)}; }
@@ -377,6 +399,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) Bw[g][t] = w_ld(w_of(cur, cc), g * W3_WSUB + t * 256);
   halo_setup(cur, cc);
+  // (all four halo items in ONE round trip - items 2 and 3 waiting in two rows of the not yet live patch - was tried and
+  // measured: the prologue stayed at 3.2 - 3.4 us on the 64^3 shapes, profiles/r11_wino3_item_boundary.txt)
 #pragma unroll
   for (int hp = 0; hp < 2; ++hp) {
 #pragma unroll
@@ -409,7 +433,10 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
     for (int s = 0; s < 64; ++s)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[s][r] = 0.f;
-    for (cc = cur.cc_begin; cc < cur.cc_end; ++cc, ++stage) {
+    // (an item has at least one chunk - conv_wino3_launch checks the split -, so the loop tests at its end: a path round it
+    // would need the 256 zeroing writes a second time)
+    cc = cur.cc_begin;
+    do {
       // what the producer side prepares during this stage: the next chunk of this item, or the first chunk of the next
       // item.  The stage body is ONE basic block (the 256 accumulators then meet the register allocator at the loop header
       // only): on the very last stage of the workgroup the producer side simply stages the current chunk again.
@@ -520,7 +547,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
 #ifdef W3_TIMELINE
       if (dbg && tid == 0) dbg[6] += HOLO_PROBE_CLOCK() - t_stage;  // the stage's own work (barrier wait included)
 #endif
-    }
+      ++stage;
+    } while (++cc < cur.cc_end);
     // ---------------- fused 1x1x1 skip connection: raw block input at the lane's own voxels -> pseudo-taps {0,3}^3.
     //   group sg = (skip chunk, half, dz): the four voxels (dy,dx) of the lane's 2 x 2 x 2 patch = one 16-MFMA group with
     //   accumulators (3dz, 3dy, 3dx).  Its operands come straight from global memory (no halo, no LDS, no barrier), THREE
@@ -573,16 +601,13 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-        // what the skip overwrote: the next stage's first weights and first patch (its A operands are formed after the
-        // epilogue, under which these requests complete)
-        const float* nbuf = s_halo + (stage & 1) * W3_HALO;
+        // what the skip overwrote: the next stage's first weights (requested here: a trip to memory, which completes under the
+        // epilogue) and its first patch (a trip to the LDS: requested inside the epilogue, behind the last accumulator read)
         const unsigned wn0 = w_of(nxt, nxt.cc_begin);
 #pragma unroll
         for (int g0 = 0; g0 < W3_WDIST; ++g0)
 #pragma unroll
           for (int t = 0; t < 4; ++t) Bw[g0][t] = w_ld(wn0, g0 * W3_WSUB + t * 256);
-#pragma unroll
-        for (int a4 = 0; a4 < 4; ++a4) load_patch_row(nbuf, 0, a4);
       }
     }
     if (dbg && tid == 0) dbg[2] = HOLO_PROBE_CLOCK();
@@ -595,22 +620,35 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
 #endif
 
     // ---------------- output transform (lane-local: x, y, z) + epilogue.  D row 4 kq + r = (y tile r, x tile kq).
-    //                  Two register indices r at a time (v_pk_add_f32); the residual is requested before anything else.
+    //   Every accumulator register leaves the accumulation file exactly once, by an explicit v_accvgpr_read in the order the
+    //   transform consumes it (register index r outermost, then xi_z pair, xi_y), eight at a time: what is live of the
+    //   transform is then one xi_y row (8 registers), the y sums of the pair (16) and the pair sums (16) - next to the patch,
+    //   the A operands and the weight ring of the next stage (128 registers) nothing has to be parked anywhere.
+    //   Addresses: out / partial, the residual, the biases and the statistics records go through buffer resources, as the
+    //   producer's requests do - the lane's part of the offset (x tile 2 kq, channel lj) is ONE register per tensor, the tile's
+    //   base and the 32 (r, dz, dy, dx) displacements are scalar (conv_plan: each tensor lies within 4 GB of its base).
     {
-      const int co = cur.n0 + wn * 16 + lj;
-      const int coc = co;  // (Cout is a multiple of 64: conv_wino3_launch)
       const bool direct = p.nsplit == 1;
       const bool has_res = direct && p.residual != nullptr;
-      float bv = (direct && p.bias) ? p.bias[coc] : 0.f;
-      if (direct && p.skip_bias) bv += p.skip_bias[coc];
-      const int64_t tbase = ((((int64_t)cur.n * p.OD + cur.tz0) * p.OH + cur.ty0) * p.OW + cur.tx0 + 2 * kq) * p.Cout + coc;
-      const int64_t zstride = (int64_t)p.OH * p.OW * p.Cout;
-      const int ystride = p.OW * p.Cout;
-      float* obase = direct ? p.out : p.partial + (int64_t)cur.split * M * p.Cout;
-      // voxel (dz, 2 r + dy, dx) of the lane's x tile
-      auto vofs = [&](int r, int dz, int dy, int dx) { return tbase + dz * zstride + (int64_t)(2 * r + dy) * ystride + dx * p.Cout; };
-      // one register index r (= y tile) at a time: 64 accumulator reads, x and y transforms on (xi_z, xi_z + 1) register
-      // pairs (v_pk_add_f32), the z transform on their halves; the residual of r + 1 is requested before r is transformed
+      int ln = lane;
+      HOLO_LAUNDER(ln);  // (the lane offsets are formed here, per item: three instructions instead of registers held through the stages)
+      const unsigned cout4 = (unsigned)p.Cout * 4u;
+      const unsigned e_lj = (unsigned)(ln & 15) * 4u;                  // channel lj of the wave's 16
+      const unsigned e_voff = HOLO_MAD_U24((unsigned)(ln >> 4) * 2u, cout4, e_lj);  // + x tile kq: voxel 2 kq of the row
+      const unsigned cbase = (unsigned)(cur.n0 + wn * 16);              // the wave's first output channel
+      float bv = 0.f;
+      if (direct && p.bias) bv = w3_bld1(w3_make_rsrc(p.bias), e_lj, cbase * 4u);
+      if (direct && p.skip_bias) bv += w3_bld1(w3_make_rsrc(p.skip_bias), e_lj, cbase * 4u);
+      const unsigned vtile = (unsigned)(((cur.n * p.OD + cur.tz0) * p.OH + cur.ty0) * p.OW + cur.tx0);
+      const unsigned sbase = vtile * cout4 + cbase * 4u;
+      const unsigned obase = direct ? sbase : sbase + (unsigned)cur.split * ((unsigned)M * cout4);
+      const unsigned zstride = (unsigned)(p.OH * p.OW) * cout4, ystride = (unsigned)p.OW * cout4;
+      const w3_rsrc rs_out = w3_make_rsrc(direct ? p.out : p.partial), rs_res = w3_make_rsrc(p.residual);
+      // voxel (dz, 2 r + dy, dx) of the lane's x tile, relative to the tile's base (wave-uniform)
+      auto vofs = [&](int r, int dz, int dy, int dx) {
+        return (unsigned)dz * zstride + (unsigned)(2 * r + dy) * ystride + (unsigned)dx * cout4;
+      };
+      // one register index r (= y tile) at a time; the residual of r + 1 is requested before r is transformed
       float res[2][2][2][2];
       auto load_res = [&](int r) {
 #pragma unroll
@@ -618,7 +656,15 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
 #pragma unroll
           for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
-            for (int dx = 0; dx < 2; ++dx) res[r & 1][dz][dy][dx] = has_res ? p.residual[vofs(r, dz, dy, dx)] : 0.f;
+            for (int dx = 0; dx < 2; ++dx) res[r & 1][dz][dy][dx] = 0.f;
+        if (has_res) {  // (ONE uniform branch round the eight requests)
+#pragma unroll
+          for (int dz = 0; dz < 2; ++dz)
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+              for (int dx = 0; dx < 2; ++dx) res[r & 1][dz][dy][dx] = w3_bld1(rs_res, e_voff, sbase + vofs(r, dz, dy, dx));
+        }
       };
       load_res(0);
       float ssum = 0.f, ssq = 0.f;
@@ -632,8 +678,16 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
 #pragma unroll
           for (int xy = 0; xy < 4; ++xy) {
             const int s0 = (2 * zp) * 16 + xy * 4, s1 = s0 + 16;
-            const f32x2 m0 = f32x2{acc[s0 + 0][r], acc[s1 + 0][r]}, m1 = f32x2{acc[s0 + 1][r], acc[s1 + 1][r]},
-                        m2 = f32x2{acc[s0 + 2][r], acc[s1 + 2][r]}, m3 = f32x2{acc[s0 + 3][r], acc[s1 + 3][r]};
+            float a0, a1, a2, a3, b0, b1, b2, b3;
+            HOLO_ACC_READ(a0, acc[s0 + 0], r);
+            HOLO_ACC_READ(b0, acc[s1 + 0], r);
+            HOLO_ACC_READ(a1, acc[s0 + 1], r);
+            HOLO_ACC_READ(b1, acc[s1 + 1], r);
+            HOLO_ACC_READ(a2, acc[s0 + 2], r);
+            HOLO_ACC_READ(b2, acc[s1 + 2], r);
+            HOLO_ACC_READ(a3, acc[s0 + 3], r);
+            HOLO_ACC_READ(b3, acc[s1 + 3], r);
+            const f32x2 m0 = f32x2{a0, b0}, m1 = f32x2{a1, b1}, m2 = f32x2{a2, b2}, m3 = f32x2{a3, b3};
             oy[xy][0] = pk_add(pk_add(m0, m1), m2);
             oy[xy][1] = pk_sub(pk_sub(m1, m2), m3);
           }
@@ -642,6 +696,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
             oz[zp][0][dx] = pk_add(pk_add(oy[0][dx], oy[1][dx]), oy[2][dx]);
             oz[zp][1][dx] = pk_sub(pk_sub(oy[1][dx], oy[2][dx]), oy[3][dx]);
           }
+          __builtin_amdgcn_sched_barrier(0);  // (the reads of the next pair stay behind this pair's sums)
+        }
+        if (SKIP && r == 3 && cur.sk_end > cur.sk_begin) {
+          // the next stage's first patch, which the skip overwrote: requested behind the LAST accumulator read (its registers
+          // are the transform's until here), under the stores; its x and y transforms follow the epilogue
+          const float* nbuf = s_halo + (stage & 1) * W3_HALO;
+#pragma unroll
+          for (int a4 = 0; a4 < 4; ++a4) load_patch_row(nbuf, 0, a4);
         }
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy)
@@ -656,9 +718,10 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
               ssum += o0 + o1;
               ssq = fmaf(o0, o0, fmaf(o1, o1, ssq));
             }
-            obase[vofs(r, 0, dy, dx)] = o0;
-            obase[vofs(r, 1, dy, dx)] = o1;
+            w3_bst1(rs_out, e_voff, obase + vofs(r, 0, dy, dx), o0);
+            w3_bst1(rs_out, e_voff, obase + vofs(r, 1, dy, dx), o1);
           }
+        __builtin_amdgcn_sched_barrier(0);
       }
       // GroupNorm statistics of the tensor just produced: one slab per tile (conv_stats_slabs)
       if (p.stats && direct) {
@@ -670,17 +733,17 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
         if (kq == 0) {
           const int tiles_per_sample = ntx * nty * ntz;
           const int slab = ((cur.tz0 >> 1) * nty + (cur.ty0 >> 3)) * ntx + (cur.tx0 >> 3);
-          double* d = p.stats + (((int64_t)cur.n * tiles_per_sample + slab) * p.Cout + co) * 2;
-          d[0] = (double)s1;
-          d[1] = (double)s2;
+          const unsigned rec = ((unsigned)(cur.n * tiles_per_sample + slab) * (unsigned)p.Cout + cbase) * 16u;  // 2 doubles
+          w3_bst_d2(w3_make_rsrc(p.stats), e_lj * 4u, rec, (double)s1, (double)s2);
         }
       }
     }
     if (dbg && tid == 0) {
       const unsigned long long t_now = HOLO_PROBE_CLOCK();
-      dbg[5] += t_now - dbg[2];  // skip-drain + output transform + stores
+      // (sums by atomics: the probe then adds no 64-bit vector arithmetic to the item loop, which scripts/wino3_isa_audit.py counts)
+      atomicAdd(dbg + 5, t_now - dbg[2]);  // skip-drain + output transform + stores
       dbg[3] = t_now;
-      dbg[7] += 1;
+      atomicAdd(dbg + 7, 1ull);
     }
     it += G;
     if (it >= nq) break;
@@ -771,6 +834,16 @@ int W3_ENTRY(const ConvParams& p, void* stream) {
   if (!p.w_wino3 || (p.skip_w && !p.skip_w_wino3) || (p.OD & 1) || (p.OH & 7) || (p.OW & 7) || (p.Cout & 63) ||
       (p.coef && !p.act)) {
     set_error("conv_wino3_launch: unsupported shape / weights not prepared");
+    return -1;
+  }
+  // every split owns at least one chunk (the stage loop tests at its end), and what the epilogue addresses through buffer
+  // resources - out / residual, all partial sums, the statistics records - lies within 4 GB of its base (conv_plan chooses
+  // another kernel otherwise)
+  const int ncc = (p.C0 + p.C1 + W3_BK - 1) / W3_BK;
+  const int64_t out_bytes = (int64_t)p.N * p.OD * p.OH * p.OW * p.Cout * 4;
+  if (p.nsplit < 1 || p.chunks_per_split < 1 || (int64_t)(p.nsplit - 1) * p.chunks_per_split >= ncc ||
+      out_bytes * p.nsplit >= ((int64_t)1 << 32)) {
+    set_error("conv_wino3_launch: empty K split, or output beyond 32-bit byte offsets");
     return -1;
   }
   const dim3 grid((unsigned)p.grid_x), block(256);
