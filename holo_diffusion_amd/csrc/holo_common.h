@@ -23,6 +23,7 @@ static inline uint32_t pack_bf16x2(float lo, float hi) { return emu_bf16_bits(lo
 static inline f32x4 mfma_bf16_16x16x32(float4 a, float4 b, f32x4 c) { return emu_mfma_f32_16x16x32_bf16(a, b, c); }
 static inline f32x16 mfma_bf16_32x32x16(float4 a, float4 b, f32x16 c) { return emu_mfma_f32_32x32x16_bf16(a, b, c); }
 #define HOLO_LAUNDER(x) asm volatile("" : "+r"(x))
+#define HOLO_LAUNDER_S(x) HOLO_LAUNDER(x)
 static inline float holo_rcp(float x) { return 1.0f / x; }
 static inline float holo_rcp_exact(float x) { return 1.0f / x; }
 static inline float holo_exp2(float x) { return std::exp2(x); }
@@ -38,6 +39,8 @@ static inline T holo_ld_sys(const T* p) { return *p; }
 #define HOLO_PIN_ACC(x) ((void)0)
 #define HOLO_MFMA16_ACC(acc, a, b) ((acc) = emu_mfma_f32_16x16x4f32((a), (b), (acc)))
 #define HOLO_MFMA16_ACC_FIRST(acc, a, b) ((acc) = emu_mfma_f32_16x16x4f32((a), (b), (acc)))
+#define HOLO_MFMA16_ZERO(acc, a, b) ((acc) = emu_mfma_f32_16x16x4f32((a), (b), f32x4{0.f, 0.f, 0.f, 0.f}))
+#define HOLO_MFMA16_ZERO_FIRST(acc, a, b) HOLO_MFMA16_ZERO(acc, a, b)
 #define HOLO_MFMA_DRAIN() ((void)0)
 #define HOLO_ACC_READ(dst, acc, r) ((dst) = (acc)[r])
 #define HOLO_MAD_U24(a, b, c) ((a) * (b) + (c))
@@ -93,6 +96,9 @@ __device__ __forceinline__ float holo_rcp_exact(float x) { return 1.0f / x; }
 // Passes a per-lane value through an empty asm: the optimiser can no longer prove it loop-invariant, so index
 // arithmetic derived from it is recomputed where it is used instead of being hoisted and kept live in VGPRs.
 #define HOLO_LAUNDER(x) asm volatile("" : "+v"(x))
+// The same for a wave-uniform value in a scalar register (e.g. a loop bound the optimiser must not correlate with a
+// condition inside the loop body: threading the two gives the loop a second entry).
+#define HOLO_LAUNDER_S(x) asm volatile("" : "+s"(x))
 // Orders the LDS traffic of ONE wave (its lanes exchange data through a region no other wave touches): the LDS unit
 // serves a wave's requests in issue order, so only the compiler has to be kept from moving accesses across this point.
 #define HOLO_WAVE_SYNC()                                   \
@@ -124,6 +130,11 @@ __device__ __forceinline__ T holo_ld_sys(const T* p) {
 #define HOLO_MFMA16_ACC(acc, a, b) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b))
 #define HOLO_MFMA16_ACC_FIRST(acc, a, b) \
   asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b))
+// The same with C = the constant 0 and an output-only accumulator: the MFMA that opens an accumulation resets its tuple
+// (the bits of 0 + a . b), so no v_accvgpr_write has to zero it first.  _FIRST as above.
+#define HOLO_MFMA16_ZERO(acc, a, b) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b))
+#define HOLO_MFMA16_ZERO_FIRST(acc, a, b) \
+  asm volatile("s_nop 1\n\tv_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b))
 #define HOLO_MFMA_DRAIN() asm volatile("s_nop 15" ::: "memory")
 // One accumulator register -> an arch VGPR, HERE: the allocator neither chooses the moment nor renames the tuple on the
 // way (after HOLO_MFMA_DRAIN(); `r` is a compile-time register index of the tuple).

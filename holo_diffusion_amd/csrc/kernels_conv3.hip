@@ -59,6 +59,20 @@ namespace holo {
 
 namespace {
 
+// The kernel's argument block, read again where it is used: scalar loads from the kernarg segment through a pointer the
+// optimiser cannot see through, so that per-launch constants (and what is derived from them) are formed on the scalar unit
+// at their use instead of being held - spilled to VGPR lanes - through the stage loop.  The cast relies on ConvParams
+// being the kernel's ONLY by-value argument, at offset 0 of the segment (conv_wino3_kernel's signature, below).  Used by
+// the fused-skip section and the epilogue alone; what the stages need too (SCin, M, ntx / nty / ntz, wnsl, dbg) is
+// still taken from `p` once, at the top of the kernel.
+#ifdef HOLO_EMU
+#define W3_KARGS(kp) const ConvParams* kp = &p
+#else
+#define W3_KARGS(kp)                                                                                        \
+  auto kp = (const ConvParams __attribute__((address_space(4)))*)(__builtin_amdgcn_kernarg_segment_ptr()); \
+  asm volatile("" : "+s"(kp))
+#endif
+
 constexpr int W3_BK = 32;                      // channels per chunk
 constexpr int W3_RS = 36;                      // words per halo column (32 channels + 4 pad: 16-byte aligned rows)
 constexpr int W3_HY = 10, W3_HX = 10;          // halo rows / columns of an 8 x 8 face
@@ -87,10 +101,14 @@ struct w3_rsrc {
   const char* base;
 };
 static inline w3_rsrc w3_make_rsrc(const void* p) { return w3_rsrc{reinterpret_cast<const char*>(p)}; }
+static inline w3_rsrc w3_make_rsrc_n(const void* p, unsigned nbytes) {
+  return w3_rsrc{nbytes ? reinterpret_cast<const char*>(p) : nullptr};
+}
 static inline w3q w3_bld(const w3_rsrc& r, unsigned voff, unsigned soff) {
   return w3_ld(reinterpret_cast<const float*>(r.base + (size_t)voff + (size_t)soff));
 }
 static inline float w3_bld1(const w3_rsrc& r, unsigned voff, unsigned soff) {
+  if (!r.base) return 0.f;  // (a descriptor of zero records)
   return *reinterpret_cast<const float*>(r.base + (size_t)voff + (size_t)soff);
 }
 static inline void w3_bst1(const w3_rsrc& r, unsigned voff, unsigned soff, float v) {
@@ -105,6 +123,10 @@ typedef __amdgpu_buffer_rsrc_t w3_rsrc;
 typedef unsigned w3u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ w3_rsrc w3_make_rsrc(const void* p) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0xffffffff, 0x00020000);
+}
+// a descriptor of `nbytes` records (wave-uniform): requests beyond them return 0 without touching memory
+__device__ __forceinline__ w3_rsrc w3_make_rsrc_n(const void* p, unsigned nbytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, nbytes, 0x00020000);
 }
 __device__ __forceinline__ w3q w3_bld(w3_rsrc r, unsigned voff, unsigned soff) {
   const w3u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
@@ -135,6 +157,10 @@ __device__ __forceinline__ void w3_static_for(F&& f, std::integer_sequence<int, 
 
 // One persistent workgroup per CU.  Work list: item = ((split * ny + cout block) * ntiles + tile), dealt round robin.
 // XF: the input passes through the per-(sample, channel) affine (GroupNorm folded with FiLM) and, with p.act, SiLU.
+// (ONE argument, by value: W3_KARGS reads it back from offset 0 of the kernarg segment - a second argument in front of it,
+// or a ConvParams that is no plain aggregate, breaks that silently)
+static_assert(std::is_trivially_copyable<ConvParams>::value && std::is_standard_layout<ConvParams>::value,
+              "W3_KARGS reads ConvParams straight from the kernarg segment");
 template <bool SKIP, bool XF>
 __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
   __shared__ __attribute__((aligned(16))) float s_halo[2 * W3_HALO];
@@ -227,9 +253,41 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
   bool h_second = false;   // the chunk's source
   bool h_chvalid = false;
   float4 h_c01 = make_float4(1.f, 0.f, 1.f, 0.f), h_c23 = h_c01;  // the chunk's affine (XF): (a,b) of the thread's 4 channels
-  // Addresses, masks and coefficients of a stage's halo (no requests yet).  Scalar work (source, planes) and the requests of
-  // the coefficients first; the vector part is the four column offsets.
-  auto halo_setup = [&](const Item& I, int cc) {
+  // Addresses, masks and coefficients of a stage's halo (no requests yet), in two parts.  The thread's four columns never
+  // change: their (hy, hx) are divided out ONCE per workgroup and packed, byte i = hy | hx << 4 of item i.
+  unsigned h_yx = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int col = min((tid >> 3) + 32 * i, W3_PLANE - 1);
+    const int hy = col / W3_HX, hx = col - hy * W3_HX;
+    h_yx |= (unsigned)(hy | (hx << 4)) << (8 * i);
+  }
+  unsigned h_vox[4];  // voxel number of item i's column inside a source plane (clamped)
+  // Per tile: the plane offsets in voxels and their mask (scalar), the four columns' voxel numbers and their mask (vector;
+  // straight-line: the range tests are unsigned compares combined bitwise, not short-circuit branches round the clump).
+  unsigned h_zvox[4];
+  auto halo_tile = [&](const Item& I) {
+    h_zvalid = 0;
+#pragma unroll
+    for (int pl = 0; pl < 4; ++pl) {
+      int z = I.tz0 + pl - 1;
+      h_zvalid |= ((unsigned)z < (unsigned)p.ID ? 1u : 0u) << pl;
+      z = min(max(z, 0), p.ID - 1) >> p.ups;
+      h_zvox[pl] = (unsigned)((I.n * SD + z) * SH * SW);
+    }
+    h_cvalid = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int y = I.ty0 - 1 + (int)((h_yx >> (8 * i)) & 15u), x = I.tx0 - 1 + (int)((h_yx >> (8 * i + 4)) & 15u);
+      const unsigned ok = (unsigned)((unsigned)y < (unsigned)p.IH) & (unsigned)((unsigned)x < (unsigned)p.IW);
+      y = min(max(y, 0), p.IH - 1) >> p.ups;
+      x = min(max(x, 0), p.IW - 1) >> p.ups;
+      h_cvalid |= ok << i;
+      h_vox[i] = (unsigned)(y * SW + x);
+    }
+  };
+  // Per chunk: the source, the channel offset, the requests of the coefficients; the byte offsets from the tile's numbers.
+  auto halo_chunk = [&](const Item& I, int cc) {
     int c = cc * W3_BK + q * 4;
     h_chvalid = c < Cin;
     if (!h_chvalid) c = 0;  // clamped, masked at commit
@@ -243,26 +301,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
     }
     const unsigned cbytes = (unsigned)Cs * 4u;
     h_second = second;
-    h_zvalid = 0;
 #pragma unroll
-    for (int pl = 0; pl < 4; ++pl) {
-      int z = I.tz0 + pl - 1;
-      h_zvalid |= (z >= 0 && z < p.ID ? 1u : 0u) << pl;
-      z = min(max(z, 0), p.ID - 1) >> p.ups;
-      h_zoff[pl] = (unsigned)((I.n * SD + z) * SH * SW) * cbytes;
-    }
-    h_cvalid = 0;
+    for (int pl = 0; pl < 4; ++pl) h_zoff[pl] = h_zvox[pl] * cbytes;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int col = min((tid >> 3) + 32 * i, W3_PLANE - 1);
-      const int hy = col / W3_HX, hx = col - hy * W3_HX;
-      int y = I.ty0 + hy - 1, x = I.tx0 + hx - 1;
-      const bool ok = y >= 0 && y < p.IH && x >= 0 && x < p.IW;
-      y = min(max(y, 0), p.IH - 1) >> p.ups;
-      x = min(max(x, 0), p.IW - 1) >> p.ups;
-      h_cvalid |= (ok ? 1u : 0u) << i;
-      h_off[i] = (unsigned)(y * SW + x) * cbytes + (unsigned)cs * 4u;
-    }
+    for (int i = 0; i < 4; ++i) h_off[i] = h_vox[i] * cbytes + (unsigned)cs * 4u;
+  };
+  auto halo_setup = [&](const Item& I, int cc) {
+    halo_tile(I);
+    halo_chunk(I, cc);
   };
   // one 16-byte request: item i, plane pl (unconditional, from a clamped address; masked at commit): scalar base + 32-bit
   // vector offset, no address arithmetic at the request
@@ -353,17 +399,23 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
   w3q Bw[4][4];  // ring of weight groups: group g lives in slot g & 3 and is requested W3_WDIST groups ahead
   // MFMA k of a group: k-step e = k >> 2 (the component of the 16-byte operands), pseudo-tap t = k & 3.  The accumulators are
   // TIED to their AGPR tuples (HOLO_MFMA16_ACC, holo_common.h): 64 sets fill the accumulation file.
-  auto mfma1 = [&](f32x4& c, const w3q& A, const w3q& B, int e, bool first) {
+  auto mfma1 = [&](f32x4& c, const w3q& A, const w3q& B, int e, bool first, bool zero = false) {
 #if W3_PROBE & 8
     HOLO_SINK8(A.lo.x, A.lo.y, A.hi.x, A.hi.y, B.lo.x, B.lo.y, B.hi.x, B.hi.y);
     return;
 #endif
     const float a = e == 0 ? A.lo.x : e == 1 ? A.lo.y : e == 2 ? A.hi.x : A.hi.y;
     const float b = e == 0 ? B.lo.x : e == 1 ? B.lo.y : e == 2 ? B.hi.x : B.hi.y;
-    if (first)
+    if (zero) {  // opens the accumulation: C = 0, whatever the tuple held
+      if (first)
+        HOLO_MFMA16_ZERO_FIRST(c, a, b);
+      else
+        HOLO_MFMA16_ZERO(c, a, b);
+    } else if (first) {
       HOLO_MFMA16_ACC_FIRST(c, a, b);
-    else
+    } else {
       HOLO_MFMA16_ACC(c, a, b);
+    }
   };
 
   // a whole group at once (the fused skip): the four accumulators advance together, k-step by k-step
@@ -429,29 +481,32 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
 #endif
   for (;;) {
     // ---------------- one item
+#if W3_PROBE & 8
 #pragma unroll
     for (int s = 0; s < 64; ++s)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[s][r] = 0.f;
-    // (an item has at least one chunk - conv_wino3_launch checks the split -, so the loop tests at its end: a path round it
-    // would need the 256 zeroing writes a second time)
+#endif
+    // The item's first stage is a copy of the stage body of its own (opens = true), in which the MFMA that opens an
+    // accumulator (half 0, k-step 0) takes C = 0: no v_accvgpr_write zeroes the 256 registers first.  An item has at least
+    // one chunk (conv_wino3_launch checks the split); the remaining chunks, if any, run the loop below.
     cc = cur.cc_begin;
-    do {
+    auto stage_body = [&](auto opens_c) __attribute__((always_inline)) {
+      constexpr bool opens = decltype(opens_c)::value;
       // what the producer side prepares during this stage: the next chunk of this item, or the first chunk of the next
       // item.  The stage body is ONE basic block (the 256 accumulators then meet the register allocator at the loop header
       // only): on the very last stage of the workgroup the producer side simply stages the current chunk again.
+      // (the successor item is formed on every stage and SELECTED - a few dozen scalar instructions: a branch round them
+      // becomes the head of the stage block, which the compiler then copies into the block's predecessors)
       const bool last_chunk = cc + 1 == cur.cc_end;
-      int ncc_ = cc + 1;
-      nxt = cur;
-      if (last_chunk) {
-        const int nit = it + G;
-        if (nit < nq) {
-          advance(cur, nxt);
-          ncc_ = nxt.cc_begin;
-        } else {
-          ncc_ = cc;
-        }
-      }
+      const bool go = last_chunk && it + G < nq;
+      Item adv;
+      advance(cur, adv);
+      nxt.n = go ? adv.n : cur.n, nxt.tz0 = go ? adv.tz0 : cur.tz0, nxt.ty0 = go ? adv.ty0 : cur.ty0;
+      nxt.tx0 = go ? adv.tx0 : cur.tx0, nxt.n0 = go ? adv.n0 : cur.n0, nxt.split = go ? adv.split : cur.split;
+      nxt.cc_begin = go ? adv.cc_begin : cur.cc_begin, nxt.cc_end = go ? adv.cc_end : cur.cc_end;
+      nxt.sk_begin = go ? adv.sk_begin : cur.sk_begin, nxt.sk_end = go ? adv.sk_end : cur.sk_end;
+      const int ncc_ = go ? adv.cc_begin : last_chunk ? cc : cc + 1;
       const float* buf = s_halo + (stage & 1) * W3_HALO;
       float* obuf = s_halo + ((stage + 1) & 1) * W3_HALO;
       const unsigned wp = w_of(cur, cc), wnext = w_of(nxt, ncc_);
@@ -488,7 +543,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
 #endif
         auto slot = [&](auto kc) {
           constexpr int k = decltype(kc)::value;
-          mfma1(acc[(st >> 1) * 16 + xy * 4 + (k & 3)], Y[g & 1][k & 3], Bw[g & 3][k & 3], k >> 2, k == 0);
+          mfma1(acc[(st >> 1) * 16 + xy * 4 + (k & 3)], Y[g & 1][k & 3], Bw[g & 3][k & 3], k >> 2, k == 0,
+                opens && (st & 1) == 0 && (k >> 2) == 0);
           if ((k & 3) == 0 && !(W3_PROBE & 2)) {
             const unsigned wsrc = g + W3_WDIST < 32 ? wp : wnext;
             constexpr int wofs = (g + W3_WDIST < 32 ? g + W3_WDIST : g + W3_WDIST - 32) * W3_WSUB + (k >> 2) * 256;
@@ -548,33 +604,40 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
       if (dbg && tid == 0) dbg[6] += HOLO_PROBE_CLOCK() - t_stage;  // the stage's own work (barrier wait included)
 #endif
       ++stage;
-    } while (++cc < cur.cc_end);
+    };
+    stage_body(std::true_type{});
+    // (the bound is opaque: the body's own "last chunk of the item" test would otherwise be threaded into the loop test, and
+    // the loop - entered along two paths - would no longer be ONE block the 256 accumulators meet at its header)
+    int cc_end = cur.cc_end;
+    HOLO_LAUNDER_S(cc_end);
+    while (++cc < cc_end) stage_body(std::false_type{});
     // ---------------- fused 1x1x1 skip connection: raw block input at the lane's own voxels -> pseudo-taps {0,3}^3.
     //   group sg = (skip chunk, half, dz): the four voxels (dy,dx) of the lane's 2 x 2 x 2 patch = one 16-MFMA group with
     //   accumulators (3dz, 3dy, 3dx).  Its operands come straight from global memory (no halo, no LDS, no barrier), THREE
     //   groups ahead, into the registers of the patch (A) and of the weight ring (B) - what the last stage left there for the
     //   next item is simply requested again afterwards, under the epilogue.  Buffer addressing: no vector instruction per
     //   request (the skip tensors lie within 4 GB: conv_plan).
+    W3_KARGS(kp);  // (the launch's constants, read HERE: nothing of the item boundary's is held through the stages)
     if (SKIP) {
       const int nsg = (cur.sk_end - cur.sk_begin) * 4;
       if (nsg > 0) {
-        const w3_rsrc rs0 = w3_make_rsrc(p.skip_src0), rs1 = w3_make_rsrc(p.skip_src1 ? p.skip_src1 : p.skip_src0);
-        const w3_rsrc rsw = w3_make_rsrc(p.skip_w_wino3);
+        const w3_rsrc rs0 = w3_make_rsrc(kp->skip_src0), rs1 = w3_make_rsrc(kp->skip_src1 ? kp->skip_src1 : kp->skip_src0);
+        const w3_rsrc rsw = w3_make_rsrc(kp->skip_w_wino3);
         const int yt = lj & 3, xt = lj >> 2;
         // voxel (dy, dx) of the lane's patch relative to the tile's first voxel, in voxels
         unsigned vrel[4];
 #pragma unroll
-        for (int d = 0; d < 4; ++d) vrel[d] = (unsigned)((2 * yt + (d >> 1)) * p.OW + 2 * xt + (d & 1));
-        const unsigned vtile = (unsigned)(((cur.n * p.OD + cur.tz0) * p.OH + cur.ty0) * p.OW + cur.tx0);
-        const unsigned zvox = (unsigned)(p.OH * p.OW);
+        for (int d = 0; d < 4; ++d) vrel[d] = (unsigned)((2 * yt + (d >> 1)) * kp->OW + 2 * xt + (d & 1));
+        const unsigned vtile = (unsigned)(((cur.n * kp->OD + cur.tz0) * kp->OH + cur.ty0) * kp->OW + cur.tx0);
+        const unsigned zvox = (unsigned)(kp->OH * kp->OW);
         const unsigned wbase = (unsigned)((cur.n0 >> 4) + wn) * (unsigned)W3_WSKIP * 4u;
         auto skip_load = [&](int sg, int slot) {
           const int sc = cur.sk_begin + (sg >> 2), half = (sg >> 1) & 1, dz = sg & 1;
           const int c0 = sc * W3_BK + half * 16;        // first channel of the 16-channel half (wave-uniform)
           const bool pad = c0 >= SCin;  // a half of padding channels: its packed weights are zero, read channel 0 instead
-          const bool second = !pad && c0 >= p.skip_C0;  // (skip_C0 is a multiple of 16 when there are two sources: conv_plan)
-          const unsigned Cs = (unsigned)(second ? p.skip_C1 : p.skip_C0);
-          const unsigned cs = pad ? 0u : (unsigned)(second ? c0 - p.skip_C0 : c0);
+          const bool second = !pad && c0 >= kp->skip_C0;  // (skip_C0 is a multiple of 16 when there are two sources: conv_plan)
+          const unsigned Cs = (unsigned)(second ? kp->skip_C1 : kp->skip_C0);
+          const unsigned cs = pad ? 0u : (unsigned)(second ? c0 - kp->skip_C0 : c0);
           const unsigned soff = ((vtile + (unsigned)dz * zvox) * Cs + cs) * 4u;
           const unsigned wsoff = (unsigned)sc * (unsigned)wnsl * (unsigned)W3_WSKIP * 4u + wbase + (unsigned)((half * 2 + dz) * 4) * 1024u;
           // (channels beyond the skip's last one: the packed weights there are zero, the activations any finite value)
@@ -628,22 +691,29 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
     //   producer's requests do - the lane's part of the offset (x tile 2 kq, channel lj) is ONE register per tensor, the tile's
     //   base and the 32 (r, dz, dy, dx) displacements are scalar (conv_plan: each tensor lies within 4 GB of its base).
     {
-      const bool direct = p.nsplit == 1;
-      const bool has_res = direct && p.residual != nullptr;
+      const bool direct = kp->nsplit == 1;
+      const bool has_res = direct && kp->residual != nullptr;
       int ln = lane;
       HOLO_LAUNDER(ln);  // (the lane offsets are formed here, per item: three instructions instead of registers held through the stages)
-      const unsigned cout4 = (unsigned)p.Cout * 4u;
+      const unsigned cout4 = (unsigned)kp->Cout * 4u;
       const unsigned e_lj = (unsigned)(ln & 15) * 4u;                  // channel lj of the wave's 16
       const unsigned e_voff = HOLO_MAD_U24((unsigned)(ln >> 4) * 2u, cout4, e_lj);  // + x tile kq: voxel 2 kq of the row
       const unsigned cbase = (unsigned)(cur.n0 + wn * 16);              // the wave's first output channel
       float bv = 0.f;
-      if (direct && p.bias) bv = w3_bld1(w3_make_rsrc(p.bias), e_lj, cbase * 4u);
-      if (direct && p.skip_bias) bv += w3_bld1(w3_make_rsrc(p.skip_bias), e_lj, cbase * 4u);
-      const unsigned vtile = (unsigned)(((cur.n * p.OD + cur.tz0) * p.OH + cur.ty0) * p.OW + cur.tx0);
+      if (direct && kp->bias) bv = w3_bld1(w3_make_rsrc(kp->bias), e_lj, cbase * 4u);
+      if (direct && kp->skip_bias) bv += w3_bld1(w3_make_rsrc(kp->skip_bias), e_lj, cbase * 4u);
+      const unsigned vtile = (unsigned)(((cur.n * kp->OD + cur.tz0) * kp->OH + cur.ty0) * kp->OW + cur.tx0);
       const unsigned sbase = vtile * cout4 + cbase * 4u;
       const unsigned obase = direct ? sbase : sbase + (unsigned)cur.split * ((unsigned)M * cout4);
-      const unsigned zstride = (unsigned)(p.OH * p.OW) * cout4, ystride = (unsigned)p.OW * cout4;
-      const w3_rsrc rs_out = w3_make_rsrc(direct ? p.out : p.partial), rs_res = w3_make_rsrc(p.residual);
+      const unsigned zstride = (unsigned)(kp->OH * kp->OW) * cout4, ystride = (unsigned)kp->OW * cout4;
+      // (no residual: a descriptor of zero records - every request is out of range and returns 0 without touching memory, so
+      // the eight requests per register index need neither a branch nor sixteen zeroing moves round them.  This is the
+      // range check of raw buffers in the CDNA ISA guide's buffer-addressing section: a load whose offset is not below
+      // num_records returns 0 - with num_records = 0 that is every offset, so it does not matter that sbase + vofs travels
+      // in the scalar offset, which the check leaves out.  has_res is wave-uniform already; HOLO_UNIFORM only tells the
+      // compiler so, which otherwise builds a waterfall loop round the descriptor.)
+      const w3_rsrc rs_out = w3_make_rsrc(direct ? kp->out : kp->partial);
+      const w3_rsrc rs_res = w3_make_rsrc_n(kp->residual, HOLO_UNIFORM(has_res ? 0xffffffffu : 0u));
       // voxel (dz, 2 r + dy, dx) of the lane's x tile, relative to the tile's base (wave-uniform)
       auto vofs = [&](int r, int dz, int dy, int dx) {
         return (unsigned)dz * zstride + (unsigned)(2 * r + dy) * ystride + (unsigned)dx * cout4;
@@ -656,15 +726,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
 #pragma unroll
           for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
-            for (int dx = 0; dx < 2; ++dx) res[r & 1][dz][dy][dx] = 0.f;
-        if (has_res) {  // (ONE uniform branch round the eight requests)
-#pragma unroll
-          for (int dz = 0; dz < 2; ++dz)
-#pragma unroll
-            for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-              for (int dx = 0; dx < 2; ++dx) res[r & 1][dz][dy][dx] = w3_bld1(rs_res, e_voff, sbase + vofs(r, dz, dy, dx));
-        }
+            for (int dx = 0; dx < 2; ++dx) res[r & 1][dz][dy][dx] = w3_bld1(rs_res, e_voff, sbase + vofs(r, dz, dy, dx));
       };
       load_res(0);
       float ssum = 0.f, ssq = 0.f;
@@ -724,7 +786,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
         __builtin_amdgcn_sched_barrier(0);
       }
       // GroupNorm statistics of the tensor just produced: one slab per tile (conv_stats_slabs)
-      if (p.stats && direct) {
+      if (kp->stats && direct) {
         float s1 = ssum, s2 = ssq;
         s1 += __shfl_xor(s1, 16);
         s2 += __shfl_xor(s2, 16);
@@ -733,8 +795,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
         if (kq == 0) {
           const int tiles_per_sample = ntx * nty * ntz;
           const int slab = ((cur.tz0 >> 1) * nty + (cur.ty0 >> 3)) * ntx + (cur.tx0 >> 3);
-          const unsigned rec = ((unsigned)(cur.n * tiles_per_sample + slab) * (unsigned)p.Cout + cbase) * 16u;  // 2 doubles
-          w3_bst_d2(w3_make_rsrc(p.stats), e_lj * 4u, rec, (double)s1, (double)s2);
+          const unsigned rec = ((unsigned)(cur.n * tiles_per_sample + slab) * (unsigned)kp->Cout + cbase) * 16u;  // 2 doubles
+          w3_bst_d2(w3_make_rsrc(kp->stats), e_lj * 4u, rec, (double)s1, (double)s2);
         }
       }
     }

@@ -5,11 +5,22 @@ Compiles holo_diffusion_amd/csrc/kernels_conv3.hip to assembly with the Makefile
 --asm), splits every conv_wino3_kernel instance by the loop-depth comments the compiler writes
 
     prologue    blocks in no loop (once per workgroup)
-    item        blocks of the item loop (depth 1) outside the stage loop - accumulator reset, fused skip, output transform,
-                epilogue, item bookkeeping
+    item        blocks of the item loop (depth 1) outside the stage loop - fused skip, output transform, epilogue, item
+                bookkeeping
+    first_stage the item's first stage, a copy of the stage body outside the stage loop whose opening MFMAs take C = 0
+                (the depth-1 blocks that hold at least half a stage's MFMAs; empty if the kernel has no such copy).
+                It is a section of its own, not part of "item": the copy carries what every stage carries (the 64-bit
+                adds of the weight pointers among it), and what "item" is judged by - no 64-bit vector add, no
+                accumulator move - would otherwise be hidden behind a stage's worth of instructions.  What the copy
+                spends BEYOND a stage of the loop belongs to the item (tests/test_wino3_isa_budget.py adds it back).
     stage       the stage loop (the depth-2 loop that holds the 512 MFMAs of a chunk)
 
-and prints, per section, the instruction counts the item boundary is judged by.
+and prints, per section, the instruction counts the item boundary is judged by, and `group0_clump_valu`: the vector
+instructions between the 16th and the 17th MFMA of the stage loop - the clump behind group 0, where the next stage's halo
+addresses are set up (next to the 8 v_pk_add_f32 that form the A operands of group 1) - and `stage_branches`: the
+conditional branches inside the stage loop (1 = the back edge alone: the stage body is ONE basic block).
+`group0_clump_valu` is a figure to READ, not to assert on: it counts by position, and where the compiler lays the set-up
+elsewhere (the XF=1 instances before the straight-line range tests: 8) it counts something else.
 
 usage: python scripts/wino3_isa_audit.py [--asm FILE.s] [--json]
 """
@@ -25,7 +36,8 @@ import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "holo_diffusion_amd", "csrc")
-SECTIONS = ("prologue", "item", "stage")
+SECTIONS = ("prologue", "item", "first_stage", "stage")
+STAGE_MFMAS = 512
 # what is counted: name -> predicate on the mnemonic
 CLASSES = collections.OrderedDict(
     [
@@ -133,15 +145,33 @@ def split_sections(lines):
     out = []
     for _, depth, header, ops in blocks:
         sec = "prologue" if depth == 0 else "stage" if (depth >= 2 and header == stage_header) else "item"
+        if sec == "item" and 2 * sum(1 for op in ops if op.startswith("v_mfma")) >= STAGE_MFMAS:
+            sec = "first_stage"
         out.extend((sec, op) for op in ops)
     return out
+
+
+def group0_clump(sec_ops):
+    """Vector instructions between MFMA 16 and MFMA 17 of the stage loop (in layout order)."""
+    n_mfma, valu = 0, 0
+    for sec, op in sec_ops:
+        if sec != "stage":
+            continue
+        if op.startswith("v_mfma"):
+            n_mfma += 1
+            if n_mfma > 16:
+                break
+        elif n_mfma == 16 and op.startswith("v_"):
+            valu += 1
+    return valu
 
 
 def audit(asm):
     res = collections.OrderedDict()
     for name, (lines, meta) in instances(asm).items():
         counts = {sec: collections.OrderedDict((k, 0) for k in CLASSES) for sec in SECTIONS}
-        for sec, op in split_sections(lines):
+        sec_ops = split_sections(lines)
+        for sec, op in sec_ops:
             for k, pred in CLASSES.items():
                 if pred(op):
                     counts[sec][k] += 1
@@ -153,7 +183,8 @@ def audit(asm):
         mm = re.search(r"; ScratchSize: (\d+)", meta)
         if mm:
             md["scratch_bytes_per_lane"] = int(mm.group(1))
-        res[name] = {"sections": counts, "meta": md}
+        res[name] = {"sections": counts, "meta": md, "group0_clump_valu": group0_clump(sec_ops),
+                     "stage_branches": sum(1 for sec, op in sec_ops if sec == "stage" and op.startswith("s_cbranch"))}
     return res
 
 
@@ -186,9 +217,10 @@ def main():
         return 0
     for name, r in res.items():
         print("conv_wino3_kernel<%s>   %s" % (name, "  ".join("%s=%d" % kv for kv in sorted(r["meta"].items()))))
-        print("  %-14s %9s %9s %9s" % (("class",) + SECTIONS))
+        print("  group0_clump_valu=%d  stage_branches=%d" % (r["group0_clump_valu"], r["stage_branches"]))
+        print("  %-14s" % "class" + "".join(" %11s" % s for s in SECTIONS))
         for k in CLASSES:
-            print("  %-14s %9d %9d %9d" % ((k,) + tuple(r["sections"][s][k] for s in SECTIONS)))
+            print("  %-14s" % k + "".join(" %11d" % r["sections"][s][k] for s in SECTIONS))
     return 0
 
 
