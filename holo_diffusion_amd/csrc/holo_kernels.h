@@ -50,7 +50,7 @@ struct ConvParams {
   int stride, pad, ksz;  // ksz = 3 (27 taps) or 1
   int Cout;
   const float* w;         // packed [ksz^3][CinP/32][CoutP/16][2][4][16][4] (repack_conv_weight_launch), zero padded:
-                          // CinP = Cin rounded up to 32, CoutP = Cout rounded up to 64 (32 when Cout < 64)
+                          // CinP = Cin rounded up to 32, CoutP = Cout rounded up to 64 (to 32 when Cout < 64)
   int CoutP, CinP;
   const float* coef;      // [N][Cin][2] = (a,b): x' = a*x+b ; null = identity
   int act;                // 1: SiLU after the affine (only with coef)

@@ -63,8 +63,9 @@ struct Block {
 enum ParamKind { P_PLAIN, P_CONV3, P_CONV1, P_EMB_W, P_EMB_B };
 
 // packed conv weights are zero padded to [taps][CoutP][CinP]: CoutP a multiple of the kernel's Cout tile
-// (64 when Cout >= 64, else 32), CinP a multiple of the 32-channel K chunk
-static inline int pad_cout(int c) { return c >= 64 ? (c + 63) / 64 * 64 : 32; }
+// (64 when Cout >= 64, else 32: 36 .. 60 channels - an in / out width of the net - are two 32-wide tiles), CinP a multiple
+// of the 32-channel K chunk
+static inline int pad_cout(int c) { return c >= 64 ? (c + 63) / 64 * 64 : (c + 31) / 32 * 32; }
 static inline int pad_cin(int c) { return (c + 31) / 32 * 32; }
 // every device copy of one convolution's weights (host-side bookkeeping; null = not prepared for this conv).
 // Planner::emit_conv copies the ones the compute mode uses into ConvParams, and conv_plan picks kernels from those.
