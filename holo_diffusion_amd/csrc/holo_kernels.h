@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "conv_weights.h"
 #include "holo_knobs.h"
 
 // per-device context of the C ABI (holo_ctx_create)
@@ -49,8 +50,8 @@ struct ConvParams {
   int OD, OH, OW;
   int stride, pad, ksz;  // ksz = 3 (27 taps) or 1
   int Cout;
-  const float* w;         // packed [ksz^3][CinP/32][CoutP/16][2][4][16][4] (repack_conv_weight_launch), zero padded:
-                          // CinP = Cin rounded up to 32, CoutP = Cout rounded up to 64 (to 32 when Cout < 64)
+  const float* w;         // packed [ksz^3][CinP/32][CoutP/16][2][4][16][4] (repack_conv_weight_launch), zero padded to the
+                          // CoutP / CinP of conv_weight_layout (conv_weights.h: the one place that rounds them)
   int CoutP, CinP;
   const float* coef;      // [N][Cin][2] = (a,b): x' = a*x+b ; null = identity
   int act;                // 1: SiLU after the affine (only with coef)
@@ -128,8 +129,7 @@ void conv1x1_bf16_stream_plan(ConvParams& p, int num_cus);
 int conv1x1_bf16_stream_slabs(const ConvParams& p);
 int conv1x1_bf16_stream_launch(const ConvParams& p, void* stream);
 
-// kernels_conv3.hip
-int64_t conv_wino3_weight_floats(int CoutP, int CinP, int src_taps);
+// kernels_conv3.hip (conv_wino3_weight_floats: conv_weights.h)
 int repack_conv_weight_wino3_launch(const float* w, float* out, int Cout, int Cin, int src_taps, int CoutP, int CinP,
                                     void* stream);
 int conv_wino3_launch(const ConvParams& p, void* stream);

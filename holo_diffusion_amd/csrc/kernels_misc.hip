@@ -971,7 +971,12 @@ int repack_conv_weight_wino2_launch(const float* w, float* out, int Cout, int Ci
     set_error("repack_conv_weight_wino2: 27 or 1 source taps");
     return -1;
   }
-  int64_t total = (int64_t)CoutP * CinP * (src_taps == 27 ? 48 : 4);
+  const ConvWeightLayout l = conv_weight_layout(Cout, Cin, src_taps);
+  if (l.CoutP != CoutP || l.CinP != CinP) {  // (the kernel indexes with the arguments, the grid is sized from the layout)
+    set_error("repack_conv_weight_wino2: paddings %d x %d are not the layout's %d x %d", CoutP, CinP, l.CoutP, l.CinP);
+    return -1;
+  }
+  int64_t total = l.wino2_floats();
   int64_t blocks = cdiv(total, 256);
   if (blocks > 8192) blocks = 8192;
   HOLO_LAUNCH(repack_conv_weight_wino2_kernel, dim3((unsigned)blocks), dim3(256), stream, w, out, Cout, Cin, src_taps,

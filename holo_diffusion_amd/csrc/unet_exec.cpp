@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/holo_abi.h"
+#include "conv_weights.h"
 #include "holo_common.h"
 #include "holo_kernels.h"
 
@@ -45,6 +46,15 @@ const char* get_error() { return g_err; }
 
 using namespace holo;
 
+int holo::pack_conv_weights(const float* src, const ConvWeights& dst, void* stream) {
+  const ConvWeightLayout& l = dst.layout;
+  int rc = repack_conv_weight_launch(src, dst.f32, l.Cout, l.Cin, l.taps, l.CoutP, l.CinP, stream);
+  if (!rc && dst.bf) rc = repack_conv_weight_bf16_launch(src, dst.bf, l.Cout, l.Cin, l.taps, l.CoutP, l.CinP, stream);
+  if (!rc && dst.wino2) rc = repack_conv_weight_wino2_launch(src, dst.wino2, l.Cout, l.Cin, l.taps, l.CoutP, l.CinP, stream);
+  if (!rc && dst.wino3) rc = repack_conv_weight_wino3_launch(src, dst.wino3, l.Cout, l.Cin, l.taps, l.CoutP, l.CinP, stream);
+  return rc;
+}
+
 // struct HoloCtx { device, num_cus }: holo_kernels.h (shared with render_exec.cpp)
 
 // ---------------------------------------------------------------------------------------------
@@ -62,20 +72,6 @@ struct Block {
 
 enum ParamKind { P_PLAIN, P_CONV3, P_CONV1, P_EMB_W, P_EMB_B };
 
-// packed conv weights are zero padded to [taps][CoutP][CinP]: CoutP a multiple of the kernel's Cout tile
-// (64 when Cout >= 64, else 32: 36 .. 60 channels - an in / out width of the net - are two 32-wide tiles), CinP a multiple
-// of the 32-channel K chunk
-static inline int pad_cout(int c) { return c >= 64 ? (c + 63) / 64 * 64 : (c + 31) / 32 * 32; }
-static inline int pad_cin(int c) { return (c + 31) / 32 * 32; }
-// every device copy of one convolution's weights (host-side bookkeeping; null = not prepared for this conv).
-// Planner::emit_conv copies the ones the compute mode uses into ConvParams, and conv_plan picks kernels from those.
-struct ConvWeights {
-  float* f32 = nullptr;     // repacked fp32 copy
-  uint16_t* bf = nullptr;   // bf16 (RNE) planes hi, mid, lo packed for v_mfma_f32_16x16x32_bf16
-  uint16_t* bft = nullptr;  // plane 3 of the same buffer: hi packed for the wide-tile kernel (conv_bf16t_kernel)
-  float* wino2 = nullptr;   // the wide top levels: (z,y) Winograd pseudo-taps (conv_wino2_kernel)
-  float* wino3 = nullptr;   // ... and the F(2x2x2, 3x3x3) pseudo-taps (conv_wino3_kernel)
-};
 struct ParamSlot {
   std::string name;
   std::vector<int64_t> shape;
@@ -83,6 +79,11 @@ struct ParamSlot {
   ParamKind kind;
   ConvWeights w;  // private device copies: f32 (repacked for a conv weight) of every parameter, the rest of conv weights only
   bool set;
+  bool is_conv() const { return kind == P_CONV3 || kind == P_CONV1; }
+  // layout of a conv weight's copies; `transposed`: of the backward's transposed convolution (Cout' = Cin, Cin' = Cout)
+  ConvWeightLayout layout(bool transposed = false) const {
+    return conv_weight_layout((int)shape[transposed ? 1 : 0], (int)shape[transposed ? 0 : 1], kind == P_CONV3 ? 27 : 1);
+  }
 };
 static bool is_downsample_weight(const std::string& name) {  // Downsample: the stride-2 convolution
   return name.size() > 10 && name.compare(name.size() - 10, 10, ".op.weight") == 0;
@@ -269,8 +270,7 @@ struct HoloUnet {
   // ([Cin][Cout] flipped taps for the stride-1 convs; [tap][Cout][Cin] for the stride-2 Downsample convs, whose stride-1
   // form lives under "<name>#s1"), supplied by holo_unet_set_dgrad_weight; this table owns every buffer it points to
   std::map<std::string, ConvWeights> dgrad;
-  float* dgrad_tmp = nullptr;
-  size_t dgrad_tmp_floats = 0;
+  float* dgrad_tmp = nullptr;  // the flipped / transposed OIDHW weight on its way into the packs: the largest conv weight's numel
   TrainPlan tplan;
   const int64_t* t_dev = nullptr;  // timesteps of the running call (time_embed backward)
   bool tape_valid = false;         // holo_unet_forward_train ran and nothing has consumed its tape
@@ -423,6 +423,45 @@ void enumerate_params(HoloUnet* u) {
   add_param(u, "out.0.bias", {u->final_ch}, P_PLAIN);
   add_param(u, "out.2.weight", {c.out_channels, u->final_ch, 3, 3, 3}, P_CONV3);
   add_param(u, "out.2.bias", {c.out_channels}, P_PLAIN);
+}
+
+// Hands every parameter its private copies out of the three stores - f32 (HoloUnet::pstore), bf16 planes (pstore_bf),
+// Winograd packs (pstore_wino) - and returns the element count of each.  holo_unet_create runs it twice, like a planner: on
+// null bases to size the stores (the pointers it leaves are null), then on the allocations.  All arithmetic is in offsets.
+struct StoreSizes {
+  int64_t f32 = 0, bf = 0, wino = 0;
+};
+StoreSizes carve_params(HoloUnet* u, float* f32, uint16_t* bf, float* wino) {
+  StoreSizes n;
+  auto take = [](auto* base, int64_t& top, int64_t count) {
+    auto* p = base ? base + top : nullptr;
+    top += round64(count);
+    return p;
+  };
+  for (ParamSlot& s : u->params) {
+    if (s.kind == P_EMB_W || s.kind == P_EMB_B) continue;  // rows of emb_w / emb_b (below)
+    if (!s.is_conv()) {
+      s.w.f32 = take(f32, n.f32, s.numel);
+      continue;
+    }
+    const ConvWeightLayout l = s.w.layout = s.layout();
+    const ConvCopies c = forward_copies(l, s.name.find("skip_connection") != std::string::npos, u->knobs);
+    s.w.f32 = take(f32, n.f32, l.f32_floats());
+    if (c.bf16) {
+      s.w.bf = take(bf, n.bf, l.bf16_elems());
+      s.w.bft = s.w.bf ? s.w.bf + l.bft_offset() : nullptr;
+    }
+    if (c.wino2) s.w.wino2 = take(wino, n.wino, l.wino2_floats());
+    if (c.wino3) s.w.wino3 = take(wino, n.wino, l.wino3_floats());
+  }
+  u->emb_w = take(f32, n.f32, (int64_t)u->emb_rows * u->ted);
+  u->emb_b = take(f32, n.f32, u->emb_rows);
+  for (ParamSlot& s : u->params)
+    if (f32 && (s.kind == P_EMB_W || s.kind == P_EMB_B)) {
+      const int row = u->emb_row_off[s.name.substr(0, s.name.rfind(".emb_layers"))];
+      s.w.f32 = s.kind == P_EMB_W ? u->emb_w + (int64_t)row * u->ted : u->emb_b + row;
+    }
+  return n;
 }
 
 // the private copies of parameter `name`: P its fp32 copy, W the whole set of a convolution weight
@@ -620,6 +659,28 @@ struct Planner {
     d.Cout = out.C;
     return d;
   }
+  // One weight's copies into the launch `p`: its main weight, or (`skip`) that of its fused 1x1x1 skip, whose sources are
+  // set.  conv_plan picks kernels from the weight pointers it finds, so which copies are handed over IS the compute mode:
+  // the bf16 ones off the exact mode (halo-path launches multiply on the bf16 matrix cores), the Winograd ones in it (where
+  // conv_plan finds 128-voxel tiles).  The padded extents are the ones the weight was PACKED with, so the weight must be
+  // this launch's own (Cin, Cout) and its CoutP must hold every Cout tile the launch walks: a tile outside it is memory that
+  // no repack wrote.
+  void hand_over(const ConvWeights& cw, ConvParams& p, bool skip) {
+    const bool bf = u->compute_mode != 0, wino = u->compute_mode == 0;
+    (skip ? p.skip_w : p.w) = cw.f32;
+    (skip ? p.skip_w_bf : p.w_bf) = bf ? cw.bf : nullptr;
+    (skip ? p.skip_w_bft : p.w_bft) = bf ? cw.bft : nullptr;
+    (skip ? p.skip_w_wino2 : p.w_wino2) = wino ? cw.wino2 : nullptr;
+    (skip ? p.skip_w_wino3 : p.w_wino3) = wino ? cw.wino3 : nullptr;
+    (skip ? p.skip_CinP : p.CinP) = cw.layout.CinP;
+    const ConvWeightLayout& l = cw.layout;
+    const int Cin = skip ? p.skip_C0 + p.skip_C1 : p.C0 + p.C1;
+    const int tile = conv_cout_tile(p.Cout);
+    if (err.empty() && (l.Cout != p.Cout || l.Cin != Cin || (p.Cout + tile - 1) / tile * tile > l.CoutP || l.CoutP != p.CoutP))
+      err = "internal: a " + std::to_string(Cin) + " -> " + std::to_string(p.Cout) + " convolution was handed weights packed for " +
+            std::to_string(l.Cin) + " -> " + std::to_string(l.Cout) + " (padded to " + std::to_string(l.CinP) + " -> " +
+            std::to_string(l.CoutP) + ")";
+  }
   void emit_conv(const ConvDesc& d) {
     Op op = make_op(OP_CONV);
     ConvParams& p = op.conv;
@@ -642,18 +703,9 @@ struct Planner {
     p.pad = d.ksz == 3 ? 1 : 0;
     p.ksz = d.ksz;
     p.Cout = d.Cout;
-    p.CoutP = pad_cout(d.Cout);
-    p.CinP = pad_cin(p.C0 + p.C1);
-    // conv_plan picks kernels from the weight pointers it finds, so which copies are handed over IS the compute mode:
-    // the bf16 ones off the exact mode (halo-path launches multiply on the bf16 matrix cores), the Winograd ones in it
-    // (where conv_plan finds 128-voxel tiles)
-    const bool bf = u->compute_mode != 0, wino = u->compute_mode == 0;
-    p.w = d.w.f32;
-    p.w_bf = bf ? d.w.bf : nullptr;
-    p.w_bft = bf ? d.w.bft : nullptr;
+    p.CoutP = d.w.layout.CoutP;
+    hand_over(d.w, p, false);
     p.bf16 = u->compute_mode;
-    p.w_wino2 = wino ? d.w.wino2 : nullptr;
-    p.w_wino3 = wino ? d.w.wino3 : nullptr;
     p.coef = d.coef ? ptr<float>(*d.coef) : nullptr;
     p.act = d.act;
     p.bias = d.bias;
@@ -664,12 +716,7 @@ struct Planner {
       p.skip_src1 = d.skip.x1 ? ptr<float>(d.skip.x1->off) : nullptr;
       p.skip_C0 = d.skip.x0->C;
       p.skip_C1 = d.skip.x1 ? d.skip.x1->C : 0;
-      p.skip_w = d.skip.w.f32;
-      p.skip_w_bf = bf ? d.skip.w.bf : nullptr;
-      p.skip_w_bft = bf ? d.skip.w.bft : nullptr;
-      p.skip_w_wino2 = wino ? d.skip.w.wino2 : nullptr;
-      p.skip_w_wino3 = wino ? d.skip.w.wino3 : nullptr;
-      p.skip_CinP = pad_cin(p.skip_C0 + p.skip_C1);
+      hand_over(d.skip.w, p, true);
       p.skip_bias = d.skip.bias;
     }
     ConvParams one = p;
@@ -1095,22 +1142,24 @@ struct TrainPlanner {
   // on weights that were not supplied yet, so there every convolution weight counts as present, and so does the stride-1
   // form "<name>#s1" of a Downsample weight whose two leading dims are multiples of 4 (the one holo_unet_set_dgrad_weight
   // creates); they count as plain fp32 copies, without Winograd forms.
-  const ConvWeights* find_dgw(const std::string& name) {
+  std::optional<ConvWeights> find_dgw(const std::string& name) {
     auto it = u->dgrad.find(name);
-    if (it != u->dgrad.end()) return &it->second;
-    if (pl.base) return nullptr;
+    if (it != u->dgrad.end()) return it->second;
+    if (pl.base) return std::nullopt;
     const bool s1 = name.size() > 3 && name.compare(name.size() - 3, 3, "#s1") == 0;
     auto pi = u->pindex.find(s1 ? name.substr(0, name.size() - 3) : name);
-    if (pi == u->pindex.end()) return nullptr;
+    if (pi == u->pindex.end()) return std::nullopt;
     const ParamSlot& s = u->params[pi->second];
-    if (s.kind != P_CONV3 && s.kind != P_CONV1) return nullptr;
-    if (s1 && (!is_downsample_weight(s.name) || (s.shape[0] & 3) || (s.shape[1] & 3))) return nullptr;
+    if (!s.is_conv()) return std::nullopt;
+    if (s1 && (!is_downsample_weight(s.name) || (s.shape[0] & 3) || (s.shape[1] & 3))) return std::nullopt;
     static float never_read;
-    static const ConvWeights assumed{&never_read};
-    return &assumed;
+    ConvWeights assumed;
+    assumed.f32 = &never_read;
+    assumed.layout = s.layout(true);
+    return assumed;
   }
-  const ConvWeights* dgw(const std::string& name) {
-    const ConvWeights* w = find_dgw(name);
+  std::optional<ConvWeights> dgw(const std::string& name) {
+    const std::optional<ConvWeights> w = find_dgw(name);
     if (!w) err = "holo_unet_backward: call holo_unet_set_dgrad_weight for '" + name + "' first";
     return w;
   }
@@ -1118,7 +1167,7 @@ struct TrainPlanner {
   // dgrad of a stride-1 conv (3x3x3 pad 1 or 1x1x1): out[M][cin] = conv(gy[M][cout], flipped weights)
   void emit_dgrad(size_t gy_off, int cout, int R, const std::string& wname, int cin, int ksz, size_t out_off,
                   bool accumulate = false) {
-    const ConvWeights* w = dgw(wname);
+    const std::optional<ConvWeights> w = dgw(wname);
     if (!w) return;
     const Act g = view(gy_off, cout, R);
     ConvDesc d;
@@ -1337,7 +1386,7 @@ struct TrainPlanner {
       }
       emit_dgrad(gout, cout, Ri, wn, cin, 3, gx_off);
     } else if (kind == B_DOWN) {
-      const ConvWeights* wt = dgw(wn);
+      const std::optional<ConvWeights> wt = dgw(wn);
       if (!wt) return;
       // (HOLO_DGRAD_S2_DIRECT=1, development / test knob: conv_dgrad_s2_kernel everywhere)
       if (!pl.knobs.dgrad_s2_direct && find_dgw(wn + "#s1") && Ri == 2 * Ro && (Ri % 8) == 0) {
@@ -1401,6 +1450,7 @@ struct TrainPlanner {
       else
         bwd_conv(t);
     }
+    if (err.empty()) err = pl.err;  // (emit_conv's refusals)
     if (!err.empty()) {
       set_error("%s", err.c_str());
       return HOLO_E_STATE;
@@ -1614,93 +1664,16 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
   enumerate_params(u);
   u->knobs = Knobs::from_env();
   // private parameter storage
-  int64_t total = 0;
-  auto priv_numel = [](const ParamSlot& s) -> int64_t {
-    if (s.kind == P_CONV3 || s.kind == P_CONV1)
-      return (int64_t)(s.kind == P_CONV3 ? 27 : 1) * pad_cout((int)s.shape[0]) * pad_cin((int)s.shape[1]);
-    return s.numel;
-  };
-  for (auto& s : u->params)
-    if (s.kind == P_PLAIN || s.kind == P_CONV3 || s.kind == P_CONV1) total += (priv_numel(s) + 63) & ~(int64_t)63;
-  total += ((int64_t)u->emb_rows * u->ted + 63) & ~(int64_t)63;
-  total += (u->emb_rows + 63) & ~63;
-  if (hipMalloc((void**)&u->pstore, (size_t)total * sizeof(float)) != hipSuccess) {
-    set_error("holo_unet_create: hipMalloc of %lld parameter floats failed", (long long)total);
+  const StoreSizes n = carve_params(u, nullptr, nullptr, nullptr);
+  if (hipMalloc((void**)&u->pstore, (size_t)n.f32 * sizeof(float)) != hipSuccess ||
+      (n.bf && hipMalloc((void**)&u->pstore_bf, (size_t)n.bf * sizeof(uint16_t)) != hipSuccess) ||
+      (n.wino && hipMalloc((void**)&u->pstore_wino, (size_t)n.wino * sizeof(float)) != hipSuccess)) {
+    set_error("holo_unet_create: hipMalloc of the parameter stores (%lld floats, %lld bf16 weights, %lld Winograd floats) failed",
+              (long long)n.f32, (long long)n.bf, (long long)n.wino);
     holo_unet_destroy(u);
     return HOLO_E_HIP;
   }
-  float* cur = u->pstore;
-  for (auto& s : u->params)
-    if (s.kind == P_PLAIN || s.kind == P_CONV3 || s.kind == P_CONV1) {
-      s.w.f32 = cur;
-      cur += (priv_numel(s) + 63) & ~(int64_t)63;
-    }
-  {  // bf16 copies of the conv weights (same padded element counts, 2 bytes each)
-    int64_t tb = 0;
-    for (auto& s : u->params)
-      if (s.kind == P_CONV3 || s.kind == P_CONV1) tb += 4 * ((priv_numel(s) + 63) & ~(int64_t)63);  // hi, mid, lo planes + the 32x32x16 packing of hi
-    if (hipMalloc((void**)&u->pstore_bf, (size_t)tb * sizeof(uint16_t)) != hipSuccess) {
-      set_error("holo_unet_create: hipMalloc of %lld bf16 weights failed", (long long)tb);
-      holo_unet_destroy(u);
-      return HOLO_E_HIP;
-    }
-    uint16_t* cb = u->pstore_bf;
-    for (auto& s : u->params)
-      if (s.kind == P_CONV3 || s.kind == P_CONV1) {
-        s.w.bf = cb;
-        s.w.bft = cb + 3 * priv_numel(s);  // plane 3 (the repack kernel lays the planes out back to back)
-        cb += 4 * ((priv_numel(s) + 63) & ~(int64_t)63);
-      }
-  }
-  {  // Winograd copies for the convolutions that can land on 128-voxel tiles: the wide top levels (a 3x3x3 conv of
-     // <= 256 channels: 48 (z,y) pseudo-taps; a ResBlock's 1x1x1 skip connection: 4).  HOLO_CONV_WINO=0: none
-    const bool enable = u->knobs.conv_wino != 0;
-    auto wino2_numel = [&](const ParamSlot& s) -> int64_t {
-      const bool c3 = s.kind == P_CONV3;
-      const bool sk = s.kind == P_CONV1 && s.name.find("skip_connection") != std::string::npos;
-      // (the levels with 8-divisible planes: up to 256 output channels, up to 768 input channels with the skip concat)
-      if (!enable || !(c3 || sk) || s.shape[0] > 256 || s.shape[1] > 768 || (s.shape[0] % 64 && !(c3 && s.shape[0] == 32))) return 0;
-      return (int64_t)(c3 ? 48 : 4) * pad_cout((int)s.shape[0]) * pad_cin((int)s.shape[1]);
-    };
-    // F(2x2x2, 3x3x3) copies (conv_wino3_kernel, 64 pseudo-taps / 8 signed skip copies): the levels whose workgroup list
-    // can fill the chip - up to 256 output channels (64^3 .. 8^3 in the released nets); HOLO_CONV_WINO3=0: none
-    const bool enable3 = u->knobs.conv_wino3 != 0;
-    auto wino3_numel = [&](const ParamSlot& s) -> int64_t {
-      if (!enable3 || wino2_numel(s) == 0 || s.shape[0] % 64 || s.shape[0] > 256 || s.shape[1] > 768) return 0;
-      return conv_wino3_weight_floats(pad_cout((int)s.shape[0]), pad_cin((int)s.shape[1]), s.kind == P_CONV3 ? 27 : 1);
-    };
-    int64_t tw = 0;
-    for (auto& s : u->params) tw += ((wino2_numel(s) + 63) & ~(int64_t)63) + ((wino3_numel(s) + 63) & ~(int64_t)63);
-    if (tw > 0) {
-      if (hipMalloc((void**)&u->pstore_wino, (size_t)tw * sizeof(float)) != hipSuccess) {
-        set_error("holo_unet_create: hipMalloc of %lld Winograd weights failed", (long long)tw);
-        holo_unet_destroy(u);
-        return HOLO_E_HIP;
-      }
-      float* cw = u->pstore_wino;
-      for (auto& s : u->params) {
-        const int64_t nw2 = wino2_numel(s);
-        if (nw2 == 0) continue;
-        s.w.wino2 = cw;
-        cw += (nw2 + 63) & ~(int64_t)63;
-        const int64_t nw3 = wino3_numel(s);
-        if (nw3) {
-          s.w.wino3 = cw;
-          cw += (nw3 + 63) & ~(int64_t)63;
-        }
-      }
-    }
-  }
-  u->emb_w = cur;
-  cur += ((int64_t)u->emb_rows * u->ted + 63) & ~(int64_t)63;
-  u->emb_b = cur;
-  for (auto& s : u->params) {
-    if (s.kind == P_EMB_W || s.kind == P_EMB_B) {
-      std::string prefix = s.name.substr(0, s.name.rfind(".emb_layers"));
-      int row = u->emb_row_off[prefix];
-      s.w.f32 = s.kind == P_EMB_W ? u->emb_w + (int64_t)row * u->ted : u->emb_b + row;
-    }
-  }
+  carve_params(u, u->pstore, u->pstore_bf, u->pstore_wino);
   *out = u;
   return 0;
 }
@@ -1758,14 +1731,8 @@ int holo_unet_set_param(HoloUnet* net, const char* name, const void* dev_ptr, in
     set_error("holo_unet_set_param: shape mismatch for '%s'", name);
     return HOLO_E_INVALID;
   }
-  if (s.kind == P_CONV3 || s.kind == P_CONV1) {
-    const float* src = (const float*)dev_ptr;
-    const int Co = (int)s.shape[0], Ci = (int)s.shape[1], taps = s.kind == P_CONV3 ? 27 : 1, CoP = pad_cout(Co), CiP = pad_cin(Ci);
-    int rc = repack_conv_weight_launch(src, s.w.f32, Co, Ci, taps, CoP, CiP, stream);
-    if (!rc) rc = repack_conv_weight_bf16_launch(src, s.w.bf, Co, Ci, taps, CoP, CiP, stream);
-    if (!rc && s.w.wino2) rc = repack_conv_weight_wino2_launch(src, s.w.wino2, Co, Ci, taps, CoP, CiP, stream);
-    if (!rc && s.w.wino3) rc = repack_conv_weight_wino3_launch(src, s.w.wino3, Co, Ci, taps, CoP, CiP, stream);
-    if (rc) return rc;
+  if (s.is_conv()) {
+    if (const int rc = pack_conv_weights((const float*)dev_ptr, s.w, stream)) return rc;
   } else {  // biases, GroupNorm parameters, Linear layers: a copy kernel with system-scope loads (holo_ld_sys) - like the
             // weight repack kernels, every ingestion of a caller-provided tensor reads it past the L2
     if (copy_sys_launch((const float*)dev_ptr, s.w.f32, s.numel, stream)) return HOLO_E_INVALID;
@@ -2023,7 +1990,7 @@ int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_
     return HOLO_E_INVALID;
   }
   auto it = net->pindex.find(name);
-  if (it == net->pindex.end() || (net->params[it->second].kind != P_CONV3 && net->params[it->second].kind != P_CONV1)) {
+  if (it == net->pindex.end() || !net->params[it->second].is_conv()) {
     set_error("holo_unet_set_dgrad_weight: '%s' is not a convolution weight", name);
     return HOLO_E_INVALID;
   }
@@ -2031,51 +1998,34 @@ int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_
   const int Co = (int)s.shape[0], Ci = (int)s.shape[1], T = s.kind == P_CONV3 ? 27 : 1;
   const std::string nm(name);
   const bool down = is_downsample_weight(nm);
-  // transposed convolution: Cout' = Ci, Cin' = Co
-  const size_t packed = down ? (size_t)T * Co * Ci : (size_t)T * pad_cout(Ci) * pad_cin(Co);
   if (down) {  // [tap][co][ci] for conv_dgrad_s2_kernel (the fallback), then the stride-1 form below under "<name>#s1":
                // the transposed stride-2 convolution runs as zero insertion + the stride-1 transposed convolution
     float*& d2 = net->dgrad[nm].f32;
-    if (!d2) HIP_TRY(hipMalloc((void**)&d2, packed * sizeof(float)));
+    if (!d2) HIP_TRY(hipMalloc((void**)&d2, (size_t)T * Co * Ci * sizeof(float)));
     if (weight_tco_ci_launch((const float*)dev_ptr, d2, Co, Ci, T, stream)) return HOLO_E_INVALID;
     if ((Co & 3) || (Ci & 3)) return 0;
   }
-  const std::string key = down ? nm + "#s1" : nm;
-  ConvWeights& dw = net->dgrad[key];
-  float*& dst = dw.f32;
-  if (!dst) HIP_TRY(hipMalloc((void**)&dst, (size_t)T * pad_cout(Ci) * pad_cin(Co) * sizeof(float)));
-  if (net->dgrad_tmp_floats < (size_t)s.numel) {
-    if (net->dgrad_tmp) {
-      HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-      (void)hipFree(net->dgrad_tmp);
-    }
-    HIP_TRY(hipMalloc((void**)&net->dgrad_tmp, (size_t)s.numel * sizeof(float)));
-    net->dgrad_tmp_floats = (size_t)s.numel;
+  // The transposed convolution (Cout' = Ci, Cin' = Co), packed like a forward weight.  Its buffers are created at the first
+  // call for this weight (an inference-only user pays nothing): the fp32 pack, and the Winograd packs of dgrad_copies - the
+  // dgrad of a wide-level 3x3x3 conv runs on conv_wino2_kernel / conv_wino3_kernel like the forward conv.
+  ConvWeights& dw = net->dgrad[down ? nm + "#s1" : nm];
+  const ConvWeightLayout l = dw.layout = s.layout(true);
+  const ConvCopies c = dgrad_copies(l, net->compute_mode, net->knobs);
+  if (!dw.f32) HIP_TRY(hipMalloc((void**)&dw.f32, (size_t)l.f32_floats() * sizeof(float)));
+  if ((c.wino2 && !dw.wino2) || (c.wino3 && !dw.wino3)) {  // a plan sized before these copies existed chose other kernels
+    net->tws_cache.clear();                                 // (and scratch sizes)
+    net->tplan.invalidate();
+    if (!dw.wino2) HIP_TRY(hipMalloc((void**)&dw.wino2, (size_t)l.wino2_floats() * sizeof(float)));
+    if (c.wino3 && !dw.wino3) HIP_TRY(hipMalloc((void**)&dw.wino3, (size_t)l.wino3_floats() * sizeof(float)));
+  }
+  if (!net->dgrad_tmp) {
+    int64_t largest = 0;
+    for (const ParamSlot& q : net->params)
+      if (q.is_conv() && q.numel > largest) largest = q.numel;
+    HIP_TRY(hipMalloc((void**)&net->dgrad_tmp, (size_t)largest * sizeof(float)));
   }
   if (flip_transpose_weight_launch((const float*)dev_ptr, net->dgrad_tmp, Co, Ci, T, stream)) return HOLO_E_INVALID;
-  if (repack_conv_weight_launch(net->dgrad_tmp, dst, Ci, Co, T, pad_cout(Ci), pad_cin(Co), stream)) return HOLO_E_INVALID;
-  // Winograd copies of the transposed convolution (the dgrad of a wide-level 3x3x3 conv runs on conv_wino2_kernel like
-  // the forward conv: 48 pseudo-taps, same eligibility as holo_unet_create's except that the transposed conv's output
-  // channels are the forward conv's INPUT channels, up to 768 with the skip concat)
-  if (net->knobs.conv_wino != 0 && net->compute_mode == 0 && T == 27 && (Ci % 64) == 0 && Ci <= 768 && Co <= 768) {
-    float*& w2 = dw.wino2;
-    if (!w2) {  // a plan sized before these copies existed chose other kernels (and scratch sizes)
-      net->tws_cache.clear();
-      net->tplan.invalidate();
-      HIP_TRY(hipMalloc((void**)&w2, 48 * (size_t)pad_cout(Ci) * pad_cin(Co) * sizeof(float)));
-    }
-    if (repack_conv_weight_wino2_launch(net->dgrad_tmp, w2, Ci, Co, 27, pad_cout(Ci), pad_cin(Co), stream)) return HOLO_E_INVALID;
-    // ... and on conv_wino3_kernel where the forward convolutions do (transposed: output channels = the forward's inputs)
-    if (net->knobs.conv_wino3 != 0 && Ci <= 256 && Co <= 768) {
-      float*& w3 = dw.wino3;
-      if (!w3) {
-        net->tws_cache.clear();
-        net->tplan.invalidate();
-        HIP_TRY(hipMalloc((void**)&w3, (size_t)conv_wino3_weight_floats(pad_cout(Ci), pad_cin(Co), 27) * sizeof(float)));
-      }
-      if (repack_conv_weight_wino3_launch(net->dgrad_tmp, w3, Ci, Co, 27, pad_cout(Ci), pad_cin(Co), stream)) return HOLO_E_INVALID;
-    }
-  }
+  if (pack_conv_weights(net->dgrad_tmp, dw, stream)) return HOLO_E_INVALID;
   return 0;
 }
 

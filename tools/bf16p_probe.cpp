@@ -89,7 +89,7 @@ int main(int argc, char** argv) {
     if (shape_no++ >= nshapes) break;
     const int R = s.R, Cin = s.C0 + s.C1, Cout = s.Cout;
     const int64_t V = (int64_t)R * R * R;
-    const int CinP = (Cin + 31) / 32 * 32, CoutP = Cout >= 64 ? (Cout + 63) / 64 * 64 : 32;
+    const ConvWeightLayout L = conv_weight_layout(Cout, Cin, 27);
     ConvParams p{};
     p.src0 = (const float*)dev_random_bf16(V * s.C0, 1.f);
     p.C0 = s.C0;
@@ -100,11 +100,11 @@ int main(int argc, char** argv) {
     p.N = 1;
     p.ID = p.IH = p.IW = p.OD = p.OH = p.OW = R;
     p.stride = 1, p.pad = 1, p.ksz = 3;
-    p.Cout = Cout, p.CoutP = CoutP, p.CinP = CinP;
+    p.Cout = Cout, p.CoutP = L.CoutP, p.CinP = L.CinP;
     p.bf16 = 1, p.in_bf16 = 1, p.res_bf16 = 1, p.out_bf16 = 1;
     p.w = dev_random(64, 0.1f);  // (not read on this path)
     p.w_bf = dev_random_bf16(64, 0.1f);
-    p.w_bft = dev_random_bf16((size_t)27 * CinP * CoutP, 0.05f);
+    p.w_bft = dev_random_bf16((size_t)L.f32_floats(), 0.05f);
     CK(hipMalloc((void**)&p.out, V * Cout * 2));
     if (s.act) {
       std::vector<float> hc((size_t)Cin * 2);
@@ -125,11 +125,11 @@ int main(int argc, char** argv) {
     if (s.skip) {
       p.skip_src0 = (const float*)dev_random_bf16(V * 64, 1.f);
       p.skip_src1 = (const float*)dev_random_bf16(V * 64, 1.f);
-      p.skip_C0 = p.skip_C1 = 64;
-      p.skip_CinP = 128;
+      const ConvWeightLayout LS = conv_weight_layout(Cout, 128, 1);  // the fused 1x1x1 skip
+      p.skip_C0 = p.skip_C1 = 64, p.skip_CinP = LS.CinP;
       p.skip_w = dev_random(64, 0.1f);
       p.skip_w_bf = dev_random_bf16(64, 0.1f);
-      p.skip_w_bft = dev_random_bf16((size_t)128 * CoutP, 0.05f);
+      p.skip_w_bft = dev_random_bf16((size_t)LS.f32_floats(), 0.05f);
       p.skip_bias = dev_random(Cout, 1.f);
     }
     printf("%s\n", s.what);

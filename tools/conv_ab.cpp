@@ -90,7 +90,7 @@ int main(int argc, char** argv) {
     const int64_t V = (int64_t)R * R * R;
     const int SR = s.ups ? R / 2 : R;
     const int64_t SV = (int64_t)SR * SR * SR;
-    const int CinP = (Cin + 31) / 32 * 32, CoutP = (Cout + 63) / 64 * 64;
+    const ConvWeightLayout L = conv_weight_layout(Cout, Cin, 27);
     ConvParams p{};
     p.src0 = dev_random(SV * s.C0, 1.f);
     p.C0 = s.C0;
@@ -102,10 +102,10 @@ int main(int argc, char** argv) {
     p.ID = p.IH = p.IW = p.OD = p.OH = p.OW = R;
     p.ups = s.ups;
     p.stride = 1, p.pad = 1, p.ksz = 3;
-    p.Cout = Cout, p.CoutP = CoutP, p.CinP = CinP;
-    p.w = dev_random((size_t)27 * CinP * CoutP, 0.1f);
-    p.w_wino2 = dev_random((size_t)48 * CinP * CoutP, 0.1f);
-    p.w_wino3 = dev_random((size_t)conv_wino3_weight_floats(CoutP, CinP, 27), 0.1f);
+    p.Cout = Cout, p.CoutP = L.CoutP, p.CinP = L.CinP;
+    p.w = dev_random((size_t)L.f32_floats(), 0.1f);
+    p.w_wino2 = dev_random((size_t)L.wino2_floats(), 0.1f);
+    p.w_wino3 = dev_random((size_t)L.wino3_floats(), 0.1f);
     CK(hipMalloc((void**)&p.out, V * Cout * 4));
     if (s.act) {
       std::vector<float> hc((size_t)Cin * 2);
@@ -126,11 +126,11 @@ int main(int argc, char** argv) {
     if (s.skip) {
       p.skip_src0 = dev_random(V * 64, 1.f);
       p.skip_src1 = dev_random(V * 64, 1.f);
-      p.skip_C0 = p.skip_C1 = 64;
-      p.skip_CinP = 128;
-      p.skip_w = dev_random((size_t)128 * CoutP, 0.1f);
-      p.skip_w_wino2 = dev_random((size_t)4 * 128 * CoutP, 0.1f);
-      p.skip_w_wino3 = dev_random((size_t)conv_wino3_weight_floats(CoutP, 128, 1), 0.1f);
+      const ConvWeightLayout LS = conv_weight_layout(Cout, 128, 1);  // the fused 1x1x1 skip
+      p.skip_C0 = p.skip_C1 = 64, p.skip_CinP = LS.CinP;
+      p.skip_w = dev_random((size_t)LS.f32_floats(), 0.1f);
+      p.skip_w_wino2 = dev_random((size_t)LS.wino2_floats(), 0.1f);
+      p.skip_w_wino3 = dev_random((size_t)LS.wino3_floats(), 0.1f);
       p.skip_bias = dev_random(Cout, 1.f);
     }
     printf("%s\n", s.what);

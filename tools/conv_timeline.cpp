@@ -22,18 +22,18 @@ int main(int argc, char** argv) {
   const int stag = argc > 6 ? atoi(argv[6]) : 0;  // microseconds
   const int64_t V = (int64_t)R * R * R;
   float *src, *w, *out; unsigned long long* dbg;
-  const int CinP = (Cin + 31) / 32 * 32, CoutP = Cout >= 64 ? (Cout + 63) / 64 * 64 : 32;
-  CK(hipMalloc(&src, V * Cin * 4)); CK(hipMalloc(&out, V * Cout * 4)); CK(hipMalloc(&w, (size_t)27 * CinP * CoutP * 4));
+  const ConvWeightLayout L = conv_weight_layout(Cout, Cin, 27);
+  CK(hipMalloc(&src, V * Cin * 4)); CK(hipMalloc(&out, V * Cout * 4)); CK(hipMalloc(&w, (size_t)L.f32_floats() * 4));
   std::vector<float> h(V * Cin); for (auto& x : h) x = (rand() % 2001 - 1000) * 1e-3f;
   CK(hipMemcpy(src, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-  std::vector<float> hw((size_t)27 * CinP * CoutP); for (auto& x : hw) x = (rand() % 2001 - 1000) * 1e-4f;
+  std::vector<float> hw((size_t)L.f32_floats()); for (auto& x : hw) x = (rand() % 2001 - 1000) * 1e-4f;
   CK(hipMemcpy(w, hw.data(), hw.size() * 4, hipMemcpyHostToDevice));
   ConvParams p{}; p.src0 = src; p.C0 = Cin; p.N = 1; p.ID = p.IH = p.IW = p.OD = p.OH = p.OW = R; p.stride = 1; p.pad = 1; p.ksz = 3;
-  p.Cout = Cout; p.w = w; p.CoutP = CoutP; p.CinP = CinP; p.out = out;
+  p.Cout = Cout; p.w = w; p.CoutP = L.CoutP; p.CinP = L.CinP; p.out = out;
   float* w2 = nullptr;
   if (gx == 2) {  // (z,y) Winograd form: 48 pseudo-taps (random values: timing only)
-    CK(hipMalloc(&w2, (size_t)48 * CinP * CoutP * 4));
-    std::vector<float> hw2((size_t)48 * CinP * CoutP); for (auto& x : hw2) x = (rand() % 2001 - 1000) * 1e-4f;
+    CK(hipMalloc(&w2, (size_t)L.wino2_floats() * 4));
+    std::vector<float> hw2((size_t)L.wino2_floats()); for (auto& x : hw2) x = (rand() % 2001 - 1000) * 1e-4f;
     CK(hipMemcpy(w2, hw2.data(), hw2.size() * 4, hipMemcpyHostToDevice));
     p.w_wino2 = w2;
   }
@@ -47,8 +47,8 @@ int main(int argc, char** argv) {
   if (gx == 3) {  // bf16 storage + wide-tile kernel: bf16 activations and packed bf16 weights (random values: timing only)
     std::vector<uint16_t> hb((size_t)V * Cin); for (auto& x : hb) x = (uint16_t)(0x3c00 + rand() % 0x300) | (rand() & 1 ? 0x8000 : 0);
     CK(hipMemcpy(src, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
-    uint16_t* wb; CK(hipMalloc(&wb, (size_t)27 * CinP * CoutP * 2));
-    std::vector<uint16_t> hwb((size_t)27 * CinP * CoutP); for (auto& x : hwb) x = (uint16_t)(0x3800 + rand() % 0x300) | (rand() & 1 ? 0x8000 : 0);
+    uint16_t* wb; CK(hipMalloc(&wb, (size_t)L.f32_floats() * 2));
+    std::vector<uint16_t> hwb((size_t)L.f32_floats()); for (auto& x : hwb) x = (uint16_t)(0x3800 + rand() % 0x300) | (rand() & 1 ? 0x8000 : 0);
     CK(hipMemcpy(wb, hwb.data(), hwb.size() * 2, hipMemcpyHostToDevice));
     p.bf16 = 1; p.w_bf = wb; p.w_bft = wb; p.in_bf16 = p.res_bf16 = p.out_bf16 = 1;
   }

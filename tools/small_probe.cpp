@@ -51,8 +51,8 @@ int main(int argc, char** argv) {
   const int Cin = argc > 1 ? atoi(argv[1]) : 512, Cout = argc > 2 ? atoi(argv[2]) : 512, R = argc > 3 ? atoi(argv[3]) : 4;
   const int iters = argc > 4 ? atoi(argv[4]) : 64;
   const int64_t V = (int64_t)R * R * R;
-  const int CinP = (Cin + 31) / 32 * 32, CoutP = (Cout + 63) / 64 * 64;
-  const size_t wfloats = (size_t)27 * CinP * CoutP;
+  const ConvWeightLayout L = conv_weight_layout(Cout, Cin, 27);
+  const size_t wfloats = (size_t)L.f32_floats();
   const int NW = 16;
   std::vector<float*> w(NW);
   {
@@ -83,7 +83,7 @@ int main(int argc, char** argv) {
   }
   ConvParams p{};
   p.src0 = src, p.C0 = Cin, p.N = 1, p.ID = p.IH = p.IW = p.OD = p.OH = p.OW = R, p.stride = 1, p.pad = 1, p.ksz = 3;
-  p.Cout = Cout, p.w = w[0], p.CoutP = CoutP, p.CinP = CinP, p.out = out, p.coef = coef, p.act = 1, p.bias = bias;
+  p.Cout = Cout, p.w = w[0], p.CoutP = L.CoutP, p.CinP = L.CinP, p.out = out, p.coef = coef, p.act = 1, p.bias = bias;
   const size_t sb = conv_plan(p, 256, Knobs::from_env());
   if (sb) CK(hipMalloc((void**)&p.partial, sb));
   printf("%d^3 %d -> %d: kernel %d, split-K %d x %d chunks, partials %.1f MB, weights %.1f MB\n", R, Cin, Cout, (int)p.kernel, p.nsplit,
