@@ -93,6 +93,9 @@ struct ConvParams {
   // (repack_conv_weight_wino3_launch); the fused skip as 8 signed copies of the 1x1x1 weight
   const float* w_wino3;
   const float* skip_w_wino3;
+  // set by conv_plan: the launch runs that kernel's upsampling form (conv_wino3_up_kernel: ups, raw input, no fused skip -
+  // the 27 pseudo-taps whose A operands are not identically zero; same results, 27/64 of the MFMAs)
+  int wino3_up;
   // bf16 wide-tile kernel (conv_bf16t_kernel, 8x8x8 output tiles, v_mfma_f32_32x32x16_bf16): plane 3 of the bf16
   // weight buffer, packed [ksz^3][CinP/16][CoutP/32][lane 64][8 bf16] = one 1 KB block of B operands per
   // (tap, 16-channel chunk, 32-Cout slice); lane's 8 values are channels 8*(lane>>5) .. +7 of output channel lane&31

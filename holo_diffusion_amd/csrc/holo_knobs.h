@@ -73,6 +73,8 @@ constexpr int64_t KNOB_UNSET = INT64_MIN;
   X(conv_bf16p_wgs, "HOLO_CONV_BF16P_WGS", INT, 0, PLAN, "at most this many persistent workgroups (0: no cap)")            \
   X(conv_wino3_min_items, "HOLO_CONV_WINO3_MIN_ITEMS", INT, KNOB_UNSET, PLAN,                                              \
     "work items from which conv_wino3_kernel runs (default: num_cus / 2)")                                                 \
+  X(conv_wino3_up, "HOLO_CONV_WINO3_UP", INT, 1, PLAN,                                                                     \
+    "0: upsampling convolutions on conv_wino3_kernel's generic form (64 pseudo-taps), not its 27-tap form")               \
   X(no_skip_fusion, "HOLO_NO_SKIP_FUSION", SET, 0, PLAN, "a ResBlock's 1x1x1 skip always as its own launch")               \
   X(skip_fusion_below_r, "HOLO_SKIP_FUSION_BELOW_R", RAW, 64, PLAN,                                                        \
     "exact fp32: the skip is fused into the second convolution below this grid edge")                                      \

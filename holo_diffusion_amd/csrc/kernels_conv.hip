@@ -2728,6 +2728,10 @@ size_t conv_plan(ConvParams& p, int num_cus, const Knobs& k, int plan_n) {
     return ConvKernel::Halo;
   }();
   p.kernel = kernel;
+  // the upsampling form of the three-axis Winograd kernel (kernels_conv3.hip): nearest x2 input read raw, no fused skip.
+  // HOLO_CONV_WINO3_UP=0 keeps the generic form.  (No shape criterion: measured per launch, the form pays on every shape of
+  // the plan, the split-K 16^3 one included - profiles/r14_wino3_upsample.txt)
+  p.wino3_up = kernel == ConvKernel::Wino3 && p.ups && !p.coef && !p.skip_w && k.conv_wino3_up != 0 ? 1 : 0;
 
   // ---- its geometry
   switch (kernel) {
@@ -2859,7 +2863,9 @@ double conv_flops(const ConvParams& p) {
 // (F(2x2x2)) or 48 per 2 x 2 outputs ((z,y) form) where the direct form spends 27 per output; the fused skip costs the
 // same in all forms (F(2x2x2): accumulated directly; (z,y): 4 pseudo-taps per 4 outputs)
 double conv_exec_flops(const ConvParams& p) {
-  const double taps = p.kernel == ConvKernel::Wino3 ? 8.0 : p.kernel == ConvKernel::Wino2 ? 12.0 : 0.0;
+  // (the upsampling form of the F(2x2x2) kernel issues the 27 of 64 pseudo-taps whose operands are not identically zero)
+  const double wino3_taps = p.wino3_up ? 27.0 / 8.0 : 8.0;
+  const double taps = p.kernel == ConvKernel::Wino3 ? wino3_taps : p.kernel == ConvKernel::Wino2 ? 12.0 : 0.0;
   if (taps == 0.0) return conv_flops(p);
   const double M = (double)p.N * p.OD * p.OH * p.OW;
   return 2.0 * M * p.Cout * ((double)(p.C0 + p.C1) * taps + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0));

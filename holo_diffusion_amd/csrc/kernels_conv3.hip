@@ -51,6 +51,12 @@
 #ifndef W3_WDIST
 #define W3_WDIST 3  // weight requests run this many 16-MFMA groups ahead (2: measured ~190 cycles of wait per group)
 #endif
+#ifndef W3_UP_ONE_REQ
+// upsampling form: 1 requests planes 1 and 2 of a halo column (the same coarse address) once and copies the registers.
+// Measured against the doubled request (profiles/r14_wino3_upsample.txt): inside the run-to-run spread on every shape of the
+// plan, so the doubled request stays
+#define W3_UP_ONE_REQ 0
+#endif
 #ifndef W3_ENTRY
 #define W3_ENTRY conv_wino3_launch
 #endif
@@ -155,14 +161,41 @@ __device__ __forceinline__ void w3_static_for(F&& f, std::integer_sequence<int, 
   (f(std::integral_constant<int, K>{}), ...);
 }
 
+// The upsampling form (UP, conv_wino3_up_kernel).  A nearest x2 halo read at tile-aligned (even) coordinates holds, on every
+// axis, the coarse values (c[i-1], c[i], c[i], c[i+1]) at the four positions of an F(2,3) tile: the two middle inputs of the
+// input transform are the same number, so xi2 = d2 - d1 is exactly +0 on all three axes and every pseudo-tap with a 2 among
+// (xi_z, xi_y, xi_x) has an all-zero A operand - 37 of the 64.  Their MFMAs add 0 . w to accumulators that stay +0; the UP
+// form leaves them (their weights, patch reads, transforms, the xi_z = 2 plane of the LDS) out and feeds the output
+// transform the constant +0 instead: only additions of exact zeros are removed, so for finite inputs and weights the results
+// are the generic kernel's bit for bit (an inf or NaN makes NaN of 0 . inf or inf - inf in the generic form's dead taps; the UP
+// form has +0 there).  What is left: xi in {0, 1, 3} per axis = 27 pseudo-taps, 18 groups of 12 MFMAs per stage.
+template <bool UP>
+constexpr int w3_live(int i) {  // the i-th live xi of an axis
+  return UP && i == 2 ? 3 : i;
+}
+constexpr bool w3_dead_set(int s) { return (s >> 4) == 2 || ((s >> 2) & 3) == 2 || (s & 3) == 2; }  // accumulator set [xi_z][xi_y][xi_x]
+// offset in floats of the 1 KB block (group gi, tap ti) of a (chunk, slice) of the weight pack, both counted over the LIVE
+// steps / taps: the pack stays [xi_z][half][xi_y][xi_x], the UP form skips the dead blocks
+template <bool UP>
+constexpr int w3_wofs(int gi, int ti) {
+  constexpr int NL = UP ? 3 : 4;
+  const int st = gi / NL;
+  return ((((w3_live<UP>(st >> 1) * 2 + (st & 1)) * 4 + w3_live<UP>(gi % NL)) * 4) + w3_live<UP>(ti)) * 256;
+}
+
 // One persistent workgroup per CU.  Work list: item = ((split * ny + cout block) * ntiles + tile), dealt round robin.
 // XF: the input passes through the per-(sample, channel) affine (GroupNorm folded with FiLM) and, with p.act, SiLU.
 // (ONE argument, by value: W3_KARGS reads it back from offset 0 of the kernarg segment - a second argument in front of it,
 // or a ConvParams that is no plain aggregate, breaks that silently)
 static_assert(std::is_trivially_copyable<ConvParams>::value && std::is_standard_layout<ConvParams>::value,
               "W3_KARGS reads ConvParams straight from the kernarg segment");
-template <bool SKIP, bool XF>
-__global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
+template <bool SKIP, bool XF, bool UP>
+__device__ __forceinline__ void conv_wino3_body(const ConvParams& p) {
+  static_assert(!UP || (!SKIP && !XF), "the upsampling form: raw input, no fused skip");
+  // groups per stage / MFMAs per group; where the stage's producer work sits (see the stage body)
+  constexpr int NL = UP ? 3 : 4, NG = 2 * NL * NL, NK = 4 * NL, NR = UP ? 6 : 4;
+  constexpr int GH0 = 1, GH1 = UP ? 7 : 16, GC0 = UP ? 6 : 8, GC1 = UP ? 8 : 12, GC2 = UP ? 12 : 20, GC3 = UP ? 14 : 24;
+  constexpr int GBAR = UP ? 16 : 28;
   __shared__ __attribute__((aligned(16))) float s_halo[2 * W3_HALO];
 
   const int tid = threadIdx.x;
@@ -313,6 +346,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
   // one 16-byte request: item i, plane pl (unconditional, from a clamped address; masked at commit): scalar base + 32-bit
   // vector offset, no address arithmetic at the request
   auto halo_load = [&](int i, int pl) {
+    if (UP && W3_UP_ONE_REQ && pl == 2) return;  // the same coarse plane as pl == 1
     const w3q v = h_second ? w3_bld(rsrc1, h_off[i], h_zoff[pl]) : w3_bld(rsrc0, h_off[i], h_zoff[pl]);
     if (i & 1)
       hrB[pl] = v;
@@ -326,6 +360,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
   auto commit_item_on = [&](w3q(&H)[4], int i, float* buf) {
     // stage by stage over the eight register pairs, each stage pinned behind the previous one: a dependent instruction is
     // then always eight instructions away from its producer (the in-order wave has no other wave to fill a latency with)
+    if (UP && W3_UP_ONE_REQ) H[2] = H[1];
     f32x2* V[8] = {&H[0].lo, &H[0].hi, &H[1].lo, &H[1].hi, &H[2].lo, &H[2].hi, &H[3].lo, &H[3].hi};
     if (XF && !(W3_PROBE & 64)) {
       f32x2 e[8];
@@ -357,10 +392,13 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
     }
     const int col = min((tid >> 3) + 32 * i, W3_PLANE - 1);
     float* dst = buf + col * W3_RS + q * 4;
-    const w3q o0 = w3_sub(H[0], H[2]), o1 = w3_add(H[1], H[2]), o2 = w3_sub(H[2], H[1]), o3 = w3_sub(H[1], H[3]);
+    const w3q o0 = w3_sub(H[0], H[2]), o1 = w3_add(H[1], H[2]), o3 = w3_sub(H[1], H[3]);
     *reinterpret_cast<float4*>(dst + 0 * W3_PLANE * W3_RS) = make_float4(o0.lo.x, o0.lo.y, o0.hi.x, o0.hi.y);
     *reinterpret_cast<float4*>(dst + 1 * W3_PLANE * W3_RS) = make_float4(o1.lo.x, o1.lo.y, o1.hi.x, o1.hi.y);
-    *reinterpret_cast<float4*>(dst + 2 * W3_PLANE * W3_RS) = make_float4(o2.lo.x, o2.lo.y, o2.hi.x, o2.hi.y);
+    if (!UP) {  // (UP: H[2] == H[1], the plane is +0 and nobody reads it)
+      const w3q o2 = w3_sub(H[2], H[1]);
+      *reinterpret_cast<float4*>(dst + 2 * W3_PLANE * W3_RS) = make_float4(o2.lo.x, o2.lo.y, o2.hi.x, o2.hi.y);
+    }
     *reinterpret_cast<float4*>(dst + 3 * W3_PLANE * W3_RS) = make_float4(o3.lo.x, o3.lo.y, o3.hi.x, o3.hi.y);
   };
   auto commit_item = [&](int i, float* buf) {
@@ -386,6 +424,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
     if (h == 0) {
       const w3q t0 = w3_sub(P[a][0], P[a][2]), t3 = w3_sub(P[a][1], P[a][3]);
       P[a][0] = t0, P[a][3] = t3;
+    } else if (UP) {  // (xi_x = 2 is +0: not formed, P[a][2] is not used again)
+      P[a][1] = w3_add(P[a][1], P[a][2]);
     } else {
       const w3q t1 = w3_add(P[a][1], P[a][2]), t2 = w3_sub(P[a][2], P[a][1]);
       P[a][1] = t1, P[a][2] = t2;
@@ -396,7 +436,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
     return xy == 0 ? w3_sub(P[0][b], P[2][b]) : xy == 1 ? w3_add(P[1][b], P[2][b]) : xy == 2 ? w3_sub(P[2][b], P[1][b]) : w3_sub(P[1][b], P[3][b]);
   };
   w3q Bdummy[4] = {};  // (W3_PROBE & 16)
-  w3q Bw[4][4];  // ring of weight groups: group g lives in slot g & 3 and is requested W3_WDIST groups ahead
+  w3q Bw[NR][4];  // ring of weight groups: group g lives in slot g % NR and is requested W3_WDIST groups ahead (NR divides NG)
   // MFMA k of a group: k-step e = k >> 2 (the component of the 16-byte operands), pseudo-tap t = k & 3.  The accumulators are
   // TIED to their AGPR tuples (HOLO_MFMA16_ACC, holo_common.h): 64 sets fill the accumulation file.
   auto mfma1 = [&](f32x4& c, const w3q& A, const w3q& B, int e, bool first, bool zero = false) {
@@ -416,6 +456,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
     } else {
       HOLO_MFMA16_ACC(c, a, b);
     }
+  };
+
+  // register r of accumulator set s -> an arch VGPR (the epilogue).  UP: a dead set was never accumulated into - the generic
+  // kernel holds +0 there -, so it enters the output transform as that constant; the additions of the zero stay
+  auto acc_read = [&](int s, int r) {
+    float v = 0.f;
+    if (!(UP && w3_dead_set(s))) HOLO_ACC_READ(v, acc[s], r);
+    return v;
   };
 
   // a whole group at once (the fused skip): the four accumulators advance together, k-step by k-step
@@ -449,7 +497,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
 #pragma unroll
   for (int g = 0; g < W3_WDIST; ++g)
 #pragma unroll
-    for (int t = 0; t < 4; ++t) Bw[g][t] = w_ld(w_of(cur, cc), g * W3_WSUB + t * 256);
+    for (int t = 0; t < NL; ++t) Bw[g][w3_live<UP>(t)] = w_ld(w_of(cur, cc), w3_wofs<UP>(g, t));
   halo_setup(cur, cc);
   // (all four halo items in ONE round trip - items 2 and 3 waiting in two rows of the not yet live patch - was tried and
   // measured: the prologue stayed at 3.2 - 3.4 us on the 64^3 shapes, profiles/r11_wino3_item_boundary.txt)
@@ -471,7 +519,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
     xform_row_half(a, 1);
   }
 #pragma unroll
-  for (int b = 0; b < 4; ++b) Y[0][b] = yform1(0, b);
+  for (int b = 0; b < 4; ++b)
+    if (!UP || b != 2) Y[0][b] = yform1(0, b);
   if (dbg && tid == 0) dbg[1] = HOLO_PROBE_CLOCK();
 
 #ifdef W3_TIMELINE
@@ -531,50 +580,57 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
       //      Group 28 opens with THE barrier of the stage: the last patch of this stage's buffer was read in group 27 and the
       //      last item of the next stage's buffer was written behind group 24, so from here on the other buffer is complete
       //      (group 31 reads the next stage's first patch from it) and this one is free for the next stage's producer.
+      //      The upsampling form (UP) runs the 27 live pseudo-taps: 18 groups = (xi_z, half) x xi_y over xi in {0, 1, 3}, of 12
+      //      MFMAs = four k-steps of the xi_x in {0, 1, 3}; three weight requests per group (k = 0, 4, 8; the dead 1 KB blocks of
+      //      the pack are skipped), the ring has six slots (18 groups: the slot of a group is the same in every stage).  Its
+      //      producer side is laid out over the shorter stage: halo requests of items 0,1 in groups 1-4, of items 2,3 (into the
+      //      registers of items 0,1) in groups 7-10, commits behind groups 6 / 8 / 12 / 14, the barrier opens group 16 (the last
+      //      patch of this buffer is read in group 14, group 17 reads the next stage's first patch).
       auto group = [&](auto gc) {  // straight-line code: accumulator sets, ring slots, slot work are compile-time choices
-        constexpr int g = decltype(gc)::value, st = g >> 2, xy = g & 3;
+        constexpr int g = decltype(gc)::value, sti = g / NL, xyi = g % NL;  // step and xi_y, counted over the live ones
+        constexpr int xz = w3_live<UP>(sti >> 1), half = sti & 1, xy = w3_live<UP>(xyi);
 #ifdef W3_TIMELINE
         const unsigned long long tA0 = clock64();
 #endif
-        if (g == 28) __syncthreads();
+        if (g == GBAR) __syncthreads();
 #ifdef W3_TIMELINE
         const unsigned long long tA = clock64();
-        if (g == 28) tl[5] += tA - tA0;
+        if (g == GBAR) tl[5] += tA - tA0;
 #endif
         auto slot = [&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-          mfma1(acc[(st >> 1) * 16 + xy * 4 + (k & 3)], Y[g & 1][k & 3], Bw[g & 3][k & 3], k >> 2, k == 0,
-                opens && (st & 1) == 0 && (k >> 2) == 0);
-          if ((k & 3) == 0 && !(W3_PROBE & 2)) {
-            const unsigned wsrc = g + W3_WDIST < 32 ? wp : wnext;
-            constexpr int wofs = (g + W3_WDIST < 32 ? g + W3_WDIST : g + W3_WDIST - 32) * W3_WSUB + (k >> 2) * 256;
+          constexpr int k = decltype(kc)::value, xx = w3_live<UP>(k % NL), e = k / NL;
+          mfma1(acc[xz * 16 + xy * 4 + xx], Y[g & 1][xx], Bw[g % NR][xx], e, k == 0, opens && half == 0 && e == 0);
+          if ((k & 3) == 0 && (k >> 2) < NL && !(W3_PROBE & 2)) {
+            constexpr int gn = g + W3_WDIST;
+            const unsigned wsrc = gn < NG ? wp : wnext;
+            constexpr int wofs = w3_wofs<UP>(gn < NG ? gn : gn - NG, k >> 2);
             if (W3_PROBE & 16)
               Bdummy[k >> 2] = w_ld(wsrc, wofs);
             else
-              Bw[(g + W3_WDIST) & 3][k >> 2] = w_ld(wsrc, wofs);
+              Bw[gn % NR][w3_live<UP>(k >> 2)] = w_ld(wsrc, wofs);
           }
-          if (xy == 3 && k < 8 && !(W3_PROBE & 4)) {
+          if (xyi == NL - 1 && k < 8 && !(W3_PROBE & 4)) {
             // the next step's patch: of this buffer, or (last step) the next stage's first patch from the other buffer
-            const float* pb = st < 7 ? buf : obuf;
-            constexpr int nstep = st < 7 ? st + 1 : 0;
-            const float* base = pb + a_off + ((nstep >> 1) * W3_PLANE + (k >> 1) * W3_HX) * W3_RS + (nstep & 1) * 16;
+            const float* pb = sti + 1 < 2 * NL ? buf : obuf;
+            constexpr int nsti = sti + 1 < 2 * NL ? sti + 1 : 0;
+            const float* base = pb + a_off + (w3_live<UP>(nsti >> 1) * W3_PLANE + (k >> 1) * W3_HX) * W3_RS + (nsti & 1) * 16;
             P[k >> 1][(2 * k) & 3] = w3_ld(base + ((2 * k) & 3) * W3_RS);
             P[k >> 1][(2 * k + 1) & 3] = w3_ld(base + ((2 * k + 1) & 3) * W3_RS);
           }
-          if (((g >= 1 && g <= 4) || (g >= 16 && g <= 19)) && (k == 2 || k == 10) && !(W3_PROBE & 1)) {
-            constexpr int hl = (g >= 16 ? g - 16 : g >= 1 ? g - 1 : 0) * 2 + (k == 10 ? 1 : 0);  // 0..7: (item of the pair, plane)
-            halo_load((g >= 16 ? 2 : 0) + (hl >> 2), hl & 3);
+          if (((g >= GH0 && g < GH0 + 4) || (g >= GH1 && g < GH1 + 4)) && (k == 2 || k == 10) && !(W3_PROBE & 1)) {
+            constexpr int hl = (g >= GH1 ? g - GH1 : g >= GH0 ? g - GH0 : 0) * 2 + (k == 10 ? 1 : 0);  // 0..7: (item of the pair, plane)
+            halo_load((g >= GH1 ? 2 : 0) + (hl >> 2), hl & 3);
           }
           __builtin_amdgcn_sched_barrier(0);  // requests stay behind THEIR MFMA
         };
-        w3_static_for(slot, std::make_integer_sequence<int, 16>{});
+        w3_static_for(slot, std::make_integer_sequence<int, NK>{});
 #ifdef W3_TIMELINE
         const unsigned long long tB = clock64();
         tl[0] += tB - tA;
 #endif
         // ---- the group's vector clump
         if (!(W3_PROBE & 4)) {
-          if (xy == 3) {
+          if (xyi == NL - 1) {
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
               xform_row_half(a, 0);
@@ -582,24 +638,25 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
             }
           }
 #pragma unroll
-          for (int b = 0; b < 4; ++b) Y[(g + 1) & 1][b] = yform1((xy + 1) & 3, b);
+          for (int b = 0; b < 4; ++b)
+            if (!UP || b != 2) Y[(g + 1) & 1][b] = yform1(w3_live<UP>((xyi + 1) % NL), b);
         }
         if (!(W3_PROBE & 1)) {
           if (g == 0) halo_setup(nxt, ncc_);
           if (!(W3_PROBE & 32)) {
-            if (g == 8) commit_item(0, obuf);
-            if (g == 12) commit_item(1, obuf);
-            if (g == 20) commit_item(2, obuf);
-            if (g == 24) commit_item(3, obuf);
+            if (g == GC0) commit_item(0, obuf);
+            if (g == GC1) commit_item(1, obuf);
+            if (g == GC2) commit_item(2, obuf);
+            if (g == GC3) commit_item(3, obuf);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
 #ifdef W3_TIMELINE
-        tl[g == 0 ? 4 : (g == 8 || g == 12 || g == 20 || g == 24) ? 3 : xy == 3 ? 2 : 1] += clock64() - tB;
+        tl[g == 0 ? 4 : (g == GC0 || g == GC1 || g == GC2 || g == GC3) ? 3 : xyi == NL - 1 ? 2 : 1] += clock64() - tB;
         if (g == 0) tl[6] += 1;
 #endif
       };
-      w3_static_for(group, std::make_integer_sequence<int, 32>{});
+      w3_static_for(group, std::make_integer_sequence<int, NG>{});
 #ifdef W3_TIMELINE
       if (dbg && tid == 0) dbg[6] += HOLO_PROBE_CLOCK() - t_stage;  // the stage's own work (barrier wait included)
 #endif
@@ -741,14 +798,10 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
           for (int xy = 0; xy < 4; ++xy) {
             const int s0 = (2 * zp) * 16 + xy * 4, s1 = s0 + 16;
             float a0, a1, a2, a3, b0, b1, b2, b3;
-            HOLO_ACC_READ(a0, acc[s0 + 0], r);
-            HOLO_ACC_READ(b0, acc[s1 + 0], r);
-            HOLO_ACC_READ(a1, acc[s0 + 1], r);
-            HOLO_ACC_READ(b1, acc[s1 + 1], r);
-            HOLO_ACC_READ(a2, acc[s0 + 2], r);
-            HOLO_ACC_READ(b2, acc[s1 + 2], r);
-            HOLO_ACC_READ(a3, acc[s0 + 3], r);
-            HOLO_ACC_READ(b3, acc[s1 + 3], r);
+            a0 = acc_read(s0 + 0, r), b0 = acc_read(s1 + 0, r);
+            a1 = acc_read(s0 + 1, r), b1 = acc_read(s1 + 1, r);
+            a2 = acc_read(s0 + 2, r), b2 = acc_read(s1 + 2, r);
+            a3 = acc_read(s0 + 3, r), b3 = acc_read(s1 + 3, r);
             const f32x2 m0 = f32x2{a0, b0}, m1 = f32x2{a1, b1}, m2 = f32x2{a2, b2}, m3 = f32x2{a3, b3};
             oy[xy][0] = pk_add(pk_add(m0, m1), m2);
             oy[xy][1] = pk_sub(pk_sub(m1, m2), m3);
@@ -828,6 +881,14 @@ __global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
   }
 #endif
 }
+
+// (ONE argument, by value, in every kernel of the body: W3_KARGS)
+template <bool SKIP, bool XF>
+__global__ __launch_bounds__(256, 1) void conv_wino3_kernel(ConvParams p) {
+  conv_wino3_body<SKIP, XF, false>(p);
+}
+// the upsampling form: nearest x2 input, raw, no fused skip (conv_plan sets ConvParams::wino3_up)
+__global__ __launch_bounds__(256, 1) void conv_wino3_up_kernel(ConvParams p) { conv_wino3_body<false, false, true>(p); }
 
 // OIDHW [Cout][Cin][27] -> the 64 pseudo-taps U = (G x G x G) g (float64, rounded once) in the wave's consumption order
 //   [chunk][slice][xi_z][half][xi_y][xi_x][lane = 16 kq + lj][e]:  output channel 16 slice + lj, input channel
@@ -909,7 +970,13 @@ int W3_ENTRY(const ConvParams& p, void* stream) {
     return -1;
   }
   const dim3 grid((unsigned)p.grid_x), block(256);
-  if (p.skip_w && p.coef) {
+  if (p.wino3_up) {
+    if (!p.ups || p.coef || p.skip_w) {
+      set_error("conv_wino3_launch: the upsampling form takes raw x2 input without a fused skip");
+      return -1;
+    }
+    HOLO_LAUNCH(conv_wino3_up_kernel, grid, block, stream, p);
+  } else if (p.skip_w && p.coef) {
     HOLO_LAUNCH((conv_wino3_kernel<true, true>), grid, block, stream, p);
   } else if (p.skip_w) {
     HOLO_LAUNCH((conv_wino3_kernel<true, false>), grid, block, stream, p);
