@@ -17,7 +17,8 @@ from .cameras import PerspectiveCameras, look_at_view_transform, get_simple_360_
 from .viewpool import ViewPooler, AngleWeightedReductionFeatureAggregator  # noqa: F401,E402
 from . import checkpoint, flyaround_output, generate, model, render, runtime, viewpool  # noqa: F401,E402
 from .checkpoint import load_experiment  # noqa: F401,E402
+from .optim import HoloAdam  # noqa: F401,E402
 
 __all__ = ["registry", "SimpleUnet3D", "Unet3DBase", "ImplicitronGaussianDiffusion", "HoloVoxelGridImplicitFunction",
            "HoloMultiPassEmissionAbsorptionRenderer", "HoloDiffusionModel", "RenderMLP", "EvaluationMode",
-           "PerspectiveCameras", "get_simple_360_camera_trajectory"]
+           "PerspectiveCameras", "get_simple_360_camera_trajectory", "HoloAdam"]

@@ -73,6 +73,16 @@ class HoloOpTiming(C.Structure):
                 ("flops", C.c_double), ("flops_executed", C.c_double)]
 
 
+class HoloAdamTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64)]
+
+
+class HoloAdamCfg(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("weight_decay", C.c_float), ("step", C.c_int32), ("adamw", C.c_int32)]
+
+
 _vp = C.c_void_p
 _i64p = C.POINTER(C.c_int64)
 
@@ -105,6 +115,11 @@ SIGNATURES = {
     "holo_unet_forward_train": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "holo_unet_backward_taped": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp]),
     "holo_unet_get_grad": (C.c_int, [_vp, C.c_char_p, _vp, C.c_int64, _vp, _vp]),
+    "holo_adam_step": (C.c_int, [_vp, C.POINTER(HoloAdamTensor), C.c_int, C.POINTER(HoloAdamCfg), _vp, _vp]),
+    "holo_adam_scalars": (C.c_int, [C.POINTER(HoloAdamCfg), C.POINTER(C.c_double)]),
+    "holo_grad_norm_workspace_bytes": (C.c_size_t, [C.POINTER(HoloAdamTensor), C.c_int]),
+    "holo_grad_norm": (C.c_int, [_vp, C.POINTER(HoloAdamTensor), C.c_int, C.c_float, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "holo_unet_adam_step": (C.c_int, [_vp, C.POINTER(HoloAdamTensor), C.c_int, C.POINTER(HoloAdamCfg), _vp, _vp]),
     "holo_ddpm_step": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "holo_ddpm_step_philox": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int,
                                         _vp, _vp, _vp, C.c_int, _vp]),

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/holo_abi.h"
 #include "conv_weights.h"
 #include "holo_knobs.h"
 
@@ -278,6 +279,43 @@ inline int upload_via_stage(float** stage, size_t* stage_floats, float* dst, con
   return e == hipSuccess ? 0 : (int)e;
 }
 int clip_launch(const float* x, float* y, float lo, float hi, int64_t n, void* stream);
+
+// ---------------------------------------------------------------------------------------------
+// Parameter update (kernels_optim.hip): multi-tensor Adam and the global gradient norm.  The tensor list travels by value in
+// the kernel arguments: a table of kAdamTensors descriptors and kAdamBlocks (tensor, chunk) entries per launch, a chunk =
+// kAdamChunk elements split over kAdamSplit workgroups.
+// ---------------------------------------------------------------------------------------------
+constexpr int kAdamTensors = 40;
+constexpr int kAdamBlocks = 320;
+constexpr int kAdamChunk = 65536;
+constexpr int kAdamSplit = 8;
+struct AdamTable {
+  float* param[kAdamTensors];
+  const float* grad[kAdamTensors];
+  float* exp_avg[kAdamTensors];
+  float* exp_avg_sq[kAdamTensors];
+  float* copy[kAdamTensors];  // optional second destination of the updated parameter
+  int64_t numel[kAdamTensors];
+  uint16_t chunk[kAdamBlocks];  // entry -> chunk of its tensor
+  uint8_t tensor[kAdamBlocks];  // entry -> slot in the arrays above
+};
+// the step's scalars, formed on the host in double like torch (adam_scalars, unet_exec.cpp) and rounded once
+struct AdamScalars {
+  float w1;             // 1 - beta1
+  float beta2, w2;      // beta2, 1 - beta2
+  float eps;
+  float neg_step_size;  // -lr / (1 - beta1^step)
+  float bc2_sqrt;       // sqrt(1 - beta2^step)
+  float weight_decay;
+  float decay;          // 1 - lr * weight_decay (adamw)
+  int32_t adamw;
+};
+// copies: n optional second destinations (or null).  Stream-ordered, no allocation, no synchronisation.
+int adam_step_launch(const HoloAdamTensor* t, float* const* copies, int n, const AdamScalars& s, const float* clip_coef,
+                     void* stream);
+int64_t grad_norm_partials(const HoloAdamTensor* t, int n);  // doubles of workspace grad_norm_launch needs
+int grad_norm_launch(const HoloAdamTensor* t, int n, float max_norm, double* partial, float* total_norm, float* clip_coef,
+                     void* stream);
 
 int repack_conv_weight_bf16_launch(const float* w, uint16_t* out, int Cout, int Cin, int taps, int CoutP, int CinP,
                                    void* stream);

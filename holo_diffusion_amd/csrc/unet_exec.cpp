@@ -270,6 +270,7 @@ struct HoloUnet {
   // ([Cin][Cout] flipped taps for the stride-1 convs; [tap][Cout][Cin] for the stride-2 Downsample convs, whose stride-1
   // form lives under "<name>#s1"), supplied by holo_unet_set_dgrad_weight; this table owns every buffer it points to
   std::map<std::string, ConvWeights> dgrad;
+  std::vector<float*> adam_copies;  // holo_unet_adam_step: per parameter, its plain private copy (null for a conv weight)
   float* dgrad_tmp = nullptr;  // the flipped / transposed OIDHW weight on its way into the packs: the largest conv weight's numel
   TrainPlan tplan;
   const int64_t* t_dev = nullptr;  // timesteps of the running call (time_embed backward)
@@ -1984,19 +1985,11 @@ int holo_unet_time_ops(HoloUnet* net, int batch, const float* x, const int64_t* 
 }
 
 // ---- training: backward of the denoiser -----------------------------------------------------------------------------
-int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_ptr, void* stream) {
-  if (!net || !name || !dev_ptr) {
-    set_error("holo_unet_set_dgrad_weight: null argument");
-    return HOLO_E_INVALID;
-  }
-  auto it = net->pindex.find(name);
-  if (it == net->pindex.end() || !net->params[it->second].is_conv()) {
-    set_error("holo_unet_set_dgrad_weight: '%s' is not a convolution weight", name);
-    return HOLO_E_INVALID;
-  }
-  const ParamSlot& s = net->params[it->second];
+// The transposed-convolution copies of convolution weight `s` from the caller's OIDHW tensor: holo_unet_set_dgrad_weight, and
+// the refresh of holo_unet_adam_step (which meets every buffer already allocated).
+static int prepare_dgrad_weight(HoloUnet* net, const ParamSlot& s, const void* dev_ptr, void* stream) {
   const int Co = (int)s.shape[0], Ci = (int)s.shape[1], T = s.kind == P_CONV3 ? 27 : 1;
-  const std::string nm(name);
+  const std::string& nm = s.name;
   const bool down = is_downsample_weight(nm);
   if (down) {  // [tap][co][ci] for conv_dgrad_s2_kernel (the fallback), then the stride-1 form below under "<name>#s1":
                // the transposed stride-2 convolution runs as zero insertion + the stride-1 transposed convolution
@@ -2027,6 +2020,19 @@ int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_
   if (flip_transpose_weight_launch((const float*)dev_ptr, net->dgrad_tmp, Co, Ci, T, stream)) return HOLO_E_INVALID;
   if (pack_conv_weights(net->dgrad_tmp, dw, stream)) return HOLO_E_INVALID;
   return 0;
+}
+
+int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_ptr, void* stream) {
+  if (!net || !name || !dev_ptr) {
+    set_error("holo_unet_set_dgrad_weight: null argument");
+    return HOLO_E_INVALID;
+  }
+  auto it = net->pindex.find(name);
+  if (it == net->pindex.end() || !net->params[it->second].is_conv()) {
+    set_error("holo_unet_set_dgrad_weight: '%s' is not a convolution weight", name);
+    return HOLO_E_INVALID;
+  }
+  return prepare_dgrad_weight(net, net->params[it->second], dev_ptr, stream);
 }
 
 size_t holo_unet_backward_workspace_bytes(HoloUnet* net, int batch) {
@@ -2106,6 +2112,128 @@ int holo_unet_get_grad(HoloUnet* net, const char* name, float* dst, int64_t nume
   }
   HIP_TRY(hipMemcpyAsync(dst, (const char*)workspace + net->tplan.grad_off[it->second], (size_t)numel * sizeof(float),
                          hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+// ---- parameter update (kernels_optim.hip) ----------------------------------------------------------------------------
+// A float of the configuration as the double the caller wrote: the shortest decimal that rounds to it (0.9f -> 0.9).  torch
+// forms 1 - beta2 and the bias corrections from the DOUBLE hyper-parameters; (double)0.999f would put 1.3e-5 of relative
+// error into 1 - beta2.
+static double widen_decimal(float f) {
+  char buf[40];
+  for (int prec = 1; prec <= 9; ++prec) {
+    snprintf(buf, sizeof(buf), "%.*g", prec, (double)f);
+    if (strtof(buf, nullptr) == f) break;
+  }
+  return strtod(buf, nullptr);
+}
+
+static int adam_scalars(const char* who, const HoloAdamCfg* cfg, AdamScalars* s, double* dbg) {
+  if (cfg->step < 1 || !(cfg->lr >= 0.f) || !(cfg->beta1 >= 0.f && cfg->beta1 < 1.f) || !(cfg->beta2 >= 0.f && cfg->beta2 < 1.f) ||
+      !(cfg->eps >= 0.f) || !(cfg->weight_decay >= 0.f)) {
+    set_error("%s: step >= 1, lr >= 0, betas in [0, 1), eps >= 0 and weight_decay >= 0 are required", who);
+    return HOLO_E_INVALID;
+  }
+  const double lr = widen_decimal(cfg->lr), b1 = widen_decimal(cfg->beta1), b2 = widen_decimal(cfg->beta2);
+  const double wd = widen_decimal(cfg->weight_decay);
+  const double bc1 = 1.0 - pow(b1, (double)cfg->step), bc2 = 1.0 - pow(b2, (double)cfg->step);
+  const double step_size = lr / bc1, bc2_sqrt = sqrt(bc2);
+  if (s) {
+    s->w1 = (float)(1.0 - b1);
+    s->beta2 = (float)b2;
+    s->w2 = (float)(1.0 - b2);
+    s->eps = cfg->eps;
+    s->neg_step_size = (float)-step_size;
+    s->bc2_sqrt = (float)bc2_sqrt;
+    s->weight_decay = (float)wd;
+    s->decay = (float)(1.0 - lr * wd);
+    s->adamw = cfg->adamw != 0;
+  }
+  if (dbg) {
+    const double v[6] = {bc1, bc2, step_size, bc2_sqrt, 1.0 - b1, 1.0 - b2};
+    memcpy(dbg, v, sizeof(v));
+  }
+  return 0;
+}
+
+int holo_adam_scalars(const HoloAdamCfg* cfg, double* out) {
+  if (!cfg || !out) {
+    set_error("holo_adam_scalars: null argument");
+    return HOLO_E_INVALID;
+  }
+  return adam_scalars("holo_adam_scalars", cfg, nullptr, out);
+}
+
+int holo_adam_step(HoloCtx* ctx, const HoloAdamTensor* tensors, int n, const HoloAdamCfg* cfg, const float* clip_coef_dev,
+                   void* stream) {
+  if (!tensors || !cfg || n < 0) {
+    set_error("holo_adam_step: null/invalid argument");
+    return HOLO_E_INVALID;
+  }
+  (void)ctx;
+  AdamScalars s;
+  if (const int rc = adam_scalars("holo_adam_step", cfg, &s, nullptr)) return rc;
+  return adam_step_launch(tensors, nullptr, n, s, clip_coef_dev, stream) ? HOLO_E_INVALID : 0;
+}
+
+size_t holo_grad_norm_workspace_bytes(const HoloAdamTensor* tensors, int n) {
+  if (!tensors || n < 0) return 0;
+  return (size_t)grad_norm_partials(tensors, n) * sizeof(double);
+}
+
+int holo_grad_norm(HoloCtx* ctx, const HoloAdamTensor* tensors, int n, float max_norm, void* workspace, size_t ws_bytes,
+                   float* total_norm_dev, float* clip_coef_dev, void* stream) {
+  if (!tensors || n < 0 || !total_norm_dev || !clip_coef_dev) {
+    set_error("holo_grad_norm: null/invalid argument");
+    return HOLO_E_INVALID;
+  }
+  (void)ctx;
+  const size_t need = holo_grad_norm_workspace_bytes(tensors, n);
+  if (need && (!workspace || ws_bytes < need || ((uintptr_t)workspace & 7))) {
+    set_error("holo_grad_norm: workspace of %zu bytes (8-byte aligned) needed, got %zu", need, ws_bytes);
+    return HOLO_E_WORKSPACE;
+  }
+  return grad_norm_launch(tensors, n, max_norm, (double*)workspace, total_norm_dev, clip_coef_dev, stream) ? HOLO_E_INVALID : 0;
+}
+
+int holo_unet_adam_step(HoloUnet* net, const HoloAdamTensor* tensors, int n, const HoloAdamCfg* cfg, const float* clip_coef_dev,
+                        void* stream) {
+  if (!net || !tensors || !cfg) {
+    set_error("holo_unet_adam_step: null argument");
+    return HOLO_E_INVALID;
+  }
+  if (n != (int)net->params.size()) {
+    set_error("holo_unet_adam_step: %d tensors for %d parameters (holo_unet_param_info order)", n, (int)net->params.size());
+    return HOLO_E_INVALID;
+  }
+  AdamScalars sc;
+  if (const int rc = adam_scalars("holo_unet_adam_step", cfg, &sc, nullptr)) return rc;
+  for (int i = 0; i < n; ++i) {
+    const ParamSlot& s = net->params[i];
+    if (!s.set) {
+      set_error("holo_unet_adam_step: parameter '%s' was never bound (holo_unet_set_param)", s.name.c_str());
+      return HOLO_E_STATE;
+    }
+    if (tensors[i].numel != s.numel || !tensors[i].param) {
+      set_error("holo_unet_adam_step: tensor %d must be '%s' with %lld elements", i, s.name.c_str(), (long long)s.numel);
+      return HOLO_E_INVALID;
+    }
+  }
+  // (a) the update; a parameter the library keeps as a plain copy is written there by the same kernel
+  if (net->adam_copies.size() != net->params.size()) {
+    net->adam_copies.clear();
+    for (const ParamSlot& s : net->params) net->adam_copies.push_back(s.is_conv() ? nullptr : s.w.f32);
+  }
+  net->tape_valid = false;  // (d) the taped activations belong to the old weights
+  if (adam_step_launch(tensors, net->adam_copies.data(), n, sc, clip_coef_dev, stream)) return HOLO_E_INVALID;
+  for (int i = 0; i < n; ++i) {
+    const ParamSlot& s = net->params[i];
+    if (!s.is_conv()) continue;
+    // (b) the forward packs, (c) the transposed-convolution packs that exist (a Downsample weight: "<name>" and "<name>#s1")
+    if (const int rc = pack_conv_weights(tensors[i].param, s.w, stream)) return rc;
+    if (net->dgrad.count(s.name) || net->dgrad.count(s.name + "#s1"))
+      if (const int rc = prepare_dgrad_weight(net, s, tensors[i].param, stream)) return rc;
+  }
   return 0;
 }
 

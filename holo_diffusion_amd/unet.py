@@ -99,6 +99,7 @@ class SimpleUnet3D(Unet3DBase):
         self._handle: Optional[C.c_void_p] = None
         self._handle_device: Optional[torch.device] = None
         self._dirty = True
+        self.rebinds = 0  # times the library's private copies were re-made from the torch tensors (forward or dgrad set)
         self._param_names = []
         self._create_parameters()
 
@@ -159,6 +160,21 @@ class SimpleUnet3D(Unet3DBase):
         writes that bypass the version counter (``p.data`` views, raw pointers)."""
         self._mark_dirty()
 
+    def _adopt_native_update(self) -> None:
+        """After ``holo_unet_adam_step`` (``optim.HoloAdam``): the library updated the parameter tensors AND re-made its packed
+        copies from them - forward packs, and the transposed-convolution packs if they had been prepared - in stream order,
+        and the caller has bumped the tensors' version counters.  The new fingerprints are recorded as what the copies were
+        made from, so the next forward does not re-bind; ``_weights_epoch`` advances (caches of this net's outputs are
+        stale) and a tape of the old weights is dropped, as after any parameter update."""
+        sd = dict(self._net.named_parameters())
+        self.__dict__["_param_versions"] = tuple((sd[k].data_ptr(), sd[k]._version) for k in self._param_names)
+        if "_dgrad_key" in self.__dict__:
+            key = tuple((k, p.data_ptr(), p._version) for k, p in sd.items() if p.dim() >= 3)
+            self.__dict__["_dgrad_key"] = (self.__dict__.get("_handle_generation", 0), key)
+        self._weights_epoch = getattr(self, "_weights_epoch", 0) + 1
+        self._dirty = False
+        self.__dict__.pop("_holo_tape", None)
+
     # ---- native handle --------------------------------------------------------------------
     def _ensure_handle(self, device: torch.device, size: Optional[int] = None) -> C.c_void_p:
         """The native handle for inputs of ``size``^3 (default: ``image_size``).  The reference's UNetModel is fully
@@ -211,6 +227,7 @@ class SimpleUnet3D(Unet3DBase):
             # re-packing the forward weights under a live tape would pair new weights with the old taped activations (and
             # stale dgrad weights) in backward_taped: the tape is dropped, the autograd node then re-runs its forward
             self.__dict__.pop("_holo_tape", None)
+            self.rebinds += 1
             st = runtime.stream_ptr(device)
             for k in self._param_names:
                 p = sd[k]
@@ -316,6 +333,7 @@ class SimpleUnet3D(Unet3DBase):
         if self.__dict__.get("_dgrad_key") == (gen, key):
             return
         L = runtime.lib()
+        self.rebinds += 1
         st = runtime.stream_ptr(device)
         keep = []
         for k, p in self._net.named_parameters():

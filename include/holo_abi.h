@@ -174,6 +174,55 @@ int holo_unet_backward_taped(HoloUnet* net, int batch, const float* grad_out, fl
 int holo_unet_get_grad(HoloUnet* net, const char* name, float* dst, int64_t numel, const void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Parameter update.  Replaces torch.optim.Adam(foreach=True).step() and torch.nn.utils.clip_grad_norm_ of the reference's
+ * training loop (trainer/optimizer_factory.py:78-149, trainer/training_loop.py:544-556, configs/apple.yaml:254-285).
+ * Arithmetic of torch/optim/adam.py::_single_tensor_adam (non-capturable path), fp32, one rounding per operation:
+ *   g *= clip_coef;  L2 decay: g += wd * p   (adamw != 0: p *= 1 - lr * wd instead)
+ *   m = lerp(m, g, 1 - beta1);  v = v * beta2 + (1 - beta2) * g * g
+ *   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),   bc1 = 1 - beta1^step, bc2 = 1 - beta2^step
+ * The scalars are formed on the host in double, like torch, and rounded to float once.  The configuration carries floats:
+ * each is widened to the double of its shortest decimal form (0.9f -> 0.9, 0.999f -> 0.999), which is the double the caller
+ * wrote; holo_adam_scalars returns what a step would use.
+ * One kernel launch updates many tensors (descriptors by value in the kernel arguments; as many launches as the list
+ * needs): stream-ordered, no allocation, no synchronisation.  Optimiser state (exp_avg, exp_avg_sq) is the caller's.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t numel;
+} HoloAdamTensor;
+typedef struct {
+  float lr, beta1, beta2, eps, weight_decay;
+  int32_t step;  /* 1-based: the count AFTER this step */
+  int32_t adamw; /* != 0: decoupled weight decay */
+} HoloAdamCfg;
+
+/* tensors: HOST array of n descriptors of contiguous fp32 device tensors.  clip_coef_dev: device scalar that scales every
+ * gradient (holo_grad_norm's output), or NULL (= 1). */
+int holo_adam_step(HoloCtx* ctx, const HoloAdamTensor* tensors, int n, const HoloAdamCfg* cfg, const float* clip_coef_dev,
+                   void* stream);
+/* out[6] = {bc1, bc2, lr / bc1, sqrt(bc2), 1 - beta1, 1 - beta2}: the doubles a step with `cfg` rounds to float. */
+int holo_adam_scalars(const HoloAdamCfg* cfg, double* out);
+
+/* Global L2 norm of the `grad` entries of the list (the other pointers are not read) and the clip coefficient of
+ * clip_grad_norm_: *total_norm_dev = ||g||_2, *clip_coef_dev = min(1, max_norm / (total_norm + 1e-6)) (1 when max_norm <= 0).
+ * Per-workgroup partial sums in double into `workspace`, added in a fixed order: no atomics, bit-identical from run to run. */
+size_t holo_grad_norm_workspace_bytes(const HoloAdamTensor* tensors, int n);
+int holo_grad_norm(HoloCtx* ctx, const HoloAdamTensor* tensors, int n, float max_norm, void* workspace, size_t ws_bytes,
+                   float* total_norm_dev, float* clip_coef_dev, void* stream);
+
+/* The Adam step of a denoiser, ending with the library's private copies CURRENT: tensors[i] belongs to parameter i of
+ * holo_unet_param_info (n == holo_unet_num_params; `param` is the caller's tensor that holo_unet_set_param bound).  In stream
+ * order: the Adam launches (a parameter that is not a convolution weight is written to its private copy by the same
+ * kernel), the forward packs of every convolution weight, the transposed-convolution packs of every weight
+ * holo_unet_set_dgrad_weight has prepared before; the tape of a holo_unet_forward_train is dropped.  No holo_unet_set_param /
+ * holo_unet_set_dgrad_weight is needed afterwards.  HOLO_E_STATE if a parameter was never bound. */
+int holo_unet_adam_step(HoloUnet* net, const HoloAdamTensor* tensors, int n, const HoloAdamCfg* cfg,
+                        const float* clip_coef_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * DDPM ancestral step.  Replaces the elementwise tail of GaussianDiffusion.p_sample:
  *   gaussian_diffusion.py:314-343 (clamp, START_X), :237-240 (posterior mean), :499-506 (noise add)
  *   tables   : (T, 4) fp32 on the device: {posterior_mean_coef1, posterior_mean_coef2,
