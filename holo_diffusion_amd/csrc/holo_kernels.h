@@ -256,6 +256,10 @@ int ddpm_step_philox_rows_launch(const float* tables, int T, const int64_t* time
 int ddim_step_philox_rows_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
                                  uint64_t seed, const uint32_t* row_streams, uint32_t timestep_index, int clip,
                                  float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
+// DPM-Solver++ multistep step: coefs is (batch, 8) fp32, rows {a, b0, b1, b2, 0...}; hist1 / hist2 may be null
+// (include/holo_abi.h, holo_dpm_step)
+int dpm_step_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
+                    const float* hist1, const float* hist2, int clip, float* sample, float* pred_xstart, void* stream);
 int tanh_launch(const float* x, float* y, int64_t n, void* stream);
 // dst = src for a SMALL caller-provided tensor, read with system-scope loads (holo_ld_sys, holo_common.h)
 int copy_sys_launch(const float* src, float* dst, int64_t n, void* stream);

@@ -8,6 +8,7 @@
 //   rows_linear all ResBlock emb_layers Linear(SiLU(emb)) at once (unet.py:199-205,245)
 //   ddpm_step  clamp + posterior mean + noise (gaussian_diffusion.py:314-343,237-240,499-506)
 //   ddim_step  clamp + DDIM update (Equation 12) + noise, and its reverse (gaussian_diffusion.py:645-727)
+//   dpm_step   clamp + DPM-Solver++ multistep update from the two previous predictions (build-side extension)
 #include <stdlib.h>
 
 #include "holo_common.h"
@@ -621,6 +622,42 @@ __global__ __launch_bounds__(256) void ddim_step_philox_kernel(const float* __re
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// DPM-Solver++ multistep update (Lu et al. 2022, data prediction), float4 per thread, grid = (blocks over per/4, batch).
+// The host expands the order-1/2/3 update into one row per sample, coefs[b*8 + 0..3] = (a, b0, b1, b2), formed in float64
+// and rounded once (ImplicitronGaussianDiffusion.dpm_coefs); hist1 / hist2 are the clipped predictions of the two steps
+// before this one.  Per element, each product and each sum rounded, in this order (no fma contraction):
+//   pred = clip ? clamp(model_out, -1, 1) : model_out ;  sample = ((a*x + b0*pred) + b1*hist1) + b2*hist2
+// A null history pointer drops its term: it is neither read nor added.  No noise, so the kernel is layout-agnostic.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float4 dpm_lin4(float4 x, float4 m, float a, float b0) {
+#pragma clang fp contract(off)
+  return make_float4(a * x.x + b0 * m.x, a * x.y + b0 * m.y, a * x.z + b0 * m.z, a * x.w + b0 * m.w);
+}
+
+__global__ __launch_bounds__(256) void dpm_step_kernel(const float* __restrict__ coefs, int64_t per,
+                                                       const float* __restrict__ x_t,
+                                                       const float* __restrict__ model_out,
+                                                       const float* __restrict__ hist1,
+                                                       const float* __restrict__ hist2, int clip,
+                                                       float* __restrict__ sample, float* __restrict__ pred) {
+  const int b = blockIdx.y;
+  float c[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) c[k] = holo_ld_sys(coefs + b * 8 + k);  // (a small table uploaded from the host: see holo_ld_sys)
+  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= per) return;
+  const int64_t o = (int64_t)b * per + i;
+  const float4 x = *reinterpret_cast<const float4*>(x_t + o);
+  float4 m = *reinterpret_cast<const float4*>(model_out + o);
+  if (clip) m = clamp4(m);
+  float4 s = dpm_lin4(x, m, c[0], c[1]);
+  if (hist1) s = add_noise4(s, c[2], *reinterpret_cast<const float4*>(hist1 + o));  // (s + c*h, each operation rounded)
+  if (hist2) s = add_noise4(s, c[3], *reinterpret_cast<const float4*>(hist2 + o));
+  *reinterpret_cast<float4*>(sample + o) = s;
+  if (pred) *reinterpret_cast<float4*>(pred + o) = m;
+}
+
 // copy of a SMALL caller-provided tensor (biases, GroupNorm affine parameters, ...) with system-scope loads (holo_ld_sys)
 __global__ __launch_bounds__(256) void copy_sys_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -923,6 +960,18 @@ int ddim_step_philox_rows_launch(const float* coefs, int batch, int64_t per, con
   else
     HOLO_LAUNCH((ddim_step_philox_kernel<false, true>), grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
                 timestep_index, clip, sample, pred_xstart, noise_out, 0, row_streams);
+  return 0;
+}
+
+int dpm_step_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
+                    const float* hist1, const float* hist2, int clip, float* sample, float* pred_xstart, void* stream) {
+  if (per & 3) {
+    set_error("dpm_step: elems_per_sample must be a multiple of 4");
+    return -1;
+  }
+  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
+  HOLO_LAUNCH(dpm_step_kernel, grid, dim3(256), stream, coefs, per, x_t, model_out, hist1, hist2, clip, sample,
+              pred_xstart);
   return 0;
 }
 

@@ -2321,6 +2321,20 @@ int holo_ddim_step_philox_rows(HoloCtx* ctx, const float* coefs, int batch, int6
   return rc ? HOLO_E_INVALID : 0;
 }
 
+// DPM-Solver++ multistep update (the elementwise tail of ImplicitronGaussianDiffusion.dpm_sample_loop*)
+int holo_dpm_step(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                  const float* model_out, const float* hist1, const float* hist2, int clip_denoised, float* sample,
+                  float* pred_xstart, void* stream) {
+  if (!coefs || !x_t || !model_out || !sample || batch < 1 || elems_per_sample < 4) {
+    set_error("holo_dpm_step: null/invalid argument");
+    return HOLO_E_INVALID;
+  }
+  (void)ctx;
+  int rc = dpm_step_launch(coefs, batch, elems_per_sample, x_t, model_out, hist1, hist2, clip_denoised, sample,
+                           pred_xstart, stream);
+  return rc ? HOLO_E_INVALID : 0;
+}
+
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream) {
   (void)ctx;
   return tanh_launch(x, y, n, stream);

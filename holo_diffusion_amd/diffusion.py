@@ -16,6 +16,11 @@ DDIM (``ddim_sample``, ``ddim_reverse_sample``, ``ddim_sample_loop*``; gaussian_
 fused kernel (``holo_ddim_step``) that reads one float32 coefficient row per sample, built on the host in the reference's
 order; a chain's rows are uploaded once.  Build-side extensions: strided "ddimS" schedules (``ddim_steps``), explicit
 ``timesteps`` and ``ddim_reverse_sample_loop`` (inversion x_0 -> x_T).
+
+DPM-Solver++ (``dpm_schedule``, ``dpm_coefs``, ``dpm_sample_loop*``; build-side extension, no reference counterpart) is the
+multistep exponential integrator in log-SNR on the clipped x_0 prediction, orders 1-3, one model call per step.  Each step's
+update is expanded on the host, in float64, into four scalars per sample; a third fused kernel (``holo_dpm_step``) applies
+them to x_t, the model output and the previous two predictions.
 """
 from __future__ import annotations
 
@@ -58,6 +63,9 @@ def ddim_timesteps(num_timesteps: int, ddim_steps: int) -> List[int]:
         if len(range(0, num_timesteps, k)) == S:
             return list(range(0, num_timesteps, k))[::-1]
     raise ValueError(f"cannot create exactly {S} DDIM steps out of {num_timesteps} timesteps with an integer stride")
+
+
+DPM_DEFAULT_STEPS = 20  # ``steps=None`` of the DPM-Solver++ schedule and loops
 
 
 class UniformSampler:
@@ -587,6 +595,170 @@ class ImplicitronGaussianDiffusion(Configurable):
                 model_output = self._model_output(model, img, ts_all[k], denoised_fn, model_kwargs)
                 img, _ = self._ddim_step(img, model_output, coefs_all[k], None, clip_denoised, want_pred=False)
         return img
+
+    # ---- DPM-Solver++ multistep (build-side extension; Lu et al. 2022, arXiv:2211.01095, Algorithm 2 and its order-3 form) ----
+    def log_snr(self) -> np.ndarray:
+        """lambda_t = log(alpha_t / sigma_t), alpha = sqrt(abar), sigma = sqrt(1 - abar): float64, decreasing in t."""
+        return np.log(self.sqrt_alphas_cumprod / self.sqrt_one_minus_alphas_cumprod)
+
+    def dpm_schedule(self, steps: Optional[int] = None, spacing: str = "logsnr",
+                     timesteps: Optional[Sequence[int]] = None) -> List[int]:
+        """The timesteps a DPM-Solver++ loop visits, descending.  ``steps`` (None: 20) with ``spacing``:
+          "logsnr"  for each of ``linspace(lambda_{T-1}, lambda_0, steps)`` the timestep of the nearest log-SNR (ties: the
+                    smaller t), duplicates removed - so the list may be SHORTER than ``steps`` where the table's timesteps are
+                    coarser than the targets (T = 1000: 20 -> 20, 50 -> 49, 100 -> 94).  More than one step: from T-1 to 0
+          "time"    ``ddim_schedule(steps)``, the "ddimS" stride
+        or an explicit strictly decreasing list (``timesteps``, validated as in ``ddim_schedule``)."""
+        if timesteps is not None:
+            if steps is not None:
+                raise ValueError("give steps or timesteps, not both")
+            return self.ddim_schedule(timesteps=timesteps)
+        steps = DPM_DEFAULT_STEPS if steps is None else int(steps)
+        if steps < 1:
+            raise ValueError(f"dpm_schedule: steps must be >= 1, got {steps}")
+        if spacing == "time":
+            return self.ddim_schedule(steps)
+        if spacing != "logsnr":
+            raise ValueError(f"dpm_schedule: spacing must be 'logsnr' or 'time', not {spacing!r}")
+        lam = self.log_snr()
+        out: List[int] = []
+        for target in np.linspace(lam[-1], lam[0], steps):
+            t = int(np.argmin(np.abs(lam - target)))  # (the first minimum: ties go to the smaller t)
+            if not out or t < out[-1]:
+                out.append(t)
+        return out
+
+    def dpm_coefs(self, indices: Sequence[int], order: int = 2, lower_order_final: bool = True):
+        """The chain over ``indices`` (descending timesteps; the last step goes past the end, abar = 1) as the rows of
+        holo_dpm_step (include/holo_abi.h): ((steps, 8) float32 rows {a, b0, b1, b2, 0, 0, 0, 0}, [effective order per step]).
+        Step k (s = indices[k] -> t = indices[k + 1], h = lambda_t - lambda_s) is the multistep DPM-Solver++ update of order
+        min(order, k + 1) on the predictions m0, m1, m2 at s and the two timesteps before it, expanded into
+        x_t = a*x + b0*m0 + b1*m1 + b2*m2 in float64 and rounded once.  The step past the end is (0, 1, 0, 0): the sample is
+        the prediction.  ``lower_order_final``: that last step counts as the order-1 one, and with order 3 the step before it
+        is at most order 2 (the high-order extrapolation is unstable over the large final log-SNR steps)."""
+        order = int(order)
+        if order not in (1, 2, 3):
+            raise ValueError(f"dpm_coefs: order must be 1, 2 or 3, got {order}")
+        idx = self.ddim_schedule(timesteps=indices)
+        n = len(idx)
+        alpha, sigma, lam = self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, self.log_snr()
+        rows = np.zeros((n, 8), dtype=np.float64)
+        orders: List[int] = []
+        for k, s in enumerate(idx):
+            if k == n - 1:  # t = -1: sigma_t = 0, alpha_t = 1, h = inf
+                rows[k, 1] = 1.0
+                orders.append(1)
+                continue
+            t = idx[k + 1]
+            eff = min(order, k + 1)
+            if lower_order_final and order == 3 and k == n - 2:  # (the only step the flag changes: the last is order 1 anyway)
+                eff = min(eff, 2)
+            h = lam[t] - lam[s]
+            phi1 = np.expm1(-h)
+            a, b0, b1, b2 = sigma[t] / sigma[s], -alpha[t] * phi1, 0.0, 0.0
+            if eff == 2:
+                r0 = (lam[s] - lam[idx[k - 1]]) / h
+                d = -0.5 * alpha[t] * phi1 / r0  # the weight of m0 - m1
+                b0, b1 = b0 + d, -d
+            elif eff == 3:
+                r0, r1 = (lam[s] - lam[idx[k - 1]]) / h, (lam[idx[k - 1]] - lam[idx[k - 2]]) / h
+                phi2 = phi1 / h + 1.0
+                phi3 = phi2 / h - 0.5
+                c = r0 / (r0 + r1)
+                p = alpha[t] * (phi2 * (1.0 + c) - phi3 / (r0 + r1)) / r0  # the weight of m0 - m1
+                q = alpha[t] * (phi3 / (r0 + r1) - phi2 * c) / r1          # the weight of m1 - m2
+                b0, b1, b2 = b0 + p, q - p, -q
+            rows[k, :4] = (a, b0, b1, b2)
+            orders.append(eff)
+        return torch.from_numpy(rows.astype(np.float32)), orders
+
+    def _dpm_step(self, x, model_output, coefs_dev, hist1, hist2, clip_denoised, want_pred=True):
+        """holo_dpm_step: (sample, pred_xstart | None).  ``coefs_dev`` is the (batch, 8) row block on the device; ``hist1`` /
+        ``hist2`` (the previous two steps' pred_xstart) may be None: the term is dropped."""
+        runtime.require_device(x, "ImplicitronGaussianDiffusion")
+        L = runtime.lib()
+        dev = x.device
+        x = x.contiguous()
+        model_output = model_output.contiguous()
+        hist1 = hist1.contiguous() if hist1 is not None else None
+        hist2 = hist2.contiguous() if hist2 is not None else None
+        sample = torch.empty_like(x)
+        pred = torch.empty_like(x) if want_pred else None
+        _lib.check(L, L.holo_dpm_step(runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x),
+                                      runtime.ptr(model_output), runtime.ptr(hist1) if hist1 is not None else None,
+                                      runtime.ptr(hist2) if hist2 is not None else None, 1 if clip_denoised else 0,
+                                      runtime.ptr(sample), runtime.ptr(pred) if want_pred else None,
+                                      runtime.stream_ptr(dev)), "holo_dpm_step")
+        return sample, pred
+
+    def dpm_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                                    device=None, progress=False, steps=None, order=2, spacing="logsnr", timesteps=None,
+                                    lower_order_final=True, noise_sampler=None, cond_fn=None,
+                                    _materialize_every_step: bool = True) -> Iterator[dict]:
+        """DPM-Solver++ multistep sampling over ``dpm_schedule(steps, spacing, timesteps)`` (``steps`` None: 20): one model call
+        per step, like DDIM, on ``holo_dpm_step``.  Deterministic: ``noise_sampler`` is asked for x_T only (when ``noise`` is
+        None), no step draws anything, and ``device_noise_seed`` plays no part.  The chain's rows and timesteps are uploaded
+        once; a step reads the one or two previous predictions the order needs.  With a ``forward_channels_last`` model the
+        chain stays channels-last (the step kernel is elementwise) under the DDIM loop's conditions minus the noise ones."""
+        if cond_fn is not None:
+            raise NotImplementedError("cond_fn guidance is not supported")
+        indices = self.dpm_schedule(steps, spacing, timesteps)
+        rows, orders = self.dpm_coefs(indices, order, lower_order_final)
+        if device is None:
+            device = next(model.parameters()).device
+        assert isinstance(shape, (tuple, list))
+        if model_kwargs is None:
+            model_kwargs = {}
+        if noise is not None:
+            img = noise
+        elif noise_sampler is not None:
+            img = noise_sampler(self.num_timesteps, shape, device)
+        else:
+            img = torch.randn(*shape, device=device)
+        B = shape[0]
+        # the chain's timesteps and coefficient rows are uploaded once: no per-step host->device traffic
+        coefs_all = rows[:, None, :].expand(-1, B, -1).contiguous().to(device)  # (steps, B, 8)
+        ts_all = torch.tensor(indices, dtype=torch.int64, device=device)[:, None].expand(-1, B).contiguous()
+        it = range(len(indices))
+        if progress:
+            try:
+                from tqdm.auto import tqdm
+                it = tqdm(it)
+            except Exception:
+                pass
+        use_cl = (denoised_fn is None and not model_kwargs and hasattr(model, "forward_channels_last")
+                  and getattr(model, "in_channels", None) == shape[1] and img.is_cuda)
+        as_out = lambda a: a  # noqa: E731
+        if use_cl:
+            as_out = (lambda a: a.permute(0, 4, 1, 2, 3).contiguous()) if _materialize_every_step else \
+                (lambda a: a.permute(0, 4, 1, 2, 3))
+            img = img.float().permute(0, 2, 3, 4, 1).contiguous()
+        hist1 = hist2 = None  # the predictions of the previous two steps, in the chain's layout
+        with torch.no_grad():
+            for k in it:
+                if use_cl:
+                    model_output = model.forward_channels_last(img, ts_all[k])
+                else:
+                    model_output = self._model_output(model, img, ts_all[k], denoised_fn, model_kwargs)
+                sample, pred = self._dpm_step(img, model_output, coefs_all[k], hist1 if orders[k] >= 2 else None,
+                                              hist2 if orders[k] >= 3 else None, clip_denoised)
+                yield {"sample": as_out(sample), "pred_xstart": as_out(pred)}
+                img, hist1, hist2 = sample, pred, hist1
+
+    def dpm_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None, device=None,
+                        progress=False, steps=None, order=2, spacing="logsnr", timesteps=None, lower_order_final=True,
+                        noise_sampler=None, cond_fn=None):
+        final = None
+        for sample in self.dpm_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                       denoised_fn=denoised_fn, model_kwargs=model_kwargs, device=device,
+                                                       progress=progress, steps=steps, order=order, spacing=spacing,
+                                                       timesteps=timesteps, lower_order_final=lower_order_final,
+                                                       noise_sampler=noise_sampler, cond_fn=cond_fn,
+                                                       _materialize_every_step=False):
+            final = sample["sample"]
+        if final is not None and not final.is_contiguous():
+            final = final.contiguous()  # (the channels-last chain: one conversion at the end of the chain)
+        return final
 
     def training_losses(self, *args, **kwargs):
         raise NotImplementedError("training losses are outside the sampling hot path (SURVEY.md §8f)")

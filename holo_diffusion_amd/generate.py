@@ -488,20 +488,34 @@ CLI_DEFAULTS = dict(exp_dir="", output_directory=None, render_size=None, video_s
                     save_voxel_features=True,
                     device_noise=False,  # (build-side extension: in-kernel Philox noise per denoising step, generate_samples)
                     sampler="ddpm", ddim_steps=None, ddim_eta=0.0,  # (build-side extension: DDIM sampling, cli_sampler_kwargs)
+                    dpm_steps=None, dpm_order=2, dpm_spacing="logsnr",  # (build-side extension: sampler=dpmpp, DPM-Solver++)
                     chains_per_gpu=1)  # (build-side extension: chains sampled together per UNet call, generate_samples)
 
 
 def cli_sampler_kwargs(cfg: Dict[str, object]) -> Optional[dict]:
-    """``sampler`` / ``ddim_steps`` / ``ddim_eta`` of the command line as the ``sampler_kwargs`` of ``generate_samples``:
-    None for the default DDPM loop, ``{"sampler": "ddim", "ddim_steps": S, "eta": eta}`` for DDIM."""
-    if cfg["sampler"] == "ddpm":
-        if cfg["ddim_steps"] is not None or float(cfg["ddim_eta"]) != 0.0:
-            raise SystemExit("generate: ddim_steps / ddim_eta need sampler=ddim")
+    """``sampler`` and its keys of the command line as the ``sampler_kwargs`` of ``generate_samples``: None for the default
+    DDPM loop, ``{"sampler": "ddim", "ddim_steps": S, "eta": eta}`` for DDIM, ``{"sampler": "dpmpp", "dpm_steps": S,
+    "dpm_order": order, "dpm_spacing": spacing}`` for DPM-Solver++.  A sampler's keys without that sampler are rejected."""
+    sampler = cfg["sampler"]
+    if sampler not in ("ddpm", "ddim", "dpmpp"):
+        raise SystemExit(f"generate: sampler must be 'ddpm', 'ddim' or 'dpmpp', not '{sampler}'")
+    if sampler != "ddim" and (cfg["ddim_steps"] is not None or float(cfg["ddim_eta"]) != 0.0):
+        raise SystemExit("generate: ddim_steps / ddim_eta need sampler=ddim")
+    if sampler != "dpmpp" and (cfg["dpm_steps"] is not None or cfg["dpm_order"] != 2 or cfg["dpm_spacing"] != "logsnr"):
+        raise SystemExit("generate: dpm_steps / dpm_order / dpm_spacing need sampler=dpmpp")
+    if sampler == "ddpm":
         return None
-    if cfg["sampler"] != "ddim":
-        raise SystemExit(f"generate: sampler must be 'ddpm' or 'ddim', not '{cfg['sampler']}'")
-    steps = cfg["ddim_steps"]
-    return {"sampler": "ddim", "ddim_steps": None if steps is None else int(steps), "eta": float(cfg["ddim_eta"])}
+    if sampler == "ddim":
+        steps = cfg["ddim_steps"]
+        return {"sampler": "ddim", "ddim_steps": None if steps is None else int(steps), "eta": float(cfg["ddim_eta"])}
+    steps, order, spacing = cfg["dpm_steps"], cfg["dpm_order"], cfg["dpm_spacing"]
+    if isinstance(order, bool) or order not in (1, 2, 3):
+        raise SystemExit(f"generate: dpm_order must be 1, 2 or 3, not {order!r}")
+    if spacing not in ("logsnr", "time"):
+        raise SystemExit(f"generate: dpm_spacing must be 'logsnr' or 'time', not {spacing!r}")
+    if steps is not None and (isinstance(steps, bool) or not isinstance(steps, int) or steps < 1):
+        raise SystemExit(f"generate: dpm_steps must be an integer >= 1, not {steps!r}")
+    return {"sampler": "dpmpp", "dpm_steps": steps, "dpm_order": int(order), "dpm_spacing": spacing}
 
 
 def parse_cli(argv: Sequence[str]) -> Dict[str, object]:
@@ -519,7 +533,7 @@ def parse_cli(argv: Sequence[str]) -> Dict[str, object]:
         cfg[k] = val
     if cfg["render_size"] is not None:
         cfg["render_size"] = tuple(int(x) for x in cfg["render_size"])
-    cli_sampler_kwargs(cfg)  # (rejects an unknown sampler or DDIM keys without sampler=ddim)
+    cli_sampler_kwargs(cfg)  # (rejects an unknown sampler, and a sampler's keys without that sampler)
     B = cfg["chains_per_gpu"]
     if isinstance(B, bool) or not isinstance(B, int) or B < 1:
         raise SystemExit(f"generate: chains_per_gpu must be an integer >= 1, not {B!r}")

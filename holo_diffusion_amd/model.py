@@ -128,23 +128,43 @@ class HoloDiffusionModel(ImplicitronModelBase, torch.nn.Module):
     def _shape(self, batch_size: int = 1):
         return (int(batch_size), self.feature_size, self.resol, self.resol, self.resol)
 
-    def _sampler_loop_kwargs(self, sampler: str, ddim_steps, timesteps, eta, loop_kwargs: dict) -> dict:
-        """The sampler choice (build-side extension): "ddpm" - the reference's ancestral loop, unchanged - or "ddim"
-        (``ddim_sample_loop``, with ``ddim_steps`` / ``timesteps`` / ``eta``)."""
+    def _sampler_loop_kwargs(self, sampler: str, ddim_steps, timesteps, eta, loop_kwargs: dict, dpm_steps=None,
+                             dpm_order: int = 2, dpm_spacing: str = "logsnr") -> dict:
+        """The sampler choice (build-side extension): "ddpm" - the reference's ancestral loop, unchanged -, "ddim"
+        (``ddim_sample_loop``, with ``ddim_steps`` / ``timesteps`` / ``eta``) or "dpmpp" (``dpm_sample_loop``, with
+        ``dpm_steps`` / ``dpm_order`` / ``dpm_spacing`` / ``timesteps``)."""
+        dpm_keys = dpm_steps is not None or dpm_order != 2 or dpm_spacing != "logsnr"
+        if sampler == "dpmpp":
+            if ddim_steps is not None or eta != 0.0:
+                raise ValueError("ddim_steps / eta apply to sampler='ddim' only")
+            return dict(loop_kwargs, steps=dpm_steps, order=dpm_order, spacing=dpm_spacing, timesteps=timesteps)
+        if dpm_keys:
+            raise ValueError("dpm_steps / dpm_order / dpm_spacing apply to sampler='dpmpp' only")
         if sampler == "ddim":
             return dict(loop_kwargs, ddim_steps=ddim_steps, timesteps=timesteps, eta=eta)
         if sampler != "ddpm":
-            raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
+            raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpmpp', not {sampler!r}")
         if ddim_steps is not None or timesteps is not None or eta != 0.0:
             raise ValueError("ddim_steps / timesteps / eta apply to sampler='ddim' only")
         return loop_kwargs
 
+    def _sampler_loop(self, sampler: str, progressive: bool):
+        d = self.diffusion
+        if sampler == "dpmpp":
+            return d.dpm_sample_loop_progressive if progressive else d.dpm_sample_loop
+        if sampler == "ddim":
+            return d.ddim_sample_loop_progressive if progressive else d.ddim_sample_loop
+        return d.p_sample_loop_progressive if progressive else d.p_sample_loop
+
     def sample_random_voxel_features_progressive(self, sampler: str = "ddpm", ddim_steps: Optional[int] = None,
-                                                 timesteps=None, eta: float = 0.0, batch_size: int = 1, **loop_kwargs):
+                                                 timesteps=None, eta: float = 0.0, batch_size: int = 1,
+                                                 dpm_steps: Optional[int] = None, dpm_order: int = 2,
+                                                 dpm_spacing: str = "logsnr", **loop_kwargs):
         """``batch_size`` (build-side extension): chains sampled together, one per batch row."""
         assert self.net_3d_enabled and self.diffusion_enabled
-        loop_kwargs = self._sampler_loop_kwargs(sampler, ddim_steps, timesteps, eta, loop_kwargs)
-        loop = self.diffusion.ddim_sample_loop_progressive if sampler == "ddim" else self.diffusion.p_sample_loop_progressive
+        loop_kwargs = self._sampler_loop_kwargs(sampler, ddim_steps, timesteps, eta, loop_kwargs, dpm_steps, dpm_order,
+                                                dpm_spacing)
+        loop = self._sampler_loop(sampler, progressive=True)
         for sample in loop(model=self.net_3d, shape=self._shape(batch_size), clip_denoised=True, progress=False,
                            **loop_kwargs):
             s = sample["sample"]
@@ -155,12 +175,15 @@ class HoloDiffusionModel(ImplicitronModelBase, torch.nn.Module):
             yield out
 
     def sample_random_voxel_features(self, sampler: str = "ddpm", ddim_steps: Optional[int] = None, timesteps=None,
-                                     eta: float = 0.0, batch_size: int = 1, **loop_kwargs) -> torch.Tensor:
-        """``batch_size`` (build-side extension): chains sampled together, one per batch row."""
+                                     eta: float = 0.0, batch_size: int = 1, dpm_steps: Optional[int] = None,
+                                     dpm_order: int = 2, dpm_spacing: str = "logsnr", **loop_kwargs) -> torch.Tensor:
+        """``batch_size`` (build-side extension): chains sampled together, one per batch row.  ``sampler="dpmpp"``:
+        DPM-Solver++ with ``dpm_steps`` (None: 20) model calls of order ``dpm_order`` on the ``dpm_spacing`` schedule."""
         assert self.net_3d_enabled and self.diffusion_enabled
         logger.info("generating random voxel features through denoising diffusion ...")
-        loop_kwargs = self._sampler_loop_kwargs(sampler, ddim_steps, timesteps, eta, loop_kwargs)
-        loop = self.diffusion.ddim_sample_loop if sampler == "ddim" else self.diffusion.p_sample_loop
+        loop_kwargs = self._sampler_loop_kwargs(sampler, ddim_steps, timesteps, eta, loop_kwargs, dpm_steps, dpm_order,
+                                                dpm_spacing)
+        loop = self._sampler_loop(sampler, progressive=False)
         return loop(model=self.net_3d, shape=self._shape(batch_size), clip_denoised=True,
                     progress=loop_kwargs.pop("progress", False), **loop_kwargs)
 

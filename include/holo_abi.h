@@ -288,6 +288,22 @@ int holo_ddim_step_philox_rows(HoloCtx* ctx, const float* coefs, int batch, int6
                                int clip_denoised, float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels,
                                void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DPM-Solver++ multistep step (Lu et al. 2022, "DPM-Solver++", the data-prediction multistep solver; build-side extension,
+ * no reference counterpart).  The host expands the order-1/2/3 update of a step into four scalars per sample:
+ *   coefs    : (batch, 8) fp32 on the device, one row per sample, {a, b0, b1, b2, 0, 0, 0, 0}, formed in float64 and
+ *              rounded once (ImplicitronGaussianDiffusion.dpm_coefs)
+ *   hist1    : the clipped prediction of the previous step (the pred_xstart it wrote), hist2 the one before; either may
+ *              be null: a null term is neither read nor added
+ *   pred = clip ? clamp(model_out, -1, 1) : model_out
+ *   sample = ((a*x_t + b0*pred) + b1*hist1) + b2*hist2   (each product and each sum rounded, in this order, no fma)
+ *   pred_xstart may be null (not written).  No noise is drawn or read: the step is deterministic and, being elementwise,
+ *   takes NCDHW and channels-last tensors alike.  elems_per_sample must be a multiple of 4.
+ * ------------------------------------------------------------------------------------------ */
+int holo_dpm_step(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                  const float* model_out, const float* hist1, const float* hist2, int clip_denoised, float* sample,
+                  float* pred_xstart, void* stream);
+
 /* Elementwise helpers on the path: torch.tanh (holo_diffusion_model.py:425) and
  * torch.clip(x,-1,1) (holo_diffusion_model.py:186). */
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream);
