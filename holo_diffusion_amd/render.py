@@ -195,6 +195,12 @@ class RenderMLP(Configurable, torch.nn.Module):
         the features are handed over as an (n, C) "grid" whose trilinear fetch at the voxel centres is the identity."""
         return _render_mlp_forward(self, features, view_dirs)
 
+    def close(self) -> None:
+        """Destroys the native handle of ``forward`` now, if one was made."""
+        nat = self.__dict__.pop("_native_rows", None)
+        if nat is not None:
+            nat.close()
+
 
 class _NativeRenderMlp:
     """Owns a HoloRenderer handle for one (implicit function, render config) and keeps the packed RenderMLP in
@@ -395,6 +401,12 @@ class HoloVoxelGridImplicitFunction(ImplicitFunctionBase, torch.nn.Module):
             features = torch.cat([features, vp.reshape(*spatial, Fd)], dim=-1)
         return dens.reshape(*spatial, 1), features, aux
 
+    def close(self) -> None:
+        """Destroys the native handle of the stand-alone ``forward`` now, if one was made."""
+        nat = self.__dict__.pop("_native", None)
+        if nat is not None:
+            nat.close()
+
 
 class ImplicitFunctionWrapper(torch.nn.Module):
     def __init__(self, fn: torch.nn.Module):
@@ -544,10 +556,20 @@ class HoloMultiPassEmissionAbsorptionRenderer(BaseRenderer, torch.nn.Module):
         _lib.check(L, L.holo_renderer_set_compute_dtype(self._handle, code), "holo_renderer_set_compute_dtype")
         return self._handle
 
+    def close(self) -> None:
+        """Destroys the native handles now - the evaluation one and the training one next to it (``_training_setup``); the
+        next call creates new ones."""
+        L = runtime.lib()
+        if self._handle is not None:
+            L.holo_renderer_destroy(self._handle)
+        self._handle, self._handle_key, self._param_versions = None, None, None
+        train = self.__dict__.pop("_train_state", None)
+        if train is not None and train[0] is not None:
+            L.holo_renderer_destroy(train[0])
+
     def __del__(self):
         try:
-            if self._handle is not None:
-                runtime.lib().holo_renderer_destroy(self._handle)
+            self.close()
         except Exception:
             pass
 

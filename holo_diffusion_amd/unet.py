@@ -260,11 +260,18 @@ class SimpleUnet3D(Unet3DBase):
             _lib.check(L, L.holo_unet_set_batch_invariant(self._handle, 1 if on else 0), "holo_unet_set_batch_invariant")
         return self
 
+    def close(self) -> None:
+        """Destroys the native handle now (the device is drained first); the next forward creates a new one.  A tape of the
+        handle dies with it."""
+        self.__dict__.pop("_holo_tape", None)
+        if self._handle is not None:
+            runtime.sync_before_destroy(self._handle_device)
+            runtime.lib().holo_unet_destroy(self._handle)
+            self._handle = None
+
     def __del__(self):
         try:
-            if self._handle is not None:
-                runtime.sync_before_destroy(self._handle_device)
-                runtime.lib().holo_unet_destroy(self._handle)
+            self.close()
         except Exception:
             pass
 

@@ -48,7 +48,16 @@ typedef struct HoloRenderer HoloRenderer;
 int holo_abi_version(void);
 const char* holo_last_error(void);
 
-/* One context per process per GPU (one process per GPU). */
+/* One context per process per GPU (one process per GPU).
+ * The context records the device's compute-unit count (multiProcessorCount; HOLO_NUM_CUS overrides it when the context is
+ * created), and every launch geometry of the library is planned from that one number: the convolution kernel and its
+ * split-K, the persistent grids, the attention key splits, the weight-gradient split, the workgroups of the renderer and of
+ * the view-pooling kernels.  Any count from 8 up to the device's own is supported; the GPU suite runs the parity tests
+ * under 8, 20 and 32 (tests/test_gpu_cu_counts.py) besides the device's 256.  A count that is no multiple of 8 is planned
+ * like any other: the bf16 persistent convolution takes num_cus & ~7 workgroups and the renderer's XCD-range tile order
+ * switches itself off (it needs a workgroup count that divides by 8).  Below 8 the planner never picks the bf16 persistent
+ * kernel by itself; that range is run by the host emulation only.  A count ABOVE the device's own is accepted but not
+ * supported: the persistent kernels assume one resident workgroup per counted CU. */
 int holo_ctx_create(int device_id, HoloCtx** out);
 int holo_ctx_destroy(HoloCtx* ctx);
 

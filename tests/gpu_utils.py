@@ -53,3 +53,16 @@ def cam_dict(cams, i):
 
 def rel_err(got: torch.Tensor, ref: torch.Tensor) -> float:
     return ((got.detach().cpu().float() - ref).abs().max() / ref.abs().max().clamp_min(1e-12)).item()
+
+
+def block_outputs_vs_oracle(net, trace, tol, what=None):
+    """Every block output of the net's LAST forward (HOLO_KEEP_INTERMEDIATES=1 when the net was created) against the oracle's
+    ``trace`` of the same forward: rel_err < tol per block."""
+    n = 0
+    for tag, r in trace.items():
+        if tag.startswith(("input_blocks", "output_blocks")) or tag == "middle_block":
+            got = net.fetch_block(tag, tuple(r.shape))
+            assert torch.isfinite(got).all(), (what, tag)
+            assert rel_err(got, r) < tol, (what, tag)
+            n += 1
+    assert n > 0

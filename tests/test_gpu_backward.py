@@ -41,6 +41,43 @@ def _check(got, ref, name, rtol=1e-3, floor=1e-12):
     assert err <= rtol * max(scale, floor), (name, err, scale)
 
 
+BACKWARD_CFGS = {"tiny": TINY_CFG,
+                 "wide": uo.UNetCfg(image_size=8, in_channels=16, out_channels=16, model_channels=64, num_res_blocks=2,
+                                    channel_mult=(1, 2), attention_resolutions=(2,), num_heads=2),
+                 "deep": uo.UNetCfg(image_size=16, in_channels=16, out_channels=16, model_channels=32, num_res_blocks=1,
+                                    channel_mult=(1, 2, 3), attention_resolutions=(4,), num_heads=2)}
+
+
+def _backward_vs_oracle(gu, cfg, batch, cfg_name, seeds=(5, 1, 2), cache=None, own=lambda net: net):
+    """The body of test_unet_backward_vs_oracle_autograd (shared with tests/test_gpu_cu_counts.py).  ``seeds``: of the weights,
+    the input and the cotangent; ``cache``: a dict that keeps the oracle's gradients for a later call with the same
+    arguments; ``own``: called with the net once it is built."""
+    net, sd = gu.make_unet(cfg, seed=seeds[0])
+    own(net)
+    shape = (batch, cfg.in_channels) + (cfg.image_size,) * 3
+    x = torch.from_numpy(np_noise(seeds[1], shape))
+    t = torch.tensor([437, 12][:batch], dtype=torch.int64)
+    G = torch.from_numpy(np_noise(seeds[2], (batch, cfg.out_channels) + (cfg.image_size,) * 3))
+    key = (cfg_name, batch, tuple(seeds))
+    if cache is None or key not in cache:
+        ref = _oracle_grads(sd, cfg, x, t, G)
+        if cache is not None:
+            cache[key] = ref
+    else:
+        ref = cache[key]
+    y_ref, gx_ref, g_ref = ref
+    y, gx, grads = net.backward(x.to(gu.DEV), t.to(gu.DEV), G.to(gu.DEV))
+    assert torch.isfinite(y).all() and torch.isfinite(gx).all() and all(torch.isfinite(v).all() for v in grads.values())
+    _check(y, y_ref, "forward output", 2e-3)
+    _check(gx, gx_ref, "grad_x")
+    assert set(grads) == set(sd)
+    floor = 1e-2 * float(np.median([g_ref[k].abs().max().item() for k in sd]))
+    worst = max(((grads[k].cpu() - g_ref[k]).abs().max().item() / max(g_ref[k].abs().max().item(), floor), k) for k in sd)
+    print(f"backward {cfg_name}: worst relative gradient error {worst[0]:.2e} ({worst[1]})")
+    for k in sd:
+        _check(grads[k], g_ref[k], k, floor=floor)
+
+
 @pytest.mark.parametrize("cfg_name,batch", [("tiny", 2), ("wide", 1), ("deep", 1), ("wide-tiled-reduce", 1), ("deep-direct-s2", 1)])
 def test_unet_backward_vs_oracle_autograd(gu, cfg_name, batch, monkeypatch):
     """Every parameter gradient and the input gradient of three small nets: `tiny` (32 channels, attention on both levels,
@@ -54,26 +91,8 @@ def test_unet_backward_vs_oracle_autograd(gu, cfg_name, batch, monkeypatch):
     if cfg_name == "deep-direct-s2":  # the scalar transposed stride-2 convolution (the default is zero insertion + stride 1)
         monkeypatch.setenv("HOLO_DGRAD_S2_DIRECT", "1")
         cfg_name = "deep"
-    cfg = {"tiny": TINY_CFG,
-           "wide": uo.UNetCfg(image_size=8, in_channels=16, out_channels=16, model_channels=64, num_res_blocks=2,
-                              channel_mult=(1, 2), attention_resolutions=(2,), num_heads=2),
-           "deep": uo.UNetCfg(image_size=16, in_channels=16, out_channels=16, model_channels=32, num_res_blocks=1,
-                              channel_mult=(1, 2, 3), attention_resolutions=(4,), num_heads=2)}[cfg_name]
-    net, sd = gu.make_unet(cfg, seed=5)
-    shape = (batch, cfg.in_channels) + (cfg.image_size,) * 3
-    x = torch.from_numpy(np_noise(1, shape))
-    t = torch.tensor([437, 12][:batch], dtype=torch.int64)
-    G = torch.from_numpy(np_noise(2, (batch, cfg.out_channels) + (cfg.image_size,) * 3))
-    y_ref, gx_ref, g_ref = _oracle_grads(sd, cfg, x, t, G)
-    y, gx, grads = net.backward(x.to(gu.DEV), t.to(gu.DEV), G.to(gu.DEV))
-    _check(y, y_ref, "forward output", 2e-3)
-    _check(gx, gx_ref, "grad_x")
-    assert set(grads) == set(sd)
-    floor = 1e-2 * float(np.median([g_ref[k].abs().max().item() for k in sd]))
-    worst = max(((grads[k].cpu() - g_ref[k]).abs().max().item() / max(g_ref[k].abs().max().item(), floor), k) for k in sd)
-    print(f"backward {cfg_name}: worst relative gradient error {worst[0]:.2e} ({worst[1]})")
-    for k in sd:
-        _check(grads[k], g_ref[k], k, floor=floor)
+    cfg = BACKWARD_CFGS[cfg_name]
+    _backward_vs_oracle(gu, cfg, batch, cfg_name)
 
 
 def test_loss_backward_through_the_plugin(gu):

@@ -42,19 +42,18 @@ CASES = [(12, 10, 16, 8, 3, 13, "all")] if EMU else [(12, 10, 16, 8, 3, 13, "all
                                                      (16, 100, 16, 16, 2, 29, "no_noise"), (64, 64, 32, 32, 4, 700, "chunks")]
 
 
-@pytest.mark.parametrize("P,Pf,C,R,n_cam,n_rays,which", CASES)
-def test_render_rays_backward_vs_oracle_autograd(gu, P, Pf, C, R, n_cam, n_rays, which):
-    """Losses on all six outputs (random cotangents), stratified depths / importance samples and density noise of std 1
-    injected; `chunks`: more points than one 65 536-point chunk, `fine_only`: no gradient on the coarse outputs (NULL
-    pointers), `no_noise`: deterministic depths, no density noise (16 + 100 samples: a 116-point merged list)."""
+def _render_rays_backward_case(gu, P, Pf, C, R, n_cam, n_rays, which, seed=0, own=lambda model: model):
+    """The body of test_render_rays_backward_vs_oracle_autograd (shared with tests/test_gpu_cu_counts.py).  ``seed``: added to
+    the seeds of the grid, the ray positions, the random streams and the cotangents; ``own``: called with the model."""
     model, _, _, _, msd = gu.make_model(R, C, 16, 16, TINY_UNET, n_fine=64)
+    own(model)
     model.raysampler.n_pts_per_ray_training = P
     model.renderer.n_pts_per_ray_fine_training = Pf
     rcfg = ro.RenderCfg(resol=R, feature_size=C, image_height=16, image_width=16, n_pts_coarse=P, n_pts_fine=Pf)
-    grid = torch.tanh(torch.from_numpy(np_noise(7, (1, C, R, R, R))))
+    grid = torch.tanh(torch.from_numpy(np_noise(7 + seed, (1, C, R, R, R))))
     cams = hda.get_simple_360_camera_trajectory(2 * math.pi, n_cam, -0.5, 10, (0.0, -1.0, 0.0), 3.2)
-    xys = (torch.from_numpy(np_noise(11, (n_cam, n_rays, 2))).clamp(-2, 2) * 0.45).contiguous()
-    rs = _streams(n_cam, n_rays, P, Pf, 500 + P)
+    xys = (torch.from_numpy(np_noise(11 + seed, (n_cam, n_rays, 2))).clamp(-2, 2) * 0.45).contiguous()
+    rs = _streams(n_cam, n_rays, P, Pf, 500 + P + seed)
     std = 1.0
     if which == "no_noise":
         model.raysampler.stratified_point_sampling_training = False
@@ -65,7 +64,7 @@ def test_render_rays_backward_vs_oracle_autograd(gu, P, Pf, C, R, n_cam, n_rays,
             "depths_coarse": ("depth_c", 1), "masks_coarse": ("mask_c", 1)}
     if which == "fine_only":
         keys = {k: v for k, v in keys.items() if not k.endswith("_coarse")}
-    cot = {k: torch.from_numpy(np_noise(900 + i, (n_cam, n_rays, 1, c))) * (0.05 if "depth" in k else 1.0)
+    cot = {k: torch.from_numpy(np_noise(900 + i + seed, (n_cam, n_rays, 1, c))) * (0.05 if "depth" in k else 1.0)
            for i, (k, (_, c)) in enumerate(keys.items())}
     for fn in model._implicit_functions:
         fn.bind_args(voxel_grid_features=grid.to(gu.DEV))
@@ -156,6 +155,14 @@ def test_render_rays_backward_vs_oracle_autograd(gu, P, Pf, C, R, n_cam, n_rays,
         print(f"   grid: {n_events} voxel positions above 2e-3 (set aside: 64), the rest within {rest:.2e}; parameters {wp_max[1]:.2e} ({wp_max[0]})")
         assert rest < 2e-3 and worst_l2[1] < 3e-3 and wp_max[1] < 1e-2, (rest, worst_l2, wp_max)
     assert moved < 5e-3 and l2 < 2e-2 and worst_free[1] < 5e-2, (moved, l2, worst_free)
+
+
+@pytest.mark.parametrize("P,Pf,C,R,n_cam,n_rays,which", CASES)
+def test_render_rays_backward_vs_oracle_autograd(gu, P, Pf, C, R, n_cam, n_rays, which):
+    """Losses on all six outputs (random cotangents), stratified depths / importance samples and density noise of std 1
+    injected; `chunks`: more points than one 65 536-point chunk, `fine_only`: no gradient on the coarse outputs (NULL
+    pointers), `no_noise`: deterministic depths, no density noise (16 + 100 samples: a 116-point merged list)."""
+    _render_rays_backward_case(gu, P, Pf, C, R, n_cam, n_rays, which)
 
 
 def test_render_backward_needs_the_forward_draws(gu):

@@ -115,10 +115,7 @@ def test_mid_size_unet_vs_oracle_blockwise(gu, image, mc, mult, attn, batch):
         with torch.no_grad():
             y = net(x.to(gu.DEV), t.to(gu.DEV))
         assert gu.rel_err(y, ref) < 1e-4
-        for tag, r in trace.items():
-            if tag.startswith(("input_blocks", "output_blocks")) or tag == "middle_block":
-                got = net.fetch_block(tag, tuple(r.shape))
-                assert gu.rel_err(got, r) < 1e-4, tag
+        gu.block_outputs_vs_oracle(net, trace, 1e-4)
     finally:
         del os.environ["HOLO_KEEP_INTERMEDIATES"]
 
@@ -449,9 +446,7 @@ def test_bf16_storage_mode_blockwise(gu, wide_tile, monkeypatch):
     with torch.no_grad():
         y = net(x.to(gu.DEV), t.to(gu.DEV))
     assert 1e-5 < gu.rel_err(y, ref) < 2e-2
-    for tag, r in trace.items():
-        if tag.startswith(("input_blocks", "output_blocks")) or tag == "middle_block":
-            assert gu.rel_err(net.fetch_block(tag, tuple(r.shape)), r) < 2e-2, tag
+    gu.block_outputs_vs_oracle(net, trace, 2e-2)
     kernels = {o.get("kernel") for o in net.time_ops(2, 1, gu.DEV) if o["op"] == "conv"}
     assert ("conv_bf16t_kernel" in kernels) == (wide_tile == "1"), kernels
     assert ("conv_bf16p_kernel" in kernels) == (wide_tile == "p"), kernels
@@ -632,9 +627,7 @@ def test_f32_bf16x3_mode_meets_the_fp32_tolerance(gu, image, mc, mult, attn, bat
         with torch.no_grad():
             y = net(x.to(gu.DEV), t.to(gu.DEV))
         assert gu.rel_err(y, ref) < 1e-4
-        for tag, r in trace.items():
-            if tag.startswith(("input_blocks", "output_blocks")) or tag == "middle_block":
-                assert gu.rel_err(net.fetch_block(tag, tuple(r.shape)), r) < 1e-4, tag
+        gu.block_outputs_vs_oracle(net, trace, 1e-4)
     finally:
         del os.environ["HOLO_KEEP_INTERMEDIATES"]
 
