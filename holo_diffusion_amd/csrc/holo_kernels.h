@@ -239,23 +239,17 @@ int rows_linear_launch(const float* in, const float* w, const float* bias, float
 int ddpm_step_launch(const float* tables, int T, const int64_t* timesteps, int batch, int64_t per, const float* x_t,
                      const float* model_out, const float* noise, int clip, float* sample, float* pred_xstart,
                      void* stream);
+// The Philox steps (include/holo_abi.h).  row_streams null: holo_*_step_philox, `offset` is the 64-bit stream offset;
+// non-null: holo_*_step_philox_rows, one stream per row and `offset` is the 32-bit timestep index.
 int ddpm_step_philox_launch(const float* tables, int T, const int64_t* timesteps, int batch, int64_t per, const float* x_t,
-                            const float* model_out, uint64_t seed, uint64_t offset, int clip, float* sample,
-                            float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
+                            const float* model_out, uint64_t seed, const uint32_t* row_streams, uint64_t offset, int clip,
+                            float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
 // DDIM step: coefs is (batch, 8) fp32, one row per sample (include/holo_abi.h, holo_ddim_step)
 int ddim_step_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
                      const float* noise, int clip, float* sample, float* pred_xstart, void* stream);
 int ddim_step_philox_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
-                            uint64_t seed, uint64_t offset, int clip, float* sample, float* pred_xstart, float* noise_out,
-                            int ncdhw_channels, void* stream);
-// the Philox steps with one stream per row (holo_ddpm_step_philox_rows / holo_ddim_step_philox_rows, include/holo_abi.h)
-int ddpm_step_philox_rows_launch(const float* tables, int T, const int64_t* timesteps, int batch, int64_t per,
-                                 const float* x_t, const float* model_out, uint64_t seed, const uint32_t* row_streams,
-                                 uint32_t timestep_index, int clip, float* sample, float* pred_xstart, float* noise_out,
-                                 int ncdhw_channels, void* stream);
-int ddim_step_philox_rows_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
-                                 uint64_t seed, const uint32_t* row_streams, uint32_t timestep_index, int clip,
-                                 float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
+                            uint64_t seed, const uint32_t* row_streams, uint64_t offset, int clip, float* sample,
+                            float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
 // DPM-Solver++ multistep step: coefs is (batch, 8) fp32, rows {a, b0, b1, b2, 0...}; hist1 / hist2 may be null
 // (include/holo_abi.h, holo_dpm_step)
 int dpm_step_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,

@@ -374,54 +374,39 @@ __global__ __launch_bounds__(256) void rows_linear_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
-// DDPM ancestral update, float4 per thread.  grid = (blocks over per/4, batch)
+// Sampler step kernels (DDPM, DDIM, DPM-Solver++): float4 per thread, grid = (blocks over per/4, batch).  Each sampler keeps
+// its own arithmetic; what they share is below: the clamp, the float4 access of the two layouts, and the in-kernel noise draw.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ddpm_step_kernel(const float* __restrict__ tables, int T,
-                                                        const int64_t* __restrict__ timesteps, int64_t per,
-                                                        const float* __restrict__ x_t,
-                                                        const float* __restrict__ model_out,
-                                                        const float* __restrict__ noise, int clip,
-                                                        float* __restrict__ sample, float* __restrict__ pred) {
-  const int b = blockIdx.y;
-  int64_t tt = holo_ld_sys(timesteps + b);
-  if (tt < 0) tt = 0;
-  if (tt >= T) tt = T - 1;
-  const float c1 = holo_ld_sys(tables + tt * 4 + 0);  // (a 16 KB table uploaded from the host: see holo_ld_sys)
-  const float c2 = holo_ld_sys(tables + tt * 4 + 1);
-  const float lv = holo_ld_sys(tables + tt * 4 + 2);
-  const float sig = tt != 0 ? expf(0.5f * lv) : 0.f;
-  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i >= per) return;
-  const int64_t o = (int64_t)b * per + i;
-  float4 x = *reinterpret_cast<const float4*>(x_t + o);
-  float4 m = *reinterpret_cast<const float4*>(model_out + o);
-  float4 e = *reinterpret_cast<const float4*>(noise + o);
-  if (clip) {
-    m.x = fminf(fmaxf(m.x, -1.f), 1.f);
-    m.y = fminf(fmaxf(m.y, -1.f), 1.f);
-    m.z = fminf(fmaxf(m.z, -1.f), 1.f);
-    m.w = fminf(fmaxf(m.w, -1.f), 1.f);
-  }
-  float4 s;
-  // reference order: (c1*x0 + c2*x) + nonzero*sigma*noise, each product rounded (no fma contraction)
-  s.x = __fadd_rn(__fadd_rn(__fmul_rn(c1, m.x), __fmul_rn(c2, x.x)), __fmul_rn(sig, e.x));
-  s.y = __fadd_rn(__fadd_rn(__fmul_rn(c1, m.y), __fmul_rn(c2, x.y)), __fmul_rn(sig, e.y));
-  s.z = __fadd_rn(__fadd_rn(__fmul_rn(c1, m.z), __fmul_rn(c2, x.z)), __fmul_rn(sig, e.z));
-  s.w = __fadd_rn(__fadd_rn(__fmul_rn(c1, m.w), __fmul_rn(c2, x.w)), __fmul_rn(sig, e.w));
-  *reinterpret_cast<float4*>(sample + o) = s;
-  *reinterpret_cast<float4*>(pred + o) = m;
+__device__ __forceinline__ float4 clamp4(float4 m) {
+  return make_float4(fminf(fmaxf(m.x, -1.f), 1.f), fminf(fmaxf(m.y, -1.f), 1.f), fminf(fmaxf(m.z, -1.f), 1.f),
+                     fminf(fmaxf(m.w, -1.f), 1.f));
+}
+// A thread's four elements from `o` on: STRIDED = false, consecutive floats (one 16-byte access); STRIDED = true, `es` apart
+template <bool STRIDED = false>
+__device__ __forceinline__ float4 ld4(const float* p, int64_t o, int64_t es = 1) {
+  if (STRIDED) return make_float4(p[o], p[o + es], p[o + 2 * es], p[o + 3 * es]);
+  return *reinterpret_cast<const float4*>(p + o);
+}
+template <bool STRIDED = false>
+__device__ __forceinline__ void st4(float* p, int64_t o, float4 v, int64_t es = 1) {
+  if (STRIDED)
+    p[o] = v.x, p[o + es] = v.y, p[o + 2 * es] = v.z, p[o + 3 * es] = v.w;
+  else
+    *reinterpret_cast<float4*>(p + o) = v;
 }
 
 // ---------------------------------------------------------------------------------------------
-// The same update with the noise drawn IN the kernel (perf mode; gaussian_diffusion.py:498 `th.randn_like(x)`, :604): a
-// thread's four elements take the four outputs of ONE Philox4x32-10 block - counter (element quad low, high, sample,
-// stream offset), key (seed low, seed high) - turned into standard normals by two Box-Muller pairs.  A draw depends on
-// nothing but (seed, offset, sample, element): bit-reproducible whatever the launch geometry; no generator state, no
-// separate randn launch, and the 4 B / element of noise never cross HBM (optionally written out for tests).
+// The noise drawn IN the kernel (perf mode; gaussian_diffusion.py:498 `th.randn_like(x)`, :604): a thread's four elements
+// take the four outputs of ONE Philox4x32-10 block - counter (element quad low, high, sample, stream offset), key (seed
+// low, seed high) - turned into standard normals by two Box-Muller pairs.  A draw depends on nothing but (seed, offset,
+// sample, element): bit-reproducible whatever the launch geometry; no generator state, no separate randn launch, and the
+// 4 B / element of noise never cross HBM (optionally written out for tests).
 // "Element" is the LOGICAL element: the quads are numbered in channels-last order (voxel, channel / 4).  NCDHW = 0: the
 // tensors are in that order in memory (the sampler's channels-last chain) - quad = four consecutive floats.  NCDHW = 1:
 // the tensors are (C, voxels) planes - a thread takes the same quad's four channels of one voxel from four planes
 // (consecutive threads = consecutive voxels: coalesced), so both layouts of a chain draw the same noise.
+// ROWS (holo_*_step_philox_rows): row b draws what a batch-1 launch draws for stream row_streams[b] - counter slot 2 is 0
+// and the key's high word is seed_hi ^ row_streams[b] - so a chain's noise does not depend on the row it runs in.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                                               uint32_t (&out)[4]) {
@@ -448,9 +433,87 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, fl
   z0 = r * cs;
   z1 = r * sn;
 }
+// the four normals of canonical quad `qd` (written in place, as box_muller does: returned by value, the DDPM update after it
+// compiles to fewer packed instructions)
+__device__ __forceinline__ void draw4(int64_t qd, uint32_t slot, uint32_t offset, uint32_t seed_lo, uint32_t key_hi,
+                                      float4& e) {
+  uint32_t rnd[4];
+  philox4x32_10((uint32_t)qd, (uint32_t)((uint64_t)qd >> 32), slot, offset, seed_lo, key_hi, rnd);
+  box_muller(rnd[0], rnd[1], e.x, e.y);
+  box_muller(rnd[2], rnd[3], e.z, e.w);
+}
+// the key's high word of row b (its counter slot 2 is ROWS ? 0 : b)
+template <bool ROWS>
+__device__ __forceinline__ uint32_t row_key(uint32_t seed_hi, const uint32_t* __restrict__ row_streams, int b) {
+  return ROWS ? seed_hi ^ holo_ld_sys(row_streams + b) : seed_hi;  // (a small table from the host)
+}
+// Thread `tid` of sample b: the canonical (channels-last) quad it draws for, where the quad's first element lives, and the
+// distance between its elements in memory
+struct StepQuad {
+  int64_t qd, o, es;
+};
+template <bool NCDHW>
+__device__ __forceinline__ StepQuad step_quad(int64_t tid, int b, int64_t per, int channels) {
+  StepQuad q = {tid, (int64_t)b * per + tid * 4, 1};
+  if (NCDHW) {
+    const int64_t V = per / channels;
+    const int64_t cq = tid / V, v = tid - cq * V;
+    q.qd = v * (channels >> 2) + cq;
+    q.o = (int64_t)b * per + cq * 4 * V + v;
+    q.es = V;
+  }
+  return q;
+}
 
-// ROWS (holo_ddpm_step_philox_rows): row b draws what a batch-1 launch draws for stream row_streams[b] - counter slot 2 is 0
-// and the key's high word is seed_hi ^ row_streams[b] - so a chain's noise does not depend on the row it runs in.
+// ---------------------------------------------------------------------------------------------
+// DDPM ancestral update (gaussian_diffusion.py:314-343,237-240,499-506): sample = c1*pred + c2*x + [t != 0]*sigma*noise with
+// c1, c2, log-variance read by timestep index from the device table.
+// ---------------------------------------------------------------------------------------------
+struct DdpmCoefs {
+  float c1, c2, sig;
+};
+__device__ __forceinline__ DdpmCoefs ddpm_coefs(const float* __restrict__ tables, int T,
+                                                const int64_t* __restrict__ timesteps, int b) {
+  int64_t tt = holo_ld_sys(timesteps + b);
+  if (tt < 0) tt = 0;
+  if (tt >= T) tt = T - 1;
+  const float c1 = holo_ld_sys(tables + tt * 4 + 0);  // (a 16 KB table uploaded from the host: see holo_ld_sys)
+  const float c2 = holo_ld_sys(tables + tt * 4 + 1);
+  const float lv = holo_ld_sys(tables + tt * 4 + 2);
+  return {c1, c2, tt != 0 ? expf(0.5f * lv) : 0.f};
+}
+// The reference rounds each product, (c1*pred + c2*x) + sigma*noise; this kernel rounds c1*pred only and fuses the other two
+// into the sums: fma(sigma, noise, fma(c2, x, c1*pred)).  Spelled out so that the source says what runs (hipcc's
+// __fmul_rn / __fadd_rn are plain operators that contract after inlining); contract(off) keeps it at exactly this.
+__device__ __forceinline__ float ddpm_update(float x, float m, float e, DdpmCoefs c) {
+#pragma clang fp contract(off)
+  return fmaf(c.sig, e, fmaf(c.c2, x, c.c1 * m));
+}
+__device__ __forceinline__ float4 ddpm_update4(float4 x, float4 m, float4 e, DdpmCoefs c) {
+  return make_float4(ddpm_update(x.x, m.x, e.x, c), ddpm_update(x.y, m.y, e.y, c), ddpm_update(x.z, m.z, e.z, c),
+                     ddpm_update(x.w, m.w, e.w, c));
+}
+
+__global__ __launch_bounds__(256) void ddpm_step_kernel(const float* __restrict__ tables, int T,
+                                                        const int64_t* __restrict__ timesteps, int64_t per,
+                                                        const float* __restrict__ x_t,
+                                                        const float* __restrict__ model_out,
+                                                        const float* __restrict__ noise, int clip,
+                                                        float* __restrict__ sample, float* __restrict__ pred) {
+  const int b = blockIdx.y;
+  const DdpmCoefs c = ddpm_coefs(tables, T, timesteps, b);
+  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= per) return;
+  const int64_t o = (int64_t)b * per + i;
+  const float4 x = ld4(x_t, o);
+  float4 m = ld4(model_out, o);
+  const float4 e = ld4(noise, o);
+  if (clip) m = clamp4(m);
+  st4(sample, o, ddpm_update4(x, m, e, c));
+  st4(pred, o, m);
+}
+
+// The same update with the noise drawn in the kernel (draw4)
 template <bool NCDHW, bool ROWS = false>
 __global__ __launch_bounds__(256) void ddpm_step_philox_kernel(const float* __restrict__ tables, int T,
                                                                const int64_t* __restrict__ timesteps, int64_t per,
@@ -461,68 +524,27 @@ __global__ __launch_bounds__(256) void ddpm_step_philox_kernel(const float* __re
                                                                float* __restrict__ noise_out, int channels,
                                                                const uint32_t* __restrict__ row_streams) {
   const int b = blockIdx.y;
-  const uint32_t slot = ROWS ? 0u : (uint32_t)b;
-  const uint32_t key_hi = ROWS ? seed_hi ^ holo_ld_sys(row_streams + b) : seed_hi;  // (a small table from the host)
-  int64_t tt = holo_ld_sys(timesteps + b);
-  if (tt < 0) tt = 0;
-  if (tt >= T) tt = T - 1;
-  const float c1 = holo_ld_sys(tables + tt * 4 + 0);
-  const float c2 = holo_ld_sys(tables + tt * 4 + 1);
-  const float lv = holo_ld_sys(tables + tt * 4 + 2);
-  const float sig = tt != 0 ? expf(0.5f * lv) : 0.f;
+  const uint32_t key_hi = row_key<ROWS>(seed_hi, row_streams, b);
+  const DdpmCoefs c = ddpm_coefs(tables, T, timesteps, b);
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (tid * 4 >= per) return;
-  int64_t qd = tid;                       // the canonical (channels-last) quad this thread draws for
-  int64_t o = (int64_t)b * per + tid * 4;  // ... and where its first element lives
-  int64_t es = 1;                          // distance between the quad's elements in memory
-  if (NCDHW) {
-    const int64_t V = per / channels;
-    const int64_t cq = tid / V, v = tid - cq * V;
-    qd = v * (channels >> 2) + cq;
-    o = (int64_t)b * per + cq * 4 * V + v;
-    es = V;
-  }
-  float4 x, m;
-  if (NCDHW) {
-    x = make_float4(x_t[o], x_t[o + es], x_t[o + 2 * es], x_t[o + 3 * es]);
-    m = make_float4(model_out[o], model_out[o + es], model_out[o + 2 * es], model_out[o + 3 * es]);
-  } else {
-    x = *reinterpret_cast<const float4*>(x_t + o);
-    m = *reinterpret_cast<const float4*>(model_out + o);
-  }
-  uint32_t rnd[4];
-  philox4x32_10((uint32_t)qd, (uint32_t)((uint64_t)qd >> 32), slot, offset, seed_lo, key_hi, rnd);
+  const StepQuad q = step_quad<NCDHW>(tid, b, per, channels);
+  const float4 x = ld4<NCDHW>(x_t, q.o, q.es);
+  float4 m = ld4<NCDHW>(model_out, q.o, q.es);
   float4 e;
-  box_muller(rnd[0], rnd[1], e.x, e.y);
-  box_muller(rnd[2], rnd[3], e.z, e.w);
-  if (clip) {
-    m.x = fminf(fmaxf(m.x, -1.f), 1.f);
-    m.y = fminf(fmaxf(m.y, -1.f), 1.f);
-    m.z = fminf(fmaxf(m.z, -1.f), 1.f);
-    m.w = fminf(fmaxf(m.w, -1.f), 1.f);
-  }
-  float4 s;
-  s.x = __fadd_rn(__fadd_rn(__fmul_rn(c1, m.x), __fmul_rn(c2, x.x)), __fmul_rn(sig, e.x));
-  s.y = __fadd_rn(__fadd_rn(__fmul_rn(c1, m.y), __fmul_rn(c2, x.y)), __fmul_rn(sig, e.y));
-  s.z = __fadd_rn(__fadd_rn(__fmul_rn(c1, m.z), __fmul_rn(c2, x.z)), __fmul_rn(sig, e.z));
-  s.w = __fadd_rn(__fadd_rn(__fmul_rn(c1, m.w), __fmul_rn(c2, x.w)), __fmul_rn(sig, e.w));
-  if (NCDHW) {
-    sample[o] = s.x, sample[o + es] = s.y, sample[o + 2 * es] = s.z, sample[o + 3 * es] = s.w;
-    if (pred) pred[o] = m.x, pred[o + es] = m.y, pred[o + 2 * es] = m.z, pred[o + 3 * es] = m.w;
-    if (noise_out) noise_out[o] = e.x, noise_out[o + es] = e.y, noise_out[o + 2 * es] = e.z, noise_out[o + 3 * es] = e.w;
-  } else {
-    *reinterpret_cast<float4*>(sample + o) = s;
-    if (pred) *reinterpret_cast<float4*>(pred + o) = m;
-    if (noise_out) *reinterpret_cast<float4*>(noise_out + o) = e;
-  }
+  draw4(q.qd, ROWS ? 0u : (uint32_t)b, offset, seed_lo, key_hi, e);
+  if (clip) m = clamp4(m);
+  st4<NCDHW>(sample, q.o, ddpm_update4(x, m, e, c), q.es);
+  if (pred) st4<NCDHW>(pred, q.o, m, q.es);
+  if (noise_out) st4<NCDHW>(noise_out, q.o, e, q.es);
 }
 
 // ---------------------------------------------------------------------------------------------
-// DDIM update (gaussian_diffusion.py:645-727: ddim_sample, and ddim_reverse_sample with c4 = 0), float4 per thread,
-// grid = (blocks over per/4, batch).  Sample b reads its row coefs[b*8 + 0..4] = (sqrt_recip_alphas_cumprod[t],
-// sqrt_recipm1_alphas_cumprod[t], sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), [t != 0] * sigma), computed on the host in
-// float32 in the reference's order, so strided schedules and the reverse step need nothing else here.  Per element, in the
-// reference's order and each operation rounded (no fma contraction, see ddim_mean):
+// DDIM update (gaussian_diffusion.py:645-727: ddim_sample, and ddim_reverse_sample with c4 = 0).  Sample b reads its row
+// coefs[b*8 + 0..4] = (sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t], sqrt(abar_prev),
+// sqrt(1 - abar_prev - sigma^2), [t != 0] * sigma), computed on the host in float32 in the reference's order, so strided
+// schedules and the reverse step need nothing else here.  Per element, in the reference's order and each operation rounded
+// (no fma contraction, see ddim_mean):
 //   eps = (c0*x - pred) / c1 ;  mean = pred*c2 + c3*eps ;  sample = mean + c4*noise
 // ---------------------------------------------------------------------------------------------
 // Plain operators under contract(off): hipcc's __fmul_rn / __fadd_rn are plain operators compiled with the header's default
@@ -535,10 +557,6 @@ __device__ __forceinline__ float ddim_mean(float x, float m, float c0, float c1,
 __device__ __forceinline__ float4 ddim_mean4(float4 x, float4 m, const float (&c)[5]) {
   return make_float4(ddim_mean(x.x, m.x, c[0], c[1], c[2], c[3]), ddim_mean(x.y, m.y, c[0], c[1], c[2], c[3]),
                      ddim_mean(x.z, m.z, c[0], c[1], c[2], c[3]), ddim_mean(x.w, m.w, c[0], c[1], c[2], c[3]));
-}
-__device__ __forceinline__ float4 clamp4(float4 m) {
-  return make_float4(fminf(fmaxf(m.x, -1.f), 1.f), fminf(fmaxf(m.y, -1.f), 1.f), fminf(fmaxf(m.z, -1.f), 1.f),
-                     fminf(fmaxf(m.w, -1.f), 1.f));
 }
 __device__ __forceinline__ float4 add_noise4(float4 s, float c4, float4 e) {
 #pragma clang fp contract(off)
@@ -557,18 +575,18 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict_
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= per) return;
   const int64_t o = (int64_t)b * per + i;
-  const float4 x = *reinterpret_cast<const float4*>(x_t + o);
-  float4 m = *reinterpret_cast<const float4*>(model_out + o);
+  const float4 x = ld4(x_t, o);
+  float4 m = ld4(model_out, o);
   if (clip) m = clamp4(m);
   float4 s = ddim_mean4(x, m, c);
-  if (noise && c[4] != 0.f) s = add_noise4(s, c[4], *reinterpret_cast<const float4*>(noise + o));
-  *reinterpret_cast<float4*>(sample + o) = s;
-  if (pred) *reinterpret_cast<float4*>(pred + o) = m;
+  if (noise && c[4] != 0.f) s = add_noise4(s, c[4], ld4(noise, o));
+  st4(sample, o, s);
+  if (pred) st4(pred, o, m);
 }
 
 // The same update with the noise drawn in the kernel: the draw of ddpm_step_philox_kernel (same counter, key and logical
-// element numbering, NCDHW as there), so a DDIM step at timestep t draws the noise a DDPM step at t would.  Samples whose
-// c4 is 0 skip the draw unless noise_out asks for it.  ROWS: per-row streams, as ddpm_step_philox_kernel.
+// element numbering), so a DDIM step at timestep t draws the noise a DDPM step at t would.  Samples whose c4 is 0 skip the
+// draw unless noise_out asks for it.
 template <bool NCDHW, bool ROWS = false>
 __global__ __launch_bounds__(256) void ddim_step_philox_kernel(const float* __restrict__ coefs, int64_t per,
                                                                const float* __restrict__ x_t,
@@ -583,50 +601,26 @@ __global__ __launch_bounds__(256) void ddim_step_philox_kernel(const float* __re
   for (int k = 0; k < 5; ++k) c[k] = holo_ld_sys(coefs + b * 8 + k);
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (tid * 4 >= per) return;
-  int64_t qd = tid, o = (int64_t)b * per + tid * 4, es = 1;  // canonical quad, its first element, element stride
-  if (NCDHW) {
-    const int64_t V = per / channels;
-    const int64_t cq = tid / V, v = tid - cq * V;
-    qd = v * (channels >> 2) + cq;
-    o = (int64_t)b * per + cq * 4 * V + v;
-    es = V;
-  }
-  float4 x, m;
-  if (NCDHW) {
-    x = make_float4(x_t[o], x_t[o + es], x_t[o + 2 * es], x_t[o + 3 * es]);
-    m = make_float4(model_out[o], model_out[o + es], model_out[o + 2 * es], model_out[o + 3 * es]);
-  } else {
-    x = *reinterpret_cast<const float4*>(x_t + o);
-    m = *reinterpret_cast<const float4*>(model_out + o);
-  }
+  const StepQuad q = step_quad<NCDHW>(tid, b, per, channels);
+  const float4 x = ld4<NCDHW>(x_t, q.o, q.es);
+  float4 m = ld4<NCDHW>(model_out, q.o, q.es);
   if (clip) m = clamp4(m);
   float4 s = ddim_mean4(x, m, c);
   float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
-  const bool draw = c[4] != 0.f || noise_out;
-  if (draw) {
-    const uint32_t key_hi = ROWS ? seed_hi ^ holo_ld_sys(row_streams + b) : seed_hi;
-    uint32_t rnd[4];
-    philox4x32_10((uint32_t)qd, (uint32_t)((uint64_t)qd >> 32), ROWS ? 0u : (uint32_t)b, offset, seed_lo, key_hi, rnd);
-    box_muller(rnd[0], rnd[1], e.x, e.y);
-    box_muller(rnd[2], rnd[3], e.z, e.w);
+  if (c[4] != 0.f || noise_out) {
+    draw4(q.qd, ROWS ? 0u : (uint32_t)b, offset, seed_lo, row_key<ROWS>(seed_hi, row_streams, b), e);
     if (c[4] != 0.f) s = add_noise4(s, c[4], e);
   }
-  if (NCDHW) {
-    sample[o] = s.x, sample[o + es] = s.y, sample[o + 2 * es] = s.z, sample[o + 3 * es] = s.w;
-    if (pred) pred[o] = m.x, pred[o + es] = m.y, pred[o + 2 * es] = m.z, pred[o + 3 * es] = m.w;
-    if (noise_out) noise_out[o] = e.x, noise_out[o + es] = e.y, noise_out[o + 2 * es] = e.z, noise_out[o + 3 * es] = e.w;
-  } else {
-    *reinterpret_cast<float4*>(sample + o) = s;
-    if (pred) *reinterpret_cast<float4*>(pred + o) = m;
-    if (noise_out) *reinterpret_cast<float4*>(noise_out + o) = e;
-  }
+  st4<NCDHW>(sample, q.o, s, q.es);
+  if (pred) st4<NCDHW>(pred, q.o, m, q.es);
+  if (noise_out) st4<NCDHW>(noise_out, q.o, e, q.es);
 }
 
 // ---------------------------------------------------------------------------------------------
-// DPM-Solver++ multistep update (Lu et al. 2022, data prediction), float4 per thread, grid = (blocks over per/4, batch).
-// The host expands the order-1/2/3 update into one row per sample, coefs[b*8 + 0..3] = (a, b0, b1, b2), formed in float64
-// and rounded once (ImplicitronGaussianDiffusion.dpm_coefs); hist1 / hist2 are the clipped predictions of the two steps
-// before this one.  Per element, each product and each sum rounded, in this order (no fma contraction):
+// DPM-Solver++ multistep update (Lu et al. 2022, data prediction).  The host expands the order-1/2/3 update into one row per
+// sample, coefs[b*8 + 0..3] = (a, b0, b1, b2), formed in float64 and rounded once (ImplicitronGaussianDiffusion.dpm_coefs);
+// hist1 / hist2 are the clipped predictions of the two steps before this one.  Per element, each product and each sum
+// rounded, in this order (no fma contraction):
 //   pred = clip ? clamp(model_out, -1, 1) : model_out ;  sample = ((a*x + b0*pred) + b1*hist1) + b2*hist2
 // A null history pointer drops its term: it is neither read nor added.  No noise, so the kernel is layout-agnostic.
 // ---------------------------------------------------------------------------------------------
@@ -648,14 +642,14 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const float* __restrict__
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= per) return;
   const int64_t o = (int64_t)b * per + i;
-  const float4 x = *reinterpret_cast<const float4*>(x_t + o);
-  float4 m = *reinterpret_cast<const float4*>(model_out + o);
+  const float4 x = ld4(x_t, o);
+  float4 m = ld4(model_out, o);
   if (clip) m = clamp4(m);
   float4 s = dpm_lin4(x, m, c[0], c[1]);
-  if (hist1) s = add_noise4(s, c[2], *reinterpret_cast<const float4*>(hist1 + o));  // (s + c*h, each operation rounded)
-  if (hist2) s = add_noise4(s, c[3], *reinterpret_cast<const float4*>(hist2 + o));
-  *reinterpret_cast<float4*>(sample + o) = s;
-  if (pred) *reinterpret_cast<float4*>(pred + o) = m;
+  if (hist1) s = add_noise4(s, c[2], ld4(hist1, o));  // (s + c*h, each operation rounded)
+  if (hist2) s = add_noise4(s, c[3], ld4(hist2, o));
+  st4(sample, o, s);
+  if (pred) st4(pred, o, m);
 }
 
 // copy of a SMALL caller-provided tensor (biases, GroupNorm affine parameters, ...) with system-scope loads (holo_ld_sys)
@@ -849,129 +843,80 @@ int rows_linear_launch(const float* in, const float* w, const float* bias, float
   return 0;
 }
 
+// The sampler step launchers.  What every step kernel needs of the shapes: elems_per_sample a multiple of 4 (a float4 per
+// thread) and, for the Philox kernels, ncdhw_channels 0 or a multiple of 4 that divides it (a quad = four channels of a voxel)
+static bool step_shape_ok(const char* name, int64_t per, int ncdhw_channels = 0) {
+  if (per & 3) {
+    set_error("%s: elems_per_sample must be a multiple of 4", name);
+    return false;
+  }
+  if (ncdhw_channels < 0 || (ncdhw_channels & 3) || (ncdhw_channels > 0 && per % ncdhw_channels)) {
+    set_error("%s: ncdhw_channels must be 0 (channels-last tensors) or a multiple of 4 that divides elems_per_sample",
+              name);
+    return false;
+  }
+  return true;
+}
+static dim3 step_grid(int64_t per, int batch) { return dim3((unsigned)cdiv(per / 4, 256), (unsigned)batch); }
+// A Philox step kernel's instance for the layout and the stream form.  Counter slot 3 is the offset's low half, and its high
+// half goes into the key, so counters stay distinct for any 64-bit stream offset; with row_streams the offset is the
+// 32-bit timestep index (high half 0) and the kernel folds each row's stream into the key instead.
+#define HOLO_LAUNCH_PHILOX_STEP(kernel, ncdhw_channels, row_streams, ...) \
+  do {                                                                    \
+    if (ncdhw_channels && row_streams)                                    \
+      HOLO_LAUNCH((kernel<true, true>), __VA_ARGS__);                     \
+    else if (ncdhw_channels)                                              \
+      HOLO_LAUNCH((kernel<true, false>), __VA_ARGS__);                    \
+    else if (row_streams)                                                 \
+      HOLO_LAUNCH((kernel<false, true>), __VA_ARGS__);                    \
+    else                                                                  \
+      HOLO_LAUNCH((kernel<false, false>), __VA_ARGS__);                   \
+  } while (0)
+
 int ddpm_step_launch(const float* tables, int T, const int64_t* timesteps, int batch, int64_t per, const float* x_t,
                      const float* model_out, const float* noise, int clip, float* sample, float* pred_xstart,
                      void* stream) {
-  if (per & 3) {
-    set_error("ddpm_step: elems_per_sample must be a multiple of 4");
-    return -1;
-  }
-  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
-  HOLO_LAUNCH(ddpm_step_kernel, grid, dim3(256), stream, tables, T, timesteps, per, x_t, model_out, noise, clip, sample,
-              pred_xstart);
+  if (!step_shape_ok("ddpm_step", per)) return -1;
+  HOLO_LAUNCH(ddpm_step_kernel, step_grid(per, batch), dim3(256), stream, tables, T, timesteps, per, x_t, model_out, noise,
+              clip, sample, pred_xstart);
   return 0;
 }
 
 int ddpm_step_philox_launch(const float* tables, int T, const int64_t* timesteps, int batch, int64_t per, const float* x_t,
-                            const float* model_out, uint64_t seed, uint64_t offset, int clip, float* sample,
-                            float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
-  if (per & 3) {
-    set_error("ddpm_step: elems_per_sample must be a multiple of 4");
-    return -1;
-  }
-  if (ncdhw_channels < 0 || (ncdhw_channels & 3) || (ncdhw_channels > 0 && per % ncdhw_channels)) {
-    set_error("ddpm_step_philox: ncdhw_channels must be 0 (channels-last tensors) or a multiple of 4 that divides elems_per_sample");
-    return -1;
-  }
-  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
-  // (the high half of the offset goes into the key: counters stay distinct for any 64-bit stream offset)
+                            const float* model_out, uint64_t seed, const uint32_t* row_streams, uint64_t offset, int clip,
+                            float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
+  if (!step_shape_ok(row_streams ? "ddpm_step_philox_rows" : "ddpm_step_philox", per, ncdhw_channels)) return -1;
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);
-  if (ncdhw_channels)
-    HOLO_LAUNCH(ddpm_step_philox_kernel<true>, grid, dim3(256), stream, tables, T, timesteps, per, x_t, model_out, k0, k1,
-                (uint32_t)offset, clip, sample, pred_xstart, noise_out, ncdhw_channels, nullptr);
-  else
-    HOLO_LAUNCH(ddpm_step_philox_kernel<false>, grid, dim3(256), stream, tables, T, timesteps, per, x_t, model_out, k0, k1,
-                (uint32_t)offset, clip, sample, pred_xstart, noise_out, 0, nullptr);
-  return 0;
-}
-
-int ddpm_step_philox_rows_launch(const float* tables, int T, const int64_t* timesteps, int batch, int64_t per,
-                                 const float* x_t, const float* model_out, uint64_t seed, const uint32_t* row_streams,
-                                 uint32_t timestep_index, int clip, float* sample, float* pred_xstart, float* noise_out,
-                                 int ncdhw_channels, void* stream) {
-  if (per & 3) {
-    set_error("ddpm_step: elems_per_sample must be a multiple of 4");
-    return -1;
-  }
-  if (ncdhw_channels < 0 || (ncdhw_channels & 3) || (ncdhw_channels > 0 && per % ncdhw_channels)) {
-    set_error("ddpm_step_philox_rows: ncdhw_channels must be 0 (channels-last tensors) or a multiple of 4 that divides elems_per_sample");
-    return -1;
-  }
-  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
-  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);  // (the kernel folds each row's stream into k1)
-  if (ncdhw_channels)
-    HOLO_LAUNCH((ddpm_step_philox_kernel<true, true>), grid, dim3(256), stream, tables, T, timesteps, per, x_t, model_out, k0,
-                k1, timestep_index, clip, sample, pred_xstart, noise_out, ncdhw_channels, row_streams);
-  else
-    HOLO_LAUNCH((ddpm_step_philox_kernel<false, true>), grid, dim3(256), stream, tables, T, timesteps, per, x_t, model_out, k0,
-                k1, timestep_index, clip, sample, pred_xstart, noise_out, 0, row_streams);
+  HOLO_LAUNCH_PHILOX_STEP(ddpm_step_philox_kernel, ncdhw_channels, row_streams, step_grid(per, batch), dim3(256), stream,
+                          tables, T, timesteps, per, x_t, model_out, k0, k1, (uint32_t)offset, clip, sample, pred_xstart,
+                          noise_out, ncdhw_channels, row_streams);
   return 0;
 }
 
 int ddim_step_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
                      const float* noise, int clip, float* sample, float* pred_xstart, void* stream) {
-  if (per & 3) {
-    set_error("ddim_step: elems_per_sample must be a multiple of 4");
-    return -1;
-  }
-  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
-  HOLO_LAUNCH(ddim_step_kernel, grid, dim3(256), stream, coefs, per, x_t, model_out, noise, clip, sample, pred_xstart);
+  if (!step_shape_ok("ddim_step", per)) return -1;
+  HOLO_LAUNCH(ddim_step_kernel, step_grid(per, batch), dim3(256), stream, coefs, per, x_t, model_out, noise, clip, sample,
+              pred_xstart);
   return 0;
 }
 
 int ddim_step_philox_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
-                            uint64_t seed, uint64_t offset, int clip, float* sample, float* pred_xstart, float* noise_out,
-                            int ncdhw_channels, void* stream) {
-  if (per & 3) {
-    set_error("ddim_step: elems_per_sample must be a multiple of 4");
-    return -1;
-  }
-  if (ncdhw_channels < 0 || (ncdhw_channels & 3) || (ncdhw_channels > 0 && per % ncdhw_channels)) {
-    set_error("ddim_step_philox: ncdhw_channels must be 0 (channels-last tensors) or a multiple of 4 that divides elems_per_sample");
-    return -1;
-  }
-  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
+                            uint64_t seed, const uint32_t* row_streams, uint64_t offset, int clip, float* sample,
+                            float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
+  if (!step_shape_ok(row_streams ? "ddim_step_philox_rows" : "ddim_step_philox", per, ncdhw_channels)) return -1;
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);  // (as ddpm_step_philox)
-  if (ncdhw_channels)
-    HOLO_LAUNCH(ddim_step_philox_kernel<true>, grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
-                (uint32_t)offset, clip, sample, pred_xstart, noise_out, ncdhw_channels, nullptr);
-  else
-    HOLO_LAUNCH(ddim_step_philox_kernel<false>, grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
-                (uint32_t)offset, clip, sample, pred_xstart, noise_out, 0, nullptr);
-  return 0;
-}
-
-int ddim_step_philox_rows_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
-                                 uint64_t seed, const uint32_t* row_streams, uint32_t timestep_index, int clip,
-                                 float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
-  if (per & 3) {
-    set_error("ddim_step: elems_per_sample must be a multiple of 4");
-    return -1;
-  }
-  if (ncdhw_channels < 0 || (ncdhw_channels & 3) || (ncdhw_channels > 0 && per % ncdhw_channels)) {
-    set_error("ddim_step_philox_rows: ncdhw_channels must be 0 (channels-last tensors) or a multiple of 4 that divides elems_per_sample");
-    return -1;
-  }
-  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
-  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);  // (as ddpm_step_philox_rows)
-  if (ncdhw_channels)
-    HOLO_LAUNCH((ddim_step_philox_kernel<true, true>), grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
-                timestep_index, clip, sample, pred_xstart, noise_out, ncdhw_channels, row_streams);
-  else
-    HOLO_LAUNCH((ddim_step_philox_kernel<false, true>), grid, dim3(256), stream, coefs, per, x_t, model_out, k0, k1,
-                timestep_index, clip, sample, pred_xstart, noise_out, 0, row_streams);
+  HOLO_LAUNCH_PHILOX_STEP(ddim_step_philox_kernel, ncdhw_channels, row_streams, step_grid(per, batch), dim3(256), stream,
+                          coefs, per, x_t, model_out, k0, k1, (uint32_t)offset, clip, sample, pred_xstart, noise_out,
+                          ncdhw_channels, row_streams);
   return 0;
 }
 
 int dpm_step_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
                     const float* hist1, const float* hist2, int clip, float* sample, float* pred_xstart, void* stream) {
-  if (per & 3) {
-    set_error("dpm_step: elems_per_sample must be a multiple of 4");
-    return -1;
-  }
-  dim3 grid((unsigned)cdiv(per / 4, 256), (unsigned)batch);
-  HOLO_LAUNCH(dpm_step_kernel, grid, dim3(256), stream, coefs, per, x_t, model_out, hist1, hist2, clip, sample,
-              pred_xstart);
+  if (!step_shape_ok("dpm_step", per)) return -1;
+  HOLO_LAUNCH(dpm_step_kernel, step_grid(per, batch), dim3(256), stream, coefs, per, x_t, model_out, hist1, hist2, clip,
+              sample, pred_xstart);
   return 0;
 }
 

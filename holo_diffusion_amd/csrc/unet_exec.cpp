@@ -1603,6 +1603,16 @@ int run_backward(const HoloUnet* u, const TrainPlan& tp, const float* grad_out, 
   return 0;
 }
 
+// The sampler step entries (holo_*_step*, include/holo_abi.h): each names the pointers it needs, then its launcher checks the shapes
+template <class Launch>
+int step_entry(const char* entry, bool args_ok, Launch launch) {
+  if (!args_ok) {
+    set_error("%s: null/invalid argument", entry);
+    return HOLO_E_INVALID;
+  }
+  return launch() ? HOLO_E_INVALID : 0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -2237,102 +2247,76 @@ int holo_unet_adam_step(HoloUnet* net, const HoloAdamTensor* tensors, int n, con
   return 0;
 }
 
-int holo_ddpm_step(HoloCtx* ctx, const float* tables, int num_timesteps, const int64_t* timesteps, int batch,
+int holo_ddpm_step(HoloCtx*, const float* tables, int num_timesteps, const int64_t* timesteps, int batch,
                    int64_t elems_per_sample, const float* x_t, const float* model_out, const float* noise,
                    int clip_denoised, float* sample, float* pred_xstart, void* stream) {
-  if (!tables || !timesteps || !x_t || !model_out || !noise || !sample || !pred_xstart || batch < 1) {
-    set_error("holo_ddpm_step: null/invalid argument");
-    return HOLO_E_INVALID;
-  }
-  (void)ctx;
-  int rc = ddpm_step_launch(tables, num_timesteps, timesteps, batch, elems_per_sample, x_t, model_out, noise,
-                            clip_denoised, sample, pred_xstart, stream);
-  return rc ? HOLO_E_INVALID : 0;
+  return step_entry("holo_ddpm_step",
+                    tables && timesteps && x_t && model_out && noise && sample && pred_xstart && batch >= 1, [&] {
+    return ddpm_step_launch(tables, num_timesteps, timesteps, batch, elems_per_sample, x_t, model_out, noise, clip_denoised,
+                            sample, pred_xstart, stream);
+  });
 }
 
-int holo_ddpm_step_philox(HoloCtx* ctx, const float* tables, int num_timesteps, const int64_t* timesteps, int batch,
+int holo_ddpm_step_philox(HoloCtx*, const float* tables, int num_timesteps, const int64_t* timesteps, int batch,
                           int64_t elems_per_sample, const float* x_t, const float* model_out, uint64_t seed,
                           uint64_t stream_offset, int clip_denoised, float* sample, float* pred_xstart, float* noise_out,
                           int ncdhw_channels, void* stream) {
-  if (!tables || !timesteps || !x_t || !model_out || !sample || batch < 1) {
-    set_error("holo_ddpm_step_philox: null/invalid argument");
-    return HOLO_E_INVALID;
-  }
-  (void)ctx;
-  int rc = ddpm_step_philox_launch(tables, num_timesteps, timesteps, batch, elems_per_sample, x_t, model_out, seed,
+  return step_entry("holo_ddpm_step_philox", tables && timesteps && x_t && model_out && sample && batch >= 1, [&] {
+    return ddpm_step_philox_launch(tables, num_timesteps, timesteps, batch, elems_per_sample, x_t, model_out, seed, nullptr,
                                    stream_offset, clip_denoised, sample, pred_xstart, noise_out, ncdhw_channels, stream);
-  return rc ? HOLO_E_INVALID : 0;
+  });
 }
 
-int holo_ddpm_step_philox_rows(HoloCtx* ctx, const float* tables, int num_timesteps, const int64_t* timesteps, int batch,
+int holo_ddpm_step_philox_rows(HoloCtx*, const float* tables, int num_timesteps, const int64_t* timesteps, int batch,
                                int64_t elems_per_sample, const float* x_t, const float* model_out, uint64_t seed,
                                const uint32_t* row_streams, uint32_t timestep_index, int clip_denoised, float* sample,
                                float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
-  if (!tables || !timesteps || !x_t || !model_out || !row_streams || !sample || batch < 1) {
-    set_error("holo_ddpm_step_philox_rows: null/invalid argument");
-    return HOLO_E_INVALID;
-  }
-  (void)ctx;
-  int rc = ddpm_step_philox_rows_launch(tables, num_timesteps, timesteps, batch, elems_per_sample, x_t, model_out, seed,
-                                        row_streams, timestep_index, clip_denoised, sample, pred_xstart, noise_out,
-                                        ncdhw_channels, stream);
-  return rc ? HOLO_E_INVALID : 0;
+  return step_entry("holo_ddpm_step_philox_rows",
+                    tables && timesteps && x_t && model_out && row_streams && sample && batch >= 1, [&] {
+    return ddpm_step_philox_launch(tables, num_timesteps, timesteps, batch, elems_per_sample, x_t, model_out, seed,
+                                   row_streams, timestep_index, clip_denoised, sample, pred_xstart, noise_out,
+                                   ncdhw_channels, stream);
+  });
 }
 
 // gaussian_diffusion.py:645-727 (ddim_sample / ddim_reverse_sample, the elementwise tail)
-int holo_ddim_step(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+int holo_ddim_step(HoloCtx*, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
                    const float* model_out, const float* noise, int clip_denoised, float* sample, float* pred_xstart,
                    void* stream) {
-  if (!coefs || !x_t || !model_out || !sample || batch < 1 || elems_per_sample < 4) {
-    set_error("holo_ddim_step: null/invalid argument");
-    return HOLO_E_INVALID;
-  }
-  (void)ctx;
-  int rc = ddim_step_launch(coefs, batch, elems_per_sample, x_t, model_out, noise, clip_denoised, sample, pred_xstart,
-                            stream);
-  return rc ? HOLO_E_INVALID : 0;
+  return step_entry("holo_ddim_step", coefs && x_t && model_out && sample && batch >= 1 && elems_per_sample >= 4, [&] {
+    return ddim_step_launch(coefs, batch, elems_per_sample, x_t, model_out, noise, clip_denoised, sample, pred_xstart, stream);
+  });
 }
 
 // gaussian_diffusion.py:645-693 with the noise of :685 drawn in the kernel
-int holo_ddim_step_philox(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+int holo_ddim_step_philox(HoloCtx*, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
                           const float* model_out, uint64_t seed, uint64_t stream_offset, int clip_denoised, float* sample,
                           float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
-  if (!coefs || !x_t || !model_out || !sample || batch < 1 || elems_per_sample < 4) {
-    set_error("holo_ddim_step_philox: null/invalid argument");
-    return HOLO_E_INVALID;
-  }
-  (void)ctx;
-  int rc = ddim_step_philox_launch(coefs, batch, elems_per_sample, x_t, model_out, seed, stream_offset, clip_denoised,
+  return step_entry("holo_ddim_step_philox", coefs && x_t && model_out && sample && batch >= 1 && elems_per_sample >= 4, [&] {
+    return ddim_step_philox_launch(coefs, batch, elems_per_sample, x_t, model_out, seed, nullptr, stream_offset, clip_denoised,
                                    sample, pred_xstart, noise_out, ncdhw_channels, stream);
-  return rc ? HOLO_E_INVALID : 0;
+  });
 }
 
-int holo_ddim_step_philox_rows(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+int holo_ddim_step_philox_rows(HoloCtx*, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
                                const float* model_out, uint64_t seed, const uint32_t* row_streams, uint32_t timestep_index,
                                int clip_denoised, float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels,
                                void* stream) {
-  if (!coefs || !x_t || !model_out || !row_streams || !sample || batch < 1 || elems_per_sample < 4) {
-    set_error("holo_ddim_step_philox_rows: null/invalid argument");
-    return HOLO_E_INVALID;
-  }
-  (void)ctx;
-  int rc = ddim_step_philox_rows_launch(coefs, batch, elems_per_sample, x_t, model_out, seed, row_streams, timestep_index,
-                                        clip_denoised, sample, pred_xstart, noise_out, ncdhw_channels, stream);
-  return rc ? HOLO_E_INVALID : 0;
+  return step_entry("holo_ddim_step_philox_rows",
+                    coefs && x_t && model_out && row_streams && sample && batch >= 1 && elems_per_sample >= 4, [&] {
+    return ddim_step_philox_launch(coefs, batch, elems_per_sample, x_t, model_out, seed, row_streams, timestep_index,
+                                   clip_denoised, sample, pred_xstart, noise_out, ncdhw_channels, stream);
+  });
 }
 
 // DPM-Solver++ multistep update (the elementwise tail of ImplicitronGaussianDiffusion.dpm_sample_loop*)
-int holo_dpm_step(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+int holo_dpm_step(HoloCtx*, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
                   const float* model_out, const float* hist1, const float* hist2, int clip_denoised, float* sample,
                   float* pred_xstart, void* stream) {
-  if (!coefs || !x_t || !model_out || !sample || batch < 1 || elems_per_sample < 4) {
-    set_error("holo_dpm_step: null/invalid argument");
-    return HOLO_E_INVALID;
-  }
-  (void)ctx;
-  int rc = dpm_step_launch(coefs, batch, elems_per_sample, x_t, model_out, hist1, hist2, clip_denoised, sample,
-                           pred_xstart, stream);
-  return rc ? HOLO_E_INVALID : 0;
+  return step_entry("holo_dpm_step", coefs && x_t && model_out && sample && batch >= 1 && elems_per_sample >= 4, [&] {
+    return dpm_step_launch(coefs, batch, elems_per_sample, x_t, model_out, hist1, hist2, clip_denoised, sample, pred_xstart,
+                           stream);
+  });
 }
 
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream) {

@@ -21,6 +21,12 @@ DPM-Solver++ (``dpm_schedule``, ``dpm_coefs``, ``dpm_sample_loop*``; build-side 
 multistep exponential integrator in log-SNR on the clipped x_0 prediction, orders 1-3, one model call per step.  Each step's
 update is expanded on the host, in float64, into four scalars per sample; a third fused kernel (``holo_dpm_step``) applies
 them to x_t, the model output and the previous two predictions.
+
+What the samplers share is written once.  ``_chain`` is the chain loop: x_T, the one upload of the chain's timesteps and rows,
+the choice of the channels-last layout, then model call, step, yield.  A sampler is its schedule, its host rows and a step
+callback; ``_last_sample`` finishes the non-progressive loops.  ``_launch`` and ``_launch_device_noise`` are the two ways into
+the library's step entries (plain, and with the noise drawn in the kernel: offset or per-row streams); ``_step``,
+``_step_device_noise``, ``_ddim_step``, ``_ddim_step_device_noise`` and ``_dpm_step`` name the entry and its leading arguments.
 """
 from __future__ import annotations
 
@@ -117,6 +123,7 @@ class ImplicitronGaussianDiffusion(Configurable):
         self._build_tables(betas)
         self._schedule_sampler = UniformSampler(self.num_timesteps)
         self._dev_tables: Dict[int, torch.Tensor] = {}
+        self._row_stream_tables: Dict[tuple, torch.Tensor] = {}
 
     # gaussian_diffusion.py:149-187
     def _build_tables(self, betas: np.ndarray) -> None:
@@ -164,22 +171,57 @@ class ImplicitronGaussianDiffusion(Configurable):
                 + self._extract(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
 
     # ---- reverse process -----------------------------------------------------------------------
-    def _step(self, x, t, model_output, noise, clip_denoised):
-        """Fused HIP tail of p_sample: returns (sample, pred_xstart)."""
+    def _launch(self, entry: str, head, x, model_output, extras, clip_denoised, want_pred=True):
+        """One plain step kernel, ``entry`` of the library: (sample, pred_xstart | None).  ``head`` are the entry's arguments
+        between the context and the batch (its table or rows), ``extras`` its optional input tensors after the model output
+        (noise, history): None goes in as a null pointer."""
         runtime.require_device(x, "ImplicitronGaussianDiffusion")
         L = runtime.lib()
         dev = x.device
-        x = x.contiguous()
-        model_output = model_output.contiguous()
-        noise = noise.contiguous()
+        x, model_output = x.contiguous(), model_output.contiguous()
+        extras = [None if e is None else e.contiguous() for e in extras]
         sample = torch.empty_like(x)
-        pred = torch.empty_like(x)
-        per = x[0].numel()
-        _lib.check(L, L.holo_ddpm_step(runtime.ctx(dev), runtime.ptr(self._tables_on(dev)), self.num_timesteps,
-                                       runtime.ptr(t), x.shape[0], per, runtime.ptr(x), runtime.ptr(model_output),
-                                       runtime.ptr(noise), 1 if clip_denoised else 0, runtime.ptr(sample),
-                                       runtime.ptr(pred), runtime.stream_ptr(dev)), "holo_ddpm_step")
+        pred = torch.empty_like(x) if want_pred else None
+        _lib.check(L, getattr(L, entry)(runtime.ctx(dev), *head, x.shape[0], x[0].numel(), runtime.ptr(x),
+                                        runtime.ptr(model_output), *[None if e is None else runtime.ptr(e) for e in extras],
+                                        1 if clip_denoised else 0, runtime.ptr(sample), runtime.ptr(pred) if want_pred else None,
+                                        runtime.stream_ptr(dev)), entry)
         return sample, pred
+
+    def _launch_device_noise(self, entry: str, head, x, model_output, timestep_index: int, clip_denoised, want_pred, want_noise,
+                             channels_last: bool):
+        """One step kernel with in-kernel Philox noise (perf mode): (sample, pred_xstart | None, noise | None).  ``entry`` is the
+        offset form (``holo_*_step_philox``); per-row streams go to its ``_rows`` form.  A draw is keyed on the LOGICAL element
+        (seed, stream, timestep, sample, channel, voxel): ``channels_last`` says which layout ``x`` is in - an (N, R, R, R, C)
+        chain and an (N, C, R, R, R) chain of the same seed draw the same noise (C a multiple of 4; otherwise the NCDHW
+        tensor's memory order is the key)."""
+        runtime.require_device(x, "ImplicitronGaussianDiffusion")
+        L = runtime.lib()
+        dev = x.device
+        x, model_output = x.contiguous(), model_output.contiguous()
+        sample = torch.empty_like(x)
+        pred = torch.empty_like(x) if want_pred else None
+        noise = torch.empty_like(x) if want_noise else None
+        ncdhw = 0 if (channels_last or x.dim() < 3 or x.shape[1] % 4) else int(x.shape[1])
+        rows = self._row_streams(x.shape[0], dev)
+        if rows is not None:  # one stream per row: each row draws its batch-1 chain's noise
+            entry += "_rows"
+            key = (runtime.ptr(rows), int(timestep_index) & 0xFFFFFFFF)
+        else:  # stream offset: (chain id, timestep) - distinct for every step of every chain that shares the seed
+            key = ((int(self.device_noise_stream) << 32) | (int(timestep_index) & 0xFFFFFFFF),)
+        _lib.check(L, getattr(L, entry)(runtime.ctx(dev), *head, x.shape[0], x[0].numel(), runtime.ptr(x),
+                                        runtime.ptr(model_output), int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, *key,
+                                        1 if clip_denoised else 0, runtime.ptr(sample), runtime.ptr(pred) if want_pred else None,
+                                        runtime.ptr(noise) if want_noise else None, ncdhw, runtime.stream_ptr(dev)), entry)
+        return sample, pred, noise
+
+    def _ddpm_head(self, x, t):
+        runtime.require_device(x, "ImplicitronGaussianDiffusion")  # (before the table is looked up on x's device)
+        return runtime.ptr(self._tables_on(x.device)), self.num_timesteps, runtime.ptr(t)
+
+    def _step(self, x, t, model_output, noise, clip_denoised):
+        """Fused HIP tail of p_sample: returns (sample, pred_xstart)."""
+        return self._launch("holo_ddpm_step", self._ddpm_head(x, t), x, model_output, [noise], clip_denoised)
 
     def _row_streams(self, batch: int, device: torch.device) -> Optional[torch.Tensor]:
         """``device_noise_stream`` as a (batch,) uint32 table on ``device`` (held as int32) when it is a sequence - the per-row
@@ -193,7 +235,7 @@ class ImplicitronGaussianDiffusion(Configurable):
         if any(v < 0 or v > 0xFFFFFFFF for v in ids):
             raise ValueError(f"device_noise_stream: stream ids must be in [0, 2^32): {ids}")
         key = (ids, str(device))
-        cache = self.__dict__.setdefault("_row_stream_tables", {})
+        cache = self._row_stream_tables
         t = cache.get(key)
         if t is None:
             cache.clear()
@@ -202,36 +244,9 @@ class ImplicitronGaussianDiffusion(Configurable):
 
     def _step_device_noise(self, x, t, model_output, timestep_index: int, clip_denoised, want_pred=True, want_noise=False,
                            channels_last: bool = False):
-        """The step with in-kernel Philox noise (perf mode): (sample, pred_xstart | None, noise | None).  A draw is keyed on the
-        LOGICAL element (seed, stream, timestep, sample, channel, voxel): ``channels_last`` says which layout ``x`` is in - an
-        (N, R, R, R, C) chain and an (N, C, R, R, R) chain of the same seed draw the same noise (C a multiple of 4; otherwise
-        the NCDHW tensor's memory order is the key)."""
-        runtime.require_device(x, "ImplicitronGaussianDiffusion")
-        L = runtime.lib()
-        dev = x.device
-        x = x.contiguous()
-        model_output = model_output.contiguous()
-        sample = torch.empty_like(x)
-        pred = torch.empty_like(x) if want_pred else None
-        noise = torch.empty_like(x) if want_noise else None
-        ncdhw = 0 if (channels_last or x.dim() < 3 or x.shape[1] % 4) else int(x.shape[1])
-        rows = self._row_streams(x.shape[0], dev)
-        if rows is not None:  # one stream per row: each row draws its batch-1 chain's noise
-            _lib.check(L, L.holo_ddpm_step_philox_rows(
-                runtime.ctx(dev), runtime.ptr(self._tables_on(dev)), self.num_timesteps, runtime.ptr(t), x.shape[0],
-                x[0].numel(), runtime.ptr(x), runtime.ptr(model_output), int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF,
-                runtime.ptr(rows), int(timestep_index) & 0xFFFFFFFF, 1 if clip_denoised else 0, runtime.ptr(sample),
-                runtime.ptr(pred) if want_pred else None, runtime.ptr(noise) if want_noise else None, ncdhw,
-                runtime.stream_ptr(dev)), "holo_ddpm_step_philox_rows")
-            return sample, pred, noise
-        # stream offset: (chain id, timestep) - distinct for every step of every chain that shares the seed
-        offset = (int(self.device_noise_stream) << 32) | (int(timestep_index) & 0xFFFFFFFF)
-        _lib.check(L, L.holo_ddpm_step_philox(
-            runtime.ctx(dev), runtime.ptr(self._tables_on(dev)), self.num_timesteps, runtime.ptr(t), x.shape[0], x[0].numel(),
-            runtime.ptr(x), runtime.ptr(model_output), int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, offset,
-            1 if clip_denoised else 0, runtime.ptr(sample), runtime.ptr(pred) if want_pred else None,
-            runtime.ptr(noise) if want_noise else None, ncdhw, runtime.stream_ptr(dev)), "holo_ddpm_step_philox")
-        return sample, pred, noise
+        """holo_ddpm_step_philox: the step with in-kernel noise, (sample, pred_xstart | None, noise | None)."""
+        return self._launch_device_noise("holo_ddpm_step_philox", self._ddpm_head(x, t), x, model_output,
+                                         timestep_index, clip_denoised, want_pred, want_noise, channels_last)
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         if model_kwargs is None:
@@ -281,27 +296,27 @@ class ImplicitronGaussianDiffusion(Configurable):
                 indices = [indices[int(i)] for i in torch.round(torch.linspace(0, len(indices) - 1, max_iter)).long()]
         return indices
 
-    def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                                  model_kwargs=None, device=None, progress=False, max_iter=None,
-                                  noise_sampler=None, _materialize_every_step: bool = True) -> Iterator[dict]:
-        """``_materialize_every_step`` (internal, used by ``p_sample_loop``): in the channels-last perf chain (below) yield
-        the steps' tensors as NCDHW VIEWS of the channels-last buffers instead of contiguous copies."""
-        if cond_fn is not None:
-            raise NotImplementedError("cond_fn guidance is not supported")
+    def _chain(self, model, shape, indices, rows, step, *, noise=None, noise_sampler=None, device=None, progress=False,
+               denoised_fn=None, model_kwargs=None, channels_last_ok=True, materialize=True) -> Iterator[dict]:
+        """The chain loop of every sampler.  Starts from ``noise``, else ``noise_sampler(T, shape, device)``, else
+        ``torch.randn``; uploads the timesteps ``indices`` and the sampler's host ``rows`` ((steps, batch, 8), or None) once, so
+        that no step talks to the host; then per step k calls the model and ``step(k, x, t, model_output, rows[k] on the
+        device, channels_last)``, which returns the step's dict (its "sample" is the next x; None values stay None).
+        With ``channels_last_ok`` and a plain ``forward_channels_last`` model the chain stays in the library's channels-last
+        layout - the step kernels are elementwise, hence layout-agnostic, and the model runs without its two layout passes -
+        and the dicts are yielded in NCDHW all the same: contiguous copies, or with ``materialize`` off (the non-progressive
+        loops, which convert the last sample only) views of the channels-last buffers."""
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
-        if model_kwargs is None:
-            model_kwargs = {}
         if noise is not None:
             img = noise
         elif noise_sampler is not None:
             img = noise_sampler(self.num_timesteps, shape, device)
         else:
             img = torch.randn(*shape, device=device)
-        indices = self._indices(max_iter)
-        # all timesteps of the chain are uploaded once: no per-step host->device traffic
         ts_all = torch.tensor(indices, dtype=torch.int64, device=device)[:, None].expand(-1, shape[0]).contiguous()
+        rows_all = rows.to(device) if rows is not None else [None] * len(indices)
         it = range(len(indices))
         if progress:
             try:
@@ -309,57 +324,70 @@ class ImplicitronGaussianDiffusion(Configurable):
                 it = tqdm(it)
             except Exception:
                 pass
-        # Perf mode (device_noise_seed): the chain stays in the library's channels-last layout - the step kernel is elementwise,
-        # hence layout-agnostic, and SimpleUnet3D.forward_channels_last runs without its two layout passes: one conversion
-        # at the start of the chain, one per materialised sample (progressive callers get NCDHW-contiguous tensors as ever).
-        use_cl = (self.device_noise_seed is not None and noise_sampler is None and denoised_fn is None and not model_kwargs
-                  and hasattr(model, "forward_channels_last")
+        use_cl = (channels_last_ok and denoised_fn is None and not model_kwargs and hasattr(model, "forward_channels_last")
                   and getattr(model, "in_channels", None) == shape[1] and img.is_cuda)
+        as_ncdhw = lambda a: a  # noqa: E731
         if use_cl:
-            as_ncdhw = (lambda a: a.permute(0, 4, 1, 2, 3).contiguous()) if _materialize_every_step else \
-                (lambda a: a.permute(0, 4, 1, 2, 3))
-            with torch.no_grad():
-                img_cl = img.float().permute(0, 2, 3, 4, 1).contiguous()
-                for k in it:
-                    t = ts_all[k]
-                    out_cl = model.forward_channels_last(img_cl, t)
-                    sample_cl, pred_cl, _ = self._step_device_noise(img_cl, t, out_cl, indices[k], clip_denoised,
-                                                                    channels_last=True)
-                    yield {"sample": as_ncdhw(sample_cl), "pred_xstart": as_ncdhw(pred_cl), "noise": None}
-                    img_cl = sample_cl
-            return
+            as_ncdhw = (lambda a: a.permute(0, 4, 1, 2, 3).contiguous()) if materialize else (lambda a: a.permute(0, 4, 1, 2, 3))
+            img = img.float().permute(0, 2, 3, 4, 1).contiguous()
         with torch.no_grad():
             for k in it:
                 t = ts_all[k]
-                model_output = model(img, t, **model_kwargs)
-                if denoised_fn is not None:
-                    model_output = denoised_fn(model_output)
-                if noise_sampler is None and self.device_noise_seed is not None:  # perf mode (no host sync: indices[k] is host-side)
-                    sample, pred, eps = self._step_device_noise(img, t, model_output, indices[k], clip_denoised)
-                elif noise_sampler is not None:
-                    eps = noise_sampler(indices[k], img.shape, img.device)
-                    sample, pred = self._step(img, t, model_output, eps, clip_denoised)
+                if use_cl:
+                    model_output = model.forward_channels_last(img, t)
                 else:
-                    eps = torch.randn_like(img)
-                    sample, pred = self._step(img, t, model_output, eps, clip_denoised)
-                yield {"sample": sample, "pred_xstart": pred, "noise": eps}
-                img = sample
+                    model_output = self._model_output(model, img, t, denoised_fn, model_kwargs)
+                out = step(k, img, t, model_output, rows_all[k], use_cl)
+                yield {name: None if v is None else as_ncdhw(v) for name, v in out.items()}
+                img = out["sample"]
+
+    @staticmethod
+    def _last_sample(steps: Iterator[dict], keep: Optional[list] = None):
+        """Runs a progressive loop to its end (collecting its dicts in ``keep``): the last sample, made contiguous - the
+        channels-last chain's one conversion at the end."""
+        final = None
+        for out in steps:
+            if keep is not None:
+                keep.append(out)
+            final = out["sample"]
+        if final is not None and not final.is_contiguous():
+            final = final.contiguous()
+        return final
+
+    def _device_noise(self, noise_sampler) -> bool:
+        """Perf mode: the steps draw their noise in the kernel, and the chain may run channels-last."""
+        return noise_sampler is None and self.device_noise_seed is not None
+
+    def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                  model_kwargs=None, device=None, progress=False, max_iter=None,
+                                  noise_sampler=None, _materialize_every_step: bool = True) -> Iterator[dict]:
+        """``_materialize_every_step`` (internal, used by ``p_sample_loop``): see ``_chain``."""
+        if cond_fn is not None:
+            raise NotImplementedError("cond_fn guidance is not supported")
+        indices = self._indices(max_iter)
+        device_noise = self._device_noise(noise_sampler)
+
+        def step(k, img, t, model_output, _, channels_last):
+            if device_noise:  # (no host sync: indices[k] is host-side; "noise": None - it never leaves the kernel)
+                sample, pred, eps = self._step_device_noise(img, t, model_output, indices[k], clip_denoised,
+                                                            channels_last=channels_last)
+            else:
+                eps = noise_sampler(indices[k], img.shape, img.device) if noise_sampler is not None else torch.randn_like(img)
+                sample, pred = self._step(img, t, model_output, eps, clip_denoised)
+            return {"sample": sample, "pred_xstart": pred, "noise": eps}
+
+        yield from self._chain(model, shape, indices, None, step, noise=noise, noise_sampler=noise_sampler, device=device,
+                               progress=progress, denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                               channels_last_ok=device_noise, materialize=_materialize_every_step)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, return_all_samples=False, max_iter=None,
                       noise_sampler=None):
         samples = [] if return_all_samples else None
-        final = None
-        for sample in self.p_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
-                                                     denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                                     model_kwargs=model_kwargs, device=device, progress=progress,
-                                                     max_iter=max_iter, noise_sampler=noise_sampler,
-                                                     _materialize_every_step=return_all_samples):
-            if return_all_samples:
-                samples.append(sample)
-            final = sample["sample"]
-        if final is not None and not final.is_contiguous():
-            final = final.contiguous()  # (the channels-last perf chain: one conversion at the end of the chain)
+        final = self._last_sample(self.p_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+            model_kwargs=model_kwargs, device=device, progress=progress, max_iter=max_iter, noise_sampler=noise_sampler,
+            _materialize_every_step=return_all_samples), samples)
         return (final, samples) if return_all_samples else final
 
     # ---- DDIM (gaussian_diffusion.py:645-815) ----------------------------------------------------
@@ -410,48 +438,14 @@ class ImplicitronGaussianDiffusion(Configurable):
 
     def _ddim_step(self, x, model_output, coefs_dev, noise, clip_denoised, want_pred=True):
         """holo_ddim_step: (sample, pred_xstart | None).  ``coefs_dev`` is the (batch, 8) row block on the device."""
-        runtime.require_device(x, "ImplicitronGaussianDiffusion")
-        L = runtime.lib()
-        dev = x.device
-        x = x.contiguous()
-        model_output = model_output.contiguous()
-        noise = noise.contiguous() if noise is not None else None
-        sample = torch.empty_like(x)
-        pred = torch.empty_like(x) if want_pred else None
-        _lib.check(L, L.holo_ddim_step(runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x),
-                                       runtime.ptr(model_output), runtime.ptr(noise) if noise is not None else None,
-                                       1 if clip_denoised else 0, runtime.ptr(sample),
-                                       runtime.ptr(pred) if want_pred else None, runtime.stream_ptr(dev)), "holo_ddim_step")
-        return sample, pred
+        return self._launch("holo_ddim_step", [runtime.ptr(coefs_dev)], x, model_output, [noise], clip_denoised, want_pred)
 
     def _ddim_step_device_noise(self, x, model_output, coefs_dev, timestep_index: int, clip_denoised, want_pred=True,
                                 want_noise=False, channels_last: bool = False):
         """holo_ddim_step_philox: (sample, pred_xstart | None, noise | None), the draw of ``_step_device_noise`` at the same
         (seed, stream, timestep)."""
-        runtime.require_device(x, "ImplicitronGaussianDiffusion")
-        L = runtime.lib()
-        dev = x.device
-        x = x.contiguous()
-        model_output = model_output.contiguous()
-        sample = torch.empty_like(x)
-        pred = torch.empty_like(x) if want_pred else None
-        noise = torch.empty_like(x) if want_noise else None
-        ncdhw = 0 if (channels_last or x.dim() < 3 or x.shape[1] % 4) else int(x.shape[1])
-        rows = self._row_streams(x.shape[0], dev)
-        if rows is not None:
-            _lib.check(L, L.holo_ddim_step_philox_rows(
-                runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x), runtime.ptr(model_output),
-                int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, runtime.ptr(rows), int(timestep_index) & 0xFFFFFFFF,
-                1 if clip_denoised else 0, runtime.ptr(sample), runtime.ptr(pred) if want_pred else None,
-                runtime.ptr(noise) if want_noise else None, ncdhw, runtime.stream_ptr(dev)), "holo_ddim_step_philox_rows")
-            return sample, pred, noise
-        offset = (int(self.device_noise_stream) << 32) | (int(timestep_index) & 0xFFFFFFFF)
-        _lib.check(L, L.holo_ddim_step_philox(
-            runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x), runtime.ptr(model_output),
-            int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, offset, 1 if clip_denoised else 0, runtime.ptr(sample),
-            runtime.ptr(pred) if want_pred else None, runtime.ptr(noise) if want_noise else None, ncdhw,
-            runtime.stream_ptr(dev)), "holo_ddim_step_philox")
-        return sample, pred, noise
+        return self._launch_device_noise("holo_ddim_step_philox", [runtime.ptr(coefs_dev)], x, model_output, timestep_index,
+                                         clip_denoised, want_pred, want_noise, channels_last)
 
     @staticmethod
     def _per_sample(v, t: torch.Tensor) -> np.ndarray:
@@ -508,76 +502,36 @@ class ImplicitronGaussianDiffusion(Configurable):
         the whole chain are built on the host and uploaded once."""
         if cond_fn is not None:
             raise NotImplementedError("cond_fn guidance is not supported")
-        if device is None:
-            device = next(model.parameters()).device
-        assert isinstance(shape, (tuple, list))
-        if model_kwargs is None:
-            model_kwargs = {}
-        if noise is not None:
-            img = noise
-        elif noise_sampler is not None:
-            img = noise_sampler(self.num_timesteps, shape, device)
-        else:
-            img = torch.randn(*shape, device=device)
         indices = self.ddim_schedule(ddim_steps, timesteps)
         B = shape[0]
         rows = torch.stack([self.ddim_coefs([t] * B, [t_prev] * B, eta)
                             for t, t_prev in zip(indices, indices[1:] + [-1])])  # (steps, B, 8)
         noisy = (rows[:, :, 4] != 0).any(dim=1).tolist()
-        # the chain's timesteps and coefficient rows are uploaded once: no per-step host->device traffic
-        coefs_all = rows.to(device)
-        ts_all = torch.tensor(indices, dtype=torch.int64, device=device)[:, None].expand(-1, B).contiguous()
-        it = range(len(indices))
-        if progress:
-            try:
-                from tqdm.auto import tqdm
-                it = tqdm(it)
-            except Exception:
-                pass
-        use_cl = (self.device_noise_seed is not None and noise_sampler is None and denoised_fn is None and not model_kwargs
-                  and hasattr(model, "forward_channels_last")
-                  and getattr(model, "in_channels", None) == shape[1] and img.is_cuda)
-        if use_cl:
-            as_ncdhw = (lambda a: a.permute(0, 4, 1, 2, 3).contiguous()) if _materialize_every_step else \
-                (lambda a: a.permute(0, 4, 1, 2, 3))
-            with torch.no_grad():
-                img_cl = img.float().permute(0, 2, 3, 4, 1).contiguous()
-                for k in it:
-                    out_cl = model.forward_channels_last(img_cl, ts_all[k])
-                    sample_cl, pred_cl, _ = self._ddim_step_device_noise(img_cl, out_cl, coefs_all[k], indices[k],
-                                                                         clip_denoised, channels_last=True)
-                    yield {"sample": as_ncdhw(sample_cl), "pred_xstart": as_ncdhw(pred_cl)}
-                    img_cl = sample_cl
-            return
-        with torch.no_grad():
-            for k in it:
-                t = ts_all[k]
-                model_output = self._model_output(model, img, t, denoised_fn, model_kwargs)
-                if noise_sampler is None and self.device_noise_seed is not None:
-                    sample, pred, _ = self._ddim_step_device_noise(img, model_output, coefs_all[k], indices[k],
-                                                                   clip_denoised)
-                else:
-                    eps = None
-                    if noisy[k]:
-                        eps = noise_sampler(indices[k], img.shape, img.device) if noise_sampler is not None else \
-                            torch.randn_like(img)
-                    sample, pred = self._ddim_step(img, model_output, coefs_all[k], eps, clip_denoised)
-                yield {"sample": sample, "pred_xstart": pred}
-                img = sample
+        device_noise = self._device_noise(noise_sampler)
+
+        def step(k, img, t, model_output, coefs, channels_last):
+            if device_noise:
+                sample, pred, _ = self._ddim_step_device_noise(img, model_output, coefs, indices[k], clip_denoised,
+                                                               channels_last=channels_last)
+            else:
+                eps = None
+                if noisy[k]:
+                    eps = noise_sampler(indices[k], img.shape, img.device) if noise_sampler is not None else \
+                        torch.randn_like(img)
+                sample, pred = self._ddim_step(img, model_output, coefs, eps, clip_denoised)
+            return {"sample": sample, "pred_xstart": pred}
+
+        yield from self._chain(model, shape, indices, rows, step, noise=noise, noise_sampler=noise_sampler, device=device,
+                               progress=progress, denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                               channels_last_ok=device_noise, materialize=_materialize_every_step)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, ddim_steps=None, timesteps=None,
                          noise_sampler=None):
-        final = None
-        for sample in self.ddim_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
-                                                        denoised_fn=denoised_fn, cond_fn=cond_fn,
-                                                        model_kwargs=model_kwargs, device=device, progress=progress,
-                                                        eta=eta, ddim_steps=ddim_steps, timesteps=timesteps,
-                                                        noise_sampler=noise_sampler, _materialize_every_step=False):
-            final = sample["sample"]
-        if final is not None and not final.is_contiguous():
-            final = final.contiguous()  # (the channels-last perf chain: one conversion at the end of the chain)
-        return final
+        return self._last_sample(self.ddim_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+            model_kwargs=model_kwargs, device=device, progress=progress, eta=eta, ddim_steps=ddim_steps, timesteps=timesteps,
+            noise_sampler=noise_sampler, _materialize_every_step=False))
 
     def ddim_reverse_sample_loop(self, model, x0, ddim_steps=None, timesteps=None, clip_denoised=True, denoised_fn=None,
                                  model_kwargs=None) -> torch.Tensor:
@@ -587,14 +541,12 @@ class ImplicitronGaussianDiffusion(Configurable):
         B = x0.shape[0]
         rows = torch.stack([self.ddim_coefs([t] * B, [t_next] * B, reverse=True)
                             for t, t_next in zip(indices, indices[1:] + [self.num_timesteps])])
-        coefs_all = rows.to(x0.device)
-        ts_all = torch.tensor(indices, dtype=torch.int64, device=x0.device)[:, None].expand(-1, B).contiguous()
-        img = x0
-        with torch.no_grad():
-            for k in range(len(indices)):
-                model_output = self._model_output(model, img, ts_all[k], denoised_fn, model_kwargs)
-                img, _ = self._ddim_step(img, model_output, coefs_all[k], None, clip_denoised, want_pred=False)
-        return img
+
+        def step(k, img, t, model_output, coefs, channels_last):
+            return {"sample": self._ddim_step(img, model_output, coefs, None, clip_denoised, want_pred=False)[0]}
+
+        return self._last_sample(self._chain(model, tuple(x0.shape), indices, rows, step, noise=x0, device=x0.device,
+                                             denoised_fn=denoised_fn, model_kwargs=model_kwargs, channels_last_ok=False))
 
     # ---- DPM-Solver++ multistep (build-side extension; Lu et al. 2022, arXiv:2211.01095, Algorithm 2 and its order-3 form) ----
     def log_snr(self) -> np.ndarray:
@@ -675,21 +627,7 @@ class ImplicitronGaussianDiffusion(Configurable):
     def _dpm_step(self, x, model_output, coefs_dev, hist1, hist2, clip_denoised, want_pred=True):
         """holo_dpm_step: (sample, pred_xstart | None).  ``coefs_dev`` is the (batch, 8) row block on the device; ``hist1`` /
         ``hist2`` (the previous two steps' pred_xstart) may be None: the term is dropped."""
-        runtime.require_device(x, "ImplicitronGaussianDiffusion")
-        L = runtime.lib()
-        dev = x.device
-        x = x.contiguous()
-        model_output = model_output.contiguous()
-        hist1 = hist1.contiguous() if hist1 is not None else None
-        hist2 = hist2.contiguous() if hist2 is not None else None
-        sample = torch.empty_like(x)
-        pred = torch.empty_like(x) if want_pred else None
-        _lib.check(L, L.holo_dpm_step(runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x),
-                                      runtime.ptr(model_output), runtime.ptr(hist1) if hist1 is not None else None,
-                                      runtime.ptr(hist2) if hist2 is not None else None, 1 if clip_denoised else 0,
-                                      runtime.ptr(sample), runtime.ptr(pred) if want_pred else None,
-                                      runtime.stream_ptr(dev)), "holo_dpm_step")
-        return sample, pred
+        return self._launch("holo_dpm_step", [runtime.ptr(coefs_dev)], x, model_output, [hist1, hist2], clip_denoised, want_pred)
 
     def dpm_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                                     device=None, progress=False, steps=None, order=2, spacing="logsnr", timesteps=None,
@@ -704,61 +642,25 @@ class ImplicitronGaussianDiffusion(Configurable):
             raise NotImplementedError("cond_fn guidance is not supported")
         indices = self.dpm_schedule(steps, spacing, timesteps)
         rows, orders = self.dpm_coefs(indices, order, lower_order_final)
-        if device is None:
-            device = next(model.parameters()).device
-        assert isinstance(shape, (tuple, list))
-        if model_kwargs is None:
-            model_kwargs = {}
-        if noise is not None:
-            img = noise
-        elif noise_sampler is not None:
-            img = noise_sampler(self.num_timesteps, shape, device)
-        else:
-            img = torch.randn(*shape, device=device)
-        B = shape[0]
-        # the chain's timesteps and coefficient rows are uploaded once: no per-step host->device traffic
-        coefs_all = rows[:, None, :].expand(-1, B, -1).contiguous().to(device)  # (steps, B, 8)
-        ts_all = torch.tensor(indices, dtype=torch.int64, device=device)[:, None].expand(-1, B).contiguous()
-        it = range(len(indices))
-        if progress:
-            try:
-                from tqdm.auto import tqdm
-                it = tqdm(it)
-            except Exception:
-                pass
-        use_cl = (denoised_fn is None and not model_kwargs and hasattr(model, "forward_channels_last")
-                  and getattr(model, "in_channels", None) == shape[1] and img.is_cuda)
-        as_out = lambda a: a  # noqa: E731
-        if use_cl:
-            as_out = (lambda a: a.permute(0, 4, 1, 2, 3).contiguous()) if _materialize_every_step else \
-                (lambda a: a.permute(0, 4, 1, 2, 3))
-            img = img.float().permute(0, 2, 3, 4, 1).contiguous()
-        hist1 = hist2 = None  # the predictions of the previous two steps, in the chain's layout
-        with torch.no_grad():
-            for k in it:
-                if use_cl:
-                    model_output = model.forward_channels_last(img, ts_all[k])
-                else:
-                    model_output = self._model_output(model, img, ts_all[k], denoised_fn, model_kwargs)
-                sample, pred = self._dpm_step(img, model_output, coefs_all[k], hist1 if orders[k] >= 2 else None,
-                                              hist2 if orders[k] >= 3 else None, clip_denoised)
-                yield {"sample": as_out(sample), "pred_xstart": as_out(pred)}
-                img, hist1, hist2 = sample, pred, hist1
+        hist = [None, None]  # the predictions of the previous two steps, in the chain's layout
+
+        def step(k, img, t, model_output, coefs, channels_last):
+            sample, pred = self._dpm_step(img, model_output, coefs, hist[0] if orders[k] >= 2 else None,
+                                          hist[1] if orders[k] >= 3 else None, clip_denoised)
+            hist[:] = pred, hist[0]
+            return {"sample": sample, "pred_xstart": pred}
+
+        yield from self._chain(model, shape, indices, rows[:, None, :].expand(-1, shape[0], -1).contiguous(), step, noise=noise,
+                               noise_sampler=noise_sampler, device=device, progress=progress, denoised_fn=denoised_fn,
+                               model_kwargs=model_kwargs, materialize=_materialize_every_step)
 
     def dpm_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None, device=None,
                         progress=False, steps=None, order=2, spacing="logsnr", timesteps=None, lower_order_final=True,
                         noise_sampler=None, cond_fn=None):
-        final = None
-        for sample in self.dpm_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
-                                                       denoised_fn=denoised_fn, model_kwargs=model_kwargs, device=device,
-                                                       progress=progress, steps=steps, order=order, spacing=spacing,
-                                                       timesteps=timesteps, lower_order_final=lower_order_final,
-                                                       noise_sampler=noise_sampler, cond_fn=cond_fn,
-                                                       _materialize_every_step=False):
-            final = sample["sample"]
-        if final is not None and not final.is_contiguous():
-            final = final.contiguous()  # (the channels-last chain: one conversion at the end of the chain)
-        return final
+        return self._last_sample(self.dpm_sample_loop_progressive(
+            model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+            device=device, progress=progress, steps=steps, order=order, spacing=spacing, timesteps=timesteps,
+            lower_order_final=lower_order_final, noise_sampler=noise_sampler, cond_fn=cond_fn, _materialize_every_step=False))
 
     def training_losses(self, *args, **kwargs):
         raise NotImplementedError("training losses are outside the sampling hot path (SURVEY.md §8f)")

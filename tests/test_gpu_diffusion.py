@@ -67,6 +67,36 @@ def test_step_kernel_bit_exact_vs_oracle(gu):
         torch.testing.assert_close(pmv[k].cpu(), refm[k], rtol=1e-6, atol=1e-7)
 
 
+def test_ddpm_step_arithmetic_is_pinned(gu):
+    """What holo_ddpm_step computes, bit for bit: pred_xstart is the clamp (or the model output), and
+    sample = fma(sigma, noise, fma(c2, x, c1 * pred)) - the product c1 * pred rounded, the other two fused into the sums
+    (the reference rounds all three; DESIGN.md, "Sampling").  With zero noise the sigma term adds +0, so the device expf
+    plays no part.  The inner fma is stated through float64: c2 * x is exact there, and one float64 sum rounded to float32
+    equals the exactly rounded fma unless an element sits on a double-rounding tie.  No element of this fixture does:
+    checked once on the CPU with fractions.Fraction, all 8192 (timestep, clip, element) cases; the separately rounded
+    products differ from it in 1346 of them, so the test tells the two apart."""
+    diff = hda.ImplicitronGaussianDiffusion()
+    shape = (2, 8, 4, 4, 4)
+    x, mo = (torch.from_numpy(np_noise(s, shape)) for s in (1, 2))
+    mo = mo * 1.5  # (so that the clamp acts)
+    tab = diff._tables_on(gu.DEV).cpu().numpy()
+    assert tab.dtype == np.float32
+    zero = torch.zeros(shape, device=gu.DEV)
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)  # noqa: E731
+    for pair in ((999, 998), (500, 499), (1, 0), (0, 0)):
+        c1, c2 = (tab[list(pair), k].reshape(2, 1, 1, 1, 1) for k in (0, 1))
+        for clip in (True, False):
+            s, p = diff._step(x.to(gu.DEV), torch.tensor(pair, device=gu.DEV), mo.to(gu.DEV), zero, clip)
+            m = np.clip(mo.numpy(), -1, 1) if clip else mo.numpy()
+            want = (c2.astype(np.float64) * x.numpy().astype(np.float64) + (c1 * m).astype(np.float64)).astype(np.float32)
+            want = want + np.float32(0)
+            assert m.dtype == np.float32 and want.dtype == np.float32
+            n_pred = int((bits(p.cpu().numpy()) != bits(m)).sum())
+            n_sample = int((bits(s.cpu().numpy()) != bits(want)).sum())
+            print(f"t={pair} clip={clip}: pred_xstart differs in {n_pred}, sample in {n_sample} of {want.size} elements")
+            assert n_pred == 0 and n_sample == 0, (pair, clip, n_pred, n_sample)
+
+
 def test_default_noise_path_runs_and_is_seeded(gu):
     net, _ = gu.make_unet(TINY_CFG)
     diff = hda.ImplicitronGaussianDiffusion()
