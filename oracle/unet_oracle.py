@@ -1,4 +1,5 @@
-"""CPU restatement (torch CPU ops, fp32) of the reference 3D UNet denoiser.
+"""CPU restatement (torch CPU ops, fp32) of the reference 3D UNet denoiser; in float64 on request
+(``unet_forward(..., dtype=torch.float64)``).
 
 TEST INFRASTRUCTURE — see ``oracle/__init__.py``.  Functional form: the network
 is described by a ``UNetCfg`` and a flat ``state_dict`` that uses the reference's
@@ -166,28 +167,30 @@ def timestep_embedding(timesteps: torch.Tensor, dim: int, max_period: int = 1000
     return emb
 
 
-def group_norm32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """nn.py:23-25,99-106: GroupNorm(32, C), fp32, eps 1e-5."""
-    return F.group_norm(x.float(), 32, w, b, eps=1e-5).type(x.dtype)
+def group_norm32(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """nn.py:23-25,99-106: GroupNorm(32, C), fp32 (``dtype``), eps 1e-5."""
+    return F.group_norm(x.to(dtype), 32, w, b, eps=1e-5).type(x.dtype)
 
 
-def time_embed(sd, cfg: UNetCfg, t: torch.Tensor) -> torch.Tensor:
-    """unet.py:645-650, 813."""
-    e = timestep_embedding(t, cfg.model_channels)
+def time_embed(sd, cfg: UNetCfg, t: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """unet.py:645-650, 813.  The sinusoid table is the reference's fp32 one in every ``dtype`` (it is the MLP's input:
+    fp32 frequencies times t <= 1000 differ from the exact ones by up to 6e-5 in the argument, which is no rounding
+    of the net)."""
+    e = timestep_embedding(t, cfg.model_channels).to(dtype)
     e = F.linear(e, sd["time_embed.0.weight"], sd["time_embed.0.bias"])
     e = F.silu(e)
     return F.linear(e, sd["time_embed.2.weight"], sd["time_embed.2.bias"])
 
 
-def res_block(sd, p: str, x: torch.Tensor, emb: torch.Tensor) -> torch.Tensor:
+def res_block(sd, p: str, x: torch.Tensor, emb: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
     """unet.py:236-256 with use_scale_shift_norm=True, no up/down, dropout 0."""
-    h = group_norm32(x, sd[p + ".in_layers.0.weight"], sd[p + ".in_layers.0.bias"])
+    h = group_norm32(x, sd[p + ".in_layers.0.weight"], sd[p + ".in_layers.0.bias"], dtype)
     h = F.silu(h)
     h = F.conv3d(h, sd[p + ".in_layers.2.weight"], sd[p + ".in_layers.2.bias"], padding=1)
     e = F.linear(F.silu(emb), sd[p + ".emb_layers.1.weight"], sd[p + ".emb_layers.1.bias"])
     e = e[..., None, None, None]
     scale, shift = torch.chunk(e, 2, dim=1)
-    h = group_norm32(h, sd[p + ".out_layers.0.weight"], sd[p + ".out_layers.0.bias"]) * (1 + scale) + shift
+    h = group_norm32(h, sd[p + ".out_layers.0.weight"], sd[p + ".out_layers.0.bias"], dtype) * (1 + scale) + shift
     h = F.silu(h)
     h = F.conv3d(h, sd[p + ".out_layers.3.weight"], sd[p + ".out_layers.3.bias"], padding=1)
     if (p + ".skip_connection.weight") in sd:
@@ -195,18 +198,18 @@ def res_block(sd, p: str, x: torch.Tensor, emb: torch.Tensor) -> torch.Tensor:
     return x + h
 
 
-def attention_block(sd, p: str, x: torch.Tensor, num_heads: int) -> torch.Tensor:
+def attention_block(sd, p: str, x: torch.Tensor, num_heads: int, dtype=torch.float32) -> torch.Tensor:
     """unet.py:396-406 + QKVAttentionLegacy :436-455 (heads split before q/k/v)."""
     b, c, *spatial = x.shape
     xf = x.reshape(b, c, -1)
-    qkv = F.conv1d(group_norm32(xf, sd[p + ".norm.weight"], sd[p + ".norm.bias"]),
+    qkv = F.conv1d(group_norm32(xf, sd[p + ".norm.weight"], sd[p + ".norm.bias"], dtype),
                    sd[p + ".qkv.weight"], sd[p + ".qkv.bias"])
     bs, width, length = qkv.shape
     ch = width // (3 * num_heads)
     q, k, v = qkv.reshape(bs * num_heads, ch * 3, length).split(ch, dim=1)
     scale = 1 / math.sqrt(math.sqrt(ch))
     weight = torch.einsum("bct,bcs->bts", q * scale, k * scale)
-    weight = torch.softmax(weight.float(), dim=-1).type(weight.dtype)
+    weight = torch.softmax(weight.to(dtype), dim=-1).type(weight.dtype)
     a = torch.einsum("bts,bcs->bct", weight, v).reshape(bs, -1, length)
     h = F.conv1d(a, sd[p + ".proj_out.weight"], sd[p + ".proj_out.bias"])
     return (xf + h).reshape(b, c, *spatial)
@@ -228,14 +231,14 @@ def upsample(sd, p: str, x: torch.Tensor, homogeneous: bool) -> torch.Tensor:
     return F.conv3d(x, sd[p + ".conv.weight"], sd[p + ".conv.bias"], padding=1)
 
 
-def _run_layers(sd, cfg, layers, h, emb, trace, tag):
+def _run_layers(sd, cfg, layers, h, emb, trace, tag, dtype=torch.float32):
     for b in layers:
         if b.kind == "conv":
             h = F.conv3d(h, sd[b.prefix + ".weight"], sd[b.prefix + ".bias"], padding=1)
         elif b.kind == "res":
-            h = res_block(sd, b.prefix, h, emb)
+            h = res_block(sd, b.prefix, h, emb, dtype)
         elif b.kind == "attn":
-            h = attention_block(sd, b.prefix, h, cfg.num_heads)
+            h = attention_block(sd, b.prefix, h, cfg.num_heads, dtype)
         elif b.kind == "down":
             h = downsample(sd, b.prefix, h, cfg.homogeneous_resample)
         elif b.kind == "up":
@@ -247,21 +250,25 @@ def _run_layers(sd, cfg, layers, h, emb, trace, tag):
 
 @torch.no_grad()
 def unet_forward(sd: Dict[str, torch.Tensor], cfg: UNetCfg, x: torch.Tensor, timesteps: torch.Tensor,
-                 trace: Optional[dict] = None) -> torch.Tensor:
-    """UNetModel.forward (unet.py:800-837).  ``trace`` (optional dict) receives every block output."""
+                 trace: Optional[dict] = None, dtype=torch.float32) -> torch.Tensor:
+    """UNetModel.forward (unet.py:800-837).  ``trace`` (optional dict) receives every block output.  ``dtype``: the
+    arithmetic - torch.float32 is the reference's; with torch.float64 nothing is cast down (parameters that are not float64
+    already are widened, exactly), which makes this the high-precision reference of the same network."""
+    if dtype != torch.float32:
+        sd = {k: (v if v.dtype == dtype else v.to(dtype)) for k, v in sd.items()}
     inputs, middle, outputs, _ = unet_structure(cfg)
-    emb = time_embed(sd, cfg, timesteps)
+    emb = time_embed(sd, cfg, timesteps, dtype)
     if trace is not None:
         trace["emb"] = emb
     hs = []
-    h = x.float()
+    h = x.to(dtype)
     for i, layers in enumerate(inputs):
-        h = _run_layers(sd, cfg, layers, h, emb, trace, f"input_blocks.{i}")
+        h = _run_layers(sd, cfg, layers, h, emb, trace, f"input_blocks.{i}", dtype)
         hs.append(h)
-    h = _run_layers(sd, cfg, middle, h, emb, trace, "middle_block")
+    h = _run_layers(sd, cfg, middle, h, emb, trace, "middle_block", dtype)
     for i, layers in enumerate(outputs):
         h = torch.cat([h, hs.pop()], dim=1)
-        h = _run_layers(sd, cfg, layers, h, emb, trace, f"output_blocks.{i}")
-    h = group_norm32(h, sd["out.0.weight"], sd["out.0.bias"])
+        h = _run_layers(sd, cfg, layers, h, emb, trace, f"output_blocks.{i}", dtype)
+    h = group_norm32(h, sd["out.0.weight"], sd["out.0.bias"], dtype)
     h = F.silu(h)
     return F.conv3d(h, sd["out.2.weight"], sd["out.2.bias"], padding=1)

@@ -22,12 +22,13 @@ def gu():
     return g
 
 
-def _oracle_grads(sd, cfg, x, t, G):
-    sdr = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
-    xr = x.clone().requires_grad_(True)
+def _oracle_grads(sd, cfg, x, t, G, dtype=torch.float32):
+    """``dtype=torch.float64``: the leaves, the forward and every gradient in double (tests/test_gpu_unet_conditioning.py)."""
+    sdr = {k: v.clone().to(dtype).requires_grad_(True) for k, v in sd.items()}
+    xr = x.clone().to(dtype).requires_grad_(True)
     with torch.enable_grad():  # (the oracle's entry point is decorated no_grad: call the undecorated function)
-        y = uo.unet_forward.__wrapped__(sdr, cfg, xr, t)
-        (y * G).sum().backward()
+        y = uo.unet_forward.__wrapped__(sdr, cfg, xr, t, None, dtype)
+        (y * G.to(dtype)).sum().backward()
     return y.detach(), xr.grad, {k: v.grad for k, v in sdr.items()}
 
 

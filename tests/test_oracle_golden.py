@@ -247,3 +247,26 @@ def test_oracle_autograd_vs_reference_module_gradients(golden_dir):
             f = f[torch.cat([torch.arange(2048), torch.linspace(2048, f.numel() - 1, 2048).long()])]
         scale = max(float(g[f"mean.scale.{k}"]), net_scale)
         assert (f - torch.from_numpy(g[f"mean.{k}"])).abs().max().item() <= 1e-5 * scale, k
+
+
+def test_float64_oracle_leaves_the_float32_one_alone():
+    """`unet_forward(..., dtype=torch.float64)` (the high-precision reference of tests/test_gpu_unet_conditioning.py): the
+    default and an explicit float32 are the SAME arithmetic bit for bit; in float64 the output and every traced block are
+    double, fp32-close to the float32 run (1e-5 of each tensor's scale, observed 1e-6), and autograd gives double gradients."""
+    cfg = TINY_CFG
+    sd = synth_state_dict(uo.unet_param_shapes(cfg), 1234)
+    x = seeded_input(cfg, 7)
+    t = torch.tensor([500])
+    tr, tr32, tr64 = {}, {}, {}
+    y = uo.unet_forward(sd, cfg, x, t, tr)
+    y32 = uo.unet_forward(sd, cfg, x, t, tr32, dtype=torch.float32)
+    assert torch.equal(y, y32) and set(tr) == set(tr32) and all(torch.equal(tr[k], tr32[k]) for k in tr)
+    y64 = uo.unet_forward(sd, cfg, x, t, tr64, dtype=torch.float64)
+    assert y64.dtype == torch.float64 and set(tr64) == set(tr) and all(v.dtype == torch.float64 for v in tr64.values())
+    for k in tr:
+        assert (tr[k].double() - tr64[k]).abs().max() <= 1e-5 * tr64[k].abs().max(), k
+    assert (y.double() - y64).abs().max() <= 1e-5 * y64.abs().max()
+    sdr = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    with torch.enable_grad():
+        uo.unet_forward.__wrapped__(sdr, cfg, x.double(), t, None, torch.float64).sum().backward()
+    assert all(v.grad is not None and v.grad.dtype == torch.float64 and torch.isfinite(v.grad).all() for v in sdr.values())
