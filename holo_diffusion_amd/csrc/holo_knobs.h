@@ -78,6 +78,11 @@ constexpr int64_t KNOB_UNSET = INT64_MIN;
   X(no_skip_fusion, "HOLO_NO_SKIP_FUSION", SET, 0, PLAN, "a ResBlock's 1x1x1 skip always as its own launch")               \
   X(skip_fusion_below_r, "HOLO_SKIP_FUSION_BELOW_R", RAW, 64, PLAN,                                                        \
     "exact fp32: the skip is fused into the second convolution below this grid edge")                                      \
+  X(side_lane_cus, "HOLO_SIDE_LANE_CUS", INT, 128, PLAN,                                                                   \
+    "exact fp32 inference: CUs the skip half of a split up-path concat convolution is planned for (0: nothing is split)")  \
+  X(side_lane_min_r, "HOLO_SIDE_LANE_MIN_R", INT, 32, PLAN, "smallest grid edge whose concat convolutions are split")      \
+  X(side_lane_fork_r, "HOLO_SIDE_LANE_FORK_R", INT, 8, PLAN,                                                               \
+    "the side lane starts in front of the first descent level whose grid edge is at most this")                            \
   X(no_flash_attn, "HOLO_NO_FLASH_ATTN", SET, 0, PLAN, "attention as GEMM + softmax + GEMM")                               \
   X(bf16_flash_min_t, "HOLO_BF16_FLASH_MIN_T", RAW, 1024, PLAN, "tokens from which the bf16 mode takes its bf16 attention") \
   X(flash_split, "HOLO_FLASH_SPLIT", INT, 0, PLAN, "key splits of the fp32 attention, clamped to [1, T/128] (0: by fill)") \

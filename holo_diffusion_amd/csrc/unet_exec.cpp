@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <functional>
 #include <map>
 #include <optional>
@@ -180,6 +181,7 @@ struct GnFinalize {  // partial sums of the (virtual concat) input -> per-(sampl
   const float *gamma, *beta, *film;
   int film_stride, film_cout;
   float *coef, *moments;  // moments: (mean, rstd) kept for the backward in a training plan, else null
+  int groups;             // 32, or fewer where one half of a split concat is normalised alone (Planner::plan_side_lane)
 };
 struct Softmax { float* S; int64_t rows; int cols; };  // in place
 struct Flash {
@@ -204,11 +206,17 @@ struct Op {  // trivially copyable: holo_unet_forward_cl patches copies of two o
     Flash flash;
     LayoutOut out;
   };
+  // The lane of the op (run_lanes): the caller's stream, or the handle's side stream.  `fork`: the side stream starts in front
+  // of this op (it waits for everything the caller's stream was given before).  `join`: on a side op, the event recorded
+  // behind it; on a main op, the event the caller's stream waits for in front of it (-1: none).
+  unsigned char side, fork;
+  short join;
 };
 static Op make_op(OpKind kind) {
   Op op;
   memset(&op, 0, sizeof op);
   op.kind = kind;
+  op.join = -1;
   return op;
 }
 
@@ -223,6 +231,7 @@ struct Plan {
   // entry cannot use this plan (null: it can)
   int first_conv = -1, last_conv = -1;
   const char* cl_refusal = nullptr;
+  int n_joins = 0;  // join events of the side lane (0: every op runs on the caller's stream)
   bool built_for(int b, const void* w) const { return batch == b && ws == w && !ops.empty(); }
   void invalidate() { *this = Plan(); }
 };
@@ -276,6 +285,11 @@ struct HoloUnet {
   const int64_t* t_dev = nullptr;  // timesteps of the running call (time_embed backward)
   bool tape_valid = false;         // holo_unet_forward_train ran and nothing has consumed its tape
   std::map<int, size_t> tws_cache;
+  // ---- the side lane of an inference plan (Planner::plan_side_lane, run_lanes): one non-blocking stream, the fork event, one
+  // join event per consumer and the event of the error path; created by the first forward whose plan has a side lane
+  void* side_stream = nullptr;
+  void *fork_event = nullptr, *tail_event = nullptr;
+  std::vector<void*> join_events;
 };
 
 namespace {
@@ -499,6 +513,11 @@ struct ConvDesc {
   } skip;
   bool in_f32 = false, out_f32 = false;  // bf16 storage mode: this operand stays fp32
   const ConvParams* qkv_pack = nullptr;  // an attention block's qkv convolution: where it may write the packed operands
+  // One half of a split concat convolution (Planner::plan_side_lane): the launch sums the input channels [w_cin0, w_cin0 + x0->C)
+  // of `w` only.  conv_wino3_kernel's pack is chunk-major, so the half is the same pack entered at its first chunk.
+  bool w_slice = false;
+  int w_cin0 = 0;
+  int cus = 0;  // CUs the launch is planned for (0: the context's)
   int in_size() const { return in_R ? in_R : x0->R; }
   int out_size() const { return out_R ? out_R : in_size(); }
 };
@@ -583,15 +602,23 @@ struct Planner {
     a.C = C;
     a.R = R;
     a.bytes = (size_t)N * vox(R) * C * ((bfs() && !f32) ? 2 : sizeof(float));
-    a.off = arena_base + arena.alloc(a.bytes);
+    a.off = guarded(arena_base + arena.alloc(a.bytes), a.bytes);
     return a;
   }
   // GroupNorm partial-sum buffer [N][slabs][C][2] doubles; the slab count depends on the producing kernel
   void alloc_stats(Act& a, int slabs) {
     a.stats_B = slabs;
     a.stats_bytes = (size_t)N * slabs * a.C * 2 * sizeof(double);
-    a.stats_off = arena_base + arena.alloc(a.stats_bytes);
+    a.stats_off = guarded(arena_base + arena.alloc(a.stats_bytes), a.stats_bytes);
   }
+  // LIFETIMES.  The first-fit arena relies on STREAM ORDER: memory released at one point of the plan may be handed to any
+  // launch planned later, because that launch runs behind the last user of the memory on the same stream.  Side-lane ops
+  // (plan_side_lane) run on a second stream between the fork and their consumer's join, in no order against the main ops of
+  // that stretch.  So everything a side op reads or writes - the skip tensor, its statistics records, the partial tensor P
+  // (its coefficients live in the bump-only small region) - is allocated BEFORE the fork in plan order and released only
+  // AFTER the consumer that waits for the join: nothing released after the fork is ever handed to a side op, and nothing a
+  // side op touches is handed out again before its join.  `side_live` holds those ranges while they are protected; every
+  // allocation is checked against them (guarded).
   void release(Act& a) {
     arena.free(a.off - arena_base, a.bytes);
     if (a.stats_bytes) arena.free(a.stats_off - arena_base, a.stats_bytes);
@@ -601,7 +628,18 @@ struct Planner {
     small_top += Arena::al(bytes);
     return off;
   }
-  size_t scratch_alloc(size_t bytes) { return arena_base + arena.alloc(bytes); }
+  size_t scratch_alloc(size_t bytes) { return guarded(arena_base + arena.alloc(bytes), bytes); }
+  struct SideRange {
+    size_t off, bytes;
+    int join;
+  };
+  std::vector<SideRange> side_live;
+  size_t guarded(size_t off, size_t bytes) {
+    for (const SideRange& r : side_live)
+      if (off < r.off + r.bytes && r.off < off + bytes && err.empty())
+        err = "internal: an allocation between the side lane's fork and join " + std::to_string(r.join) + " overlaps a buffer of that side op";
+    return off;
+  }
   void scratch_free(size_t off, size_t bytes) { arena.free(off - arena_base, bytes); }
 
   void emit_stats(Act& a) {
@@ -639,6 +677,25 @@ struct Planner {
     f.film_stride = u->emb_rows;
     f.film_cout = film_cout;
     f.coef = ptr<float>(coef);
+    f.groups = 32;
+    ops.push_back(op);
+    return coef;
+  }
+  // The same GroupNorm of ONE half `x` of a virtual concat whose groups (cpg channels each) do not straddle the seam: the
+  // half's channels start at c_first of the norm's parameters, and the coefficients get a buffer [N][x.C][2] of their own
+  size_t emit_finalize_half(const Act& x, int c_first, int cpg, const std::string& norm) {
+    size_t coef = small_alloc((size_t)N * x.C * 2 * sizeof(float));
+    Op op = make_op(OP_FINAL);
+    GnFinalize& f = op.fin;
+    f.part0 = ptr<double>(x.stats_off);
+    f.C0 = x.C;
+    f.B0 = x.stats_B;
+    f.V = vox(x.R);
+    f.gamma = P(u, norm + ".weight") + c_first;
+    f.beta = P(u, norm + ".bias") + c_first;
+    f.film_stride = u->emb_rows;
+    f.coef = ptr<float>(coef);
+    f.groups = x.C / cpg;
     ops.push_back(op);
     return coef;
   }
@@ -666,7 +723,10 @@ struct Planner {
   // conv_plan finds 128-voxel tiles).  The padded extents are the ones the weight was PACKED with, so the weight must be
   // this launch's own (Cin, Cout) and its CoutP must hold every Cout tile the launch walks: a tile outside it is memory that
   // no repack wrote.
-  void hand_over(const ConvWeights& cw, ConvParams& p, bool skip) {
+  // (`cin0` >= 0: the launch is one half of a split concat convolution and sums the weight's input channels from cin0 on:
+  // whole 32-channel chunks, on conv_wino3_kernel only - its pack is chunk-major, [chunk][16-Cout slice]..., so the half is the
+  // same pack entered at chunk cin0 / 32; every other copy is handed over whole and must not be read: emit_conv checks)
+  void hand_over(const ConvWeights& cw, ConvParams& p, bool skip, int cin0 = -1) {
     const bool bf = u->compute_mode != 0, wino = u->compute_mode == 0;
     (skip ? p.skip_w : p.w) = cw.f32;
     (skip ? p.skip_w_bf : p.w_bf) = bf ? cw.bf : nullptr;
@@ -677,14 +737,18 @@ struct Planner {
     const ConvWeightLayout& l = cw.layout;
     const int Cin = skip ? p.skip_C0 + p.skip_C1 : p.C0 + p.C1;
     const int tile = conv_cout_tile(p.Cout);
-    if (err.empty() && (l.Cout != p.Cout || l.Cin != Cin || (p.Cout + tile - 1) / tile * tile > l.CoutP || l.CoutP != p.CoutP))
+    const bool slice_ok = cin0 >= 0 && !skip && wino && cw.wino3 && l.taps == 27 && (cin0 % 32) == 0 && (Cin % 32) == 0 && cin0 + Cin <= l.Cin;
+    if (slice_ok) {
+      p.w_wino3 = cw.wino3 + conv_wino3_weight_floats(l.CoutP, cin0, l.taps);
+      p.CinP = Cin;
+    }
+    if (err.empty() && (l.Cout != p.Cout || (l.Cin != Cin && !slice_ok) || (cin0 >= 0 && !slice_ok) || (p.Cout + tile - 1) / tile * tile > l.CoutP || l.CoutP != p.CoutP))
       err = "internal: a " + std::to_string(Cin) + " -> " + std::to_string(p.Cout) + " convolution was handed weights packed for " +
             std::to_string(l.Cin) + " -> " + std::to_string(l.Cout) + " (padded to " + std::to_string(l.CinP) + " -> " +
             std::to_string(l.CoutP) + ")";
   }
-  void emit_conv(const ConvDesc& d) {
-    Op op = make_op(OP_CONV);
-    ConvParams& p = op.conv;
+  // the launch of `d` with its kernel and geometry chosen (conv_plan), its split-K scratch not yet placed; returns that scratch's bytes
+  size_t plan_conv(const ConvDesc& d, ConvParams& p) {
     if (const ConvParams* q = d.qkv_pack) {  // (conv_plan may fuse the attention's operand packing into the launch)
       p.qkv_q = q->qkv_q, p.qkv_k = q->qkv_k, p.qkv_vt = q->qkv_vt;
       p.qkv_scale = q->qkv_scale, p.qkv_T = q->qkv_T, p.qkv_CH = q->qkv_CH, p.qkv_H = q->qkv_H;
@@ -705,7 +769,7 @@ struct Planner {
     p.ksz = d.ksz;
     p.Cout = d.Cout;
     p.CoutP = d.w.layout.CoutP;
-    hand_over(d.w, p, false);
+    hand_over(d.w, p, false, d.w_slice ? d.w_cin0 : -1);
     p.bf16 = u->compute_mode;
     p.coef = d.coef ? ptr<float>(*d.coef) : nullptr;
     p.act = d.act;
@@ -721,10 +785,11 @@ struct Planner {
       p.skip_bias = d.skip.bias;
     }
     ConvParams one = p;
-    size_t sb = conv_plan(p, u->ctx->num_cus, knobs, plan_n());
+    const int cus = d.cus > 0 ? d.cus : u->ctx->num_cus;
+    size_t sb = conv_plan(p, cus, knobs, plan_n());
     if (plan_n() != N) {  // the batch-invariant plan: the launch must compute each sample as the batch-1 launch does
       one.N = 1;
-      conv_plan(one, u->ctx->num_cus, knobs);
+      conv_plan(one, cus, knobs);
       if (err.empty() && (one.kernel != p.kernel || one.tz != p.tz || one.nsplit != p.nsplit ||
                           one.chunks_per_split != p.chunks_per_split || one.skip_chunks_per_split != p.skip_chunks_per_split))
         err = "batch-invariant plan: at batch " + std::to_string(N) + " the " + std::to_string(p.C0 + p.C1) + " -> " +
@@ -732,6 +797,14 @@ struct Planner {
               std::to_string((int)one.kernel) + ", split-K " + std::to_string(one.nsplit) + " -> kernel " +
               std::to_string((int)p.kernel) + ", split-K " + std::to_string(p.nsplit) + "; an addressing limit of the batch)";
     }
+    if (d.w_slice && err.empty() && p.kernel != ConvKernel::Wino3)  // (no other kernel can enter its weights at a chunk)
+      err = "internal: one half of a split concat convolution left conv_wino3_kernel";
+    return sb;
+  }
+  void emit_conv(const ConvDesc& d) {
+    Op op = make_op(OP_CONV);
+    ConvParams& p = op.conv;
+    const size_t sb = plan_conv(d, p);
     size_t so = 0;
     if (sb) {
       so = scratch_alloc(sb);
@@ -754,18 +827,128 @@ struct Planner {
     if (d.stats_of && slabs == 0) emit_stats(*d.stats_of);
   }
 
+  // ---- the side lane (exact-fp32 inference plans).  The first convolution of an up-path ResBlock sums over the virtual
+  // concat [h | encoder skip].  GroupNorm(32) over it has Cin / 32 channels per group; where no group straddles the seam, the
+  // skip half's statistics, coefficients and its chunks of the sum depend on the skip tensor alone, which exists since the
+  // descent.  plan_side_lane runs in front of the deep levels (build) and emits, for every such convolution that plans onto
+  // conv_wino3_kernel, gn_finalize of the skip half + an un-split conv_wino3_kernel launch of it into a partial tensor P, on
+  // the side lane and planned for HOLO_SIDE_LANE_CUS CUs, so that they run beside the latency-bound 8^3 / 4^3 stretch.  The
+  // ResBlock later launches the h half alone with P as its residual (resblock).  Parts are emitted in consumption order.
+  // WHERE the sum is split is numerics (one fp32 addition per output element changes its place), so a batch-invariant plan
+  // splits exactly where the batch-1 plan does; which stream runs a part is free.
+  struct SidePart {
+    Act P;
+    int id = 0, join = -1;  // join: the event behind the side launch (-1: it ran on the caller's stream)
+    bool consumed = false;
+  };
+  std::map<std::string, SidePart> side_parts;  // up-path ResBlock prefix -> the skip half of its first convolution
+  // (both lanes on ONE stream cost 12 % of the B = 4 chain rate, DESIGN.md section 8: the parts always take the side stream)
+  bool side_stream_used() const { return true; }
+  bool split_eligible(const Block& b, const Act& x1, int n_for) {
+    const int C0 = b.cin - x1.C, cpg = b.cin / 32;
+    if (x1.R < knobs.side_lane_min_r || C0 <= 0 || (b.cin % 32) || (C0 % 32) || (C0 % cpg)) return false;
+    const std::string saved = err;  // (trial launches: their refusals are answers, not errors)
+    const int saved_N = N;
+    N = n_for;
+    const Act x0 = view(x1.off, C0, x1.R), out = view(x1.off, b.cout, x1.R);
+    const std::string layer = b.prefix + ".in_layers.2";
+    bool ok = true;
+    for (int form = 0; form < 3 && ok; ++form) {  // the whole launch, the h half, the skip half
+      ConvDesc d = conv_of(layer, form == 2 ? x1 : x0, out);
+      d.x1 = form == 0 ? &x1 : nullptr;
+      d.coef = x1.off;  // (any non-null address: conv_plan asks only whether there are coefficients)
+      d.act = 1;
+      d.w_slice = form != 0;
+      d.w_cin0 = form == 2 ? C0 : 0;
+      d.cus = form == 2 ? (int)knobs.side_lane_cus : 0;
+      if (form == 1) d.residual = ptr<float>(x1.off);
+      if (form == 2) d.bias = nullptr;
+      ConvParams p;
+      memset(&p, 0, sizeof p);
+      plan_conv(d, p);
+      // (the skip half is a DIRECT launch: no split-K scratch and no reduce launch on the side lane)
+      ok = err.empty() && p.kernel == ConvKernel::Wino3 && !p.wino3_up && (form != 2 || p.nsplit == 1);
+      err = saved;
+    }
+    N = saved_N;
+    return ok;
+  }
+  void plan_side_lane(const std::vector<Act>& hs) {
+    if (tape || u->compute_mode != 0 || knobs.side_lane_cus <= 0) return;
+    // A free plan of a batch keeps the whole launches (its numerics owe nothing to batch 1, and the deep levels of a batch leave
+    // less of the chip idle); a batch-invariant one must split where batch 1 does.
+    if (N > 1 && !u->batch_invariant) return;
+    const size_t fork_at = ops.size(), n_in = u->inputs.size();
+    int n_parts = 0;
+    for (size_t i = 0; i < u->outputs.size(); ++i) {
+      const size_t j = n_in - 1 - i;  // build(): output block i pops hs[j]
+      const Block& b = u->outputs[i][0];
+      if (j >= hs.size() || b.kind != B_RES) continue;  // (a skip tensor the descent has yet to produce)
+      const Act& x1 = hs[j];
+      const bool ok = split_eligible(b, x1, N);
+      if (plan_n() != N && ok != split_eligible(b, x1, 1) && err.empty())
+        err = "batch-invariant plan: at batch " + std::to_string(N) + " the concat convolution of " + b.prefix +
+              " cannot be split where the batch-1 plan splits it";
+      if (!ok) continue;
+      const int C0 = b.cin - x1.C, cpg = b.cin / 32;
+      SidePart part;
+      part.id = n_parts++;
+      part.P = new_act(b.cout, x1.R);
+      const size_t coef = emit_finalize_half(x1, C0, cpg, b.prefix + ".in_layers.0");
+      ops.back().side = side_stream_used();
+      ConvDesc d = conv_of(b.prefix + ".in_layers.2", x1, part.P);
+      d.bias = nullptr;
+      d.coef = coef;
+      d.act = 1;
+      d.w_slice = true;
+      d.w_cin0 = C0;
+      d.cus = (int)knobs.side_lane_cus;
+      emit_conv(d);
+      if (ops.back().conv.nsplit != 1 && err.empty()) err = "internal: the skip half of " + b.prefix + " is no direct launch";
+      if (side_stream_used()) {
+        ops.back().side = 1;
+        ops.back().join = (short)(part.join = plan.n_joins++);
+        side_live.push_back({part.P.off, part.P.bytes, part.id});
+        side_live.push_back({x1.off, x1.bytes, part.id});
+        if (x1.stats_bytes) side_live.push_back({x1.stats_off, x1.stats_bytes, part.id});
+      }
+      if (knobs.debug_plan)
+        fprintf(stderr, "[plan] side lane: %s %d + %d -> %d @%d^3 split, skip half on %s, grid_x %d, join %d\n", b.prefix.c_str(), C0, x1.C,
+                b.cout, x1.R, side_stream_used() ? "the side stream" : "the caller's stream", ops.back().conv.grid_x, part.join);
+      side_parts[b.prefix] = part;
+    }
+    if (plan.n_joins) ops[fork_at].fork = 1;
+  }
+
   Act resblock(const Block& b, Act& x0, Act* x1) {
     const std::string& p = b.prefix;
     const int R = x0.R;
-    size_t coefA = emit_finalize(x0, x1, p + ".in_layers.0");
+    const auto sp = x1 ? side_parts.find(p) : side_parts.end();
+    const bool split = sp != side_parts.end();
+    // (split: the skip half of the sum is the partial tensor P of plan_side_lane; this launch adds the h half, the bias and P)
+    size_t coefA = split ? emit_finalize_half(x0, 0, b.cin / 32, p + ".in_layers.0") : emit_finalize(x0, x1, p + ".in_layers.0");
     const size_t momA = last_mom;
     Act h1 = new_act(b.cout, R);
     ConvDesc c1 = conv_of(p + ".in_layers.2", x0, h1);
-    c1.x1 = x1;
+    c1.x1 = split ? nullptr : x1;
     c1.coef = coefA;
     c1.act = 1;
     c1.stats_of = &h1;
-    emit_conv(c1);
+    if (split) {
+      SidePart& part = sp->second;
+      c1.w_slice = true;
+      c1.residual = ptr<float>(part.P.off);
+      const size_t at = ops.size();
+      emit_conv(c1);
+      ops[at].join = (short)part.join;  // (-1 where the side part ran on the caller's stream)
+      // the join is behind us in stream order: P and the skip tensor are ordinary main-lane memory again
+      side_live.erase(std::remove_if(side_live.begin(), side_live.end(), [&](const SideRange& r) { return r.join == part.id; }),
+                      side_live.end());
+      release(part.P);
+      part.consumed = true;
+    } else {
+      emit_conv(c1);
+    }
     const float* film = ptr<float>(eml_off) + u->emb_row_off.at(p);
     size_t coefB = emit_finalize(h1, nullptr, p + ".out_layers.0", film, b.cout);
     const size_t momB = last_mom;
@@ -997,13 +1180,20 @@ struct Planner {
     std::vector<Act> hs;
     Act h = x;
     char tag[64];
+    bool forked = false;
     for (size_t i = 0; i < u->inputs.size(); ++i) {
+      // the side lane starts in front of the first level whose edge is at most HOLO_SIDE_LANE_FORK_R (else in front of the middle)
+      if (!forked && (u->inputs[i][0].kind == B_DOWN ? h.R / 2 : h.R) <= knobs.side_lane_fork_r) {
+        plan_side_lane(hs);
+        forked = true;
+      }
       // h is also referenced by hs (except the raw input x): do not release it when consumed
       h = run_layers(u->inputs[i], h, nullptr, /*release_h=*/i == 0);
       hs.push_back(h);
       snprintf(tag, sizeof tag, "input_blocks.%d", (int)i);
       plan.block_outputs[tag] = h;
     }
+    if (!forked) plan_side_lane(hs);
     // middle: h == hs.back(); keep it alive for the skip connection
     h = run_layers(u->middle, h, nullptr, false);
     plan.block_outputs["middle_block"] = h;
@@ -1014,6 +1204,8 @@ struct Planner {
       snprintf(tag, sizeof tag, "output_blocks.%d", (int)i);
       plan.block_outputs[tag] = h;
     }
+    for (const auto& kv : side_parts)
+      if (!kv.second.consumed && err.empty()) err = "internal: the side part of " + kv.first + " has no consumer";
     size_t coef = emit_finalize(h, nullptr, "out.0");
     Act y = new_act(c.out_channels, R, /*f32=*/true);  // the network output stays fp32
     if (tape) {
@@ -1558,7 +1750,7 @@ int run_op(const HoloUnet* u, const Op& op, int N, const float* x, const int64_t
       return gn_stats_launch(op.stats.x, op.stats.part, N, op.stats.C, op.stats.V, stream, op.stats.x_bf16);
     case OP_FINAL: {
       const GnFinalize& f = op.fin;
-      return gn_finalize_launch(f.part0, f.C0, f.B0, f.part1, f.C1, f.B1, N, f.V, 32, 1e-5f, f.gamma, f.beta, f.film,
+      return gn_finalize_launch(f.part0, f.C0, f.B0, f.part1, f.C1, f.B1, N, f.V, f.groups, 1e-5f, f.gamma, f.beta, f.film,
                                 f.film_stride, f.film_cout, f.coef, stream, f.moments);
     }
     case OP_CONV:
@@ -1578,14 +1770,74 @@ int run_op(const HoloUnet* u, const Op& op, int N, const float* x, const int64_t
   return 0;
 }
 
-// the forward of a plan (inference or training) on the caller's tensors; y may be null where the caller does not want it
-int run_plan(const HoloUnet* u, const Plan& plan, const float* x, const int64_t* t, float* y, void* stream) {
-  for (const Op& op : plan.ops) {
-    if (op.kind == OP_OUT && !y) continue;
-    const int rc = run_op(u, op, plan.batch, x, t, y, stream);
-    if (rc) return rc < 0 ? rc : HOLO_E_INVALID;
+// The side lane's stream and events (the handle owns them; holo_unet_destroy).  The emulation build has one stream: its
+// side lane is the caller's stream, fork and join are nothing (run_lanes).
+int ensure_lanes(HoloUnet* u, int n_joins) {
+#ifndef HOLO_EMU
+  if (!u->side_stream) HIP_TRY(hipStreamCreateWithFlags((hipStream_t*)&u->side_stream, hipStreamNonBlocking));
+  for (void** e : {&u->fork_event, &u->tail_event})
+    if (!*e) HIP_TRY(hipEventCreateWithFlags((hipEvent_t*)e, hipEventDisableTiming));
+  while ((int)u->join_events.size() < n_joins) {
+    hipEvent_t e;
+    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    u->join_events.push_back(e);
   }
+#endif
+  (void)u, (void)n_joins;
   return 0;
+}
+
+// Issues the ops of a plan in plan order from the host, each on its lane: `run(i, op, stream)` launches op i (or skips it)
+// and returns its code.  Plan order is a valid serial order, and a side op stands in front of its consumer in it, so every
+// event is recorded before anything waits for it - host order alone guarantees that.  The side stream starts behind everything
+// the caller's stream holds at the fork, so the side ops of one call cannot overtake the previous call either.  Whatever
+// happens after the fork, the caller's stream is left waiting for the side stream: on success through the consumers' joins
+// (the last of them stands behind every side op, the side stream runs in order), on an error through the tail event.
+template <class Run>
+int run_lanes(HoloUnet* u, const Plan& plan, void* stream, Run run) {
+  int rc = 0;
+#ifdef HOLO_EMU
+  for (size_t i = 0; i < plan.ops.size() && !rc; ++i) rc = run((int)i, plan.ops[i], stream);
+#else
+  if (!plan.n_joins) {
+    for (size_t i = 0; i < plan.ops.size() && !rc; ++i) rc = run((int)i, plan.ops[i], stream);
+    return rc ? (rc < 0 ? rc : HOLO_E_INVALID) : 0;
+  }
+  if ((rc = ensure_lanes(u, plan.n_joins))) return rc;
+  const hipStream_t main = (hipStream_t)stream, side = (hipStream_t)u->side_stream;
+  bool forked = false;
+  hipError_t he = hipSuccess;
+  for (size_t i = 0; i < plan.ops.size() && !rc && he == hipSuccess; ++i) {
+    const Op& op = plan.ops[i];
+    if (op.fork) {
+      if ((he = hipEventRecord((hipEvent_t)u->fork_event, main)) != hipSuccess) break;
+      if ((he = hipStreamWaitEvent(side, (hipEvent_t)u->fork_event, 0)) != hipSuccess) break;
+      forked = true;
+    }
+    if (op.side) {
+      rc = run((int)i, op, side);
+      if (!rc && op.join >= 0) he = hipEventRecord((hipEvent_t)u->join_events[op.join], side);
+    } else {
+      if (op.join >= 0 && (he = hipStreamWaitEvent(main, (hipEvent_t)u->join_events[op.join], 0)) != hipSuccess) break;
+      rc = run((int)i, op, main);
+    }
+  }
+  if (he != hipSuccess) {
+    set_error("the side lane of the forward failed: %s", hipGetErrorString(he));
+    rc = HOLO_E_HIP;
+  }
+  if (rc && forked) {  // (best effort: the caller's stream still ends behind the side stream)
+    if (hipEventRecord((hipEvent_t)u->tail_event, side) == hipSuccess) (void)hipStreamWaitEvent(main, (hipEvent_t)u->tail_event, 0);
+  }
+#endif
+  return rc ? (rc < 0 ? rc : HOLO_E_INVALID) : 0;
+}
+
+// the forward of a plan (inference or training) on the caller's tensors; y may be null where the caller does not want it
+int run_plan(HoloUnet* u, const Plan& plan, const float* x, const int64_t* t, float* y, void* stream) {
+  return run_lanes(u, plan, stream, [&](int, const Op& op, void* st) {
+    return op.kind == OP_OUT && !y ? 0 : run_op(u, op, plan.batch, x, t, y, st);
+  });
 }
 // the backward launches of a training plan whose taped forward has run on `workspace`
 int run_backward(const HoloUnet* u, const TrainPlan& tp, const float* grad_out, float* grad_x, void* workspace, void* stream) {
@@ -1698,6 +1950,15 @@ int holo_unet_destroy(HoloUnet* net) {
     for (float* buf : {kv.second.f32, kv.second.wino2, kv.second.wino3})
       if (buf) (void)hipFree(buf);
   if (net->dgrad_tmp) (void)hipFree(net->dgrad_tmp);
+#ifndef HOLO_EMU
+  if (net->side_stream) {  // (every forward left the caller's stream waiting for it; drain it before its events go)
+    (void)hipStreamSynchronize((hipStream_t)net->side_stream);
+    (void)hipStreamDestroy((hipStream_t)net->side_stream);
+  }
+  for (void* e : {net->fork_event, net->tail_event})
+    if (e) (void)hipEventDestroy((hipEvent_t)e);
+  for (void* e : net->join_events) (void)hipEventDestroy((hipEvent_t)e);
+#endif
   delete net;
   return 0;
 }
@@ -1837,24 +2098,18 @@ int holo_unet_forward_cl(HoloUnet* net, int batch, const float* x_cl, const int6
   // the first / last convolution (Planner::find_cl_ends) run on the caller's channels-last tensors instead of the plan's
   // own input / output buffers, and the two layout passes are skipped
   const bool bf16_storage = net->compute_mode == 1;  // the plan's input buffer is bf16: a cast replaces the layout pass
-  for (int i = 0; i < (int)plan.ops.size(); ++i) {
-    const Op& op = plan.ops[i];
-    if (op.kind == OP_IN && bf16_storage) {  // fp32 channels-last -> the plan's bf16 channels-last input buffer
-      if (f32_to_bf16_launch(x_cl, op.in.dst, (int64_t)batch * op.in.C * op.in.V, stream)) return HOLO_E_INVALID;
-      continue;
-    }
-    if (op.kind == OP_IN || op.kind == OP_OUT) continue;
+  return run_lanes(net, plan, stream, [&](int i, const Op& op, void* st) {
+    if (op.kind == OP_IN && bf16_storage)  // fp32 channels-last -> the plan's bf16 channels-last input buffer
+      return f32_to_bf16_launch(x_cl, op.in.dst, (int64_t)batch * op.in.C * op.in.V, st) ? (int)HOLO_E_INVALID : 0;
+    if (op.kind == OP_IN || op.kind == OP_OUT) return 0;
     if (i == plan.first_conv || i == plan.last_conv) {
       Op o2 = op;
       if (i == plan.first_conv && !bf16_storage) o2.conv.src0 = x_cl;
       if (i == plan.last_conv) o2.conv.out = y_cl;
-      rc = run_op(net, o2, batch, x_cl, timesteps, y_cl, stream);
-    } else {
-      rc = run_op(net, op, batch, x_cl, timesteps, y_cl, stream);
+      return run_op(net, o2, batch, x_cl, timesteps, y_cl, st);
     }
-    if (rc) return rc < 0 ? rc : HOLO_E_INVALID;
-  }
-  return 0;
+    return run_op(net, op, batch, x_cl, timesteps, y_cl, st);
+  });
 }
 
 int holo_unet_fetch_block(HoloUnet* net, const char* tag, float* dst, int64_t dst_capacity, int64_t* numel,
