@@ -42,15 +42,19 @@ CASES = [(12, 10, 16, 8, 3, 13, "all")] if EMU else [(12, 10, 16, 8, 3, 13, "all
                                                      (16, 100, 16, 16, 2, 29, "no_noise"), (64, 64, 32, 32, 4, 700, "chunks")]
 
 
-def _render_rays_backward_case(gu, P, Pf, C, R, n_cam, n_rays, which, seed=0, own=lambda model: model):
-    """The body of test_render_rays_backward_vs_oracle_autograd (shared with tests/test_gpu_cu_counts.py).  ``seed``: added to
-    the seeds of the grid, the ray positions, the random streams and the cotangents; ``own``: called with the model."""
-    model, _, _, _, msd = gu.make_model(R, C, 16, 16, TINY_UNET, n_fine=64)
+def _render_rays_backward_case(gu, P, Pf, C, R, n_cam, n_rays, which, seed=0, own=lambda model: model, grid_scale=1.0,
+                               density_bias=0.0, probe=None):
+    """The body of test_render_rays_backward_vs_oracle_autograd (shared with tests/test_gpu_cu_counts.py and
+    tests/test_gpu_render_sample_counts.py).  ``seed``: added to the seeds of the grid, the ray positions, the random streams
+    and the cotangents; ``own``: called with the model; ``grid_scale``: factor on the tanh noise grid; ``density_bias``: added
+    to the density output's bias; ``probe``: called with (grid, msd, cams, xys, rs, rcfg) before anything runs (a caller's
+    check that the inputs are the case it means)."""
+    model, _, _, _, msd = gu.make_model(R, C, 16, 16, TINY_UNET, n_fine=64, density_bias=density_bias)
     own(model)
     model.raysampler.n_pts_per_ray_training = P
     model.renderer.n_pts_per_ray_fine_training = Pf
     rcfg = ro.RenderCfg(resol=R, feature_size=C, image_height=16, image_width=16, n_pts_coarse=P, n_pts_fine=Pf)
-    grid = torch.tanh(torch.from_numpy(np_noise(7 + seed, (1, C, R, R, R))))
+    grid = torch.tanh(torch.from_numpy(np_noise(7 + seed, (1, C, R, R, R)))) * grid_scale
     cams = hda.get_simple_360_camera_trajectory(2 * math.pi, n_cam, -0.5, 10, (0.0, -1.0, 0.0), 3.2)
     xys = (torch.from_numpy(np_noise(11 + seed, (n_cam, n_rays, 2))).clamp(-2, 2) * 0.45).contiguous()
     rs = _streams(n_cam, n_rays, P, Pf, 500 + P + seed)
@@ -60,6 +64,8 @@ def _render_rays_backward_case(gu, P, Pf, C, R, n_cam, n_rays, which, seed=0, ow
         model.renderer.stratified_sampling_coarse_training = False
         model.renderer.density_noise_std_train = std = 0.0
         rs = {}
+    if probe is not None:
+        probe(grid, msd, cams, xys, rs, rcfg)
     keys = {"features": ("rgb", 3), "depths": ("depth", 1), "masks": ("mask", 1), "features_coarse": ("rgb_c", 3),
             "depths_coarse": ("depth_c", 1), "masks_coarse": ("mask_c", 1)}
     if which == "fine_only":
