@@ -3,6 +3,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/holo_abi.h"
 #include "conv_weights.h"
@@ -170,6 +171,20 @@ struct GemmParams {
   float alpha;
 };
 int gemm_launch(const GemmParams& p, void* stream);
+// nb products C[b] (M x N, ldc) = A[b] (M x K, lda) . B[b] (b_kmajor ? K x N : N x K; ldb), strides sa / sb / sc between them
+inline int gemm_batch_launch(const float* A, int lda, const float* B, int ldb, int b_kmajor, float* C, int ldc, int M, int N,
+                             int K, int nb, int64_t sa, int64_t sb, int64_t sc, void* stream) {
+  GemmParams g;
+  memset(&g, 0, sizeof g);
+  g.A = A, g.B = B, g.C = C;
+  g.M = M, g.Nn = N, g.K = K;
+  g.lda = lda, g.ldb = ldb, g.ldc = ldc;
+  g.nb0 = nb, g.nb1 = 1;
+  g.sa0 = sa, g.sb0 = sb, g.sc0 = sc;
+  g.b_kmajor = b_kmajor;
+  g.alpha = 1.f;
+  return gemm_launch(g, stream);
+}
 
 // Flash-style attention over the token-major qkv buffer [N][T][3C] (head-major channel order: q,k,v blocks of
 // C/H channels per head, unet.py:448); out is token-major [N][T][C].  scale2 = 1/sqrt(head channels).
@@ -257,6 +272,22 @@ int dpm_step_launch(const float* coefs, int batch, int64_t per, const float* x_t
 int tanh_launch(const float* x, float* y, int64_t n, void* stream);
 // dst = src for a SMALL caller-provided tensor, read with system-scope loads (holo_ld_sys, holo_common.h)
 int copy_sys_launch(const float* src, float* dst, int64_t n, void* stream);
+// ---- shared by the host files (*_exec.cpp, host_params.h)
+// returns HOLO_E_HIP from the calling function, with the failed call in the error text
+#define HIP_TRY(expr)                                                                        \
+  do {                                                                                       \
+    hipError_t _e = (expr);                                                                  \
+    if (_e != hipSuccess) {                                                                  \
+      holo::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+      return HOLO_E_HIP;                                                                     \
+    }                                                                                        \
+  } while (0)
+// every part of a workspace starts on a 256-byte boundary
+inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// 0.5 * (R - 1) * voxel_size: the VolumeLocator's local -> world scale of an R^3 grid
+inline float grid_half_extent(int resol, float volume_extent) {
+  return 0.5f * (float)(resol - 1) * (volume_extent / (float)resol);
+}
 // Host -> device upload of a packed parameter image into a buffer that kernels have been reading (a re-commit after a
 // parameter update): the bytes land in a staging buffer that only copy_sys_kernel ever reads (system-scope loads), which
 // then writes `dst` like any kernel - so no kernel can meet a stale cached line of `dst` (holo_ld_sys).  Synchronises.

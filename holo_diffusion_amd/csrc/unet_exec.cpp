@@ -34,15 +34,6 @@ void set_error(const char* fmt, ...) {
 }
 const char* get_error() { return g_err; }
 
-#define HIP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess) {                                                            \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return HOLO_E_HIP;                                                               \
-    }                                                                                  \
-  } while (0)
-
 }  // namespace holo
 
 using namespace holo;

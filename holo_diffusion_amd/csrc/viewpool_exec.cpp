@@ -8,31 +8,56 @@
 #include <math.h>
 #include <string.h>
 
-#include <map>
-#include <string>
 #include <vector>
 
 #include "../../include/holo_abi.h"
 #include "holo_common.h"
 #include "holo_kernels.h"
+#include "host_params.h"
+#include "mlp_folds.h"
 
 using namespace holo;
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// channels-last images of all source-view feature maps (channels padded to fours), each on a 256-byte boundary
+static size_t maps_bytes(const HoloViewFeature* feats, int n_feats, int n_views, size_t elem_bytes) {
+  size_t b = 0;
+  for (int k = 0; k < n_feats; ++k)
+    b += align256((size_t)n_views * feats[k].height * feats[k].width * ((feats[k].channels + 3) / 4 * 4) * elem_bytes);
+  return b;
+}
+static int sum_channels(const HoloViewFeature* feats, int n_feats) {
+  int c = 0;
+  for (int k = 0; k < n_feats; ++k) c += feats[k].channels;
+  return c;
+}
+// the channels-last copy of one map at ws (advanced behind it)
+static int stage_map(const HoloViewFeature& f, int n_views, ViewPoolParams::Feat& o, char*& ws, void* stream) {
+  o.C = f.channels;
+  o.Cp = (f.channels + 3) / 4 * 4;
+  o.H = f.height;
+  o.W = f.width;
+  o.data = (const float*)ws;
+  if (nchw_to_nhwc_pad_launch(f.feats, (float*)ws, n_views, o.C, o.Cp, (int64_t)o.H * o.W, stream)) return HOLO_E_INVALID;
+  ws += align256((size_t)n_views * o.H * o.W * o.Cp * sizeof(float));
+  return 0;
+}
+// one source view and its camera centre C = -T R^T (custom_modules.py:288-296, 304-312)
+static void fill_pool_cam(const HoloCamera& c, ViewPoolParams::Cam& o) {
+  for (int k = 0; k < 9; ++k) o.Rm[k] = c.R[k];
+  for (int k = 0; k < 3; ++k) o.T[k] = c.T[k];
+  for (int k = 0; k < 2; ++k) {
+    o.focal[k] = c.focal[k];
+    o.pp[k] = c.principal_point[k];
+  }
+  for (int j = 0; j < 3; ++j) o.centre[j] = -(c.T[0] * c.R[j * 3 + 0] + c.T[1] * c.R[j * 3 + 1] + c.T[2] * c.R[j * 3 + 2]);
+}
 
 extern "C" {
 
 size_t holo_view_pool_workspace_bytes(const HoloViewPoolCfg* cfg, const HoloViewFeature* feats, int n_feats, int n_views) {
   if (!cfg || !feats || n_feats < 1 || n_views < 1) return 0;
-  size_t b = 0;
-  int sumC = 0;
-  for (int k = 0; k < n_feats; ++k) {
-    const size_t Cp = (size_t)((feats[k].channels + 3) / 4 * 4);
-    b += align256((size_t)n_views * feats[k].height * feats[k].width * Cp * sizeof(float));
-    sumC += feats[k].channels;
-  }
-  b += align256((size_t)2 * sumC * cfg->feature_size * sizeof(float));  // transposed mapper weight
-  return b + 256;
+  return maps_bytes(feats, n_feats, n_views, sizeof(float)) +
+         align256((size_t)2 * sum_channels(feats, n_feats) * cfg->feature_size * sizeof(float)) + 256;  // + transposed mapper weight
 }
 
 }  // extern "C"
@@ -66,15 +91,9 @@ static int setup_view_pool(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloV
       return HOLO_E_INVALID;
     }
     ViewPoolParams::Feat& o = p.feat[k];
-    o.C = f.channels;
-    o.Cp = (f.channels + 3) / 4 * 4;
-    o.H = f.height;
-    o.W = f.width;
     o.quad0 = quad;
     o.out0 = outc;
-    o.data = (const float*)ws;
-    if (nchw_to_nhwc_pad_launch(f.feats, (float*)ws, n_views, o.C, o.Cp, (int64_t)o.H * o.W, stream)) return HOLO_E_INVALID;
-    ws += align256((size_t)n_views * o.H * o.W * o.Cp * sizeof(float));
+    if (stage_map(f, n_views, o, ws, stream)) return HOLO_E_INVALID;
     quad += o.Cp / 4;
     outc += 2 * o.C;
   }
@@ -91,20 +110,9 @@ static int setup_view_pool(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloV
   ws += align256((size_t)p.A * p.F * sizeof(float));
   p.bias = mapper_bias;
   p.n_views = n_views;
-  for (int v = 0; v < n_views; ++v) {
-    const HoloCamera& c = cameras[v];
-    ViewPoolParams::Cam& o = p.cams[v];
-    for (int k = 0; k < 9; ++k) o.Rm[k] = c.R[k];
-    for (int k = 0; k < 3; ++k) o.T[k] = c.T[k];
-    for (int k = 0; k < 2; ++k) {
-      o.focal[k] = c.focal[k];
-      o.pp[k] = c.principal_point[k];
-    }
-    for (int j = 0; j < 3; ++j)  // camera centre C = -T R^T (custom_modules.py:288-296)
-      o.centre[j] = -(c.T[0] * c.R[j * 3 + 0] + c.T[1] * c.R[j * 3 + 1] + c.T[2] * c.R[j * 3 + 2]);
-  }
+  for (int v = 0; v < n_views; ++v) fill_pool_cam(cameras[v], p.cams[v]);
   p.R = cfg->resol;
-  p.half_extent = 0.5f * (float)(cfg->resol - 1) * (cfg->volume_extent / (float)cfg->resol);
+  p.half_extent = grid_half_extent(cfg->resol, cfg->volume_extent);
   p.gamma = cfg->weight_by_ray_angle_gamma;
   p.min_weight = cfg->min_ray_angle_weight;
   p.proj_eps = cfg->projection_eps;
@@ -141,21 +149,11 @@ static int view_pool_bwd_wgs(HoloCtx* ctx, int resol) {
 size_t holo_view_pool_backward_workspace_bytes(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloViewFeature* feats,
                                                int n_feats, int n_views) {
   if (!ctx || !cfg || !feats || n_feats < 1 || n_views < 1) return 0;
-  size_t b = holo_view_pool_workspace_bytes(cfg, feats, n_feats, n_views);
-  int sumC = 0;
-  for (int k = 0; k < n_feats; ++k) {
-    const size_t Cp = (size_t)((feats[k].channels + 3) / 4 * 4);
-    b += align256((size_t)n_views * feats[k].height * feats[k].width * Cp * sizeof(float));
-    sumC += feats[k].channels;
-  }
+  size_t b = holo_view_pool_workspace_bytes(cfg, feats, n_feats, n_views) + maps_bytes(feats, n_feats, n_views, sizeof(float));
+  const int sumC = sum_channels(feats, n_feats);
   b += align256((size_t)view_pool_bwd_wgs(ctx, cfg->resol) * ((size_t)2 * sumC * cfg->feature_size + cfg->feature_size) * sizeof(float));
-  if (ctx->deterministic) {  // 64-bit fixed-point images of the gradient maps + one word per map (holo_ctx_set_deterministic)
-    for (int k = 0; k < n_feats; ++k) {
-      const size_t Cp = (size_t)((feats[k].channels + 3) / 4 * 4);
-      b += align256((size_t)n_views * feats[k].height * feats[k].width * Cp * sizeof(long long));
-    }
-    b += 256;
-  }
+  // 64-bit fixed-point images of the gradient maps + one word per map (holo_ctx_set_deterministic)
+  if (ctx->deterministic) b += maps_bytes(feats, n_feats, n_views, sizeof(long long)) + 256;
   return b + 256;
 }
 
@@ -227,8 +225,8 @@ struct HoloMlpMeanPooler {
   HoloCtx* ctx;
   HoloMlpMeanCfg cfg;
   Knobs knobs;  // snapshot of holo_mlp_mean_create (holo_knobs.h): the backward's chunk layout, for its size query and its run
-  std::map<std::string, std::vector<float>> host;
-  std::map<std::string, std::vector<int64_t>> expected;
+  HostParams params;  // raw parameters (host copies)
+  MlpMeanShape shape;  // of the fold (mlp_folds.h)
   int D = 0, E = 0, dp = 0, emb0 = 0;
   int quad0[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   float* dev = nullptr;  // a | am | cb | g | g0 | l
@@ -236,20 +234,11 @@ struct HoloMlpMeanPooler {
   size_t stage_floats = 0;
   float l0 = 0.f;
   bool committed = false;
-  std::map<std::string, std::vector<float>> grads;  // holo_mlp_mean_backward: by reference parameter name
+  HostGrads grads{"holo_mlp_mean_backward"};  // by reference parameter name
 };
 
 static int mlp_mean_fill(HoloMlpMeanPooler* h, const HoloViewFeature* feats, int n_feats, const HoloCamera* cameras, int n_views,
                          void* stream, MlpMeanParams& p, char*& ws);
-
-#define HIP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess) {                                                            \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return HOLO_E_HIP;                                                               \
-    }                                                                                  \
-  } while (0)
 
 int holo_mlp_mean_create(HoloCtx* ctx, const HoloMlpMeanCfg* cfg, HoloMlpMeanPooler** out) {
   if (!ctx || !cfg || !out) {
@@ -291,18 +280,21 @@ int holo_mlp_mean_create(HoloCtx* ctx, const HoloMlpMeanCfg* cfg, HoloMlpMeanPoo
     return HOLO_E_UNSUPPORTED;
   }
   const int64_t nh = cfg->n_hidden, D = h->D, dout = cfg->dim_out, F = cfg->feature_size;
-  h->expected["_first_sampled.weight"] = {nh, D};
-  h->expected["_first_sampled.bias"] = {nh};
-  h->expected["_first_mean.weight"] = {nh, D};
-  h->expected["_first_mean.bias"] = {nh};
-  h->expected["_mlp.mlp.0.0.weight"] = {nh, nh};
-  h->expected["_mlp.mlp.0.0.bias"] = {nh};
-  h->expected["_last.weight"] = {dout, nh};
-  h->expected["_last.bias"] = {dout};
-  h->expected["pooled_feature_mapper.weight"] = {F, dout};
-  h->expected["pooled_feature_mapper.bias"] = {F};
-  const size_t n = (size_t)(2 * nh * h->dp + nh + F * nh + F + nh + 64);
-  if (hipMalloc((void**)&h->dev, n * sizeof(float)) != hipSuccess) {
+  h->params.declare("_first_sampled.weight", {nh, D});
+  h->params.declare("_first_sampled.bias", {nh});
+  h->params.declare("_first_mean.weight", {nh, D});
+  h->params.declare("_first_mean.bias", {nh});
+  h->params.declare("_mlp.mlp.0.0.weight", {nh, nh});
+  h->params.declare("_mlp.mlp.0.0.bias", {nh});
+  h->params.declare("_last.weight", {dout, nh});
+  h->params.declare("_last.bias", {dout});
+  h->params.declare("pooled_feature_mapper.weight", {F, dout});
+  h->params.declare("pooled_feature_mapper.bias", {F});
+  h->shape = {(int)nh, h->D, h->dp, (int)F, (int)dout, {}};
+  for (int k = 0; k < cfg->n_feats; ++k)
+    for (int j = 0; j < cfg->channels[k]; ++j) h->shape.col.push_back(h->quad0[k] * 4 + j);
+  for (int j = 0; j < h->E; ++j) h->shape.col.push_back(h->emb0 + j);
+  if (hipMalloc((void**)&h->dev, (h->shape.image_floats() + 64) * sizeof(float)) != hipSuccess) {
     delete h;
     set_error("holo_mlp_mean_create: hipMalloc failed");
     return HOLO_E_HIP;
@@ -315,6 +307,7 @@ int holo_mlp_mean_destroy(HoloMlpMeanPooler* h) {
   if (!h) return 0;
   if (h->dev) (void)hipFree(h->dev);
   if (h->stage) (void)hipFree(h->stage);
+  h->grads.release();
   delete h;
   return 0;
 }
@@ -325,91 +318,28 @@ int holo_mlp_mean_set_param(HoloMlpMeanPooler* h, const char* name, const void* 
     set_error("holo_mlp_mean_set_param: null argument");
     return HOLO_E_INVALID;
   }
-  auto it = h->expected.find(name);
-  if (it == h->expected.end()) {
-    set_error("holo_mlp_mean_set_param: unknown parameter '%s'", name);
-    return HOLO_E_INVALID;
-  }
-  bool ok = ndim == (int)it->second.size();
-  int64_t numel = 1;
-  for (int i = 0; ok && i < ndim; ++i) {
-    ok = shape[i] == it->second[i];
-    numel *= shape[i];
-  }
-  if (!ok) {
-    set_error("holo_mlp_mean_set_param: shape mismatch for '%s'", name);
-    return HOLO_E_INVALID;
-  }
-  std::vector<float>& v = h->host[name];
-  v.resize((size_t)numel);
-  HIP_TRY(hipMemcpyAsync(v.data(), dev_ptr, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  h->committed = false;
-  return 0;
+  const int rc = h->params.set("holo_mlp_mean_set_param", name, dev_ptr, ndim, shape, stream);
+  if (!rc) h->committed = false;
+  return rc;
 }
 
+// Folds the affine stretches on both sides of the LeakyReLU (mlp_folds.h) and uploads the kernels' image of them.
 int holo_mlp_mean_commit(HoloMlpMeanPooler* h, void* stream) {
   if (!h) {
     set_error("holo_mlp_mean_commit: null");
     return HOLO_E_INVALID;
   }
-  for (auto& kv : h->expected)
-    if (!h->host.count(kv.first)) {
-      set_error("holo_mlp_mean_commit: parameter '%s' has not been set", kv.first.c_str());
-      return HOLO_E_STATE;
-    }
-  const int nh = h->cfg.n_hidden, D = h->D, dp = h->dp, dout = h->cfg.dim_out, F = h->cfg.feature_size;
-  auto W = [&](const char* n) -> const std::vector<float>& { return h->host[n]; };
-  const auto &Ws = W("_first_sampled.weight"), &bs = W("_first_sampled.bias"), &Wm = W("_first_mean.weight"),
-             &bm = W("_first_mean.bias"), &W1 = W("_mlp.mlp.0.0.weight"), &b1 = W("_mlp.mlp.0.0.bias"),
-             &Wl = W("_last.weight"), &bl = W("_last.bias"), &M = W("pooled_feature_mapper.weight"),
-             &mb = W("pooled_feature_mapper.bias");
-  // column of reference channel c (torch.cat order: maps in dict order, then the embedding) in the padded order
-  std::vector<int> col(D);
-  {
-    int c = 0;
-    for (int k = 0; k < h->cfg.n_feats; ++k)
-      for (int j = 0; j < h->cfg.channels[k]; ++j) col[c++] = h->quad0[k] * 4 + j;
-    for (int j = 0; j < h->E; ++j) col[c++] = h->emb0 + j;
+  if (const char* missing = h->params.first_missing()) {
+    set_error("holo_mlp_mean_commit: parameter '%s' has not been set", missing);
+    return HOLO_E_STATE;
   }
-  std::vector<float> pk((size_t)(2 * nh * dp + nh + F * nh + F + nh), 0.f);
-  float* a = pk.data();
-  float* am = a + (size_t)nh * dp;
-  float* cb = am + (size_t)nh * dp;
-  float* g = cb + nh;
-  float* g0 = g + (size_t)F * nh;
-  float* l = g0 + F;
-  for (int i = 0; i < nh; ++i) {
-    std::vector<double> ra(D, 0.0), rm(D, 0.0);
-    double c = b1[i];
-    for (int k = 0; k < nh; ++k) {
-      const double w = W1[(size_t)i * nh + k];
-      c += w * ((double)bs[k] + (double)bm[k]);
-      for (int j = 0; j < D; ++j) {
-        ra[j] += w * Ws[(size_t)k * D + j];
-        rm[j] += w * Wm[(size_t)k * D + j];
-      }
-    }
-    for (int j = 0; j < D; ++j) {
-      a[(size_t)i * dp + col[j]] = (float)ra[j];
-      am[(size_t)i * dp + col[j]] = (float)rm[j];
-    }
-    cb[i] = (float)c;
-    l[i] = Wl[i];  // row 0 of _last
-  }
-  for (int f = 0; f < F; ++f) {
-    double c = mb[f];
-    std::vector<double> rg(nh, 0.0);
-    for (int o = 0; o < dout; ++o) {
-      const double w = M[(size_t)f * dout + o];
-      c += w * bl[o];
-      for (int k = 0; k < nh; ++k) rg[k] += w * Wl[(size_t)o * nh + k];
-    }
-    for (int k = 0; k < nh; ++k) g[(size_t)f * nh + k] = (float)rg[k];
-    g0[f] = (float)c;
-  }
-  h->l0 = bl[0];
-  if (upload_via_stage(&h->stage, &h->stage_floats, h->dev, pk.data(), pk.size(), stream)) {
+  const HostParams& P = h->params;
+  const MlpMeanFold fold =
+      fold_mlp_mean(h->shape, P["_first_sampled.weight"], P["_first_sampled.bias"], P["_first_mean.weight"], P["_first_mean.bias"],
+                    P["_mlp.mlp.0.0.weight"], P["_mlp.mlp.0.0.bias"], P["_last.weight"], P["_last.bias"],
+                    P["pooled_feature_mapper.weight"], P["pooled_feature_mapper.bias"]);
+  h->l0 = fold.l0;
+  if (upload_via_stage(&h->stage, &h->stage_floats, h->dev, fold.image.data(), fold.image.size(), stream)) {
     set_error("holo_mlp_mean_commit: upload of the folded weights failed");
     return HOLO_E_HIP;
   }
@@ -419,12 +349,7 @@ int holo_mlp_mean_commit(HoloMlpMeanPooler* h, void* stream) {
 
 size_t holo_mlp_mean_workspace_bytes(const HoloMlpMeanPooler* h, const HoloViewFeature* feats, int n_feats, int n_views) {
   if (!h || !feats || n_feats < 1 || n_views < 1) return 0;
-  size_t b = 0;
-  for (int k = 0; k < n_feats; ++k) {
-    const size_t Cp = (size_t)((feats[k].channels + 3) / 4 * 4);
-    b += align256((size_t)n_views * feats[k].height * feats[k].width * Cp * sizeof(float));
-  }
-  return b + 256;
+  return maps_bytes(feats, n_feats, n_views, sizeof(float)) + 256;
 }
 
 int holo_mlp_mean_pool(HoloMlpMeanPooler* h, const HoloViewFeature* feats, int n_feats, const HoloCamera* cameras,
@@ -466,32 +391,14 @@ static int mlp_mean_fill(HoloMlpMeanPooler* h, const HoloViewFeature* feats, int
       set_error("holo_mlp_mean_pool: feature map %d must have %d channels", k, h->cfg.channels[k]);
       return HOLO_E_INVALID;
     }
-    ViewPoolParams::Feat& o = p.vp.feat[k];
-    o.C = f.channels;
-    o.Cp = (f.channels + 3) / 4 * 4;
-    o.H = f.height;
-    o.W = f.width;
-    o.quad0 = h->quad0[k];
-    o.data = (const float*)ws;
-    if (nchw_to_nhwc_pad_launch(f.feats, (float*)ws, n_views, o.C, o.Cp, (int64_t)o.H * o.W, stream)) return HOLO_E_INVALID;
-    ws += align256((size_t)n_views * o.H * o.W * o.Cp * sizeof(float));
+    p.vp.feat[k].quad0 = h->quad0[k];
+    if (stage_map(f, n_views, p.vp.feat[k], ws, stream)) return HOLO_E_INVALID;
   }
   p.vp.n_feats = n_feats;
   p.vp.n_views = n_views;
-  for (int v = 0; v < n_views; ++v) {
-    const HoloCamera& c = cameras[v];
-    ViewPoolParams::Cam& o = p.vp.cams[v];
-    for (int k = 0; k < 9; ++k) o.Rm[k] = c.R[k];
-    for (int k = 0; k < 3; ++k) o.T[k] = c.T[k];
-    for (int k = 0; k < 2; ++k) {
-      o.focal[k] = c.focal[k];
-      o.pp[k] = c.principal_point[k];
-    }
-    for (int j = 0; j < 3; ++j)  // camera centre C = -T R^T (custom_modules.py:304-312)
-      o.centre[j] = -(c.T[0] * c.R[j * 3 + 0] + c.T[1] * c.R[j * 3 + 1] + c.T[2] * c.R[j * 3 + 2]);
-  }
+  for (int v = 0; v < n_views; ++v) fill_pool_cam(cameras[v], p.vp.cams[v]);
   p.vp.R = h->cfg.resol;
-  p.vp.half_extent = 0.5f * (float)(h->cfg.resol - 1) * (h->cfg.volume_extent / (float)h->cfg.resol);
+  p.vp.half_extent = grid_half_extent(h->cfg.resol, h->cfg.volume_extent);
   p.vp.proj_eps = h->cfg.projection_eps;
   p.vp.F = h->cfg.feature_size;
   const int nh = h->cfg.n_hidden, F = h->cfg.feature_size;
@@ -516,6 +423,22 @@ struct MmBwdLayout {
   int S, S2, FW, dp;
   size_t maps, gmaps, X, MEAN, CM, PRE, H, U, DUL, DULT, DPRET, DC, DCT, DX, DCA, part, fold, gfix, fixmax, total;
   bool fixed;  // deterministic mode (holo_ctx_set_deterministic): fixed-point images of the gradient maps
+  // typed pointers into the workspace, straight into the kernels' parameters (b.fwd is filled): the row buffers, and for
+  // every map whose gradient is wanted its channels-last image and, in the deterministic mode, the fixed-point one
+  void bind(char* base, float* const* grad_feats, MlpMeanBwdParams& b) const {
+    auto fp = [&](size_t off) { return (float*)(base + off); };
+    b.X = fp(X), b.MEAN = fp(MEAN), b.CM = fp(CM), b.PRE = fp(PRE), b.H = fp(H), b.U = fp(U), b.DUL = fp(DUL);
+    b.DULT = fp(DULT), b.DPRET = fp(DPRET), b.DC = fp(DC), b.DCT = fp(DCT), b.DX = fp(DX), b.DCA = fp(DCA);
+    char *g = base + gmaps, *gx = base + gfix;
+    for (int k = 0; k < b.fwd.vp.n_feats; ++k) {
+      const ViewPoolParams::Feat& f = b.fwd.vp.feat[k];
+      const size_t bytes = align256((size_t)b.fwd.vp.n_views * f.H * f.W * f.Cp * sizeof(float));
+      if (grad_feats && grad_feats[k]) b.gfeat[k] = (float*)g;
+      if (fixed && b.gfeat[k]) b.gfix[k] = (long long*)gx;
+      g += bytes, gx += 2 * bytes;
+    }
+    if (fixed) b.fix_max = (uint32_t*)(base + fixmax);
+  }
 };
 static MmBwdLayout mm_bwd_layout(const HoloMlpMeanPooler* h, const HoloViewFeature* feats, int n_feats, int n_views) {
   MmBwdLayout L;
@@ -553,9 +476,7 @@ static MmBwdLayout mm_bwd_layout(const HoloMlpMeanPooler* h, const HoloViewFeatu
     off += align256(floats * sizeof(float));
     return o;
   };
-  size_t mapf = 0;
-  for (int k = 0; k < n_feats; ++k)
-    mapf += align256((size_t)n_views * feats[k].height * feats[k].width * ((feats[k].channels + 3) / 4 * 4) * sizeof(float)) / sizeof(float);
+  const size_t mapf = maps_bytes(feats, n_feats, n_views, sizeof(float)) / sizeof(float);
   L.maps = take(mapf);
   L.gmaps = take(mapf);
   L.X = take((size_t)L.NRp * L.dp);
@@ -580,20 +501,6 @@ static MmBwdLayout mm_bwd_layout(const HoloMlpMeanPooler* h, const HoloViewFeatu
   L.fixmax = L.fixed ? take(64) : off;
   L.total = off + 256;
   return L;
-}
-
-static int mm_gemm(const float* A, int lda, const float* B, int ldb, int b_kmajor, float* C, int ldc, int M, int N, int K, int nb,
-                   int64_t sa, int64_t sb, int64_t sc, void* stream) {
-  GemmParams g;
-  memset(&g, 0, sizeof g);
-  g.A = A, g.B = B, g.C = C;
-  g.M = M, g.Nn = N, g.K = K;
-  g.lda = lda, g.ldb = ldb, g.ldc = ldc;
-  g.nb0 = nb, g.nb1 = 1;
-  g.sa0 = sa, g.sb0 = sb, g.sc0 = sc;
-  g.b_kmajor = b_kmajor;
-  g.alpha = 1.f;
-  return gemm_launch(g, stream);
 }
 
 extern "C" {
@@ -638,28 +545,9 @@ int holo_mlp_mean_backward(HoloMlpMeanPooler* h, const HoloViewFeature* feats, i
   b.FW = FW;
   b.NRp = L.NRp;
   b.Pp = L.Pp;
-  auto fp = [&](size_t off) { return (float*)(base + off); };
-  b.X = fp(L.X), b.MEAN = fp(L.MEAN), b.CM = fp(L.CM), b.PRE = fp(L.PRE), b.H = fp(L.H), b.U = fp(L.U), b.DUL = fp(L.DUL);
-  b.DULT = fp(L.DULT), b.DPRET = fp(L.DPRET), b.DC = fp(L.DC), b.DCT = fp(L.DCT), b.DX = fp(L.DX), b.DCA = fp(L.DCA);
-  {
-    char* g = base + L.gmaps;
-    for (int k = 0; k < n_feats; ++k) {
-      const ViewPoolParams::Feat& f = b.fwd.vp.feat[k];
-      if (grad_feats && grad_feats[k]) b.gfeat[k] = (float*)g;
-      g += align256((size_t)n_views * f.H * f.W * f.Cp * sizeof(float));
-    }
-    if (L.fixed) {
-      char* gx = base + L.gfix;
-      for (int k = 0; k < n_feats; ++k) {
-        const ViewPoolParams::Feat& f = b.fwd.vp.feat[k];
-        if (b.gfeat[k]) b.gfix[k] = (long long*)gx;
-        gx += 2 * align256((size_t)n_views * f.H * f.W * f.Cp * sizeof(float));
-      }
-      b.fix_max = (uint32_t*)(base + L.fixmax);
-    }
-  }
-  float* part = fp(L.part);
-  float* fold = fp(L.fold);
+  L.bind(base, grad_feats, b);
+  float* part = (float*)(base + L.part);
+  float* fold = (float*)(base + L.fold);
   float *dA = fold, *dAm = dA + (size_t)128 * dp, *dcb = dAm + (size_t)128 * dp, *dG = dcb + 128, *dgl = dG + (size_t)FW * 128;
   const int NR = (int)L.NR, P = (int)L.P;
   const int Kc = (int)(L.NRp / L.S), Kc2 = (int)(L.Pp / L.S2);
@@ -676,25 +564,25 @@ int holo_mlp_mean_backward(HoloMlpMeanPooler* h, const HoloViewFeature* feats, i
     const int acc = ck > 0 ? 1 : 0;  // the parameter gradients of the chunks add up in chunk order
     // forward recomputation
     MM_TRY(mm_bwd_step_launch(b, 0, stream));                                                                    // X, MEAN
-    MM_TRY(mm_gemm(b.MEAN, dp, b.fwd.am, dp, 0, b.CM, 128, P, 128, dp, 1, 0, 0, 0, stream));                     // CM = MEAN Am^T
-    MM_TRY(mm_gemm(b.X, dp, b.fwd.a, dp, 0, b.PRE, 128, NR, 128, dp, 1, 0, 0, 0, stream));                       // PRE = X A^T
+    MM_TRY(gemm_batch_launch(b.MEAN, dp, b.fwd.am, dp, 0, b.CM, 128, P, 128, dp, 1, 0, 0, 0, stream));                     // CM = MEAN Am^T
+    MM_TRY(gemm_batch_launch(b.X, dp, b.fwd.a, dp, 0, b.PRE, 128, NR, 128, dp, 1, 0, 0, 0, stream));                       // PRE = X A^T
     MM_TRY(mm_bwd_step_launch(b, 1, stream));                                                                    // + CM + b', H
-    MM_TRY(mm_gemm(b.H, 128, b.fwd.g, 128, 0, b.U, FW, NR, F, 128, 1, 0, 0, 0, stream));                         // U = H G^T
+    MM_TRY(gemm_batch_launch(b.H, 128, b.fwd.g, 128, 0, b.U, FW, NR, F, 128, 1, 0, 0, 0, stream));                         // U = H G^T
     MM_TRY(mm_bwd_step_launch(b, 2, stream));                                                                    // DUL, DULT
     // dG (rows 0..F-1) and dl (row F) = DULT H, split over the rows
-    MM_TRY(mm_gemm(b.DULT, (int)L.NRp, b.H, 128, 1, part, 128, FW, 128, Kc, L.S, Kc, (int64_t)Kc * 128, (int64_t)FW * 128, stream));
+    MM_TRY(gemm_batch_launch(b.DULT, (int)L.NRp, b.H, 128, 1, part, 128, FW, 128, Kc, L.S, Kc, (int64_t)Kc * 128, (int64_t)FW * 128, stream));
     MM_TRY(mm_sum_partials_launch(part, L.S, (int64_t)FW * 128, dG, stream, acc));
     MM_TRY(mm_colsum_launch(b.DUL, L.NR, FW, FW, part, 1024, dgl, stream, acc));                                 // dg0 | dl0
-    MM_TRY(mm_gemm(b.DUL, FW, b.fwd.g, 128, 1, b.H, 128, NR, 128, F, 1, 0, 0, 0, stream));                       // DH = DU G  (into H)
+    MM_TRY(gemm_batch_launch(b.DUL, FW, b.fwd.g, 128, 1, b.H, 128, NR, 128, F, 1, 0, 0, 0, stream));                       // DH = DU G  (into H)
     MM_TRY(mm_bwd_step_launch(b, 3, stream));                                                                    // DPRE (in PRE), DPRET, DC, DCT
-    MM_TRY(mm_gemm(b.DPRET, (int)L.NRp, b.X, dp, 1, part, dp, 128, dp, Kc, L.S, Kc, (int64_t)Kc * dp, (int64_t)128 * dp, stream));
+    MM_TRY(gemm_batch_launch(b.DPRET, (int)L.NRp, b.X, dp, 1, part, dp, 128, dp, Kc, L.S, Kc, (int64_t)Kc * dp, (int64_t)128 * dp, stream));
     MM_TRY(mm_sum_partials_launch(part, L.S, (int64_t)128 * dp, dA, stream, acc));
-    MM_TRY(mm_gemm(b.DCT, (int)L.Pp, b.MEAN, dp, 1, part, dp, 128, dp, Kc2, L.S2, Kc2, (int64_t)Kc2 * dp, (int64_t)128 * dp, stream));
+    MM_TRY(gemm_batch_launch(b.DCT, (int)L.Pp, b.MEAN, dp, 1, part, dp, 128, dp, Kc2, L.S2, Kc2, (int64_t)Kc2 * dp, (int64_t)128 * dp, stream));
     MM_TRY(mm_sum_partials_launch(part, L.S2, (int64_t)128 * dp, dAm, stream, acc));
     MM_TRY(mm_colsum_launch(b.DC, L.P, 128, 128, part, 256, dcb, stream, acc));
     if (want) {
-      MM_TRY(mm_gemm(b.PRE, 128, b.fwd.a, dp, 1, b.DX, dp, NR, dp, 128, 1, 0, 0, 0, stream));                    // DX = DPRE A
-      MM_TRY(mm_gemm(b.DC, 128, b.fwd.am, dp, 1, b.DCA, dp, P, dp, 128, 1, 0, 0, 0, stream));                    // DCA = DC Am
+      MM_TRY(gemm_batch_launch(b.PRE, 128, b.fwd.a, dp, 1, b.DX, dp, NR, dp, 128, 1, 0, 0, 0, stream));                    // DX = DPRE A
+      MM_TRY(gemm_batch_launch(b.DC, 128, b.fwd.am, dp, 1, b.DCA, dp, P, dp, 128, 1, 0, 0, 0, stream));                    // DCA = DC Am
       if (L.fixed && ck > 0) HIP_TRY(hipMemsetAsync(b.fix_max, 0, 64, st));  // every chunk has its own binary point
       MM_TRY(mm_bwd_step_launch(b, 4, stream));
       if (L.fixed)  // the chunk's sums are added to the gradient maps in chunk order
@@ -714,72 +602,20 @@ int holo_mlp_mean_backward(HoloMlpMeanPooler* h, const HoloViewFeature* feats, i
   }
 #undef MM_TRY
   // ---- the folded gradients come to the host and are un-folded in float64 (the chain rule of holo_mlp_mean_commit's fold)
-  const size_t nfold = (size_t)2 * 128 * dp + 128 + (size_t)FW * 128 + FW;
-  std::vector<float> hf(nfold);
-  HIP_TRY(hipMemcpyAsync(hf.data(), fold, nfold * sizeof(float), hipMemcpyDeviceToHost, st));
+  FVec hf((size_t)2 * 128 * dp + 128 + (size_t)FW * 128 + FW);
+  HIP_TRY(hipMemcpyAsync(hf.data(), fold, hf.size() * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  const int nh = 128, D = h->D, dout = h->cfg.dim_out;
-  const float *hA = hf.data(), *hAm = hA + (size_t)128 * dp, *hcb = hAm + (size_t)128 * dp, *hG = hcb + 128, *hgl = hG + (size_t)FW * 128;
-  auto W = [&](const char* n) -> const std::vector<float>& { return h->host[n]; };
-  const auto &Ws = W("_first_sampled.weight"), &bs = W("_first_sampled.bias"), &Wm = W("_first_mean.weight"),
-             &bm = W("_first_mean.bias"), &W1 = W("_mlp.mlp.0.0.weight"), &Wl = W("_last.weight"), &bl = W("_last.bias"),
-             &M = W("pooled_feature_mapper.weight");
-  std::vector<int> col(D);
-  {
-    int c = 0;
-    for (int k = 0; k < h->cfg.n_feats; ++k)
-      for (int j = 0; j < h->cfg.channels[k]; ++j) col[c++] = h->quad0[k] * 4 + j;
-    for (int j = 0; j < h->E; ++j) col[c++] = h->emb0 + j;
-  }
-  std::vector<double> gW1((size_t)nh * nh, 0.0), gWs((size_t)nh * D, 0.0), gWm((size_t)nh * D, 0.0), gbsm(nh, 0.0), gb1(nh, 0.0);
-  for (int i = 0; i < nh; ++i) {  // A = W1 Ws, Am = W1 Wm, b' = W1 (bs + bm) + b1
-    gb1[i] = hcb[i];
-    for (int k = 0; k < nh; ++k) {
-      double acc = (double)hcb[i] * ((double)bs[k] + (double)bm[k]);
-      const double w = W1[(size_t)i * nh + k];
-      for (int j = 0; j < D; ++j) {
-        const double da = hA[(size_t)i * dp + col[j]], dam = hAm[(size_t)i * dp + col[j]];
-        acc += da * Ws[(size_t)k * D + j] + dam * Wm[(size_t)k * D + j];
-        gWs[(size_t)k * D + j] += w * da;
-        gWm[(size_t)k * D + j] += w * dam;
-      }
-      gW1[(size_t)i * nh + k] = acc;
-      gbsm[k] += w * hcb[i];
-    }
-  }
-  std::vector<double> gM((size_t)F * dout, 0.0), gWl((size_t)dout * nh, 0.0), gbl(dout, 0.0), gmb(F, 0.0);
-  for (int f = 0; f < F; ++f) {  // G = M Wl, g0 = M bl + mapper bias
-    gmb[f] = hgl[f];
-    for (int o = 0; o < dout; ++o) {
-      double acc = (double)hgl[f] * bl[o];
-      const double w = M[(size_t)f * dout + o];
-      for (int k = 0; k < nh; ++k) {
-        const double dg = hG[(size_t)f * 128 + k];
-        acc += dg * Wl[(size_t)o * nh + k];
-        gWl[(size_t)o * nh + k] += w * dg;
-      }
-      gM[(size_t)f * dout + o] = acc;
-      gbl[o] += w * hgl[f];
-    }
-  }
-  for (int k = 0; k < nh; ++k) gWl[k] += hG[(size_t)F * 128 + k];  // l = Wl[0]
-  gbl[0] += hgl[F];                                                  // l0 = bl[0]
-  auto put = [&](const char* name, const std::vector<double>& v) {
-    std::vector<float>& o = h->grads[name];
-    o.resize(v.size());
-    for (size_t i = 0; i < v.size(); ++i) o[i] = (float)v[i];
-  };
-  put("_first_sampled.weight", gWs);
-  put("_first_sampled.bias", gbsm);
-  put("_first_mean.weight", gWm);
-  put("_first_mean.bias", gbsm);
-  put("_mlp.mlp.0.0.weight", gW1);
-  put("_mlp.mlp.0.0.bias", gb1);
-  put("_last.weight", gWl);
-  put("_last.bias", gbl);
-  put("pooled_feature_mapper.weight", gM);
-  put("pooled_feature_mapper.bias", gmb);
-  return 0;
+  const HostParams& W = h->params;
+  MlpMeanGrads d = unfold_mlp_mean_grads(h->shape, FW, W["_first_sampled.weight"], W["_first_sampled.bias"], W["_first_mean.weight"],
+                                         W["_first_mean.bias"], W["_mlp.mlp.0.0.weight"], W["_last.weight"], W["_last.bias"],
+                                         W["pooled_feature_mapper.weight"], hf);
+  HostGrads& G = h->grads;
+  G.put("_first_sampled.weight", std::move(d.dWs)), G.put("_first_mean.weight", std::move(d.dWm));
+  G.put("_first_sampled.bias", d.dbsm), G.put("_first_mean.bias", std::move(d.dbsm));  // the fold sees only bs + bm
+  G.put("_mlp.mlp.0.0.weight", std::move(d.dW1)), G.put("_mlp.mlp.0.0.bias", std::move(d.db1));
+  G.put("_last.weight", std::move(d.dWl)), G.put("_last.bias", std::move(d.dbl));
+  G.put("pooled_feature_mapper.weight", std::move(d.dM)), G.put("pooled_feature_mapper.bias", std::move(d.dmb));
+  return G.publish(stream);
 }
 
 int holo_mlp_mean_get_grad(HoloMlpMeanPooler* h, const char* name, float* out_dev, int64_t numel, void* stream) {
@@ -787,20 +623,7 @@ int holo_mlp_mean_get_grad(HoloMlpMeanPooler* h, const char* name, float* out_de
     set_error("holo_mlp_mean_get_grad: null argument");
     return HOLO_E_INVALID;
   }
-  auto it = h->grads.find(name);
-  if (it == h->grads.end()) {
-    set_error("holo_mlp_mean_get_grad: no gradient for '%s' (run holo_mlp_mean_backward first)", name);
-    return HOLO_E_STATE;
-  }
-  if ((int64_t)it->second.size() != numel) {
-    set_error("holo_mlp_mean_get_grad: '%s' has %lld elements, not %lld", name, (long long)it->second.size(), (long long)numel);
-    return HOLO_E_INVALID;
-  }
-  if (upload_via_stage(&h->stage, &h->stage_floats, out_dev, it->second.data(), it->second.size(), stream)) {
-    set_error("holo_mlp_mean_get_grad: upload failed");
-    return HOLO_E_HIP;
-  }
-  return 0;
+  return h->grads.fetch("holo_mlp_mean_get_grad", name, out_dev, numel, stream);
 }
 
 }  // extern "C"
