@@ -74,7 +74,8 @@ static int setup_view_pool(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloV
   }
   if (n_views < 1 || n_views > ViewPoolParams::MAX_VIEWS || n_feats < 1 || n_feats > ViewPoolParams::MAX_FEATS ||
       cfg->resol < 2 || cfg->feature_size < 1) {
-    set_error("holo_view_pool: 1..%d source views, 1..%d feature maps", ViewPoolParams::MAX_VIEWS, ViewPoolParams::MAX_FEATS);
+    set_error("holo_view_pool: 1..%d source views, 1..%d feature maps, resol >= 2, feature_size >= 1", ViewPoolParams::MAX_VIEWS,
+              ViewPoolParams::MAX_FEATS);
     return HOLO_E_UNSUPPORTED;
   }
   if (workspace_bytes < workspace_need) {

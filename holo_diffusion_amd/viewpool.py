@@ -276,6 +276,11 @@ class ViewPooler(Configurable, torch.nn.Module):
         from .render import _camera_array
         agg: MLPMeanFeatureAggregator = self.feature_aggregator
         keys = list(feats)
+        if not keys:
+            raise ValueError("view pooling needs at least one feature map")
+        max_feats = len(_lib.HoloMlpMeanCfg().channels)
+        if len(keys) > max_feats:  # before anything is sized by the maps: HoloMlpMeanCfg.channels has this many entries
+            raise _lib.HoloError(f"MLPMeanFeatureAggregator: {len(keys)} feature maps (at most {max_feats})")
         t0 = feats[keys[0]]
         runtime.require_device(t0, "ViewPooler.pool_to_voxel_features")
         dev, n_src = t0.device, int(t0.shape[0])

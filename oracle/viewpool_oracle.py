@@ -34,10 +34,10 @@ import torch
 import torch.nn.functional as F
 
 
-def coord_grid(resol: int, volume_extent: float) -> torch.Tensor:
+def coord_grid(resol: int, volume_extent: float, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """World coordinates of the voxel centres, (R^3, 3), voxel v = (z*R + y)*R + x."""
     half = 0.5 * (resol - 1) * (volume_extent / resol)
-    lin = torch.linspace(-1.0, 1.0, resol, dtype=torch.float32) * half
+    lin = torch.linspace(-1.0, 1.0, resol, dtype=dtype) * half
     Z, Y, X = torch.meshgrid(lin, lin, lin, indexing="ij")
     return torch.stack([X, Y, Z], dim=-1).reshape(-1, 3)
 
@@ -69,11 +69,17 @@ def ray_dirs_to_cameras(pts: torch.Tensor, R: torch.Tensor, T: torch.Tensor) -> 
     return F.normalize(pts - centre[None], dim=-1)
 
 
-def pool_views(feats: Dict[str, torch.Tensor], cams: dict, resol: int, volume_extent: float, gamma: float = 1.0,
-               min_weight: float = 0.1, eps_proj: float = 1e-2) -> torch.Tensor:
-    """feats: key -> (n_src, C_k, H_k, W_k); cams: R (n,3,3), T (n,3), focal (n,2), pp (n,2).
-    Returns the aggregated features (R^3, 2 * sum C_k): per key [AVG | STD], keys in dict order."""
-    pts = coord_grid(resol, volume_extent)
+def _as_dtype(feats: Dict[str, torch.Tensor], cams: dict, dtype: torch.dtype):
+    """``dtype`` = float64: the whole restatement (grid, weights, samples, reductions) in double, to tell which side of a
+    float32 comparison is off.  float32 (the default) leaves every tensor as it is."""
+    return {k: v.to(dtype) for k, v in feats.items()}, {k: v.to(dtype) for k, v in cams.items()}
+
+
+def pool_views_moments(feats: Dict[str, torch.Tensor], cams: dict, resol: int, volume_extent: float, gamma: float = 1.0,
+                       min_weight: float = 0.1, eps_proj: float = 1e-2, dtype: torch.dtype = torch.float32):
+    """Per key the weighted mean and the weighted variance BEFORE its clamp at 1e-4, each (R^3, C_k), keys in dict order."""
+    feats, cams = _as_dtype(feats, cams, dtype)
+    pts = coord_grid(resol, volume_extent, dtype)
     n = cams["R"].shape[0]
     dirs = torch.stack([ray_dirs_to_cameras(pts, cams["R"][v], cams["T"][v]) for v in range(n)])      # (n,P,3)
     dots = (dirs * dirs[:1]).sum(-1)                                                                    # vs view 0
@@ -86,6 +92,15 @@ def pool_views(feats: Dict[str, torch.Tensor], cams: dict, resol: int, volume_ex
         den = w.sum(0).clamp(1e-2)[:, None]
         mu = (x * w[..., None]).sum(0) / den
         var = (((x - mu[None]) ** 2) * w[..., None]).sum(0) / den
+        outs.append((mu, var))
+    return outs
+
+
+def pool_views(feats: Dict[str, torch.Tensor], cams: dict, resol: int, volume_extent: float, **kw) -> torch.Tensor:
+    """feats: key -> (n_src, C_k, H_k, W_k); cams: R (n,3,3), T (n,3), focal (n,2), pp (n,2); keywords of
+    ``pool_views_moments``.  Returns the aggregated features (R^3, 2 * sum C_k): per key [AVG | STD], keys in dict order."""
+    outs = []
+    for mu, var in pool_views_moments(feats, cams, resol, volume_extent, **kw):
         outs += [mu, var.clamp(1e-4).sqrt()]
     return torch.cat(outs, dim=-1)
 
@@ -105,7 +120,7 @@ def voxel_features_from_views(feats: Dict[str, torch.Tensor], cams: dict, mapper
 # (ViewSampler) is PyTorch3D's and stays restated.
 # ---------------------------------------------------------------------------------------------------------------------
 def harmonic_embedding(x: torch.Tensor, n: int) -> torch.Tensor:
-    freqs = 2.0 ** torch.arange(n, dtype=torch.float32)
+    freqs = 2.0 ** torch.arange(n, dtype=x.dtype)
     e = (x[..., None] * freqs).reshape(*x.shape[:-1], -1)
     return torch.cat((e.sin(), e.cos(), x), dim=-1)
 
@@ -136,15 +151,18 @@ def mlp_mean_aggregate(feats_sampled: Sequence[torch.Tensor], ray_dirs: torch.Te
 
 
 def pool_views_mlp_mean(feats: Dict[str, torch.Tensor], cams: dict, sd: Dict[str, torch.Tensor], resol: int,
-                        volume_extent: float, n_harmonic: int = 3, eps_proj: float = 1e-2, prefix: str = "") -> torch.Tensor:
-    """ViewSampler (restated) + MLPMeanFeatureAggregator at the voxel centres: (R^3, dim_out)."""
-    pts = coord_grid(resol, volume_extent)
+                        volume_extent: float, n_harmonic: int = 3, eps_proj: float = 1e-2, prefix: str = "",
+                        dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """ViewSampler (restated) + MLPMeanFeatureAggregator at the voxel centres: (R^3, dim_out).  ``dtype``: see ``_as_dtype``
+    (the caller passes ``sd`` in the same type)."""
+    feats, cams = _as_dtype(feats, cams, dtype)
+    pts = coord_grid(resol, volume_extent, dtype)
     n = cams["R"].shape[0]
     dirs = torch.stack([ray_dirs_to_cameras(pts, cams["R"][v], cams["T"][v]) for v in range(n)])
     ndc = torch.stack([project_ndc(pts, cams["R"][v], cams["T"][v], cams["focal"][v], cams["pp"][v], eps_proj)
                        for v in range(n)])
     sampled = [torch.stack([ndc_grid_sample(f[v], ndc[v]) for v in range(n)]) for f in feats.values()]
-    w = torch.ones(n, pts.shape[0])  # masked_sampling false -> masks 1; exclude_target_view forced False (:114-116)
+    w = torch.ones(n, pts.shape[0], dtype=dtype)  # masked_sampling false -> masks 1; exclude_target_view forced False (:114-116)
     return mlp_mean_aggregate(sampled, dirs, w, sd, n_harmonic, prefix)
 
 
