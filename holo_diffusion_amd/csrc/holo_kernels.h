@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/holo_abi.h"
+#include "conv_plan.h"
 #include "conv_weights.h"
 #include "holo_knobs.h"
 
@@ -18,138 +19,17 @@ struct HoloCtx {
 
 namespace holo {
 
-// ---------------------------------------------------------------------------------------------
-// conv3d as implicit GEMM on fp32 MFMA (kernels_conv.hip).
-//   out[m][co] = bias[co] + residual[m][co] + sum_{tap,ci} W[tap][co][ci] * in'(m, tap, ci)
-// with m = ((n*OD+od)*OH+oh)*OW+ow over channels-last (NDHWC) activations.
-// in' = optional per-(n,channel) affine (GroupNorm folded with FiLM) + optional SiLU, applied while
-// the tile is staged, zero padding applied AFTER the activation; optional nearest x2 upsample on load;
-// optional virtual channel concat of two sources (UNet skip connection, unet.py:829).
-// ---------------------------------------------------------------------------------------------
-// The kernel conv_plan chose for a launch.  The values are the HoloOpTiming.kernel ids of holo_unet_time_ops
-// (include/holo_abi.h); id 3, the retired depth-only Winograd form, is not used.
-enum class ConvKernel : int32_t {
-  Gather = 0,          // per-tap gather kernel (conv_igemm_kernel)
-  Halo = 1,            // LDS voxel-halo kernel (conv_halo_kernel; conv_halo_split_kernel in the bf16x3 mode)
-  RowTile = 2,         // row-tile kernel (conv_small_kernel): 1x1x1, strided and deepest-level convolutions
-  Wino2 = 4,           // (z,y) Winograd form of the 128-voxel halo kernel (conv_wino2_kernel)
-  Bf16Wide = 5,        // bf16 wide-tile kernel (conv_bf16t_kernel)
-  Wino3 = 6,           // F(2x2x2, 3x3x3) Winograd form (conv_wino3_kernel, kernels_conv3.hip)
-  Stream1x1 = 7,       // streaming 1x1x1 kernel (conv1x1_stream_kernel): large grids, raw input
-  Bf16Persistent = 8,  // the wide-tile kernel's persistent wave-specialised form (conv_bf16p_kernel, kernels_conv_bf16p.hip)
-  S2Bf16 = 9,          // stride-2 bf16 halo kernel (conv_s2_bf16_kernel, kernels_conv_s2.hip)
-  Qkv = 10,            // qkv convolution fused with the attention's operand packing (conv1x1_qkv_bf16_kernel)
-  Bf16Stream1x1 = 11,  // streaming 1x1x1 convolution on bf16 storage (conv1x1_bf16_stream_kernel)
-  Small1x1 = 12,       // exact-fp32 1x1x1 convolution of a small grid, K split over the waves (conv1x1_small_kernel)
-};
-
-struct ConvParams {
-  const float* src0;
-  const float* src1;  // may be null
-  int C0, C1;         // channels of src0 / src1; C0 % 32 == 0 when src1 != null; (C0+C1) % 4 == 0
-  int N, ID, IH, IW;  // logical input dims (AFTER upsampling when ups=1)
-  int ups;            // 1: sources have dims ID/2 x IH/2 x IW/2 and are read at (z>>1,y>>1,x>>1)
-  int OD, OH, OW;
-  int stride, pad, ksz;  // ksz = 3 (27 taps) or 1
-  int Cout;
-  const float* w;         // packed [ksz^3][CinP/32][CoutP/16][2][4][16][4] (repack_conv_weight_launch), zero padded to the
-                          // CoutP / CinP of conv_weight_layout (conv_weights.h: the one place that rounds them)
-  int CoutP, CinP;
-  const float* coef;      // [N][Cin][2] = (a,b): x' = a*x+b ; null = identity
-  int act;                // 1: SiLU after the affine (only with coef)
-  const float* bias;      // [Cout] or null
-  const float* residual;  // [M][Cout] or null
-  float* out;             // [M][Cout]
-  // optional fused 1x1x1 skip connection (halo kernel only): out += skip_w . [skip_src0 | skip_src1] + skip_bias
-  const float* skip_src0;
-  const float* skip_src1;
-  int skip_C0, skip_C1;
-  const float* skip_w;    // packed like w with one tap
-  // bf16-multiply variant of the halo kernel (opt-in, holo_unet_set_compute_dtype): the same weights rounded to
-  // bf16 (RNE), packed [ksz^3][CinP/32][CoutP/16][lane 64][8 bf16] = one 1 KB block of B operands of
-  // v_mfma_f32_16x16x32_bf16 per (tap, chunk, 16-Cout slice).  Used when bf16 != 0 and the launch is on the halo path.
-  // The buffer holds THREE such planes (hi, mid, lo: w = hi + mid + lo exactly); bf16 == 1 uses plane 0 only,
-  // bf16 == 2 the fp32-accurate bf16x3 kernel (conv_halo_split_kernel) all three.
-  const uint16_t* w_bf;
-  const uint16_t* skip_w_bf;
-  int bf16;
-  int skip_CinP;
-  const float* skip_bias;
-  double* stats;          // optional: GroupNorm partial sums of `out`, [N][conv_stats_slabs(p)][Cout][2]
-  float* partial;         // [nsplit][M][Cout] scratch when nsplit > 1
-  int nsplit;             // split-K factor over (tap, cin-chunk) chunks
-  int chunks_per_split;
-  int skip_chunks_per_split;  // halo kernel with a fused skip: skip chunks are dealt evenly to the same splits
-  int tz;                 // halo forms: tile depth (set by conv_plan; left 0 for the other kernels)
-  int grid_x;             // halo kernel: persistent workgroups along x (set by conv_plan)
-  int stagger_ticks;      // halo kernel: phase offset (100 MHz ticks) of the workgroup in the odd slot of a CU
-  unsigned long long* dbg;  // optional timeline probe (scripts/conv_timeline.cpp): [tile][8] {t_start, t_first_halo,
-                            // t_loops_done, t_end (100 MHz wall clock), HW_ID, XCC_ID, 0, 0}; null in production
-  ConvKernel kernel;      // set by conv_plan
-  // (z,y) Winograd form (conv_wino2_kernel): U = sum_kz,ky G[xi_z][kz] G[xi_y][ky] w[kz][ky][kx], 48 pseudo-taps
-  // (xi_z*4 + xi_y)*3 + kx; the fused skip as 4 pseudo-taps (xi_z,xi_y in {1,2}^2: +-w/4).  Null = not prepared for this
-  // conv (the direct kernel runs).
-  const float* w_wino2;
-  const float* skip_w_wino2;
-  // F(2x2x2, 3x3x3) form (conv_wino3_kernel, kernels_conv3.hip): the 64 pseudo-taps in the wave's consumption order
-  // (repack_conv_weight_wino3_launch); the fused skip as 8 signed copies of the 1x1x1 weight
-  const float* w_wino3;
-  const float* skip_w_wino3;
-  // set by conv_plan: the launch runs that kernel's upsampling form (conv_wino3_up_kernel: ups, raw input, no fused skip -
-  // the 27 pseudo-taps whose A operands are not identically zero; same results, 27/64 of the MFMAs)
-  int wino3_up;
-  // bf16 wide-tile kernel (conv_bf16t_kernel, 8x8x8 output tiles, v_mfma_f32_32x32x16_bf16): plane 3 of the bf16
-  // weight buffer, packed [ksz^3][CinP/16][CoutP/32][lane 64][8 bf16] = one 1 KB block of B operands per
-  // (tap, 16-channel chunk, 32-Cout slice); lane's 8 values are channels 8*(lane>>5) .. +7 of output channel lane&31
-  const uint16_t* w_bft;
-  const uint16_t* skip_w_bft;
-  // bf16 STORAGE (compute mode bf16): the buffers behind these float* are bf16 (uint16_t) channels-last tensors;
-  // coefficients, bias, statistics and split-K scratch stay fp32 / double
-  int in_bf16;            // src0 / src1 / skip_src0 / skip_src1
-  int res_bf16;           // residual
-  int out_bf16;           // out
-  // the qkv convolution of an AttentionBlock fused with the operand packing of the bf16 attention (kernels_conv1x1_bf16.hip;
-  // set by the planner when the launch may take that form, conv_plan decides: ConvKernel::Qkv): `out` is then NOT written
-  uint16_t* qkv_q;        // bf16 [sample, head][T][CH], scaled by qkv_scale
-  uint16_t* qkv_k;        // bf16 [sample, head][T][CH]
-  uint16_t* qkv_vt;       // bf16 [sample, head][CH][T]
-  float qkv_scale;        // CH^-1/2 * log2 e
-  int qkv_T, qkv_CH, qkv_H;
-  int qkv_sb, qkv_rows;   // set by conv_plan: 32-channel slices / rows per workgroup
-};
-
-// kernels_conv_s2.hip: the stride-2 3x3x3 convolution of a Downsample block on bf16 activation storage (raw input, 2 x 8 x 8
-// output tiles x 64 output channels, GroupNorm statistics: one slab per tile)
-bool conv_s2_bf16_supported(const ConvParams& p);
-int conv_s2_bf16_launch(const ConvParams& p, void* stream);
-
-// kernels_conv1x1_bf16.hip: the qkv convolution of an AttentionBlock (bf16 storage) writing the packed operands of
-// flash_attn_bf16v2_kernel (ConvParams::qkv_*) instead of fp32 qkv
-bool conv1x1_qkv_bf16_supported(const ConvParams& p);
-void conv1x1_qkv_bf16_plan(ConvParams& p, int num_cus);
-int conv1x1_qkv_bf16_launch(const ConvParams& p, void* stream);
-// ... and the same streaming GEMM with a plain [M][Cout] bf16 output (+ bias, + residual, GroupNorm slabs: one per workgroup row block)
-bool conv1x1_bf16_stream_supported(const ConvParams& p);
-void conv1x1_bf16_stream_plan(ConvParams& p, int num_cus);
-int conv1x1_bf16_stream_slabs(const ConvParams& p);
-int conv1x1_bf16_stream_launch(const ConvParams& p, void* stream);
-
+// conv3d (ConvParams, conv_plan: conv_plan.h).  conv_launch runs the kernel conv_plan chose; the launchers of the kernels
+// that live in files of their own pick the instantiation only (conv_can_launch has checked the launch).
+int conv_launch(const ConvParams& p, void* stream);
+int conv_s2_bf16_launch(const ConvParams& p, void* stream);         // kernels_conv_s2.hip
+int conv1x1_qkv_bf16_launch(const ConvParams& p, void* stream);     // kernels_conv1x1_bf16.hip
+int conv1x1_bf16_stream_launch(const ConvParams& p, void* stream);  // kernels_conv1x1_bf16.hip
+int conv_wino3_launch(const ConvParams& p, void* stream);           // kernels_conv3.hip
+int conv_bf16p_launch(const ConvParams& p, void* stream);           // kernels_conv_bf16p.hip
 // kernels_conv3.hip (conv_wino3_weight_floats: conv_weights.h)
 int repack_conv_weight_wino3_launch(const float* w, float* out, int Cout, int Cin, int src_taps, int CoutP, int CinP,
                                     void* stream);
-int conv_wino3_launch(const ConvParams& p, void* stream);
-// kernels_conv_bf16p.hip
-int conv_bf16p_launch(const ConvParams& p, void* stream);
-
-// Picks split-K so that the grid fills the chip; returns bytes of `partial` scratch needed (0 if none).
-// plan_n > 0: every choice (kernel, tile depth, split-K) is made as for a launch of plan_n samples, and only the grid and the
-// scratch are sized for p.N - with plan_n = 1 each sample of a batch is computed as at batch 1 (the batch-invariant plan of
-// holo_unet_set_batch_invariant).  0: choices for p.N.  `k`: the caller's snapshot of the knobs (holo_knobs.h).
-size_t conv_plan(ConvParams& p, int num_cus, const Knobs& k, int plan_n = 0);
-int conv_launch(const ConvParams& p, void* stream);
-int conv_stats_slabs(const ConvParams& p);
-double conv_flops(const ConvParams& p);       // algorithmic (the reference's multiply-adds x 2)
-double conv_exec_flops(const ConvParams& p);  // issued to the matrix pipe (differs for the Winograd kernels)
 
 // ---------------------------------------------------------------------------------------------
 // batched GEMM on fp32 MFMA (kernels_gemm.hip):  C[b] = alpha * A[b] * B[b]^T
@@ -231,8 +111,7 @@ int ndhwc_to_ncdhw_launch(const float* in, float* out, int N, int C, int64_t V, 
 int f32_to_bf16_launch(const float* in, float* out_bf16, int64_t n, void* stream);  // element-wise, n % 8 == 0
 
 // GroupNorm statistics, stage 1: partial[n][b][c] = (sum, sumsq) in double over voxel slab b (deterministic,
-// no atomics).  gn_stats_geometry gives the slab count B(C, V) the buffers must be sized for.
-void gn_stats_geometry(int C, int64_t V, int* n_blocks, int* vox_per_block);
+// no atomics).  gn_stats_geometry (conv_plan.h) gives the slab count B(C, V) the buffers must be sized for.
 int gn_stats_launch(const float* x, double* partial, int N, int C, int64_t V, void* stream, int x_bf16 = 0);
 
 // stage 2: GroupNorm(32 groups, eps) folded to per-channel (a,b), optionally composed with FiLM

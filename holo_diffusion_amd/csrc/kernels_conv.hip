@@ -30,10 +30,10 @@
 
 namespace holo {
 
+using namespace conv_tile;  // BM, BK, SM_ROWS, SG: conv_plan.h
+
 namespace {
 
-constexpr int BM = 128;
-constexpr int BK = 32;
 constexpr int LDK = 36;
 
 __device__ __forceinline__ float silu_f(float v) { return v / (1.0f + __expf(-v)); }
@@ -1881,8 +1881,6 @@ __global__ __launch_bounds__(256 * TZ, 2 / TZ) void conv_halo_split_kernel(ConvP
 //   * split-K over (tap, chunk) fills the chip with ~2 workgroups per CU; un-split launches produce the
 //     GroupNorm statistics of their output in the epilogue.
 // ---------------------------------------------------------------------------------------------
-constexpr int SM_ROWS = 64;
-constexpr int SG = 8;
 constexpr int SGH = 4;  // activation chunks requested per staging batch (register budget)
 
 // BF (bf16 compute mode): the activation rows are rounded to bf16 when they are committed to LDS (80-byte rows), the
@@ -2556,329 +2554,18 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
-const char* conv_kernel_name(ConvKernel k) {
-  switch (k) {
-    case ConvKernel::Gather: return "conv_igemm_kernel";
-    case ConvKernel::Halo: return "conv_halo_kernel";
-    case ConvKernel::RowTile: return "conv_small_kernel";
-    case ConvKernel::Wino2: return "conv_wino2_kernel";
-    case ConvKernel::Bf16Wide: return "conv_bf16t_kernel";
-    case ConvKernel::Wino3: return "conv_wino3_kernel";
-    case ConvKernel::Stream1x1: return "conv1x1_stream_kernel";
-    case ConvKernel::Bf16Persistent: return "conv_bf16p_kernel";
-    case ConvKernel::S2Bf16: return "conv_s2_bf16_kernel";
-    case ConvKernel::Qkv: return "conv1x1_qkv_bf16_kernel";
-    case ConvKernel::Bf16Stream1x1: return "conv1x1_bf16_stream_kernel";
-    case ConvKernel::Small1x1: return "conv1x1_small_kernel";
-  }
-  return "?";
-}
-
-// workgroups per CU the row-tile kernel's split-K aims at
-constexpr int SM_SPLIT_WGS_PER_CU = 2;
-// the bf16 wide-tile kernel also runs on under-filled levels (split over 16-channel chunks) once the K extent is long
-// enough to pay for the partials - measured at 128^3: from 192 input channels (main + fused skip) it beats the 64/128-voxel
-// halo kernel (32^3 .. 8^3 levels together 1.96 -> 1.7 ms), below that it loses
-constexpr int BF16T_LONG_K = 192;
-// workgroups per CU its split-K aims at: two on the 32^3 level and above, ONE below it and for raw-input launches
-// (measured at 128^3, profiles/r06_bf16t_split_target.txt: the 16^3 / 8^3 launches 43.6 -> 39.0, 41.5 -> 36.4,
-// 41.2 -> 35.9 us with half the partial sums to write and reduce; the 32^3 launches the other way round, 59.8 vs 66.4;
-// the raw-input Upsample convolution at 32^3 un-split lands on the persistent form: 126.7 -> 91.5 us)
-constexpr int BF16T_SPLIT_WGS_PER_CU_TOP = 2;
-constexpr int BF16T_SPLIT_WGS_PER_CU = 1;
-
-struct KSplit {
-  int n, cps;  // splits, chunks per split
-};
-// split-K over `chunks` chunks: `want` splits, at most `max_split` (<= chunks), the chunks dealt evenly (the last split
-// may get fewer)
-KSplit ksplit(int64_t want, int max_split, int chunks) {
-  const int cps = (int)cdiv(chunks, want < max_split ? want : max_split);
-  return {(int)cdiv(chunks, cps), cps};
-}
-
-// conv1x1_small_kernel: an exact-fp32 1x1x1 convolution of a small grid (16 .. 4096 voxels per sample, 32 .. 256 input
-// channels in 32-channel chunks, 64-channel output blocks, one source) whose input is normalised without an activation
-// (an AttentionBlock's qkv) or that adds a residual (its proj_out).  Raw-input 1x1x1 convolutions (ResBlock skips) keep
-// their kernels.
-bool conv1x1_small_supported(const ConvParams& p) {
-  const int Cin = p.C0 + p.C1;
-  const int64_t V = (int64_t)p.OD * p.OH * p.OW;
-  return p.ksz == 1 && p.stride == 1 && p.pad == 0 && !p.ups && p.bf16 == 0 && !p.in_bf16 && !p.out_bf16 && !p.res_bf16 &&
-         !p.skip_w && !p.src1 && p.C1 == 0 && !p.qkv_q && ((p.coef && !p.act) || p.residual) && (Cin % 32) == 0 &&
-         Cin >= 32 && Cin <= 256 && p.CinP == Cin && (p.Cout % 64) == 0 && p.CoutP == p.Cout && p.ID == p.OD &&
-         p.IH == p.OH && p.IW == p.OW && (V % 16) == 0 && V <= 4096 && (int64_t)p.N * V * (Cin > p.Cout ? Cin : p.Cout) < ((int64_t)1 << 31);
-}
-
-KSplit bf16t_split(const ConvParams& p, int64_t t8, int ncc16, int num_cus) {
-  const int64_t tgt = (int64_t)num_cus * (p.OD >= 32 && p.coef ? BF16T_SPLIT_WGS_PER_CU_TOP : BF16T_SPLIT_WGS_PER_CU);
-  return ksplit(t8 < tgt ? cdiv(tgt, t8) : 1, ncc16, ncc16);
-}
-
-// F(2x2x2, 3x3x3) form: ONE persistent 4-wave workgroup per CU walks (tile, 64-Cout block, split) items, so the chip is
-// full from num_cus items on; split-K only up to that
-KSplit wino3_split(int64_t t3, int ncc, int num_cus) { return ksplit(t3 < num_cus ? cdiv(num_cus, t3) : 1, ncc, ncc); }
-
 }  // namespace
 
-size_t conv_plan(ConvParams& p, int num_cus, const Knobs& k, int plan_n) {
-  const int Cin = p.C0 + p.C1;
-  const int ncc = (Cin + BK - 1) / BK;
-  const int nchunks = p.ksz * p.ksz * p.ksz * ncc;
-  const int nsk = p.skip_w ? (int)cdiv(p.skip_C0 + p.skip_C1, BK) : 0;  // fused skip chunks (one tap each)
-  const int ncc16 = (Cin + 15) / 16;                                    // the wide-tile kernels' 16-channel chunks
-  const int nsk16 = p.skip_w ? (p.skip_C0 + p.skip_C1 + 15) / 16 : 0;
-  const int64_t M = (int64_t)p.N * p.OD * p.OH * p.OW;
-  // the rows the choices are made for (plan_n samples); M (all samples) sizes the grids and the scratch.  (The addressing
-  // limits below stay on p.N: a batch past them takes another kernel - the batch-invariant planner checks for that.)
-  const int64_t Mc = (int64_t)(plan_n > 0 ? plan_n : p.N) * p.OD * p.OH * p.OW;
-  const int bn = p.Cout >= 64 ? 64 : 32;
-  const int64_t tiles = cdiv(Mc, BM) * cdiv(p.Cout, bn);
-  const int64_t t8 = (Mc / 512) * cdiv(p.Cout, bn);  // wide-tile kernels: 8^3 tiles x Cout slices
-  const int64_t t3 = (Mc / 128) * (p.Cout / 64);     // F(2x2x2) form: 2 x 8 x 8 tiles x 64-Cout blocks
-  const int64_t target = 2 * (int64_t)num_cus;
-  const int64_t src_vox = (int64_t)p.ID * p.IH * p.IW;  // the halo kernel addresses a source sample with 32-bit byte offsets
-  const int cmax = p.C0 > p.C1 ? p.C0 : p.C1;
-  const int skmax = p.skip_C0 > p.skip_C1 ? p.skip_C0 : p.skip_C1;
-  const bool fits32 = src_vox * (cmax > skmax ? cmax : skmax) * 4 < ((int64_t)1 << 32) &&
-                      (int64_t)p.OD * p.OH * p.OW * p.Cout * 4 < ((int64_t)1 << 32);  // (the wide-tile epilogue: output sample too)
-  const bool halo = p.ksz == 3 && p.stride == 1 && p.pad == 1 && (p.OD % 2) == 0 && (p.OH % 8) == 0 && (p.OW % 8) == 0 &&  // (TZ=1 tiles need no z divisibility)
-                    p.ID == p.OD && p.IH == p.OH && p.IW == p.OW && (Cin % 16) == 0 && fits32;
-  // the (z,y) Winograd form of 64-channel output blocks, where its weights were prepared
-  const bool wino2_wide = p.w_wino2 && p.bf16 == 0 && p.Cout >= 64 && (p.Cout % 64) == 0 && (!p.skip_w || p.skip_w_wino2);
-  // the halo forms' tile depth: 128-voxel tiles, or on an under-filled chip 64-voxel tiles that double the workgroups before
-  // resorting to split-K.  Exact-fp32 launches whose Winograd weights exist keep the 128-voxel tile on under-filled levels
-  // too: the Winograd kernels do 4/9 (8/27) of the MFMAs per voxel, which buys more than the doubled workgroup count of
-  // 64-voxel tiles; the chip is filled by split-K over the channel chunks instead.  HOLO_CONV_WINO_SMALL=0 turns that off,
-  // HOLO_CONV_FORCE_TZ2=1 (tests) takes 128-voxel tiles (hence the Winograd kernels) on small grids
-  const bool wino_small = k.conv_wino_small != 0 && wino2_wide && ncc >= 2;
-  const int tz = tiles < target && k.conv_force_tz2 != 1 && !wino_small ? 1 : 2;
-
-  // ---- the kernel: the first of these whose conditions hold
-  const ConvKernel kernel = [&] {
-    // the qkv convolution of an AttentionBlock, fused with the operand packing of the bf16 attention (the planner offers it by
-    // setting qkv_q; HOLO_CONV_QKV_FUSED=0 keeps the row-tile kernel + attn_pack_kernel)
-    if (p.qkv_q) {
-      if (k.conv_qkv_fused != 0 && conv1x1_qkv_bf16_supported(p)) return ConvKernel::Qkv;
-      p.qkv_q = nullptr;  // (not this launch: the caller packs)
-    }
-    // any other 1x1x1 convolution of a large grid on bf16 storage (the attention's proj_out): the same streaming GEMM with a
-    // plain output (HOLO_CONV1X1_BF16_STREAM=0 keeps the row-tile kernel)
-    if (k.conv1x1_bf16_stream != 0 && conv1x1_bf16_stream_supported(p)) return ConvKernel::Bf16Stream1x1;
-    if (!halo) {
-      // a 1x1x1 convolution of raw input over a LARGE grid (a ResBlock's skip_connection on the 64^3 level): the streaming
-      // GEMM (HOLO_CONV1X1_STREAM_MIN_M=<rows>: development knob, default 131 072 rows; 0 = off)
-      const int64_t min_m = k.conv1x1_stream_min_m;
-      if (min_m > 0 && Mc >= min_m && p.ksz == 1 && p.stride == 1 && !p.ups && !p.coef && !p.residual && !p.skip_w && p.bf16 == 0 &&
-          !p.in_bf16 && !p.out_bf16 && (p.Cout % 64) == 0 && (Cin % 32) == 0 && Cin >= 32 && Cin <= 256 &&
-          (!p.src1 || (p.C0 % 32) == 0) && (Mc % 16) == 0 && p.ID == p.OD && p.IH == p.OH && p.IW == p.OW)
-        return ConvKernel::Stream1x1;
-      // an attention block's qkv / proj_out in exact fp32 (16^3, 8^3): one 16-row tile per workgroup, K split over its
-      // waves (HOLO_CONV1X1_SMALL=0 keeps the row-tile kernel)
-      if (k.conv1x1_small != 0 && conv1x1_small_supported(p)) return ConvKernel::Small1x1;
-      // the stride-2 convolution of a Downsample block in the bf16 storage mode, where its 128-voxel tiles give the chip at
-      // least a workgroup per four CUs (128^3 net: 128^3 -> 64^3 540 -> ~100 us, and the two levels below; deeper the row-tile
-      // kernel's split-K fills the chip better).  HOLO_CONV_S2T=0 keeps the row-tile kernel, =1 takes this one wherever it is
-      // defined (tests)
-      const int64_t s2t = k.conv_s2t;
-      if (s2t != 0 && conv_s2_bf16_supported(p) && ((Mc / 128) * (p.Cout / 64) >= num_cus / 4 || s2t == 1))
-        return ConvKernel::S2Bf16;
-      // 1x1x1, strided and deepest-level convs: row-tile kernel (also for the 32^3 stride-2 convolution with its 32 768 rows:
-      // the per-tap gather kernel takes 118 us there, this one 95)
-      return p.Cout >= 64 ? ConvKernel::RowTile : ConvKernel::Gather;
-    }
-    // bf16 wide-tile kernel (8^3 voxels x 64 | 32 output channels per workgroup): where it fills the chip without split-K,
-    // and on the under-filled levels once the K extent is long (BF16T_LONG_K).  HOLO_CONV_BF16T=0 disables it, =1 forces it
-    // everywhere (tests)
-    const int64_t bt = k.conv_bf16t;
-    if (p.bf16 == 1 && p.in_bf16 && p.w_bft && (!p.skip_w || p.skip_w_bft) && (p.OD % 8) == 0 && (p.OH % 8) == 0 &&
-        (p.OW % 8) == 0 && (p.Cout % 32) == 0 && (p.C0 % 8) == 0 && (p.skip_C0 % 8) == 0 && ((p.skip_C0 + p.skip_C1) % 8) == 0 &&
-        (p.Cout >= 64 || !p.skip_w) && bt != 0 &&
-        (t8 >= target || Cin + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0) >= BF16T_LONG_K || bt == 1)) {
-      // the filled levels (every CU gets whole tiles without split-K): the persistent wave-specialised form
-      // (kernels_conv_bf16p.hip) - by default only for launches that stage their input RAW (no GroupNorm / SiLU on load: the
-      // input convolution, the Upsample convolutions): there its producer waves keep up with the consumers (tools/bf16p_probe:
-      // 128^3 32 -> 64 282 vs 293 us); with the activation arithmetic they do not yet (540 vs 479 us) and conv_bf16t_kernel
-      // stays.  HOLO_CONV_BF16P=0 keeps conv_bf16t_kernel everywhere, =2 takes the persistent form for activated input too,
-      // =1 forces it onto every wide-tile launch, without split-K (tests: small grids)
-      const int64_t bp = k.conv_bf16p;
-      const int wgs = num_cus & ~7;
-      if (bp != 0 && (bp == 1 || bp == 2 || !p.coef) &&
-          ((bf16t_split(p, t8, ncc16, num_cus).n == 1 && wgs >= 8 && t8 >= wgs) || bp == 1) &&
-          (p.C1 == 0 || (p.C0 % 16) == 0) &&  // (a 16-channel chunk / a 32-channel skip step lies in ONE source)
-          (!p.skip_w || (((p.skip_C0 + p.skip_C1) % 32) == 0 && (p.skip_C1 == 0 || (p.skip_C0 % 32) == 0))) &&
-          src_vox < ((int64_t)1 << 24))  // (24-bit voxel indices in the producers' address arithmetic)
-        return ConvKernel::Bf16Persistent;
-      return ConvKernel::Bf16Wide;
-    }
-    // F(2x2x2, 3x3x3) form (kernels_conv3.hip) from HOLO_CONV_WINO3_MIN_ITEMS work items on (default num_cus / 2: the (z,y)
-    // form needs 2 workgroups per CU).  HOLO_CONV_WINO3=0 disables it
-    if (tz == 2 && k.conv_wino3 != 0 && p.w_wino3 && p.bf16 == 0 && !p.in_bf16 && !p.out_bf16 && p.Cout >= 64 &&
-        (p.Cout % 64) == 0 && (!p.skip_w || p.skip_w_wino3) && (p.OH % 8) == 0 && (p.OW % 8) == 0 && (p.OD % 2) == 0 &&
-        (!p.coef || p.act) &&  // (its staging applies the affine and SiLU together)
-        (int64_t)p.N * src_vox * (cmax > skmax ? cmax : skmax) * 4 < ((int64_t)1 << 32) &&  // (buffer addressing of whole tensors)
-        // (... and of what its epilogue writes and reads: out / residual, every split's partial sums, the statistics records)
-        (int64_t)wino3_split(t3, ncc, num_cus).n * Mc * p.Cout * 4 < ((int64_t)1 << 32) &&
-        (!p.stats || (Mc / 128) * p.Cout * 16 < ((int64_t)1 << 32)) &&
-        (!p.skip_w || ((p.skip_C0 % 16) == 0 && (p.skip_C1 % 4) == 0)) &&
-        t3 * wino3_split(t3, ncc, num_cus).n >= (k.conv_wino3_min_items != KNOB_UNSET ? k.conv_wino3_min_items : num_cus / 2))
-      return ConvKernel::Wino3;
-    // exact-fp32 128-voxel tiles: the (z,y) Winograd form when its weights were prepared (32-channel convolutions: two wave rows)
-    if (tz == 2 && (wino2_wide || (p.w_wino2 && p.bf16 == 0 && p.Cout == 32 && !p.skip_w))) return ConvKernel::Wino2;
-    return ConvKernel::Halo;
-  }();
-  p.kernel = kernel;
-  // the upsampling form of the three-axis Winograd kernel (kernels_conv3.hip): nearest x2 input read raw, no fused skip.
-  // HOLO_CONV_WINO3_UP=0 keeps the generic form.  (No shape criterion: measured per launch, the form pays on every shape of
-  // the plan, the split-K 16^3 one included - profiles/r14_wino3_upsample.txt)
-  p.wino3_up = kernel == ConvKernel::Wino3 && p.ups && !p.coef && !p.skip_w && k.conv_wino3_up != 0 ? 1 : 0;
-
-  // ---- its geometry
-  switch (kernel) {
-    case ConvKernel::Qkv:
-    case ConvKernel::Bf16Stream1x1:
-    case ConvKernel::Stream1x1:
-    case ConvKernel::Small1x1:
-      p.nsplit = 1;
-      p.chunks_per_split = ncc;
-      if (kernel == ConvKernel::Qkv) conv1x1_qkv_bf16_plan(p, num_cus);
-      if (kernel == ConvKernel::Bf16Stream1x1) conv1x1_bf16_stream_plan(p, num_cus);
-      break;
-    case ConvKernel::S2Bf16:
-      p.nsplit = 1;
-      p.chunks_per_split = Cin / 16;
-      break;
-    case ConvKernel::RowTile: {
-      // (a fused 1x1x1 skip: its chunks follow the (tap, chunk) list; stride 1 and no upsampling there: conv_launch)
-      const int64_t t2 = cdiv(Mc, SM_ROWS) * cdiv(p.Cout, 64);
-      const int64_t tgt = SM_SPLIT_WGS_PER_CU * (int64_t)num_cus;
-      const int nall = nchunks + nsk;
-      const int max_split = nall / SG > 1 ? nall / SG : 1;  // a split below one full staging group only adds a reduce launch
-      const KSplit s = ksplit(t2 < tgt ? cdiv(tgt, t2) : 1, max_split, nall);
-      p.nsplit = s.n;
-      p.chunks_per_split = s.cps;
-      break;
-    }
-    case ConvKernel::Gather: {
-      const int max_split = nchunks / 4 > 1 ? nchunks / 4 : 1;  // keep >= 4 chunks per block
-      const KSplit s = ksplit(tiles < target ? cdiv(target, tiles) : 1, max_split, nchunks);
-      p.nsplit = s.n;
-      p.chunks_per_split = s.cps;
-      break;
-    }
-    case ConvKernel::Bf16Wide: {
-      const KSplit s = bf16t_split(p, t8, ncc16, num_cus);
-      p.tz = 8;
-      p.nsplit = s.n;
-      p.chunks_per_split = s.cps;
-      p.skip_chunks_per_split = (int)cdiv(nsk16, s.n);
-      p.grid_x = (int)(M / 512);
-      break;
-    }
-    case ConvKernel::Bf16Persistent: {  // no split-K: grid_x persistent workgroups, a multiple of 8 up to the CUs' multiple of 8
-      const int64_t wcap = (num_cus & ~7) >= 8 ? (num_cus & ~7) : 8;
-      const int64_t t8a = (M / 512) * cdiv(p.Cout, bn);  // (the tiles of all samples)
-      int64_t g = t8a < wcap ? ((t8a + 7) & ~(int64_t)7) : wcap;
-      const int64_t max_wgs = k.conv_bf16p_wgs;  // test knob: at most this many persistent workgroups
-      if (max_wgs > 0 && max_wgs < g) g = max_wgs;
-      p.tz = 8;
-      p.nsplit = 1;
-      p.chunks_per_split = ncc16;
-      p.skip_chunks_per_split = nsk16;
-      p.grid_x = (int)g;
-      break;
-    }
-    case ConvKernel::Wino3: {
-      const KSplit s = wino3_split(t3, ncc, num_cus);
-      const int64_t items = (M / 128) * (p.Cout / 64) * s.n;
-      p.tz = 2;
-      p.nsplit = s.n;
-      p.chunks_per_split = s.cps;
-      p.skip_chunks_per_split = (int)cdiv(nsk, s.n);
-      // every workgroup gets the same number of items when the list allows it (the last round is then full)
-      p.grid_x = (int)cdiv(items, cdiv(items, num_cus));
-      break;
-    }
-    case ConvKernel::Halo:
-    case ConvKernel::Wino2: {  // split over 32-channel chunks (each split walks all 27 taps)
-      const int64_t htiles = tz == 2 ? tiles : (Mc / 64) * cdiv(p.Cout, bn);
-      const KSplit s = ksplit(htiles < target ? cdiv(target, htiles) : 1, ncc, ncc);
-      p.tz = tz;
-      p.nsplit = s.n;
-      p.chunks_per_split = s.cps;
-      p.skip_chunks_per_split = (int)cdiv(nsk, s.n);
-      // One workgroup per tile.  (The kernel can also walk several tiles per workgroup - grid_x < tiles - with the
-      // next tile's halo prefetched under the last tap; measured on MI355X that is no faster than letting the
-      // dispatcher refill the slots, which also balances the load dynamically: tools/conv_timeline.cpp.)
-      p.grid_x = (int)(M / (64 * tz));
-      break;
-    }
-  }
-  const size_t scratch = p.nsplit > 1 ? (size_t)p.nsplit * M * p.Cout * sizeof(float) : 0;
-  if (k.debug_plan)
-    fprintf(stderr, "[plan] conv %d->%d k%d s%d @%d^3 batch %d%s: %s, tz %d, split-K %d x %d chunks (skip %d), grid_x %d, qkv %d rows x %d slices, scratch %zu bytes\n",
-            Cin, p.Cout, p.ksz, p.stride, p.OD, p.N, p.skip_w ? " +skip" : "", conv_kernel_name(kernel), p.tz, p.nsplit,
-            p.chunks_per_split, p.skip_chunks_per_split, p.grid_x, p.qkv_rows, p.qkv_sb, scratch);
-  return scratch;
-}
-
-// Number of GroupNorm-statistics slabs per sample the launch of `p` writes into p.stats (0 = this launch cannot
-// produce them: un-split gather kernel; use gn_stats_launch on the output instead).
-int conv_stats_slabs(const ConvParams& p) {
-  const int64_t V = (int64_t)p.OD * p.OH * p.OW;
-  if (p.nsplit > 1) {
-    int B, vpb;
-    gn_stats_geometry(p.Cout < 1024 ? p.Cout : 1024, V, &B, &vpb);
-    return B;
-  }
-  switch (p.kernel) {
-    case ConvKernel::Bf16Wide:
-    case ConvKernel::Bf16Persistent:
-      return (int)(V / 512);  // one slab per tile
-    case ConvKernel::Halo:
-      if (p.bf16 == 2 && p.w_bf && p.Cout >= 64 && !p.skip_w) return (int)(V / 32);  // bf16x3 kernel: per half 8x8 slab
-      [[fallthrough]];
-    case ConvKernel::Wino2:
-    case ConvKernel::Wino3:
-      return (int)(V / (64 * p.tz)) * (p.Cout >= 64 ? 1 : 2);
-    case ConvKernel::RowTile:
-      return V % SM_ROWS == 0 ? (int)(V / SM_ROWS) : 0;
-    case ConvKernel::S2Bf16:
-      return (int)(V / 128);  // one slab per 2 x 8 x 8 tile
-    case ConvKernel::Bf16Stream1x1:
-      return conv1x1_bf16_stream_slabs(p);  // one slab per workgroup row block
-    case ConvKernel::Small1x1:
-      return (int)(V / 16);  // one slab per workgroup
-    default:
-      return 0;
-  }
-}
-
-double conv_flops(const ConvParams& p) {
-  const double M = (double)p.N * p.OD * p.OH * p.OW;
-  return 2.0 * M * p.Cout * ((double)(p.C0 + p.C1) * p.ksz * p.ksz * p.ksz + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0));
-}
-
-// multiply-adds actually issued to the matrix pipe (x2): the Winograd kernels spend 64 pseudo-taps per 2 x 2 x 2 outputs
-// (F(2x2x2)) or 48 per 2 x 2 outputs ((z,y) form) where the direct form spends 27 per output; the fused skip costs the
-// same in all forms (F(2x2x2): accumulated directly; (z,y): 4 pseudo-taps per 4 outputs)
-double conv_exec_flops(const ConvParams& p) {
-  // (the upsampling form of the F(2x2x2) kernel issues the 27 of 64 pseudo-taps whose operands are not identically zero)
-  const double wino3_taps = p.wino3_up ? 27.0 / 8.0 : 8.0;
-  const double taps = p.kernel == ConvKernel::Wino3 ? wino3_taps : p.kernel == ConvKernel::Wino2 ? 12.0 : 0.0;
-  if (taps == 0.0) return conv_flops(p);
-  const double M = (double)p.N * p.OD * p.OH * p.OW;
-  return 2.0 * M * p.Cout * ((double)(p.C0 + p.C1) * taps + (p.skip_w ? p.skip_C0 + p.skip_C1 : 0));
-}
-
+// Runs the kernel conv_plan chose.  What a kernel can run, and the geometry it needs, is conv_can_launch (conv_plan.cpp): the
+// switch below only picks the instantiation.
 int conv_launch(const ConvParams& p, void* stream) {
   const int Cin = p.C0 + p.C1;
-  if ((Cin & 3) || (p.C0 & 3) || (p.Cout & 3) || (p.src1 && (p.C0 % BK))) {
-    set_error("conv_launch: unsupported channel counts C0=%d C1=%d Cout=%d", p.C0, p.C1, p.Cout);
-    return -1;
-  }
-  if (p.nsplit > 1 && !p.partial) {
-    set_error("conv_launch: split-K without scratch");
+  if (!conv_can_launch(p)) {
+    set_error("conv_launch: %s cannot run %d+%d -> %d channels k%d s%d%s @%dx%dx%d batch %d (bf16 %d, storage %d/%d/%d%s%s%s%s), "
+              "split-K %d x %d chunks, tz %d, grid_x %d",
+              conv_kernel_name(p.kernel), p.C0, p.C1, p.Cout, p.ksz, p.stride, p.ups ? " ups" : "", p.OD, p.OH, p.OW, p.N, p.bf16,
+              p.in_bf16, p.out_bf16, p.res_bf16, p.coef ? (p.act ? ", coef+act" : ", coef") : "", p.residual ? ", residual" : "",
+              p.skip_w ? ", skip" : "", p.stats ? ", stats" : "", p.nsplit, p.chunks_per_split, p.tz, p.grid_x);
     return -1;
   }
   const int64_t M = (int64_t)p.N * p.OD * p.OH * p.OW;
@@ -2887,6 +2574,21 @@ int conv_launch(const ConvParams& p, void* stream) {
   const int bn = wide ? 64 : 32;
   dim3 block(256);
   dim3 hgrid((unsigned)p.grid_x, (unsigned)cdiv(p.Cout, bn), (unsigned)p.nsplit);  // the halo forms
+// the NCH = Cin / 32 = 1..8 instantiations of the exact-fp32 1x1x1 kernels
+#define HOLO_NCH(KERNEL_, GRID_)                                          \
+  switch (Cin / 32) {                                                     \
+    case 1: HOLO_LAUNCH(KERNEL_<1>, GRID_, block, stream, p); break;      \
+    case 2: HOLO_LAUNCH(KERNEL_<2>, GRID_, block, stream, p); break;      \
+    case 3: HOLO_LAUNCH(KERNEL_<3>, GRID_, block, stream, p); break;      \
+    case 4: HOLO_LAUNCH(KERNEL_<4>, GRID_, block, stream, p); break;      \
+    case 5: HOLO_LAUNCH(KERNEL_<5>, GRID_, block, stream, p); break;      \
+    case 6: HOLO_LAUNCH(KERNEL_<6>, GRID_, block, stream, p); break;      \
+    case 7: HOLO_LAUNCH(KERNEL_<7>, GRID_, block, stream, p); break;      \
+    case 8: HOLO_LAUNCH(KERNEL_<8>, GRID_, block, stream, p); break;      \
+    default: /* (conv_can_launch admits no other) */                      \
+      set_error("conv_launch: no instantiation for %d input channels", Cin); \
+      return -1;                                                          \
+  }
   switch (p.kernel) {
     case ConvKernel::Gather: {
       dim3 grid((unsigned)cdiv(M, BM), (unsigned)cdiv(p.Cout, bn), (unsigned)p.nsplit);
@@ -2898,7 +2600,7 @@ int conv_launch(const ConvParams& p, void* stream) {
       break;
     }
     case ConvKernel::Halo: {
-      if (p.bf16 == 2 && p.w_bf && wide && !sk) {  // the bf16x3 form
+      if (conv_halo_bf16x3(p)) {
         if (p.tz == 2) {
           HOLO_LAUNCH(conv_halo_split_kernel<2>, hgrid, dim3(512), stream, p);
         } else {
@@ -2906,15 +2608,7 @@ int conv_launch(const ConvParams& p, void* stream) {
         }
         break;
       }
-      const bool bf = p.bf16 == 1 && p.w_bf && (!sk || p.skip_w_bf);
-      if ((p.in_bf16 != 0) != bf || (p.residual && (p.res_bf16 != 0) != bf)) {
-        set_error("conv_launch: the bf16 halo kernel and bf16 activation storage go together");
-        return -1;
-      }
-      if (!wide && sk) {
-        set_error("conv_launch: fused skip needs Cout >= 64");
-        return -1;
-      }
+      const bool bf = conv_halo_bf16(p);
 #define HOLO_HALO(NWN_, TZ_, SK_)                                                                 \
   do {                                                                                            \
     if (bf) {                                                                                     \
@@ -2940,14 +2634,6 @@ int conv_launch(const ConvParams& p, void* stream) {
       break;
     }
     case ConvKernel::RowTile: {
-      if (M >= ((int64_t)1 << 31)) {
-        set_error("conv_launch: the row-tile kernel indexes output voxels in 32 bits (M = %lld)", (long long)M);
-        return -1;
-      }
-      if (sk && (p.stride != 1 || p.ups || p.ID != p.OD || (p.bf16 == 1 && p.w_bf && !p.skip_w_bf))) {
-        set_error("conv_launch: the row-tile kernel fuses a skip connection at stride 1 without upsampling only");
-        return -1;
-      }
       dim3 sgrid((unsigned)cdiv(M, SM_ROWS), (unsigned)cdiv(p.Cout, 64), (unsigned)p.nsplit);
       if (p.bf16 == 1 && p.w_bf) {  // bf16 compute mode
         HOLO_LAUNCH(conv_small_kernel<true>, sgrid, block, stream, p);
@@ -2966,10 +2652,6 @@ int conv_launch(const ConvParams& p, void* stream) {
       }
       break;
     case ConvKernel::Bf16Wide:
-      if (!p.in_bf16 || (p.residual && !p.res_bf16)) {
-        set_error("conv_launch: the wide-tile bf16 kernel runs on bf16 activation storage");
-        return -1;
-      }
       if (!wide) {
         HOLO_LAUNCH((conv_bf16t_kernel<1, false, true>), hgrid, block, stream, p);
       } else if (sk) {
@@ -2978,71 +2660,29 @@ int conv_launch(const ConvParams& p, void* stream) {
         HOLO_LAUNCH((conv_bf16t_kernel<2, false, true>), hgrid, block, stream, p);
       }
       break;
-    case ConvKernel::Wino3:
-      if (conv_wino3_launch(p, stream)) return -1;
-      break;
     case ConvKernel::Stream1x1: {
-      if (p.stats || p.residual || p.coef || p.nsplit != 1) {
-        set_error("conv_launch: the streaming 1x1x1 kernel takes raw input and produces no statistics");
-        return -1;
-      }
       // two workgroups per CU, every wave walks 16-row tiles with a stride of the whole grid
       int64_t wgs = cdiv(M >> 4, 4 * 4);  // >= 4 tiles per wave
       if (wgs > 512) wgs = 512;
       if (wgs < 1) wgs = 1;
       dim3 g3((unsigned)wgs, (unsigned)(p.Cout / 64));
-      switch (Cin / 32) {
-        case 1: HOLO_LAUNCH(conv1x1_stream_kernel<1>, g3, block, stream, p); break;
-        case 2: HOLO_LAUNCH(conv1x1_stream_kernel<2>, g3, block, stream, p); break;
-        case 3: HOLO_LAUNCH(conv1x1_stream_kernel<3>, g3, block, stream, p); break;
-        case 4: HOLO_LAUNCH(conv1x1_stream_kernel<4>, g3, block, stream, p); break;
-        case 5: HOLO_LAUNCH(conv1x1_stream_kernel<5>, g3, block, stream, p); break;
-        case 6: HOLO_LAUNCH(conv1x1_stream_kernel<6>, g3, block, stream, p); break;
-        case 7: HOLO_LAUNCH(conv1x1_stream_kernel<7>, g3, block, stream, p); break;
-        case 8: HOLO_LAUNCH(conv1x1_stream_kernel<8>, g3, block, stream, p); break;
-        default:
-          set_error("conv_launch: streaming 1x1x1 kernel: %d input channels", Cin);
-          return -1;
-      }
+      HOLO_NCH(conv1x1_stream_kernel, g3);
       break;
     }
     case ConvKernel::Small1x1: {
-      if (!conv1x1_small_supported(p) || p.nsplit != 1) {
-        set_error("conv_launch: conv1x1_small_kernel: unsupported launch (%d -> %d channels, %d^3)", Cin, p.Cout, p.OD);
-        return -1;
-      }
       dim3 g1((unsigned)(M / 16), (unsigned)(p.Cout / 64));
-      switch (Cin / 32) {
-        case 1: HOLO_LAUNCH(conv1x1_small_kernel<1>, g1, block, stream, p); break;
-        case 2: HOLO_LAUNCH(conv1x1_small_kernel<2>, g1, block, stream, p); break;
-        case 3: HOLO_LAUNCH(conv1x1_small_kernel<3>, g1, block, stream, p); break;
-        case 4: HOLO_LAUNCH(conv1x1_small_kernel<4>, g1, block, stream, p); break;
-        case 5: HOLO_LAUNCH(conv1x1_small_kernel<5>, g1, block, stream, p); break;
-        case 6: HOLO_LAUNCH(conv1x1_small_kernel<6>, g1, block, stream, p); break;
-        case 7: HOLO_LAUNCH(conv1x1_small_kernel<7>, g1, block, stream, p); break;
-        case 8: HOLO_LAUNCH(conv1x1_small_kernel<8>, g1, block, stream, p); break;
-        default:
-          set_error("conv_launch: conv1x1_small_kernel: %d input channels", Cin);
-          return -1;
-      }
+      HOLO_NCH(conv1x1_small_kernel, g1);
       break;
     }
-    case ConvKernel::Bf16Persistent:
-      if (conv_bf16p_launch(p, stream)) return -1;
+    case ConvKernel::Wino3:  // (may be split: the reduce below)
+      if (conv_wino3_launch(p, stream)) return -1;
       break;
-    case ConvKernel::S2Bf16:
-      if (conv_s2_bf16_launch(p, stream)) return -1;
-      break;
-    case ConvKernel::Qkv:
-      if (conv1x1_qkv_bf16_launch(p, stream)) return -1;
-      break;
-    case ConvKernel::Bf16Stream1x1:
-      if (conv1x1_bf16_stream_launch(p, stream)) return -1;
-      break;
-    default:
-      set_error("conv_launch: unknown kernel %d", (int)p.kernel);
-      return -1;
+    case ConvKernel::Bf16Persistent: return conv_bf16p_launch(p, stream);
+    case ConvKernel::S2Bf16: return conv_s2_bf16_launch(p, stream);
+    case ConvKernel::Qkv: return conv1x1_qkv_bf16_launch(p, stream);
+    case ConvKernel::Bf16Stream1x1: return conv1x1_bf16_stream_launch(p, stream);
   }
+#undef HOLO_NCH
   if (p.nsplit > 1) {
     const int64_t MC = M * p.Cout;
     const int64_t V = (int64_t)p.OD * p.OH * p.OW;

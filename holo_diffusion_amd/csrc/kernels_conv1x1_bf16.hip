@@ -23,9 +23,10 @@
 #include "holo_kernels.h"
 
 namespace holo {
-namespace {
 
-constexpr int Q1_MAXK = 16;  // k-steps of 16 input channels (Cin <= 256)
+using namespace conv_tile;  // Q1_MAXK, Q1_MAXSB: conv_plan.h
+
+namespace {
 
 template <int NK>  // NK = Cin / 16
 __global__ __launch_bounds__(256, 2) void conv1x1_qkv_bf16_kernel(ConvParams p) {
@@ -124,7 +125,6 @@ __global__ __launch_bounds__(256, 2) void conv1x1_qkv_bf16_kernel(ConvParams p) 
 }
 
 
-constexpr int Q1_MAXSB = 12;  // slices per workgroup (48 KB of weights at 64 input channels)
 
 template <int NK>  // NK = Cin / 16
 __global__ __launch_bounds__(256, 2) void conv1x1_bf16_stream_kernel(ConvParams p) {
@@ -241,55 +241,9 @@ __global__ __launch_bounds__(256, 2) void conv1x1_bf16_stream_kernel(ConvParams 
 
 }  // namespace
 
-// the 32-channel slices a workgroup takes (its weights <= 48 KB of LDS); 0 = the launch is not for this kernel
-static int q1_slices_per_block(const ConvParams& p) {
-  const int Cin = p.C0 + p.C1;
-  int sb = 49152 / (Cin * 64);
-  const int nsl = p.Cout / 32;
-  while (sb > 1 && nsl % sb) --sb;
-  return sb < 1 ? 0 : sb;
-}
-
-bool conv1x1_qkv_bf16_supported(const ConvParams& p) {
-  const int Cin = p.C0 + p.C1;
-  const int64_t M = (int64_t)p.N * p.OD * p.OH * p.OW;
-  return p.qkv_q && p.ksz == 1 && p.stride == 1 && !p.ups && p.bf16 == 1 && p.in_bf16 && p.w_bft && !p.residual && !p.skip_w && !p.stats &&
-         p.C1 == 0 && (Cin % 16) == 0 && Cin >= 64 && Cin <= 16 * Q1_MAXK && (p.Cout % 32) == 0 && p.Cout == p.CoutP &&
-         p.qkv_CH % 32 == 0 && p.Cout == 3 * p.qkv_CH * p.qkv_H && p.qkv_T % 128 == 0 && M == (int64_t)p.N * p.qkv_T &&
-         q1_slices_per_block(p) > 0;
-}
-
-// rows per workgroup: a multiple of 128 that divides the sample, about two workgroups per CU
-void conv1x1_qkv_bf16_plan(ConvParams& p, int num_cus) {
-  p.qkv_sb = q1_slices_per_block(p);
-  const int nby = (p.Cout / 32) / p.qkv_sb;
-  int rows = 128;
-  while (rows * 2 <= p.qkv_T && (p.qkv_T % (rows * 2)) == 0 && ((int64_t)p.N * p.qkv_T / (rows * 2)) * nby >= 2 * (int64_t)num_cus) rows *= 2;
-  p.qkv_rows = rows;
-}
-
-bool conv1x1_bf16_stream_supported(const ConvParams& p) {
-  const int Cin = p.C0 + p.C1;
-  const int64_t V = (int64_t)p.OD * p.OH * p.OW;
-  return !p.qkv_q && p.ksz == 1 && p.stride == 1 && !p.ups && p.bf16 == 1 && p.in_bf16 && p.out_bf16 && (!p.residual || p.res_bf16) &&
-         p.w_bft && !p.skip_w && (!p.coef || !p.act) && p.C1 == 0 && (Cin % 16) == 0 && Cin >= 64 && Cin <= 16 * Q1_MAXK &&
-         (p.Cout % 32) == 0 && p.Cout == p.CoutP && p.ID == p.OD && p.IH == p.OH && p.IW == p.OW && V >= 4096 && (V % 128) == 0 &&
-         V < ((int64_t)1 << 31) && q1_slices_per_block(p) > 0 && q1_slices_per_block(p) <= 12;
-}
-
-// (shares ConvParams::qkv_T / qkv_sb / qkv_rows with the fused qkv form: rows per sample, slices and rows per workgroup)
-void conv1x1_bf16_stream_plan(ConvParams& p, int num_cus) {
-  p.qkv_T = (int)((int64_t)p.OD * p.OH * p.OW);
-  conv1x1_qkv_bf16_plan(p, num_cus);
-}
-
-int conv1x1_bf16_stream_slabs(const ConvParams& p) { return p.qkv_rows > 0 ? p.qkv_T / p.qkv_rows : 0; }
-
+// ConvKernel::Bf16Stream1x1 and ConvKernel::Qkv: the NK = Cin / 16 instantiations (conv_launch has checked the launch:
+// conv_can_launch; slices and rows per workgroup: conv_plan)
 int conv1x1_bf16_stream_launch(const ConvParams& p, void* stream) {
-  if (!conv1x1_bf16_stream_supported(p) || p.qkv_sb < 1 || p.qkv_rows < 128) {
-    set_error("conv1x1_bf16_stream_launch: unsupported launch (%d -> %d channels, %d^3)", p.C0 + p.C1, p.Cout, p.OD);
-    return -1;
-  }
   const int NK = (p.C0 + p.C1) / 16;
   const dim3 grid((unsigned)((int64_t)p.N * p.qkv_T / p.qkv_rows), (unsigned)((p.Cout / 32) / p.qkv_sb));
 #define HOLO_S1(NK_)                                                              \
@@ -301,8 +255,8 @@ int conv1x1_bf16_stream_launch(const ConvParams& p, void* stream) {
     HOLO_S1(8);
     HOLO_S1(12);
     HOLO_S1(16);
-    default:
-      set_error("conv1x1_bf16_stream_launch: %d input channels", NK * 16);
+    default:  // (conv_can_launch admits no other)
+      set_error("conv1x1_bf16_stream_launch: no instantiation for %d input channels", NK * 16);
       return -1;
   }
 #undef HOLO_S1
@@ -310,10 +264,6 @@ int conv1x1_bf16_stream_launch(const ConvParams& p, void* stream) {
 }
 
 int conv1x1_qkv_bf16_launch(const ConvParams& p, void* stream) {
-  if (!conv1x1_qkv_bf16_supported(p) || p.qkv_sb < 1 || p.qkv_rows < 128) {
-    set_error("conv1x1_qkv_bf16_launch: unsupported launch (%d -> %d channels, T %d)", p.C0 + p.C1, p.Cout, p.qkv_T);
-    return -1;
-  }
   const int Cin = p.C0 + p.C1, NK = Cin / 16;
   const dim3 grid((unsigned)((int64_t)p.N * p.qkv_T / p.qkv_rows), (unsigned)((p.Cout / 32) / p.qkv_sb));
 #define HOLO_Q1(NK_)                                                            \
@@ -325,8 +275,8 @@ int conv1x1_qkv_bf16_launch(const ConvParams& p, void* stream) {
     HOLO_Q1(8);
     HOLO_Q1(12);
     HOLO_Q1(16);
-    default:
-      set_error("conv1x1_qkv_bf16_launch: %d input channels", Cin);
+    default:  // (conv_can_launch admits no other)
+      set_error("conv1x1_qkv_bf16_launch: no instantiation for %d input channels", Cin);
       return -1;
   }
 #undef HOLO_Q1

@@ -954,27 +954,12 @@ int repack_conv_weight_wino3_launch(const float* w, float* out, int Cout, int Ci
 
 // ConvKernel::Wino3 (conv_plan): p.grid_x persistent workgroups
 int W3_ENTRY(const ConvParams& p, void* stream) {
-  if (!p.w_wino3 || (p.skip_w && !p.skip_w_wino3) || (p.OD & 1) || (p.OH & 7) || (p.OW & 7) || (p.Cout & 63) ||
-      (p.coef && !p.act)) {
-    set_error("conv_wino3_launch: unsupported shape / weights not prepared");
-    return -1;
-  }
-  // every split owns at least one chunk (the stage loop tests at its end), and what the epilogue addresses through buffer
-  // resources - out / residual, all partial sums, the statistics records - lies within 4 GB of its base (conv_plan chooses
-  // another kernel otherwise)
-  const int ncc = (p.C0 + p.C1 + W3_BK - 1) / W3_BK;
-  const int64_t out_bytes = (int64_t)p.N * p.OD * p.OH * p.OW * p.Cout * 4;
-  if (p.nsplit < 1 || p.chunks_per_split < 1 || (int64_t)(p.nsplit - 1) * p.chunks_per_split >= ncc ||
-      out_bytes * p.nsplit >= ((int64_t)1 << 32)) {
-    set_error("conv_wino3_launch: empty K split, or output beyond 32-bit byte offsets");
+  if (p.kernel != ConvKernel::Wino3 || !conv_can_launch(p)) {  // (also the entry of the probe copies: tools/conv_ab)
+    set_error("conv_wino3_launch: not a launch conv_plan made for this kernel");
     return -1;
   }
   const dim3 grid((unsigned)p.grid_x), block(256);
   if (p.wino3_up) {
-    if (!p.ups || p.coef || p.skip_w) {
-      set_error("conv_wino3_launch: the upsampling form takes raw x2 input without a fused skip");
-      return -1;
-    }
     HOLO_LAUNCH(conv_wino3_up_kernel, grid, block, stream, p);
   } else if (p.skip_w && p.coef) {
     HOLO_LAUNCH((conv_wino3_kernel<true, true>), grid, block, stream, p);

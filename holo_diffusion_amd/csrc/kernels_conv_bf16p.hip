@@ -811,17 +811,13 @@ __global__ __launch_bounds__(512, 2) void conv_bf16p_kernel(ConvParams p) {
 
 // Launch of the persistent wave-specialised kernel: p.grid_x workgroups of 512 threads (conv_plan: one per CU, a multiple of 8).
 int P_ENTRY(const ConvParams& p, void* stream) {
-  if (!p.in_bf16 || (p.residual && !p.res_bf16) || p.nsplit != 1 || !p.w_bft || (p.skip_w && !p.skip_w_bft)) {
-    set_error("conv_bf16p_launch: bf16 activation storage, prepared wide-tile weights, no split-K");
+  if (p.kernel != ConvKernel::Bf16Persistent || !conv_can_launch(p)) {  // (also the entry of the probe copies: tools/bf16p_probe)
+    set_error("conv_bf16p_launch: not a launch conv_plan made for this kernel");
     return -1;
   }
   const dim3 grid((unsigned)p.grid_x), block(512);
   const bool sk = p.skip_w != nullptr;
   if (p.Cout < 64) {
-    if (sk) {
-      set_error("conv_bf16p_launch: a fused skip needs Cout >= 64");
-      return -1;
-    }
     HOLO_LAUNCH((conv_bf16p_kernel<1, false>), grid, block, stream, p);
   } else if (sk) {
     HOLO_LAUNCH((conv_bf16p_kernel<2, true>), grid, block, stream, p);

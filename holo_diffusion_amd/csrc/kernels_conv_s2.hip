@@ -181,20 +181,8 @@ __global__ __launch_bounds__(256, 3) void conv_s2_bf16_kernel(ConvParams p) {
 
 }  // namespace
 
-bool conv_s2_bf16_supported(const ConvParams& p) {
-  const int Cin = p.C0 + p.C1;
-  return p.ksz == 3 && p.stride == 2 && p.pad == 1 && !p.ups && p.bf16 == 1 && p.in_bf16 && p.out_bf16 && p.w_bft && !p.coef &&
-         !p.residual && !p.skip_w && p.C1 == 0 && (Cin % 16) == 0 && (p.Cout % 64) == 0 && p.ID == 2 * p.OD && p.IH == 2 * p.OH &&
-         p.IW == 2 * p.OW && (p.OD % 2) == 0 && (p.OH % 8) == 0 && (p.OW % 8) == 0 &&
-         (int64_t)p.ID * p.IH * p.IW * Cin < ((int64_t)1 << 31);
-}
-
+// ConvKernel::S2Bf16 (conv_launch has checked the launch: conv_can_launch)
 int conv_s2_bf16_launch(const ConvParams& p, void* stream) {
-  if (!conv_s2_bf16_supported(p) || p.nsplit != 1) {
-    set_error("conv_s2_bf16_launch: unsupported launch (stride %d, %d -> %d channels, %d^3 -> %d^3)", p.stride, p.C0 + p.C1, p.Cout,
-              p.ID, p.OD);
-    return -1;
-  }
   const int64_t tiles = (int64_t)p.N * (p.OD >> 1) * (p.OH >> 3) * (p.OW >> 3);
   HOLO_LAUNCH(conv_s2_bf16_kernel, dim3((unsigned)tiles, (unsigned)(p.Cout / 64)), dim3(256), stream, p);
   return 0;

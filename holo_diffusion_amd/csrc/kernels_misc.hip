@@ -789,17 +789,6 @@ int ndhwc_to_ncdhw_launch(const float* in, float* out, int N, int C, int64_t V, 
   return 0;
 }
 
-// slab decomposition shared by the planner (buffer sizes) and the launcher
-void gn_stats_geometry(int C, int64_t V, int* n_blocks, int* vox_per_block) {
-  const int cq = C >> 2;
-  const int rows = 256 / cq;
-  int64_t B = cdiv(V, rows);
-  if (B > 256) B = 256;
-  int64_t vpb = cdiv(cdiv(V, B), rows) * rows;
-  *n_blocks = (int)cdiv(V, vpb);
-  *vox_per_block = (int)vpb;
-}
-
 int gn_stats_launch(const float* x, double* partial, int N, int C, int64_t V, void* stream, int x_bf16) {
   if ((C & 3) || (C >> 2) > 256) {
     set_error("gn_stats: unsupported C=%d", C);

@@ -132,6 +132,30 @@ def test_channel_widths_vs_oracle_blockwise(gu, row, compute, monkeypatch):
         assert names.count("flash_attn") == 6 and names.count("gemm") == 0, names
 
 
+def test_bf16_1x1_at_96_input_channels_leaves_the_streaming_kernels(gu, monkeypatch, capfd):
+    """A bf16-mode forward with a 1x1x1 convolution of 96 input channels over 4096 voxels - the smallest net that has one the bf16
+    streaming kernels' conditions used to admit: the un-fused skip_connection 96 -> 32 of the first ResBlock below the top level
+    (channel_mult (3, 1) at model_channels 32; 32 output channels, so it is not fused into the 3x3x3 convolution).
+    conv1x1_bf16_stream_kernel and conv1x1_qkv_bf16_kernel exist for 64 / 128 / 192 / 256 input channels only; the planner
+    used to pick the former here and the launcher then refused the forward.  (An attention block 96 wide never met this: its qkv
+    and proj_out have 288 and 96 output channels, not the whole 64-wide tiles those kernels ask for.)  The forward runs to the
+    end, no [plan] line names either kernel, and `y` and every block meet the bf16 bound of this file against the oracle."""
+    _heavy(gu)
+    monkeypatch.setenv("HOLO_KEEP_INTERMEDIATES", "1")
+    monkeypatch.setenv("HOLO_DEBUG_PLAN", "1")
+    cfg = uo.UNetCfg(image_size=32, in_channels=4, out_channels=4, model_channels=32, num_res_blocks=1, channel_mult=(3, 1),
+                     attention_resolutions=(), num_heads=1)
+    capfd.readouterr()
+    _forward_blockwise(gu, cfg, 1, "bf16", 99, 11, "96-to-32")
+    cap = capfd.readouterr()
+    plan = [line for line in cap.err.splitlines() if line.startswith("[plan] conv ")]
+    print(cap.out + "\n".join(plan))
+    skips = [line for line in plan if line.startswith("[plan] conv 96->32 k1 s1 @16^3 ")]
+    assert skips, plan
+    for line in plan:
+        assert "conv1x1_qkv_bf16_kernel" not in line and "conv1x1_bf16_stream_kernel" not in line, line
+
+
 # ---- 2. forced kernel families on `96-192` ---------------------------------------------------------------------------------
 # Seen on the MI355X: every setting leaves 12 -> 96 and the stride-2 96 -> 96 on conv_small_kernel, 96 -> 20 and - in fp32 -
 # every 96-wide convolution on conv_halo_kernel; the 14 192-wide ones and the Upsample 192 -> 192 move to the forced family,

@@ -16,4 +16,4 @@ $H $F -DP_TIMELINE -DP_ENTRY=conv_bf16p_launch_tl -c holo_diffusion_amd/csrc/ker
 $H -O2 --offload-arch=gfx950 -c tools/bf16p_probe.cpp -o /tmp/bf16p_probe.o
 $H --offload-arch=gfx950 /tmp/bf16p_probe.o holo_diffusion_amd/csrc/kernels_conv.o holo_diffusion_amd/csrc/kernels_conv3.o \
    holo_diffusion_amd/csrc/kernels_conv_bf16p.o holo_diffusion_amd/csrc/kernels_conv_s2.o holo_diffusion_amd/csrc/kernels_conv1x1_bf16.o \
-   holo_diffusion_amd/csrc/kernels_misc.o $O /tmp/bf16p_tl.o -o tools/bf16p_probe
+   holo_diffusion_amd/csrc/kernels_misc.o holo_diffusion_amd/csrc/conv_plan.o $O /tmp/bf16p_tl.o -o tools/bf16p_probe

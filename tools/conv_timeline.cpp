@@ -1,6 +1,6 @@
 // conv_timeline — per-workgroup timeline of one LDS-halo conv3d launch (development probe, not part of the library).
 // Build: hipcc -O2 --offload-arch=gfx950 tools/conv_timeline.cpp holo_diffusion_amd/csrc/kernels_conv.o \
-//              holo_diffusion_amd/csrc/kernels_misc.o -o tools/conv_timeline
+//              holo_diffusion_amd/csrc/kernels_misc.o holo_diffusion_amd/csrc/conv_plan.o -o tools/conv_timeline
 // Usage: conv_timeline [R=64] [Cin=64] [Cout=64] [kernel: 0 direct, 2 = (z,y) Winograd, 3 = bf16 wide-tile (bf16 storage)]
 //                      [tile_depth=0 (planner)] [stagger_us=0] [act=0: 1 = GroupNorm affine + SiLU while staging]
 //                      [epi=0: 1 = residual + bias + GroupNorm statistics in the epilogue]

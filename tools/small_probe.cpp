@@ -3,7 +3,8 @@
 // weights COLD (NW weight sets cycled: 16 x 27.6 MB pass the memory-side cache) or hot (one set), next to a kernel that does
 // nothing but read the same bytes with the same workgroup count.
 // Build: hipcc -O3 --offload-arch=gfx950 tools/small_probe.cpp holo_diffusion_amd/csrc/kernels_conv.o \
-//              holo_diffusion_amd/csrc/kernels_conv3.o holo_diffusion_amd/csrc/kernels_misc.o -o tools/small_probe
+//              holo_diffusion_amd/csrc/kernels_conv3.o holo_diffusion_amd/csrc/kernels_misc.o \
+//              holo_diffusion_amd/csrc/conv_plan.o -o tools/small_probe
 // Usage: small_probe [Cin=512] [Cout=512] [R=4] [iters=64]
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
