@@ -18,7 +18,8 @@ from .viewpool import ViewPooler, AngleWeightedReductionFeatureAggregator  # noq
 from . import checkpoint, flyaround_output, generate, model, render, runtime, viewpool  # noqa: F401,E402
 from .checkpoint import load_experiment  # noqa: F401,E402
 from .optim import HoloAdam  # noqa: F401,E402
+from .guidance import PhotometricGuidance  # noqa: F401,E402
 
 __all__ = ["registry", "SimpleUnet3D", "Unet3DBase", "ImplicitronGaussianDiffusion", "HoloVoxelGridImplicitFunction",
            "HoloMultiPassEmissionAbsorptionRenderer", "HoloDiffusionModel", "RenderMLP", "EvaluationMode",
-           "PerspectiveCameras", "get_simple_360_camera_trajectory", "HoloAdam"]
+           "PerspectiveCameras", "get_simple_360_camera_trajectory", "HoloAdam", "PhotometricGuidance"]

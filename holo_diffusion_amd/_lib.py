@@ -131,6 +131,13 @@ SIGNATURES = {
     "holo_ddim_step_philox_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_int,
                                              _vp, _vp, _vp, C.c_int, _vp]),
     "holo_dpm_step": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "holo_ddpm_step_guided": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, _vp,
+                                        _vp, _vp]),
+    "holo_ddpm_step_guided_philox": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_uint64,
+                                               C.c_uint64, _vp, C.c_uint32, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    "holo_ddim_step_guided": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "holo_ddim_step_guided_philox": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp,
+                                               C.c_uint32, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     "holo_tanh": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
     "holo_clip": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_float, C.c_int64, _vp]),
     "holo_renderer_create": (C.c_int, [_vp, C.POINTER(HoloRenderCfg), C.POINTER(_vp)]),

@@ -144,6 +144,21 @@ int ddim_step_launch(const float* coefs, int batch, int64_t per, const float* x_
 int ddim_step_philox_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
                             uint64_t seed, const uint32_t* row_streams, uint64_t offset, int clip, float* sample,
                             float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
+// The guided steps (include/holo_abi.h, holo_ddpm_step_guided / holo_ddim_step_guided): `grad` is the cond_fn gradient,
+// `variances` the (T,) posterior_variance table, slot 5 of a DDIM row sqrt(1 - abar_t); the Philox forms as above
+int ddpm_step_guided_launch(const float* tables, int T, const int64_t* timesteps, const float* variances, int batch,
+                            int64_t per, const float* x_t, const float* model_out, const float* grad, const float* noise,
+                            int clip, float* sample, float* pred_xstart, void* stream);
+int ddpm_step_guided_philox_launch(const float* tables, int T, const int64_t* timesteps, const float* variances, int batch,
+                                   int64_t per, const float* x_t, const float* model_out, const float* grad, uint64_t seed,
+                                   const uint32_t* row_streams, uint64_t offset, int clip, float* sample,
+                                   float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
+int ddim_step_guided_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
+                            const float* grad, const float* noise, int clip, float* sample, float* pred_xstart,
+                            void* stream);
+int ddim_step_guided_philox_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
+                                   const float* grad, uint64_t seed, const uint32_t* row_streams, uint64_t offset, int clip,
+                                   float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
 // DPM-Solver++ multistep step: coefs is (batch, 8) fp32, rows {a, b0, b1, b2, 0...}; hist1 / hist2 may be null
 // (include/holo_abi.h, holo_dpm_step)
 int dpm_step_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,

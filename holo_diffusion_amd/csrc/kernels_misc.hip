@@ -472,11 +472,16 @@ __device__ __forceinline__ StepQuad step_quad(int64_t tid, int b, int64_t per, i
 struct DdpmCoefs {
   float c1, c2, sig;
 };
-__device__ __forceinline__ DdpmCoefs ddpm_coefs(const float* __restrict__ tables, int T,
-                                                const int64_t* __restrict__ timesteps, int b) {
+// sample b's timestep, clamped into the table
+__device__ __forceinline__ int64_t ddpm_timestep(int T, const int64_t* __restrict__ timesteps, int b) {
   int64_t tt = holo_ld_sys(timesteps + b);
   if (tt < 0) tt = 0;
   if (tt >= T) tt = T - 1;
+  return tt;
+}
+__device__ __forceinline__ DdpmCoefs ddpm_coefs(const float* __restrict__ tables, int T,
+                                                const int64_t* __restrict__ timesteps, int b) {
+  const int64_t tt = ddpm_timestep(T, timesteps, b);
   const float c1 = holo_ld_sys(tables + tt * 4 + 0);  // (a 16 KB table uploaded from the host: see holo_ld_sys)
   const float c2 = holo_ld_sys(tables + tt * 4 + 1);
   const float lv = holo_ld_sys(tables + tt * 4 + 2);
@@ -485,9 +490,13 @@ __device__ __forceinline__ DdpmCoefs ddpm_coefs(const float* __restrict__ tables
 // The reference rounds each product, (c1*pred + c2*x) + sigma*noise; this kernel rounds c1*pred only and fuses the other two
 // into the sums: fma(sigma, noise, fma(c2, x, c1*pred)).  Spelled out so that the source says what runs (hipcc's
 // __fmul_rn / __fadd_rn are plain operators that contract after inlining); contract(off) keeps it at exactly this.
+__device__ __forceinline__ float ddpm_mean(float x, float m, DdpmCoefs c) {
+#pragma clang fp contract(off)
+  return fmaf(c.c2, x, c.c1 * m);
+}
 __device__ __forceinline__ float ddpm_update(float x, float m, float e, DdpmCoefs c) {
 #pragma clang fp contract(off)
-  return fmaf(c.sig, e, fmaf(c.c2, x, c.c1 * m));
+  return fmaf(c.sig, e, ddpm_mean(x, m, c));
 }
 __device__ __forceinline__ float4 ddpm_update4(float4 x, float4 m, float4 e, DdpmCoefs c) {
   return make_float4(ddpm_update(x.x, m.x, e.x, c), ddpm_update(x.y, m.y, e.y, c), ddpm_update(x.z, m.z, e.z, c),
@@ -535,6 +544,71 @@ __global__ __launch_bounds__(256) void ddpm_step_philox_kernel(const float* __re
   draw4(q.qd, ROWS ? 0u : (uint32_t)b, offset, seed_lo, key_hi, e);
   if (clip) m = clamp4(m);
   st4<NCDHW>(sample, q.o, ddpm_update4(x, m, e, c), q.es);
+  if (pred) st4<NCDHW>(pred, q.o, m, q.es);
+  if (noise_out) st4<NCDHW>(noise_out, q.o, e, q.es);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Guided DDPM update (condition_mean, gaussian_diffusion.py:429-433, inside p_sample :499-506): the posterior mean is moved
+// by variance * grad before the noise is added; pred_xstart stays the clamped model output.  v = variances[t] is
+// posterior_variance as its own (T,) table (slot 3 of `tables` stays 0).  Per element
+//   mean = ddpm_mean ;  mean_g = mean + v*grad (product rounded, sum rounded) ;  sample = fma(sigma, noise, mean_g)
+// so that grad == 0 gives ddpm_update's bits.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float ddpm_guided_update(float x, float m, float g, float e, DdpmCoefs c, float v) {
+#pragma clang fp contract(off)
+  const float mean_g = ddpm_mean(x, m, c) + v * g;
+  return fmaf(c.sig, e, mean_g);
+}
+__device__ __forceinline__ float4 ddpm_guided_update4(float4 x, float4 m, float4 g, float4 e, DdpmCoefs c, float v) {
+  return make_float4(ddpm_guided_update(x.x, m.x, g.x, e.x, c, v), ddpm_guided_update(x.y, m.y, g.y, e.y, c, v),
+                     ddpm_guided_update(x.z, m.z, g.z, e.z, c, v), ddpm_guided_update(x.w, m.w, g.w, e.w, c, v));
+}
+
+__global__ __launch_bounds__(256) void ddpm_step_guided_kernel(const float* __restrict__ tables, int T,
+                                                               const int64_t* __restrict__ timesteps,
+                                                               const float* __restrict__ variances, int64_t per,
+                                                               const float* __restrict__ x_t,
+                                                               const float* __restrict__ model_out,
+                                                               const float* __restrict__ grad,
+                                                               const float* __restrict__ noise, int clip,
+                                                               float* __restrict__ sample, float* __restrict__ pred) {
+  const int b = blockIdx.y;
+  const DdpmCoefs c = ddpm_coefs(tables, T, timesteps, b);
+  const float v = holo_ld_sys(variances + ddpm_timestep(T, timesteps, b));
+  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= per) return;
+  const int64_t o = (int64_t)b * per + i;
+  const float4 x = ld4(x_t, o);
+  float4 m = ld4(model_out, o);
+  const float4 g = ld4(grad, o);
+  const float4 e = ld4(noise, o);
+  if (clip) m = clamp4(m);
+  st4(sample, o, ddpm_guided_update4(x, m, g, e, c, v));
+  if (pred) st4(pred, o, m);
+}
+
+// The same update with the noise drawn in the kernel: the draw of ddpm_step_philox_kernel
+template <bool NCDHW, bool ROWS = false>
+__global__ __launch_bounds__(256) void ddpm_step_guided_philox_kernel(
+    const float* __restrict__ tables, int T, const int64_t* __restrict__ timesteps, const float* __restrict__ variances,
+    int64_t per, const float* __restrict__ x_t, const float* __restrict__ model_out, const float* __restrict__ grad,
+    uint32_t seed_lo, uint32_t seed_hi, uint32_t offset, int clip, float* __restrict__ sample, float* __restrict__ pred,
+    float* __restrict__ noise_out, int channels, const uint32_t* __restrict__ row_streams) {
+  const int b = blockIdx.y;
+  const uint32_t key_hi = row_key<ROWS>(seed_hi, row_streams, b);
+  const DdpmCoefs c = ddpm_coefs(tables, T, timesteps, b);
+  const float v = holo_ld_sys(variances + ddpm_timestep(T, timesteps, b));
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid * 4 >= per) return;
+  const StepQuad q = step_quad<NCDHW>(tid, b, per, channels);
+  const float4 x = ld4<NCDHW>(x_t, q.o, q.es);
+  float4 m = ld4<NCDHW>(model_out, q.o, q.es);
+  const float4 g = ld4<NCDHW>(grad, q.o, q.es);
+  float4 e;
+  draw4(q.qd, ROWS ? 0u : (uint32_t)b, offset, seed_lo, key_hi, e);
+  if (clip) m = clamp4(m);
+  st4<NCDHW>(sample, q.o, ddpm_guided_update4(x, m, g, e, c, v), q.es);
   if (pred) st4<NCDHW>(pred, q.o, m, q.es);
   if (noise_out) st4<NCDHW>(noise_out, q.o, e, q.es);
 }
@@ -613,6 +687,79 @@ __global__ __launch_bounds__(256) void ddim_step_philox_kernel(const float* __re
   }
   st4<NCDHW>(sample, q.o, s, q.es);
   if (pred) st4<NCDHW>(pred, q.o, m, q.es);
+  if (noise_out) st4<NCDHW>(noise_out, q.o, e, q.es);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Guided DDIM update (condition_score, gaussian_diffusion.py:445-453, then ddim_sample :674-693): the score is moved by
+// sqrt(1 - abar_t) * grad, the prediction is re-derived from it (and NOT clamped again), then the DDIM update runs on that
+// prediction.  The row of holo_ddim_step with c5 = sqrt(1 - abar_t) in slot 5.  Per element, each operation rounded:
+//   eps0 = (c0*x - pred) / c1 ;  eps1 = eps0 - c5*grad ;  predg = c0*x - c1*eps1 ;  eps = (c0*x - predg) / c1
+//   sample = predg*c2 + c3*eps + c4*noise ;  pred_xstart = predg
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float ddim_guided_mean(float x, float m, float g, const float (&c)[6], float& predg) {
+#pragma clang fp contract(off)
+  const float eps0 = (c[0] * x - m) / c[1];
+  const float eps1 = eps0 - c[5] * g;
+  predg = c[0] * x - c[1] * eps1;
+  return ddim_mean(x, predg, c[0], c[1], c[2], c[3]);
+}
+__device__ __forceinline__ float4 ddim_guided_mean4(float4 x, float4 m, float4 g, const float (&c)[6], float4& predg) {
+  return make_float4(ddim_guided_mean(x.x, m.x, g.x, c, predg.x), ddim_guided_mean(x.y, m.y, g.y, c, predg.y),
+                     ddim_guided_mean(x.z, m.z, g.z, c, predg.z), ddim_guided_mean(x.w, m.w, g.w, c, predg.w));
+}
+
+__global__ __launch_bounds__(256) void ddim_step_guided_kernel(const float* __restrict__ coefs, int64_t per,
+                                                               const float* __restrict__ x_t,
+                                                               const float* __restrict__ model_out,
+                                                               const float* __restrict__ grad,
+                                                               const float* __restrict__ noise, int clip,
+                                                               float* __restrict__ sample, float* __restrict__ pred) {
+  const int b = blockIdx.y;
+  float c[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) c[k] = holo_ld_sys(coefs + b * 8 + k);  // (a small table uploaded from the host: see holo_ld_sys)
+  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= per) return;
+  const int64_t o = (int64_t)b * per + i;
+  const float4 x = ld4(x_t, o);
+  float4 m = ld4(model_out, o);
+  const float4 g = ld4(grad, o);
+  if (clip) m = clamp4(m);
+  float4 pg;
+  float4 s = ddim_guided_mean4(x, m, g, c, pg);
+  if (noise && c[4] != 0.f) s = add_noise4(s, c[4], ld4(noise, o));
+  st4(sample, o, s);
+  if (pred) st4(pred, o, pg);
+}
+
+// The same update with the noise drawn in the kernel: the draw of ddim_step_philox_kernel
+template <bool NCDHW, bool ROWS = false>
+__global__ __launch_bounds__(256) void ddim_step_guided_philox_kernel(
+    const float* __restrict__ coefs, int64_t per, const float* __restrict__ x_t, const float* __restrict__ model_out,
+    const float* __restrict__ grad, uint32_t seed_lo, uint32_t seed_hi, uint32_t offset, int clip,
+    float* __restrict__ sample, float* __restrict__ pred, float* __restrict__ noise_out, int channels,
+    const uint32_t* __restrict__ row_streams) {
+  const int b = blockIdx.y;
+  float c[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) c[k] = holo_ld_sys(coefs + b * 8 + k);
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid * 4 >= per) return;
+  const StepQuad q = step_quad<NCDHW>(tid, b, per, channels);
+  const float4 x = ld4<NCDHW>(x_t, q.o, q.es);
+  float4 m = ld4<NCDHW>(model_out, q.o, q.es);
+  const float4 g = ld4<NCDHW>(grad, q.o, q.es);
+  if (clip) m = clamp4(m);
+  float4 pg;
+  float4 s = ddim_guided_mean4(x, m, g, c, pg);
+  float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (c[4] != 0.f || noise_out) {
+    draw4(q.qd, ROWS ? 0u : (uint32_t)b, offset, seed_lo, row_key<ROWS>(seed_hi, row_streams, b), e);
+    if (c[4] != 0.f) s = add_noise4(s, c[4], e);
+  }
+  st4<NCDHW>(sample, q.o, s, q.es);
+  if (pred) st4<NCDHW>(pred, q.o, pg, q.es);
   if (noise_out) st4<NCDHW>(noise_out, q.o, e, q.es);
 }
 
@@ -898,6 +1045,48 @@ int ddim_step_philox_launch(const float* coefs, int batch, int64_t per, const fl
   HOLO_LAUNCH_PHILOX_STEP(ddim_step_philox_kernel, ncdhw_channels, row_streams, step_grid(per, batch), dim3(256), stream,
                           coefs, per, x_t, model_out, k0, k1, (uint32_t)offset, clip, sample, pred_xstart, noise_out,
                           ncdhw_channels, row_streams);
+  return 0;
+}
+
+// The guided steps (include/holo_abi.h): one Philox launcher per sampler, row_streams null or not as above
+int ddpm_step_guided_launch(const float* tables, int T, const int64_t* timesteps, const float* variances, int batch,
+                            int64_t per, const float* x_t, const float* model_out, const float* grad, const float* noise,
+                            int clip, float* sample, float* pred_xstart, void* stream) {
+  if (!step_shape_ok("ddpm_step_guided", per)) return -1;
+  HOLO_LAUNCH(ddpm_step_guided_kernel, step_grid(per, batch), dim3(256), stream, tables, T, timesteps, variances, per, x_t,
+              model_out, grad, noise, clip, sample, pred_xstart);
+  return 0;
+}
+
+int ddpm_step_guided_philox_launch(const float* tables, int T, const int64_t* timesteps, const float* variances, int batch,
+                                   int64_t per, const float* x_t, const float* model_out, const float* grad, uint64_t seed,
+                                   const uint32_t* row_streams, uint64_t offset, int clip, float* sample,
+                                   float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
+  if (!step_shape_ok("ddpm_step_guided_philox", per, ncdhw_channels)) return -1;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);  // (as ddpm_step_philox)
+  HOLO_LAUNCH_PHILOX_STEP(ddpm_step_guided_philox_kernel, ncdhw_channels, row_streams, step_grid(per, batch), dim3(256),
+                          stream, tables, T, timesteps, variances, per, x_t, model_out, grad, k0, k1, (uint32_t)offset,
+                          clip, sample, pred_xstart, noise_out, ncdhw_channels, row_streams);
+  return 0;
+}
+
+int ddim_step_guided_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
+                            const float* grad, const float* noise, int clip, float* sample, float* pred_xstart,
+                            void* stream) {
+  if (!step_shape_ok("ddim_step_guided", per)) return -1;
+  HOLO_LAUNCH(ddim_step_guided_kernel, step_grid(per, batch), dim3(256), stream, coefs, per, x_t, model_out, grad, noise,
+              clip, sample, pred_xstart);
+  return 0;
+}
+
+int ddim_step_guided_philox_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
+                                   const float* grad, uint64_t seed, const uint32_t* row_streams, uint64_t offset, int clip,
+                                   float* sample, float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
+  if (!step_shape_ok("ddim_step_guided_philox", per, ncdhw_channels)) return -1;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);  // (as ddpm_step_philox)
+  HOLO_LAUNCH_PHILOX_STEP(ddim_step_guided_philox_kernel, ncdhw_channels, row_streams, step_grid(per, batch), dim3(256),
+                          stream, coefs, per, x_t, model_out, grad, k0, k1, (uint32_t)offset, clip, sample, pred_xstart,
+                          noise_out, ncdhw_channels, row_streams);
   return 0;
 }
 

@@ -2565,6 +2565,55 @@ int holo_dpm_step(HoloCtx*, const float* coefs, int batch, int64_t elems_per_sam
   });
 }
 
+// gaussian_diffusion.py:429-433 (condition_mean) inside p_sample :499-506
+int holo_ddpm_step_guided(HoloCtx*, const float* tables, int num_timesteps, const int64_t* timesteps, const float* variances,
+                          int batch, int64_t elems_per_sample, const float* x_t, const float* model_out, const float* grad,
+                          const float* noise, int clip_denoised, float* sample, float* pred_xstart, void* stream) {
+  return step_entry("holo_ddpm_step_guided",
+                    tables && timesteps && variances && x_t && model_out && grad && noise && sample && batch >= 1, [&] {
+    return ddpm_step_guided_launch(tables, num_timesteps, timesteps, variances, batch, elems_per_sample, x_t, model_out, grad,
+                                   noise, clip_denoised, sample, pred_xstart, stream);
+  });
+}
+
+// the same with the noise of :498 drawn in the kernel; row_streams null: the offset form, else one stream per row
+int holo_ddpm_step_guided_philox(HoloCtx*, const float* tables, int num_timesteps, const int64_t* timesteps,
+                                 const float* variances, int batch, int64_t elems_per_sample, const float* x_t,
+                                 const float* model_out, const float* grad, uint64_t seed, uint64_t stream_offset,
+                                 const uint32_t* row_streams, uint32_t timestep_index, int clip_denoised, float* sample,
+                                 float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
+  return step_entry("holo_ddpm_step_guided_philox",
+                    tables && timesteps && variances && x_t && model_out && grad && sample && batch >= 1, [&] {
+    return ddpm_step_guided_philox_launch(tables, num_timesteps, timesteps, variances, batch, elems_per_sample, x_t, model_out,
+                                          grad, seed, row_streams, row_streams ? (uint64_t)timestep_index : stream_offset,
+                                          clip_denoised, sample, pred_xstart, noise_out, ncdhw_channels, stream);
+  });
+}
+
+// gaussian_diffusion.py:445-453 (condition_score) followed by ddim_sample :674-693
+int holo_ddim_step_guided(HoloCtx*, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                          const float* model_out, const float* grad, const float* noise, int clip_denoised, float* sample,
+                          float* pred_xstart, void* stream) {
+  return step_entry("holo_ddim_step_guided",
+                    coefs && x_t && model_out && grad && sample && batch >= 1 && elems_per_sample >= 4, [&] {
+    return ddim_step_guided_launch(coefs, batch, elems_per_sample, x_t, model_out, grad, noise, clip_denoised, sample,
+                                   pred_xstart, stream);
+  });
+}
+
+// the same with the noise of :685 drawn in the kernel; row_streams as holo_ddpm_step_guided_philox
+int holo_ddim_step_guided_philox(HoloCtx*, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                                 const float* model_out, const float* grad, uint64_t seed, uint64_t stream_offset,
+                                 const uint32_t* row_streams, uint32_t timestep_index, int clip_denoised, float* sample,
+                                 float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream) {
+  return step_entry("holo_ddim_step_guided_philox",
+                    coefs && x_t && model_out && grad && sample && batch >= 1 && elems_per_sample >= 4, [&] {
+    return ddim_step_guided_philox_launch(coefs, batch, elems_per_sample, x_t, model_out, grad, seed, row_streams,
+                                          row_streams ? (uint64_t)timestep_index : stream_offset, clip_denoised, sample,
+                                          pred_xstart, noise_out, ncdhw_channels, stream);
+  });
+}
+
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream) {
   (void)ctx;
   return tanh_launch(x, y, n, stream);

@@ -27,6 +27,11 @@ the choice of the channels-last layout, then model call, step, yield.  A sampler
 callback; ``_last_sample`` finishes the non-progressive loops.  ``_launch`` and ``_launch_device_noise`` are the two ways into
 the library's step entries (plain, and with the noise drawn in the kernel: offset or per-row streams); ``_step``,
 ``_step_device_noise``, ``_ddim_step``, ``_ddim_step_device_noise`` and ``_dpm_step`` name the entry and its leading arguments.
+
+Guidance (``cond_fn``; gaussian_diffusion.py:420-457, used at :502-505 and :669-670): ``p_sample*`` and ``ddim_sample*`` take the
+reference's ``cond_fn(x, t, **model_kwargs)``, called once per step after the model, and hand its gradient to the guided forms
+of the two step kernels (``holo_ddpm_step_guided``: condition_mean; ``holo_ddim_step_guided``: condition_score on
+``ddim_guided_coefs`` rows).  A guided chain runs NCDHW.  Without ``cond_fn`` every path is the unguided one above.
 """
 from __future__ import annotations
 
@@ -123,6 +128,7 @@ class ImplicitronGaussianDiffusion(Configurable):
         self._build_tables(betas)
         self._schedule_sampler = UniformSampler(self.num_timesteps)
         self._dev_tables: Dict[int, torch.Tensor] = {}
+        self._dev_variances: Dict[int, torch.Tensor] = {}
         self._row_stream_tables: Dict[tuple, torch.Tensor] = {}
 
     # gaussian_diffusion.py:149-187
@@ -155,6 +161,14 @@ class ImplicitronGaussianDiffusion(Configurable):
             self._dev_tables[idx] = t
         return t
 
+    def _variances_on(self, device: torch.device) -> torch.Tensor:
+        """posterior_variance as a (T,) float32 table on ``device`` (holo_ddpm_step_guided), uploaded once like ``_tables_on``."""
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        v = self._dev_variances.get(idx)
+        if v is None:
+            v = self._dev_variances[idx] = torch.from_numpy(self.posterior_variance.astype(np.float32)).to(device).contiguous()
+        return v
+
     @staticmethod
     def _extract(arr: np.ndarray, timesteps: torch.Tensor, shape) -> torch.Tensor:
         res = torch.from_numpy(arr).to(device=timesteps.device)[timesteps].float()
@@ -174,7 +188,7 @@ class ImplicitronGaussianDiffusion(Configurable):
     def _launch(self, entry: str, head, x, model_output, extras, clip_denoised, want_pred=True):
         """One plain step kernel, ``entry`` of the library: (sample, pred_xstart | None).  ``head`` are the entry's arguments
         between the context and the batch (its table or rows), ``extras`` its optional input tensors after the model output
-        (noise, history): None goes in as a null pointer."""
+        (guidance gradient, noise, history): None goes in as a null pointer."""
         runtime.require_device(x, "ImplicitronGaussianDiffusion")
         L = runtime.lib()
         dev = x.device
@@ -189,28 +203,39 @@ class ImplicitronGaussianDiffusion(Configurable):
         return sample, pred
 
     def _launch_device_noise(self, entry: str, head, x, model_output, timestep_index: int, clip_denoised, want_pred, want_noise,
-                             channels_last: bool):
+                             channels_last: bool, grad=None):
         """One step kernel with in-kernel Philox noise (perf mode): (sample, pred_xstart | None, noise | None).  ``entry`` is the
         offset form (``holo_*_step_philox``); per-row streams go to its ``_rows`` form.  A draw is keyed on the LOGICAL element
         (seed, stream, timestep, sample, channel, voxel): ``channels_last`` says which layout ``x`` is in - an (N, R, R, R, C)
         chain and an (N, C, R, R, R) chain of the same seed draw the same noise (C a multiple of 4; otherwise the NCDHW
-        tensor's memory order is the key)."""
+        tensor's memory order is the key).  With ``grad`` (a guided entry, ``holo_*_step_guided_philox``) the gradient follows
+        the model output and the one entry takes both stream forms."""
         runtime.require_device(x, "ImplicitronGaussianDiffusion")
         L = runtime.lib()
         dev = x.device
         x, model_output = x.contiguous(), model_output.contiguous()
+        inputs = [runtime.ptr(x), runtime.ptr(model_output)]
+        if grad is not None:
+            grad = grad.contiguous()
+            inputs.append(runtime.ptr(grad))
         sample = torch.empty_like(x)
         pred = torch.empty_like(x) if want_pred else None
         noise = torch.empty_like(x) if want_noise else None
         ncdhw = 0 if (channels_last or x.dim() < 3 or x.shape[1] % 4) else int(x.shape[1])
         rows = self._row_streams(x.shape[0], dev)
-        if rows is not None:  # one stream per row: each row draws its batch-1 chain's noise
+        tidx = int(timestep_index) & 0xFFFFFFFF
+        # one stream per row: each row draws its batch-1 chain's noise; else the stream offset (chain id, timestep) - distinct
+        # for every step of every chain that shares the seed
+        offset = 0 if rows is not None else (int(self.device_noise_stream) << 32) | tidx
+        if grad is not None:  # one guided entry for both forms: (stream_offset, row_streams | NULL, timestep_index)
+            key = (offset, None if rows is None else runtime.ptr(rows), tidx)
+        elif rows is not None:
             entry += "_rows"
-            key = (runtime.ptr(rows), int(timestep_index) & 0xFFFFFFFF)
-        else:  # stream offset: (chain id, timestep) - distinct for every step of every chain that shares the seed
-            key = ((int(self.device_noise_stream) << 32) | (int(timestep_index) & 0xFFFFFFFF),)
-        _lib.check(L, getattr(L, entry)(runtime.ctx(dev), *head, x.shape[0], x[0].numel(), runtime.ptr(x),
-                                        runtime.ptr(model_output), int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, *key,
+            key = (runtime.ptr(rows), tidx)
+        else:
+            key = (offset,)
+        _lib.check(L, getattr(L, entry)(runtime.ctx(dev), *head, x.shape[0], x[0].numel(), *inputs,
+                                        int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, *key,
                                         1 if clip_denoised else 0, runtime.ptr(sample), runtime.ptr(pred) if want_pred else None,
                                         runtime.ptr(noise) if want_noise else None, ncdhw, runtime.stream_ptr(dev)), entry)
         return sample, pred, noise
@@ -219,9 +244,23 @@ class ImplicitronGaussianDiffusion(Configurable):
         runtime.require_device(x, "ImplicitronGaussianDiffusion")  # (before the table is looked up on x's device)
         return runtime.ptr(self._tables_on(x.device)), self.num_timesteps, runtime.ptr(t)
 
-    def _step(self, x, t, model_output, noise, clip_denoised):
-        """Fused HIP tail of p_sample: returns (sample, pred_xstart)."""
+    def _ddpm_guided_head(self, x, t):
+        return (*self._ddpm_head(x, t), runtime.ptr(self._variances_on(x.device)))
+
+    def _step(self, x, t, model_output, noise, clip_denoised, grad=None):
+        """Fused HIP tail of p_sample: returns (sample, pred_xstart).  ``grad`` (a cond_fn's gradient): holo_ddpm_step_guided."""
+        if grad is not None:
+            return self._launch("holo_ddpm_step_guided", self._ddpm_guided_head(x, t), x, model_output, [grad, noise],
+                                clip_denoised)
         return self._launch("holo_ddpm_step", self._ddpm_head(x, t), x, model_output, [noise], clip_denoised)
+
+    @staticmethod
+    def _guidance(cond_fn, x, t, model_kwargs):
+        """The gradient of a step: ``cond_fn(x, t, **model_kwargs).float()`` (gaussian_diffusion.py:429-431, :449), x's shape."""
+        grad = cond_fn(x, t, **(model_kwargs or {})).float()
+        if grad.shape != x.shape:
+            raise ValueError(f"cond_fn returned shape {tuple(grad.shape)} for x of shape {tuple(x.shape)}")
+        return grad
 
     def _row_streams(self, batch: int, device: torch.device) -> Optional[torch.Tensor]:
         """``device_noise_stream`` as a (batch,) uint32 table on ``device`` (held as int32) when it is a sequence - the per-row
@@ -243,8 +282,12 @@ class ImplicitronGaussianDiffusion(Configurable):
         return t
 
     def _step_device_noise(self, x, t, model_output, timestep_index: int, clip_denoised, want_pred=True, want_noise=False,
-                           channels_last: bool = False):
-        """holo_ddpm_step_philox: the step with in-kernel noise, (sample, pred_xstart | None, noise | None)."""
+                           channels_last: bool = False, grad=None):
+        """holo_ddpm_step_philox: the step with in-kernel noise, (sample, pred_xstart | None, noise | None).  ``grad``:
+        holo_ddpm_step_guided_philox, the same draw."""
+        if grad is not None:
+            return self._launch_device_noise("holo_ddpm_step_guided_philox", self._ddpm_guided_head(x, t), x, model_output,
+                                             timestep_index, clip_denoised, want_pred, want_noise, channels_last, grad)
         return self._launch_device_noise("holo_ddpm_step_philox", self._ddpm_head(x, t), x, model_output,
                                          timestep_index, clip_denoised, want_pred, want_noise, channels_last)
 
@@ -268,22 +311,23 @@ class ImplicitronGaussianDiffusion(Configurable):
 
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                  noise_sampler=None):
-        if cond_fn is not None:
-            raise NotImplementedError("cond_fn guidance is not used by HoloDiffusion and is not supported")
+        """``cond_fn(x, t, **model_kwargs)`` (gaussian_diffusion.py:429-433, condition_mean): the gradient of a conditional
+        log-probability with respect to x; the posterior mean moves by variance * gradient, pred_xstart does not."""
         if model_kwargs is None:
             model_kwargs = {}
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         model_output = model(x, t, **model_kwargs)
         if denoised_fn is not None:
             model_output = denoised_fn(model_output)
+        grad = None if cond_fn is None else self._guidance(cond_fn, x, t, model_kwargs)
         if noise_sampler is None and self.device_noise_seed is not None:  # perf mode: noise drawn inside the kernel
-            sample, pred, noise = self._step_device_noise(x, t, model_output, int(t[0].item()), clip_denoised)
+            sample, pred, noise = self._step_device_noise(x, t, model_output, int(t[0].item()), clip_denoised, grad=grad)
             return {"sample": sample, "pred_xstart": pred, "noise": noise}  # ("noise": None - it never left the kernel)
         if noise_sampler is not None:
             noise = noise_sampler(int(t[0].item()), x.shape, x.device)  # same host sync as the reference (:495-496)
         else:
             noise = torch.randn_like(x)
-        sample, pred = self._step(x, t, model_output, noise, clip_denoised)
+        sample, pred = self._step(x, t, model_output, noise, clip_denoised, grad)
         return {"sample": sample, "pred_xstart": pred, "noise": noise}
 
     def _indices(self, max_iter: Optional[int]):
@@ -361,24 +405,24 @@ class ImplicitronGaussianDiffusion(Configurable):
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                   model_kwargs=None, device=None, progress=False, max_iter=None,
                                   noise_sampler=None, _materialize_every_step: bool = True) -> Iterator[dict]:
-        """``_materialize_every_step`` (internal, used by ``p_sample_loop``): see ``_chain``."""
-        if cond_fn is not None:
-            raise NotImplementedError("cond_fn guidance is not supported")
+        """``_materialize_every_step`` (internal, used by ``p_sample_loop``): see ``_chain``.  ``cond_fn`` as in ``p_sample``: called
+        once per step after the model, on the NCDHW x_t, under the loop's ``torch.no_grad()`` (gaussian_diffusion.py:551)."""
         indices = self._indices(max_iter)
         device_noise = self._device_noise(noise_sampler)
 
         def step(k, img, t, model_output, _, channels_last):
+            grad = None if cond_fn is None else self._guidance(cond_fn, img, t, model_kwargs)
             if device_noise:  # (no host sync: indices[k] is host-side; "noise": None - it never leaves the kernel)
                 sample, pred, eps = self._step_device_noise(img, t, model_output, indices[k], clip_denoised,
-                                                            channels_last=channels_last)
+                                                            channels_last=channels_last, grad=grad)
             else:
                 eps = noise_sampler(indices[k], img.shape, img.device) if noise_sampler is not None else torch.randn_like(img)
-                sample, pred = self._step(img, t, model_output, eps, clip_denoised)
+                sample, pred = self._step(img, t, model_output, eps, clip_denoised, grad)
             return {"sample": sample, "pred_xstart": pred, "noise": eps}
 
         yield from self._chain(model, shape, indices, None, step, noise=noise, noise_sampler=noise_sampler, device=device,
                                progress=progress, denoised_fn=denoised_fn, model_kwargs=model_kwargs,
-                               channels_last_ok=device_noise, materialize=_materialize_every_step)
+                               channels_last_ok=device_noise and cond_fn is None, materialize=_materialize_every_step)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                       model_kwargs=None, device=None, progress=False, return_all_samples=False, max_iter=None,
@@ -436,16 +480,29 @@ class ImplicitronGaussianDiffusion(Configurable):
         row[:, 4] = torch.from_numpy(t != 0).float() * sigma
         return row
 
-    def _ddim_step(self, x, model_output, coefs_dev, noise, clip_denoised, want_pred=True):
-        """holo_ddim_step: (sample, pred_xstart | None).  ``coefs_dev`` is the (batch, 8) row block on the device."""
+    def ddim_guided_coefs(self, t: Sequence[int], t_prev: Sequence[int], eta: float = 0.0) -> torch.Tensor:
+        """The rows of holo_ddim_step_guided: ``ddim_coefs`` with slot 5 = sqrt(1 - abar_t), the factor of the gradient in
+        condition_score (gaussian_diffusion.py:445-451): float32, from the float32 cast of alphas_cumprod[t]."""
+        row = self.ddim_coefs(t, t_prev, eta)
+        alpha_bar = torch.from_numpy(self.alphas_cumprod[np.asarray(t, dtype=np.int64).reshape(-1)]).float()
+        row[:, 5] = torch.from_numpy(np.sqrt((1 - alpha_bar).numpy()))  # (correctly rounded, as ddim_coefs' sqrt)
+        return row
+
+    def _ddim_step(self, x, model_output, coefs_dev, noise, clip_denoised, want_pred=True, grad=None):
+        """holo_ddim_step: (sample, pred_xstart | None).  ``coefs_dev`` is the (batch, 8) row block on the device.  ``grad`` (a
+        cond_fn's gradient): holo_ddim_step_guided on ``ddim_guided_coefs`` rows."""
+        if grad is not None:
+            return self._launch("holo_ddim_step_guided", [runtime.ptr(coefs_dev)], x, model_output, [grad, noise],
+                                clip_denoised, want_pred)
         return self._launch("holo_ddim_step", [runtime.ptr(coefs_dev)], x, model_output, [noise], clip_denoised, want_pred)
 
     def _ddim_step_device_noise(self, x, model_output, coefs_dev, timestep_index: int, clip_denoised, want_pred=True,
-                                want_noise=False, channels_last: bool = False):
+                                want_noise=False, channels_last: bool = False, grad=None):
         """holo_ddim_step_philox: (sample, pred_xstart | None, noise | None), the draw of ``_step_device_noise`` at the same
-        (seed, stream, timestep)."""
-        return self._launch_device_noise("holo_ddim_step_philox", [runtime.ptr(coefs_dev)], x, model_output, timestep_index,
-                                         clip_denoised, want_pred, want_noise, channels_last)
+        (seed, stream, timestep).  ``grad``: holo_ddim_step_guided_philox."""
+        entry = "holo_ddim_step_philox" if grad is None else "holo_ddim_step_guided_philox"
+        return self._launch_device_noise(entry, [runtime.ptr(coefs_dev)], x, model_output, timestep_index,
+                                         clip_denoised, want_pred, want_noise, channels_last, grad)
 
     @staticmethod
     def _per_sample(v, t: torch.Tensor) -> np.ndarray:
@@ -463,22 +520,23 @@ class ImplicitronGaussianDiffusion(Configurable):
                     t_prev=None, noise_sampler=None):
         """One DDIM step t -> t_prev (default t - 1; < 0: the end of the chain).  The noise: ``noise_sampler(t, shape,
         device)``, else the in-kernel draw with ``device_noise_seed``, else ``torch.randn_like``; none is drawn when every
-        sample's sigma is 0 (eta = 0, or t = 0)."""
-        if cond_fn is not None:
-            raise NotImplementedError("cond_fn guidance is not used by HoloDiffusion and is not supported")
+        sample's sigma is 0 (eta = 0, or t = 0).  ``cond_fn(x, t, **model_kwargs)`` (gaussian_diffusion.py:445-453,
+        condition_score): the score moves by sqrt(1 - abar_t) * gradient, and pred_xstart is re-derived from it."""
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         t_host = t.cpu().numpy()
         t_prev = t_host - 1 if t_prev is None else self._per_sample(t_prev, t)
-        coefs = self.ddim_coefs(t_host, t_prev, eta)
+        coefs = (self.ddim_coefs if cond_fn is None else self.ddim_guided_coefs)(t_host, t_prev, eta)
         model_output = self._model_output(model, x, t, denoised_fn, model_kwargs)
+        grad = None if cond_fn is None else self._guidance(cond_fn, x, t, model_kwargs)
         coefs_dev = coefs.to(x.device)
         if noise_sampler is None and self.device_noise_seed is not None:
-            sample, pred, _ = self._ddim_step_device_noise(x, model_output, coefs_dev, int(t_host[0]), clip_denoised)
+            sample, pred, _ = self._ddim_step_device_noise(x, model_output, coefs_dev, int(t_host[0]), clip_denoised,
+                                                           grad=grad)
             return {"sample": sample, "pred_xstart": pred}
         noise = None
         if bool((coefs[:, 4] != 0).any()):
             noise = noise_sampler(int(t_host[0]), x.shape, x.device) if noise_sampler is not None else torch.randn_like(x)
-        sample, pred = self._ddim_step(x, model_output, coefs_dev, noise, clip_denoised)
+        sample, pred = self._ddim_step(x, model_output, coefs_dev, noise, clip_denoised, grad=grad)
         return {"sample": sample, "pred_xstart": pred}
 
     def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0,
@@ -499,31 +557,32 @@ class ImplicitronGaussianDiffusion(Configurable):
                                      ) -> Iterator[dict]:
         """DDIM over ``ddim_schedule(ddim_steps, timesteps)``.  Noise and the perf mode as ``p_sample_loop_progressive``:
         with ``device_noise_seed`` the chain runs channels-last through ``holo_ddim_step_philox``.  The coefficient rows of
-        the whole chain are built on the host and uploaded once."""
-        if cond_fn is not None:
-            raise NotImplementedError("cond_fn guidance is not supported")
+        the whole chain are built on the host and uploaded once.  ``cond_fn`` as in ``ddim_sample``: called once per step after
+        the model, on the NCDHW x_t, under the loop's ``torch.no_grad()``; the chain then runs NCDHW on the guided rows."""
         indices = self.ddim_schedule(ddim_steps, timesteps)
         B = shape[0]
-        rows = torch.stack([self.ddim_coefs([t] * B, [t_prev] * B, eta)
+        coefs_of = self.ddim_coefs if cond_fn is None else self.ddim_guided_coefs
+        rows = torch.stack([coefs_of([t] * B, [t_prev] * B, eta)
                             for t, t_prev in zip(indices, indices[1:] + [-1])])  # (steps, B, 8)
         noisy = (rows[:, :, 4] != 0).any(dim=1).tolist()
         device_noise = self._device_noise(noise_sampler)
 
         def step(k, img, t, model_output, coefs, channels_last):
+            grad = None if cond_fn is None else self._guidance(cond_fn, img, t, model_kwargs)
             if device_noise:
                 sample, pred, _ = self._ddim_step_device_noise(img, model_output, coefs, indices[k], clip_denoised,
-                                                               channels_last=channels_last)
+                                                               channels_last=channels_last, grad=grad)
             else:
                 eps = None
                 if noisy[k]:
                     eps = noise_sampler(indices[k], img.shape, img.device) if noise_sampler is not None else \
                         torch.randn_like(img)
-                sample, pred = self._ddim_step(img, model_output, coefs, eps, clip_denoised)
+                sample, pred = self._ddim_step(img, model_output, coefs, eps, clip_denoised, grad=grad)
             return {"sample": sample, "pred_xstart": pred}
 
         yield from self._chain(model, shape, indices, rows, step, noise=noise, noise_sampler=noise_sampler, device=device,
                                progress=progress, denoised_fn=denoised_fn, model_kwargs=model_kwargs,
-                               channels_last_ok=device_noise, materialize=_materialize_every_step)
+                               channels_last_ok=device_noise and cond_fn is None, materialize=_materialize_every_step)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, ddim_steps=None, timesteps=None,
@@ -639,7 +698,8 @@ class ImplicitronGaussianDiffusion(Configurable):
         once; a step reads the one or two previous predictions the order needs.  With a ``forward_channels_last`` model the
         chain stays channels-last (the step kernel is elementwise) under the DDIM loop's conditions minus the noise ones."""
         if cond_fn is not None:
-            raise NotImplementedError("cond_fn guidance is not supported")
+            raise NotImplementedError("cond_fn guidance is not supported by the DPM-Solver++ loops: guidance on the multistep "
+                                      "history is a separate piece of work; use p_sample_loop or ddim_sample_loop")
         indices = self.dpm_schedule(steps, spacing, timesteps)
         rows, orders = self.dpm_coefs(indices, order, lower_order_final)
         hist = [None, None]  # the predictions of the previous two steps, in the chain's layout

@@ -442,11 +442,13 @@ class AdaptiveRaySampler(Configurable):
         apply_config(self, kwargs)
 
     def __call__(self, cameras: PerspectiveCameras, evaluation_mode: EvaluationMode, mask=None,
-                 sampling_mode: Optional[RenderSamplingMode] = None, xys: Optional[torch.Tensor] = None) -> ImplicitronRayBundle:
+                 sampling_mode: Optional[RenderSamplingMode] = None, xys: Optional[torch.Tensor] = None,
+                 n_rays: Optional[int] = None, generator: Optional[torch.Generator] = None) -> ImplicitronRayBundle:
         """EVALUATION: the full pixel grid (regenerated inside the kernel).  TRAINING: ``mask_sample`` draws
         ``n_rays_per_image_sampled_from_mask`` pixels per camera from the (nearest-resized) mask as a multinomial
         distribution, without replacement while the mask has enough support (PyTorch3D MultinomialRaysampler._sample_mask /
-        _safe_multinomial, restated - a random draw, UNPINNED by nature); ``xys`` (n_cam, n_rays, 2) overrides the draw."""
+        _safe_multinomial, restated - a random draw, UNPINNED by nature); ``xys`` (n_cam, n_rays, 2) overrides the draw.
+        ``n_rays`` (None: the configured count) and ``generator`` (None: torch's global one) are the draw's size and source."""
         training = evaluation_mode == EvaluationMode.TRAINING
         if not training:
             if self.stratified_point_sampling_evaluation:
@@ -458,11 +460,12 @@ class AdaptiveRaySampler(Configurable):
         H, W = self.image_height, self.image_width
         if xys is None:
             if sampling_mode == RenderSamplingMode.MASK_SAMPLE and mask is not None:
-                n_rays = self.n_rays_per_image_sampled_from_mask
+                n_rays = self.n_rays_per_image_sampled_from_mask if n_rays is None else int(n_rays)
                 wts = torch.nn.functional.interpolate(mask.float(), size=[H, W], mode="nearest").reshape(n_cam, -1)
                 enough = (wts > 0).sum(dim=1) >= n_rays
                 idx = torch.stack([torch.multinomial(wts[i] if bool(wts[i].sum() > 0) else torch.ones_like(wts[i]), n_rays,
-                                                     replacement=not bool(enough[i])) for i in range(n_cam)])
+                                                     replacement=not bool(enough[i]), generator=generator)
+                                   for i in range(n_cam)])
             else:  # full grid in training mode
                 idx = torch.arange(H * W, device=cameras.R.device)[None].expand(n_cam, -1)
             rx, ry = (W / H, 1.0) if W >= H else (1.0, H / W)

@@ -313,6 +313,49 @@ int holo_dpm_step(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per
                   const float* model_out, const float* hist1, const float* hist2, int clip_denoised, float* sample,
                   float* pred_xstart, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Guided steps: the sampler steps with a cond_fn gradient (`grad`, x_t's shape; null is HOLO_E_INVALID).
+ *
+ * Guided DDPM step: condition_mean (gaussian_diffusion.py:429-433) inside p_sample (:499-506).
+ *   tables, num_timesteps, timesteps : as holo_ddpm_step (slot 3 of the table stays 0)
+ *   variances : (T,) fp32 on the device, posterior_variance cast from the float64 schedule
+ *   pred = clip ? clamp(model_out, -1, 1) : model_out ;  mean = fma(c2, x_t, c1*pred)   (holo_ddpm_step's mean)
+ *   mean_g = mean + v*grad   (product rounded, sum rounded) ;  sample = fma(sigma, noise, mean_g)
+ *   pred_xstart = pred (condition_mean leaves it alone; may be null).  grad == 0 gives holo_ddpm_step bit for bit.
+ * ------------------------------------------------------------------------------------------ */
+int holo_ddpm_step_guided(HoloCtx* ctx, const float* tables, int num_timesteps, const int64_t* timesteps,
+                          const float* variances, int batch, int64_t elems_per_sample, const float* x_t,
+                          const float* model_out, const float* grad, const float* noise, int clip_denoised, float* sample,
+                          float* pred_xstart, void* stream);
+
+/* The same step with the noise of :498 drawn inside the kernel: the draw of holo_ddpm_step_philox (row_streams null, keyed
+ * by stream_offset; timestep_index unused) or of holo_ddpm_step_philox_rows (row_streams non-null, keyed by row_streams[b]
+ * and timestep_index; stream_offset unused), so a guided and an unguided chain of one seed see the same noise.
+ * ncdhw_channels, pred_xstart and noise_out as there. */
+int holo_ddpm_step_guided_philox(HoloCtx* ctx, const float* tables, int num_timesteps, const int64_t* timesteps,
+                                 const float* variances, int batch, int64_t elems_per_sample, const float* x_t,
+                                 const float* model_out, const float* grad, uint64_t seed, uint64_t stream_offset,
+                                 const uint32_t* row_streams, uint32_t timestep_index, int clip_denoised, float* sample,
+                                 float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
+
+/* Guided DDIM step: condition_score (gaussian_diffusion.py:445-453) followed by ddim_sample (:674-693).
+ *   coefs : the rows of holo_ddim_step with slot 5 = sqrt(1 - abar_t), float32 from the float32 cast of alphas_cumprod[t]
+ *           (ImplicitronGaussianDiffusion.ddim_guided_coefs)
+ *   pred = clip ? clamp(model_out, -1, 1) : model_out ;  eps0 = (c0*x_t - pred) / c1 ;  eps1 = eps0 - c5*grad
+ *   predg = c0*x_t - c1*eps1   (not clamped again: the reference does not) ;  eps = (c0*x_t - predg) / c1
+ *   sample = predg*c2 + c3*eps + c4*noise   (each operation rounded, no fma; noise read only if non-null and c4 != 0)
+ *   pred_xstart = predg (may be null).  With grad == 0 this is close to holo_ddim_step, not bit-equal: predg is re-derived. */
+int holo_ddim_step_guided(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                          const float* model_out, const float* grad, const float* noise, int clip_denoised, float* sample,
+                          float* pred_xstart, void* stream);
+
+/* The same step with the noise of :685 drawn inside the kernel: the draw of holo_ddim_step_philox / _rows, selected by
+ * row_streams as in holo_ddpm_step_guided_philox. */
+int holo_ddim_step_guided_philox(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_t,
+                                 const float* model_out, const float* grad, uint64_t seed, uint64_t stream_offset,
+                                 const uint32_t* row_streams, uint32_t timestep_index, int clip_denoised, float* sample,
+                                 float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
+
 /* Elementwise helpers on the path: torch.tanh (holo_diffusion_model.py:425) and
  * torch.clip(x,-1,1) (holo_diffusion_model.py:186). */
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream);
