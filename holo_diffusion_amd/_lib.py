@@ -158,6 +158,12 @@ SIGNATURES = {
     "holo_implicit_workspace_bytes": (C.c_size_t, [_vp, C.c_int64, C.c_int64, C.c_int]),
     "holo_implicit_eval_features": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "holo_implicit_normals": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
+    "holo_density_lattice_workspace_bytes": (C.c_size_t, [_vp]),
+    "holo_density_lattice": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "holo_surface_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "holo_surface_count": (C.c_int, [_vp, _vp, C.c_int, C.c_float, _vp, _vp, C.c_size_t, _vp]),
+    "holo_surface_emit": (C.c_int, [_vp, _vp, C.c_int, C.c_float, C.c_float, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_size_t,
+                                    _vp]),
     "holo_view_pool_workspace_bytes": (C.c_size_t, [C.POINTER(HoloViewPoolCfg), C.POINTER(HoloViewFeature), C.c_int, C.c_int]),
     "holo_view_pool": (C.c_int, [_vp, C.POINTER(HoloViewPoolCfg), C.POINTER(HoloViewFeature), C.c_int,
                                  C.POINTER(HoloCamera), C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

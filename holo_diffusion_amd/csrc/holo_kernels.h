@@ -559,6 +559,16 @@ int implicit_dirs_launch(const ImplicitEvalParams& p, void* stream);
 int implicit_points_launch(const ImplicitEvalParams& p, void* stream);
 int implicit_normals_launch(const ImplicitEvalParams& p, float* normals, void* stream);  // uses grid_cl, pts, n_points, mlp
 int density_field_launch(const float* grid_cl, const float* w_dens, int C, int64_t nvox, float* out, void* stream);
+// ---- mesh export (kernels_mesh.hip): the density on a lattice of m^3 points and surface nets on a lattice field
+// 2h / (m - 1), rounded once from double: the float32 spacing every lattice coordinate is formed with
+inline float lattice_spacing(float half_extent, int m) { return (float)(2.0 * (double)half_extent / (double)(m - 1)); }
+// field [m][m][m] = LeakyReLU(trilerp(S)(p) + b_dens); S [R][R][R] from density_field_launch
+int density_lattice_launch(const float* S, int R, float half_extent, float b_dens, int m, float* field, void* stream);
+size_t surface_workspace_bytes(int m);
+int surface_count_launch(const float* field, int m, float level, int64_t* counts, void* workspace, void* stream);
+// verts / faces null: that pass is not launched
+int surface_emit_launch(const float* field, int m, float level, float half_extent, float* verts, int64_t verts_capacity,
+                        int32_t* faces, int64_t tris_capacity, void* workspace, void* stream);
 // (`k`: the renderer handle's snapshot of the knobs - the three must see the same one)
 int render_launch(const RenderKernelParams& p, const Knobs& k, void* stream, int n_workgroups);
 int render_waves_per_wg(const Knobs& k, int C, int n_fine, int with_normals, int split3 = 0, int train = 0);

@@ -575,6 +575,34 @@ int holo_implicit_normals(HoloRenderer* r, const float* grid, const float* pts, 
   return implicit_normals_launch(p, normals, stream) ? HOLO_E_INVALID : 0;
 }
 
+// workspace of holo_density_lattice: the channels-last grid | S[v] = w_dens . F[v]
+size_t holo_density_lattice_workspace_bytes(const HoloRenderer* r) { return r ? grid_cl_bytes(r) + dens_field_bytes(r) : 0; }
+
+int holo_density_lattice(HoloRenderer* r, const float* grid, int m, float* field, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  if (!r || !grid || !field || !workspace) {
+    set_error("holo_density_lattice: null argument");
+    return HOLO_E_INVALID;
+  }
+  if (m < 2 || m > 1024) {
+    set_error("holo_density_lattice: the lattice has 2 <= m <= 1024 points per axis (got %d)", m);
+    return HOLO_E_INVALID;
+  }
+  if (const int rc = ready("holo_density_lattice", r, COMMITTED)) return rc;
+  if (workspace_bytes < holo_density_lattice_workspace_bytes(r)) {
+    set_error("holo_density_lattice: workspace too small (holo_density_lattice_workspace_bytes)");
+    return HOLO_E_WORKSPACE;
+  }
+  const float* grid_cl = grid_to_channels_last(r, grid, workspace, stream);
+  if (!grid_cl) return HOLO_E_INVALID;
+  MlpParams mp;
+  fill_mlp(r, mp);
+  float* S = (float*)((char*)workspace + grid_cl_bytes(r));
+  if (density_field_launch(grid_cl, mp.w_dens, r->cfg.feature_size, grid_voxels(r), S, stream)) return HOLO_E_INVALID;
+  return density_lattice_launch(S, r->cfg.resol, grid_half_extent(r->cfg.resol, r->cfg.volume_extent), mp.b_dens, m, field,
+                                stream);
+}
+
 }  // extern "C"
 
 // ---- backward of the training-mode renderer (kernels_render_bwd.hip) ------------------------------------

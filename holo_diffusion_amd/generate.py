@@ -98,7 +98,9 @@ def _render_flyaround_reference_form(dataset=None, sequence_name: str = "sample"
                                      video_resize=None, output_video_frames_dir: Optional[str] = None,
                                      sample_mode: bool = False, progressive_sampling_steps_per_render: int = -1,
                                      visualize_preds_keys=("images_render", "masks_render", "depths_render"),
-                                     save_voxel_features: bool = False) -> Dict[str, torch.Tensor]:
+                                     save_voxel_features: bool = False, save_mesh: bool = False,
+                                     mesh_resolution: Optional[int] = None,
+                                     mesh_opacity_level: float = 0.5) -> Dict[str, torch.Tensor]:
     if model is None:
         raise TypeError("render_flyaround: `model` is required")
     if trajectory_type.lower() != "simple_360":
@@ -125,6 +127,10 @@ def _render_flyaround_reference_form(dataset=None, sequence_name: str = "sample"
         export_flyaround_frames({k: v for k, v in out.items() if k in tuple(visualize_preds_keys)}, frames_dir, name)
         if save_voxel_features and out.get("voxel_features") is not None:  # flyaround.py:288-294
             torch.save(out["voxel_features"], os.path.join(frames_dir, f"{sequence_name}_voxel_features.pth"))
+        if save_mesh and out.get("voxel_features") is not None:  # build-side addition, beside the features
+            from .mesh import save_ply
+            m = model.extract_mesh(out["voxel_features"], resolution=mesh_resolution, opacity_level=mesh_opacity_level)
+            save_ply(os.path.join(frames_dir, f"{sequence_name}_mesh.ply"), m["verts"], m["faces"], m["normals"], m["colours"])
     return out
 
 
@@ -342,7 +348,8 @@ def generate_samples(model, num_samples: int = 2, n_eval_cameras: int = 25 * 3, 
                      camera_elevation: float = -30.0 * (2 * math.pi / 360),
                      progressive_sampling_steps_per_render: int = -1, device: Optional[torch.device] = None,
                      gather: bool = True, sampler_kwargs: Optional[dict] = None,
-                     device_noise: bool = False, chains_per_gpu: int = 1) -> Dict[str, torch.Tensor]:
+                     device_noise: bool = False, chains_per_gpu: int = 1,
+                     mesh_kwargs: Optional[dict] = None) -> Dict[str, torch.Tensor]:
     """Sharded counterpart of generate_samples.py:105-138.  Every rank renders its own samples; with
     ``gather`` all ranks end up with the frames of all samples.  ``device_noise`` (build-side extension, default off): the
     per-step noise of every chain is drawn inside the step kernel (``ImplicitronGaussianDiffusion.device_noise_seed`` =
@@ -352,7 +359,11 @@ def generate_samples(model, num_samples: int = 2, n_eval_cameras: int = 25 * 3, 
     per step for the group, with the denoiser in batch-invariant mode (``SimpleUnet3D.set_batch_invariant``).  Sample ``i``
     stays the sample of ``seed + i`` whatever the group size: its x_T and, in the torch-noise mode, its step noise come from
     its own generator seeded ``seed + i``; with ``device_noise`` its rows draw Philox stream ``i``.  Not with progressive
-    rendering."""
+    rendering.
+
+    ``mesh_kwargs`` (build-side extension, default None): keyword arguments of ``HoloDiffusionModel.extract_mesh``; every
+    sample of this rank is then also meshed, and the result carries ``"meshes"``: {sample index: mesh as numpy arrays} of
+    THIS rank's samples (meshes are not gathered)."""
     if chains_per_gpu > 1 and progressive_sampling_steps_per_render > 0:
         raise ValueError("generate_samples: chains_per_gpu > 1 needs progressive_sampling_steps_per_render <= 0 "
                          "(a progressive fly-around renders one chain while it is being sampled)")
@@ -368,6 +379,13 @@ def generate_samples(model, num_samples: int = 2, n_eval_cameras: int = 25 * 3, 
     local_img: Dict[int, torch.Tensor] = {}
     local_dep: Dict[int, torch.Tensor] = {}
     local_msk: Dict[int, torch.Tensor] = {}
+    local_mesh: Dict[int, dict] = {}
+
+    def keep_mesh(i, voxel_features):
+        if mesh_kwargs is not None:
+            m = model.extract_mesh(voxel_features, **mesh_kwargs)
+            local_mesh[i] = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in m.items()}
+
     H, W = model.render_image_height, model.render_image_width
     diffusion = getattr(model, "diffusion", None)
     perf_noise = device_noise and diffusion is not None and hasattr(diffusion, "device_noise_seed")
@@ -388,6 +406,7 @@ def generate_samples(model, num_samples: int = 2, n_eval_cameras: int = 25 * 3, 
                                        progressive_sampling_steps_per_render=progressive_sampling_steps_per_render,
                                        sampler_kwargs=sampler_kwargs)
                 local_img[i], local_dep[i], local_msk[i] = out["images_render"], out["depths_render"], out["masks_render"]
+                keep_mesh(i, out["voxel_features"])
         else:
             net.set_batch_invariant(True)  # row b of every UNet call = the batch-1 call of its chain
             groups = chain_groups(mine, chains_per_gpu)
@@ -398,17 +417,20 @@ def generate_samples(model, num_samples: int = 2, n_eval_cameras: int = 25 * 3, 
                                            camera_elevation=camera_elevation, device=device,
                                            voxel_features=vf[b:b + 1])
                     local_img[i], local_dep[i], local_msk[i] = out["images_render"], out["depths_render"], out["masks_render"]
+                    keep_mesh(i, vf[b:b + 1])
     finally:
         if saved is not None:
             diffusion.device_noise_seed, diffusion.device_noise_stream = saved
         if saved_inv is not None:
             net.set_batch_invariant(saved_inv)
+    extra = {"meshes": local_mesh} if mesh_kwargs is not None else {}
     if not gather:
-        return {"images_render": local_img, "depths_render": local_dep, "masks_render": local_msk}
+        return {"images_render": local_img, "depths_render": local_dep, "masks_render": local_msk, **extra}
     return {
         "images_render": gather_frames(local_img, num_samples, (n_eval_cameras, 3, H, W), device),
         "depths_render": gather_frames(local_dep, num_samples, (n_eval_cameras, 1, H, W), device),
         "masks_render": gather_frames(local_msk, num_samples, (n_eval_cameras, 1, H, W), device),
+        **extra,
     }
 
 
@@ -441,13 +463,17 @@ def generate_samples_from_experiment(exp_dir: str, output_directory: Optional[st
                                      device: Optional[torch.device] = None, load_fn=None,
                                      device_noise: bool = False,
                                      sampler_kwargs: Optional[dict] = None,
-                                     chains_per_gpu: int = 1) -> Dict[str, torch.Tensor]:
+                                     chains_per_gpu: int = 1, save_mesh: bool = False,
+                                     mesh_resolution: Optional[int] = None,
+                                     mesh_opacity_level: float = 0.5) -> Dict[str, torch.Tensor]:
     """``generate_samples(exp_dir=...)`` of the reference script (generate_samples.py:37-138) on the HIP path:
     experiment directory -> model (``checkpoint.load_experiment``) -> sharded sampling + fly-around renders.
 
     Output stage: rank 0 writes ``<output_directory>/sample_%05d_frames.pt`` (images / depths / masks of the
     fly-around as tensors) and, through ``flyaround_output``, one directory of displayable frames per key; video
-    encoding and visdom are outside this path."""
+    encoding and visdom are outside this path.  ``save_mesh`` (build-side extension): every rank also writes its samples as
+    ``sample_%05d_mesh.ply`` (``HoloDiffusionModel.extract_mesh`` at ``mesh_resolution`` / ``mesh_opacity_level``,
+    ``mesh.save_ply``)."""
     if load_fn is None:
         from .checkpoint import load_experiment as load_fn  # ``load_fn``: same signature (tests inject a stand-in)
     rank, world = dist_info()
@@ -463,7 +489,15 @@ def generate_samples_from_experiment(exp_dir: str, output_directory: Optional[st
     out = generate_samples(model, num_samples=num_samples, n_eval_cameras=n_eval_cameras, seed=seed, up=up,
                            camera_elevation=camera_elevation,
                            progressive_sampling_steps_per_render=progressive_sampling_steps_per_render, device=device,
-                           sampler_kwargs=sampler_kwargs, device_noise=device_noise, chains_per_gpu=chains_per_gpu)
+                           sampler_kwargs=sampler_kwargs, device_noise=device_noise, chains_per_gpu=chains_per_gpu,
+                           mesh_kwargs=dict(resolution=mesh_resolution, opacity_level=mesh_opacity_level) if save_mesh else None)
+    meshes = out.pop("meshes", {})
+    if meshes:
+        from .mesh import save_ply
+        os.makedirs(output_directory, exist_ok=True)
+        for i, m in meshes.items():
+            save_ply(os.path.join(output_directory, f"sample_{i:05d}_mesh.ply"), m["verts"], m["faces"], m["normals"],
+                     m["colours"])
     if save_frames and rank == 0:
         from .flyaround_output import export_flyaround_frames
         os.makedirs(output_directory, exist_ok=True)
@@ -473,6 +507,8 @@ def generate_samples_from_experiment(exp_dir: str, output_directory: Optional[st
             # displayable frames per key (flyaround.py:422-488,553-610), ready for a video encoder
             export_flyaround_frames({k: v[i] for k, v in out.items()}, output_directory, f"sample_{i:05d}")
     out["load_report"] = report
+    if save_mesh:
+        out["meshes"] = meshes
     return out
 
 
@@ -489,7 +525,9 @@ CLI_DEFAULTS = dict(exp_dir="", output_directory=None, render_size=None, video_s
                     device_noise=False,  # (build-side extension: in-kernel Philox noise per denoising step, generate_samples)
                     sampler="ddpm", ddim_steps=None, ddim_eta=0.0,  # (build-side extension: DDIM sampling, cli_sampler_kwargs)
                     dpm_steps=None, dpm_order=2, dpm_spacing="logsnr",  # (build-side extension: sampler=dpmpp, DPM-Solver++)
-                    chains_per_gpu=1)  # (build-side extension: chains sampled together per UNet call, generate_samples)
+                    chains_per_gpu=1,  # (build-side extension: chains sampled together per UNet call, generate_samples)
+                    # (build-side extension: sample_%05d_mesh.ply per sample, HoloDiffusionModel.extract_mesh)
+                    save_mesh=False, mesh_resolution=None, mesh_opacity_level=0.5)
 
 
 def cli_sampler_kwargs(cfg: Dict[str, object]) -> Optional[dict]:
@@ -537,6 +575,13 @@ def parse_cli(argv: Sequence[str]) -> Dict[str, object]:
     B = cfg["chains_per_gpu"]
     if isinstance(B, bool) or not isinstance(B, int) or B < 1:
         raise SystemExit(f"generate: chains_per_gpu must be an integer >= 1, not {B!r}")
+    if not isinstance(cfg["save_mesh"], bool):
+        raise SystemExit(f"generate: save_mesh must be true or false, not {cfg['save_mesh']!r}")
+    mr, mo = cfg["mesh_resolution"], cfg["mesh_opacity_level"]
+    if mr is not None and (isinstance(mr, bool) or not isinstance(mr, int) or not 2 <= mr <= 1024):
+        raise SystemExit(f"generate: mesh_resolution must be an integer in [2, 1024], not {mr!r}")
+    if isinstance(mo, bool) or not isinstance(mo, (int, float)) or not 0.0 < mo < 1.0:
+        raise SystemExit(f"generate: mesh_opacity_level must be in (0, 1), not {mo!r}")
     return cfg
 
 
@@ -576,7 +621,8 @@ def main(argv: Optional[Sequence[str]] = None, load_fn=None) -> int:
                 up=tuple(cfg["up"]), camera_elevation=float(cfg["camera_elevation"]),
                 progressive_sampling_steps_per_render=int(cfg["progressive_sampling_steps_per_render"]), device=device,
                 load_fn=load_fn, device_noise=bool(cfg["device_noise"]), sampler_kwargs=cli_sampler_kwargs(cfg),
-                chains_per_gpu=int(cfg["chains_per_gpu"]))
+                chains_per_gpu=int(cfg["chains_per_gpu"]), save_mesh=cfg["save_mesh"],
+                mesh_resolution=cfg["mesh_resolution"], mesh_opacity_level=float(cfg["mesh_opacity_level"]))
         if rank == 0:
             img = out["images_render"]
             print(f"generate: {int(cfg['num_samples'])} samples x {int(cfg['n_eval_cameras'])} frames "

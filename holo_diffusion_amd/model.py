@@ -507,3 +507,23 @@ class HoloDiffusionModel(ImplicitronModelBase, torch.nn.Module):
         if rendered.normals is not None:
             out["normals_render"] = rendered.normals.permute(0, 3, 1, 2)
         return out
+
+    @torch.no_grad()
+    def extract_mesh(self, voxel_features: torch.Tensor, resolution: Optional[int] = None, opacity_level: float = 0.5,
+                     density_level: Optional[float] = None, colours: bool = True) -> Dict[str, Any]:
+        """The object as geometry (build-side addition, ``mesh.extract_mesh``): the isosurface of the density field the
+        last render pass integrates, as ``verts (V, 3) float32``, ``faces (F, 3) int32``, outward ``normals (V, 3)``,
+        ``colours (V, 3)`` in [0, 1] and the ``density_level`` used.  The grid meshed is the grid rendered: one grid (a batch
+        raises ``ValueError``, like the renderer's), refined by the denoiser at t = 0 as ``forward`` does.  ``resolution``
+        None: 2 R - 1 lattice points per axis.  ``density_level`` None: ln 2 / voxel_size * (-log2(1 - opacity_level)),
+        the density at which one voxel's length of material reaches ``opacity_level``; it must be > 0.  Whether 0.5 suits a
+        trained checkpoint is not measured (there is no checkpoint to measure it on)."""
+        from . import mesh
+        if voxel_features.dim() != 5 or voxel_features.shape[0] != 1:
+            raise ValueError(f"extract_mesh: one grid (1, C, R, R, R) at a time, got {tuple(voxel_features.shape)}")
+        if density_level is not None and not float(density_level) > 0.0:
+            raise ValueError(f"extract_mesh: density_level must be > 0, got {density_level}")
+        if self.net_3d_enabled:
+            voxel_features = self._refine(voxel_features)
+        return mesh.extract_mesh(self._implicit_functions[-1]._fn, voxel_features, resolution=resolution,
+                                 opacity_level=opacity_level, density_level=density_level, colours=colours)

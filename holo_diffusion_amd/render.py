@@ -372,12 +372,7 @@ class HoloVoxelGridImplicitFunction(ImplicitFunctionBase, torch.nn.Module):
         n = ptsf.shape[0]
         if dirsf.shape[0] * per_dir != n:
             raise _lib.HoloError("directions do not match the ray points")
-        if not hasattr(self, "_native"):
-            self._native = _NativeRenderMlp()
-        h = self._native.ensure(dev, self.render_mlp, dict(
-            resol=self.resol, feature_size=self.n_hidden, image_height=8, image_width=8,
-            volume_extent=float(self.volume_extent), dnet_hidden_dim=self.render_mlp.dnet_hidden_dim,
-            dir_emb_dims=self.render_mlp.dir_emb_dims, feature_dim=self.feature_dim))
+        h = self.native_handle(dev)
         L = runtime.lib()
         dens = torch.empty(n, device=dev)
         col = torch.empty(n, 3, device=dev)
@@ -400,6 +395,16 @@ class HoloVoxelGridImplicitFunction(ImplicitFunctionBase, torch.nn.Module):
         if vp is not None:  # features = cat(colour, view-point independent features) (:265-269)
             features = torch.cat([features, vp.reshape(*spatial, Fd)], dim=-1)
         return dens.reshape(*spatial, 1), features, aux
+
+    def native_handle(self, dev) -> C.c_void_p:
+        """The HoloRenderer handle of the stand-alone evaluations (``forward``, mesh export) on ``dev``, with the
+        RenderMLP's current parameters committed."""
+        if not hasattr(self, "_native"):
+            self._native = _NativeRenderMlp()
+        return self._native.ensure(dev, self.render_mlp, dict(
+            resol=self.resol, feature_size=self.n_hidden, image_height=8, image_width=8,
+            volume_extent=float(self.volume_extent), dnet_hidden_dim=self.render_mlp.dnet_hidden_dim,
+            dir_emb_dims=self.render_mlp.dir_emb_dims, feature_dim=self.feature_dim))
 
     def close(self) -> None:
         """Destroys the native handle of the stand-alone ``forward`` now, if one was made."""

@@ -505,7 +505,53 @@ int holo_implicit_normals(HoloRenderer* r, const float* grid, const float* pts, 
                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * View pooling: source-view feature maps -> voxel feature grid.  Replaces, fused in one kernel, the image_rgb branch
+ * Mesh export: the rendered density field as a closed triangle mesh (surface nets).  Build-side addition: the reference
+ * makes meshes from depth maps only (shaded_depth_render.py, mesh_render.py) and has no isosurface of the field.
+ * Non-finite field values are out of scope of every entry below.
+ *
+ * Lattice.  m points per axis, 2 <= m <= 1024, over the grid's volume: with h = the renderer's half extent
+ * ((R-1)/R * volume_extent / 2) and spacing = (float)(2 * (double)h / (m - 1)), index i of any axis has the float32 world
+ * coordinate  (float)i * spacing - h  (one rounding per operation, no fused multiply-add).  Fields are (m, m, m) fp32
+ * indexed [z][y][x].
+ *
+ * The density of the rendered field on the lattice: density = LeakyReLU(trilerp(S)(p) + b_dens) with
+ * S[v] = w_dens . F[v] the folded density row on every voxel.  From the world coordinate on, the arithmetic is the implicit
+ * function's (local coordinate p / h, voxel index ((l + 1) * 0.5) * (R - 1), zero weight for corners outside the grid), so
+ * the value differs from what the implicit function returns for the same float32 point by summation order only.
+ *   grid : (1, C, R, R, R) fp32;  field : (m, m, m) */
+size_t holo_density_lattice_workspace_bytes(const HoloRenderer* r);
+int holo_density_lattice(HoloRenderer* r, const float* grid, int m, float* field, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
+/* Surface nets on any scalar lattice field (a plain field on purpose: analytic shapes go through the same entry).
+ *   f'       the field, except on the outermost lattice layer, where f' = level - |field - level|: the boundary is never
+ *            inside, so every mesh is closed
+ *   inside   f' > level (a value equal to level is outside)
+ *   cells    cell (i, j, k), 0 <= i, j, k < m - 1, is active when its 8 corners are not all on one side
+ *   vertices one per active cell: the sum of the crossing points of its sign-changing edges divided by their number,
+ *            summed in the order axis x, y, z and within an axis (u, v) = (0,0), (0,1), (1,0), (1,1) over the axes
+ *            (axis+1)%3, (axis+2)%3; the crossing of an edge from corner a to corner b is at t = (f'a - level) / (f'a - f'b)
+ *            from a; world position (index + local) * spacing - h; numbered by increasing cell index (k*(m-1) + j)*(m-1) + i
+ *   faces    one quad per lattice edge whose endpoints differ, from the vertices of the cells at offsets (-1,-1), (0,-1),
+ *            (0,0), (-1,0) in the axes (axis+1)%3, (axis+2)%3, reversed when the edge's first endpoint is outside (normals
+ *            point from inside to outside); triangles (q0,q1,q2), (q0,q2,q3); ordered by (lattice point index, axis)
+ * float32 throughout.  Offsets come from a scan: no atomics, so the output order is exactly the one above.
+ * The caller reads the two counts (a synchronisation of the CALLER's) and allocates between the calls:
+ *   holo_surface_count   counts_dev[2] (device) = (vertices, triangles); leaves the cell -> vertex map and the face offsets
+ *                        in the workspace
+ *   holo_surface_emit    consumes that workspace (same field, m, level).  verts (verts_capacity, 3) fp32, faces
+ *                        (tris_capacity, 3) int32; a null buffer (capacity 0) skips its pass.  Nothing is written past a
+ *                        capacity: the first two int32 words of the workspace are then set to 1 (vertices, triangles did
+ *                        not fit; both 0 after a complete emit) for the caller to read. */
+size_t holo_surface_workspace_bytes(int m);
+int holo_surface_count(HoloCtx* ctx, const float* field, int m, float level, int64_t* counts_dev, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int holo_surface_emit(HoloCtx* ctx, const float* field, int m, float level, float half_extent, float* verts,
+                      int64_t verts_capacity, int32_t* faces, int64_t tris_capacity, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * View pooling: source-view feature maps -> voxel feature grid. Replaces, fused in one kernel, the image_rgb branch
  * of HoloDiffusionModel.forward behind the image feature extractor (holo_diffusion_model.py:340-373):
  *   VolumeLocator.get_coord_grid, ViewPooler (PyTorch3D ViewSampler: NDC projection + bilinear ndc_grid_sample, masks = 1
  *   with masked_sampling false; AngleWeightedReductionFeatureAggregator with [AVG, STD], configs/apple.yaml:183-196;
