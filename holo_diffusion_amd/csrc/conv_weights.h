@@ -1,6 +1,6 @@
 // conv_weights.h — the packed format of one convolution's weights: padding, the size of every device copy, which copies a
-// weight gets, and the set of pointers that goes with them.  Host-only arithmetic (no HIP header), shared by unet_exec.cpp,
-// the repack launchers and tools/.
+// weight gets, and the set of pointers that goes with them.  Host-only arithmetic (no HIP header), shared by unet_plan.cpp,
+// unet_exec.cpp, the repack launchers and tools/.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -9,7 +9,12 @@
 
 namespace holo {
 
-int64_t conv_wino3_weight_floats(int CoutP, int CinP, int src_taps);  // kernels_conv3.hip: that kernel's chunk constants
+// F(2x2x2, 3x3x3) pack (conv_wino3_kernel, kernels_conv3.hip): floats per (32-channel chunk, 16-Cout slice) of a 3x3x3 weight
+// - 64 pseudo-taps x 2 halves x 1 KB - and of a fused 1x1x1 skip - 8 destinations x 2 halves x 1 KB
+constexpr int WINO3_CHUNK_FLOATS = 32 * 1024, WINO3_SKIP_FLOATS = 4 * 1024;
+inline int64_t conv_wino3_weight_floats(int CoutP, int CinP, int src_taps) {
+  return (int64_t)(CinP >> 5) * (CoutP >> 4) * (src_taps == 27 ? WINO3_CHUNK_FLOATS : WINO3_SKIP_FLOATS);
+}
 
 // every copy starts on a 64-element boundary of its store
 inline int64_t round64(int64_t n) { return (n + 63) & ~(int64_t)63; }

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/holo_abi.h"
+#include "attn_plan.h"
 #include "conv_plan.h"
 #include "conv_weights.h"
 #include "holo_knobs.h"
@@ -27,29 +28,11 @@ int conv1x1_qkv_bf16_launch(const ConvParams& p, void* stream);     // kernels_c
 int conv1x1_bf16_stream_launch(const ConvParams& p, void* stream);  // kernels_conv1x1_bf16.hip
 int conv_wino3_launch(const ConvParams& p, void* stream);           // kernels_conv3.hip
 int conv_bf16p_launch(const ConvParams& p, void* stream);           // kernels_conv_bf16p.hip
-// kernels_conv3.hip (conv_wino3_weight_floats: conv_weights.h)
+// kernels_conv3.hip (conv_wino3_weight_floats and the pack constants behind it: conv_weights.h)
 int repack_conv_weight_wino3_launch(const float* w, float* out, int Cout, int Cin, int src_taps, int CoutP, int CinP,
                                     void* stream);
 
-// ---------------------------------------------------------------------------------------------
-// batched GEMM on fp32 MFMA (kernels_gemm.hip):  C[b] = alpha * A[b] * B[b]^T
-//   A[b][m][k] at A + b*sa + m*lda + k            (k contiguous)
-//   B[b][n][k] at B + b*sb + n*ldb + k            (b_kmajor = 0, k contiguous)
-//              at B + b*sb + k*ldb + n            (b_kmajor = 1, n contiguous)
-//   C[b][m][n] at C + b*sc + m*ldc + n
-// batch index b = b0*nb1 + b1 with separate strides for the two levels (sample, head).
-// ---------------------------------------------------------------------------------------------
-struct GemmParams {
-  const float* A;
-  const float* B;
-  float* C;
-  int M, Nn, K;
-  int lda, ldb, ldc;
-  int nb0, nb1;
-  int64_t sa0, sa1, sb0, sb1, sc0, sc1;
-  int b_kmajor;
-  float alpha;
-};
+// batched GEMM on fp32 MFMA (kernels_gemm.hip; GemmParams: attn_plan.h)
 int gemm_launch(const GemmParams& p, void* stream);
 // nb products C[b] (M x N, ldc) = A[b] (M x K, lda) . B[b] (b_kmajor ? K x N : N x K; ldb), strides sa / sb / sc between them
 inline int gemm_batch_launch(const float* A, int lda, const float* B, int ldb, int b_kmajor, float* C, int ldc, int M, int N,
@@ -66,38 +49,11 @@ inline int gemm_batch_launch(const float* A, int lda, const float* B, int ldb, i
   return gemm_launch(g, stream);
 }
 
-// Flash-style attention over the token-major qkv buffer [N][T][3C] (head-major channel order: q,k,v blocks of
-// C/H channels per head, unet.py:448); out is token-major [N][T][C].  scale2 = 1/sqrt(head channels).
-struct AttnParams {
-  const float* qkv;
-  float* out;
-  int N, T, C, H;
-  float scale2;
-  // fp32 kernel: key splits (flash_attn_splits) and, when > 1, the workspace of their partials
-  // (flash_attn_workspace_bytes): part [nsplit][N][T][C] unnormalised O, part_ml [nsplit][N][H][T][2] (m, l)
-  int nsplit;
-  float* part;
-  float* part_ml;
-};
-bool flash_attn_supported(int T, int head_channels);
-int flash_attn_splits(int N, int T, int H, int num_cus, const Knobs& k);
-size_t flash_attn_workspace_bytes(const AttnParams& p);
+// attention (AttnParams and the sizing rules the planner shares with these launchers: attn_plan.h)
 int flash_attn_launch(const AttnParams& p, void* stream);
-// bf16-product variant (shared K/V tiles in LDS, v_mfma_f32_16x16x32_bf16), for the opt-in bf16 mode
-// Second form of the bf16 attention (bf16 storage mode, long sequences): a pre-pass rewrites qkv once per call as
-// bf16 Q (pre-scaled) / K per head and V TRANSPOSED per head, so that the main kernel stages plain 16-byte rows;
-// 64-key blocks, 64 queries per wave, v_mfma_f32_32x32x16_bf16, exp2-domain softmax; the key range is split across
-// workgroups (and recombined) when one workgroup per 256 queries would leave half of the chip's wave slots empty.
-// `work` (flash_attn_bf16v2_workspace_bytes) holds the packed operands and the split partials; out_bf16: `out` is bf16.
-// The plan decides ONCE how the key range is split (flash_attn_bf16v2_ksplit) and whether the LAZY pass runs before the exact
-// kernel (`lazy`; head channels 32 / 64 only); the workspace is sized and laid out from that same split count.
-bool flash_attn_bf16v2_supported(int T, int head_channels);
-int flash_attn_bf16v2_ksplit(const AttnParams& p, int num_cus, const Knobs& k);
-size_t flash_attn_bf16v2_workspace_bytes(const AttnParams& p, int ksplit);
 // packed != 0: the operands in `work` have been written already (the fused qkv convolution), the packing pre-pass is skipped;
 // flash_attn_bf16v2_operands: where they go and the scale folded into Q
 int flash_attn_bf16v2_launch(const AttnParams& p, void* work, int out_bf16, int ksplit, int lazy, void* stream, int packed = 0);
-void flash_attn_bf16v2_operands(const AttnParams& p, void* work, uint16_t** q, uint16_t** k, uint16_t** vt, float* qscale);
 
 // in-place row softmax over `rows` rows of length `cols` (unet.py:453, fp32)
 int softmax_rows_launch(float* s, int64_t rows, int cols, void* stream);

@@ -598,31 +598,7 @@ int flash_attn_bf16v2_lazy_launch(const void* attn_v2, int ch, unsigned grid, vo
 #else
 int flash_attn_bf16v2_lazy_launch(const void* attn_v2, int ch, unsigned grid, void* stream);  // (kernels_attn_bf16_lazy.hip)
 
-bool flash_attn_bf16v2_supported(int T, int ch) { return (T % 256) == 0 && (ch == 32 || ch == 64 || ch == 128); }
-int flash_attn_bf16v2_ksplit(const AttnParams& p, int num_cus, const Knobs& k) {
-  const int64_t wgs = (int64_t)p.N * p.H * (p.T / (p.C / p.H == 128 ? 128 : 256));
-  int ks = 1;
-  // two workgroups per CU for the kernels that run two waves per SIMD; the LAZY kernel (head channels 32 / 64) runs one
-  const int per_cu = 2;
-  while (wgs * ks < per_cu * (int64_t)num_cus && ks < 8 && (p.T / (ks * 2)) % 128 == 0) ks *= 2;  // (an even number of 64-key blocks per split: the LAZY loop takes two per trip)
-  const int64_t v = k.flash_v2_ksplit;  // development knob
-  if (v >= 1 && v <= 8 && (p.T / v) % 128 == 0) ks = (int)v;
-  return ks;
-}
-size_t flash_attn_bf16v2_workspace_bytes(const AttnParams& p, int ks) {
-  const size_t ntc = (size_t)p.N * p.T * p.C;
-  size_t b = 3 * ntc * sizeof(uint16_t);
-  if (ks > 1) b += (size_t)ks * ntc * sizeof(float) + (size_t)ks * p.N * p.H * p.T * 2 * sizeof(float);
-  b += (size_t)p.N * p.H * ks * (p.T / 128) * sizeof(int);  // the LAZY kernel's redo flags, one per workgroup
-  return b;
-}
-void flash_attn_bf16v2_operands(const AttnParams& p, void* work, uint16_t** q, uint16_t** k, uint16_t** vt, float* qscale) {
-  const size_t ntc = (size_t)p.N * p.T * p.C;
-  uint16_t* w16 = reinterpret_cast<uint16_t*>(work);
-  *q = w16, *k = w16 + ntc, *vt = w16 + 2 * ntc;
-  *qscale = p.scale2 * 1.4426950408889634f;  // softmax in the exp2 domain
-}
-
+// (flash_attn_bf16v2_supported, _ksplit, _workspace_bytes, _operands: attn_plan.h)
 int flash_attn_bf16v2_launch(const AttnParams& p, void* work, int out_bf16, int ksplit, int lazy_pass, void* stream, int packed) {
   const int ch = p.C / p.H;
   if (!flash_attn_bf16v2_supported(p.T, ch)) {

@@ -2106,7 +2106,7 @@ __global__ __launch_bounds__(256, 2) void conv_small_kernel(ConvParams p) {  // 
   }
   // ---- the fused skip's chunks (p.skip_w; launches without one never enter): raw block input at the row's OWN voxel (stride 1,
   //      same resolution: conv_launch), zero for rows / channels beyond the ends, its own packed weights
-  if (!BF && kc_end > nmain) {  // (fp32 mode only: unet_exec.cpp fuses the skip below 8^3 there)
+  if (!BF && kc_end > nmain) {  // (fp32 mode only: unet_plan.cpp fuses the skip below 8^3 there)
     const float* skw_lane = (BF ? reinterpret_cast<const float*>(p.skip_w_bf) : p.skip_w) + (int64_t)((n0 >> 4) + wave) * WBLK + lane * 4;
     const int sk_lo = (kc_begin > nmain ? kc_begin : nmain) - nmain, sk_hi = kc_end - nmain;  // skip chunks [sk_lo, sk_hi)
     for (int g = sk_lo; g < sk_hi; g += SG) {

@@ -85,8 +85,9 @@ constexpr int W3_HY = 10, W3_HX = 10;          // halo rows / columns of an 8 x 
 constexpr int W3_PLANE = W3_HY * W3_HX;        // 100 (y,x) columns
 constexpr int W3_HALO = 4 * W3_PLANE * W3_RS;  // words per buffer: four xi_z planes (57.6 KB)
 constexpr int W3_WSUB = 4 * 256;               // floats per 16-MFMA group of weights: 4 pseudo-taps x 64 lanes x 4
-constexpr int W3_WCHUNK = 32 * W3_WSUB;        // floats per (chunk, slice): 64 pseudo-taps x 2 halves x 1 KB
-constexpr int W3_WSKIP = 4 * W3_WSUB;          // floats per (skip chunk, slice): 8 destinations x 2 halves x 1 KB
+constexpr int W3_WCHUNK = WINO3_CHUNK_FLOATS;  // floats per (chunk, slice): 64 pseudo-taps x 2 halves x 1 KB (conv_weights.h)
+constexpr int W3_WSKIP = WINO3_SKIP_FLOATS;    // floats per (skip chunk, slice): 8 destinations x 2 halves x 1 KB
+static_assert(W3_WCHUNK == 32 * W3_WSUB && W3_WSKIP == 4 * W3_WSUB, "the pack constants of conv_weights.h are this kernel's");
 
 __device__ __forceinline__ float w3_silu(float v) { return v * holo_rcp(1.0f + __expf(-v)); }
 
@@ -936,10 +937,6 @@ __global__ __launch_bounds__(256) void repack_conv_weight_wino3_kernel(const flo
 }  // namespace
 
 #if W3_PROBE == 0 && !defined(W3_TIMELINE)
-int64_t conv_wino3_weight_floats(int CoutP, int CinP, int src_taps) {
-  return (int64_t)(CinP >> 5) * (CoutP >> 4) * (src_taps == 27 ? W3_WCHUNK : W3_WSKIP);
-}
-
 int repack_conv_weight_wino3_launch(const float* w, float* out, int Cout, int Cin, int src_taps, int CoutP, int CinP,
                                     void* stream) {
   const int64_t total = conv_wino3_weight_floats(CoutP, CinP, src_taps);

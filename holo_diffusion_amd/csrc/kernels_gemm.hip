@@ -445,24 +445,7 @@ int gemm_launch(const GemmParams& p, void* stream) {
   return 0;
 }
 
-bool flash_attn_supported(int T, int ch) { return (T % 128) == 0 && (ch == 16 || ch == 32 || ch == 64 || ch == 128); }
-
-// Key splits: enough workgroups for one per CU, at most one key tile per wave.  Measured on MI355X (profiles/r07_attn_*):
-// T = 512, two heads of 128 channels: 32 workgroups -> 128 with four splits; at T = 4096 the un-split grid has 256
-// workgroups already.  HOLO_FLASH_SPLIT=<n> sets the split count (clamped to [1, T/128]; tests, A/B).
-int flash_attn_splits(int N, int T, int H, int num_cus, const Knobs& k) {
-  const int max_split = T / 128;
-  const int64_t base = (int64_t)N * H * (T / 32);
-  int64_t s = k.flash_split;
-  if (s <= 0) s = base < num_cus ? cdiv(num_cus, base) : 1;
-  return (int)(s < 1 ? 1 : s > max_split ? max_split : s);
-}
-
-size_t flash_attn_workspace_bytes(const AttnParams& p) {
-  if (p.nsplit <= 1) return 0;
-  return (size_t)p.nsplit * ((size_t)p.N * p.T * p.C + (size_t)p.N * p.H * p.T * 2) * sizeof(float);
-}
-
+// (flash_attn_supported, flash_attn_splits, flash_attn_workspace_bytes: attn_plan.h)
 int flash_attn_launch(const AttnParams& p, void* stream) {
   const int ch = p.C / p.H;
   if (!flash_attn_supported(p.T, ch)) {

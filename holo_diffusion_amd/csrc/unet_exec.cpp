@@ -1,10 +1,9 @@
-// unet_exec.cpp — native runtime of the denoiser: builds the static launch plan of
-// UNetModel.forward (holo_diffusion/guided_diffusion/unet.py:800-837, block construction :645-798 as
-// configured by SimpleUnet3D, holo_diffusion/utils/diffusion_utils.py:56-75) and replays it on a stream.
+// unet_exec.cpp — native runtime of the denoiser: replays the static launch plan of UNetModel.forward (built by Planner,
+// unet_plan.h) on streams, builds the training plan on top of it, and holds the C ABI of the denoiser, the sampler steps,
+// Adam and the timers.
 //
-// Everything is static for a given (config, batch): tensor shapes, workspace offsets, split-K factors,
-// kernel parameters.  The plan is a flat vector of ops; forward() only patches the three caller pointers
-// (x, timesteps, y) and launches.  No allocation, no host synchronisation inside forward().
+// The plan is a flat vector of ops; forward() only patches the three caller pointers (x, timesteps, y) and launches.  No
+// allocation, no host synchronisation inside forward().
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -22,6 +21,7 @@
 #include "conv_weights.h"
 #include "holo_common.h"
 #include "holo_kernels.h"
+#include "unet_plan.h"
 
 namespace holo {
 
@@ -37,6 +37,7 @@ const char* get_error() { return g_err; }
 }  // namespace holo
 
 using namespace holo;
+using namespace holo::unetplan;
 
 int holo::pack_conv_weights(const float* src, const ConvWeights& dst, void* stream) {
   const ConvWeightLayout& l = dst.layout;
@@ -49,183 +50,12 @@ int holo::pack_conv_weights(const float* src, const ConvWeights& dst, void* stre
 
 // struct HoloCtx { device, num_cus }: holo_kernels.h (shared with render_exec.cpp)
 
-// ---------------------------------------------------------------------------------------------
-// structure description
-// ---------------------------------------------------------------------------------------------
 namespace {
 
-// (B_HEAD, the output head GroupNorm + SiLU + conv, is not a block of the structure: only the training tape records it)
-enum BlockKind { B_CONV, B_RES, B_ATTN, B_DOWN, B_UP, B_HEAD };
-struct Block {
-  BlockKind kind;
-  std::string prefix;
-  int cin, cout;
-};
-
-enum ParamKind { P_PLAIN, P_CONV3, P_CONV1, P_EMB_W, P_EMB_B };
-
-struct ParamSlot {
-  std::string name;
-  std::vector<int64_t> shape;
-  int64_t numel;
-  ParamKind kind;
-  ConvWeights w;  // private device copies: f32 (repacked for a conv weight) of every parameter, the rest of conv weights only
-  bool set;
-  bool is_conv() const { return kind == P_CONV3 || kind == P_CONV1; }
-  // layout of a conv weight's copies; `transposed`: of the backward's transposed convolution (Cout' = Cin, Cin' = Cout)
-  ConvWeightLayout layout(bool transposed = false) const {
-    return conv_weight_layout((int)shape[transposed ? 1 : 0], (int)shape[transposed ? 0 : 1], kind == P_CONV3 ? 27 : 1);
-  }
-};
 static bool is_downsample_weight(const std::string& name) {  // Downsample: the stride-2 convolution
   return name.size() > 10 && name.compare(name.size() - 10, 10, ".op.weight") == 0;
 }
 
-struct Arena {
-  size_t top = 0, peak = 0;
-  bool keep = false;
-  std::vector<std::pair<size_t, size_t>> fl;  // free list (off, size), sorted by off
-  static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
-  size_t alloc(size_t bytes) {
-    bytes = al(bytes);
-    for (size_t i = 0; i < fl.size(); ++i) {
-      if (fl[i].second >= bytes) {
-        size_t off = fl[i].first;
-        if (fl[i].second == bytes)
-          fl.erase(fl.begin() + i);
-        else {
-          fl[i].first += bytes;
-          fl[i].second -= bytes;
-        }
-        return off;
-      }
-    }
-    size_t off = top;
-    top += bytes;
-    if (top > peak) peak = top;
-    return off;
-  }
-  void free(size_t off, size_t bytes) {
-    if (keep) return;
-    bytes = al(bytes);
-    size_t i = 0;
-    while (i < fl.size() && fl[i].first < off) ++i;
-    fl.insert(fl.begin() + i, std::make_pair(off, bytes));
-    // coalesce
-    if (i + 1 < fl.size() && fl[i].first + fl[i].second == fl[i + 1].first) {
-      fl[i].second += fl[i + 1].second;
-      fl.erase(fl.begin() + i + 1);
-    }
-    if (i > 0 && fl[i - 1].first + fl[i - 1].second == fl[i].first) {
-      fl[i - 1].second += fl[i].second;
-      fl.erase(fl.begin() + i);
-    }
-    if (!fl.empty() && fl.back().first + fl.back().second == top) {
-      top = fl.back().first;
-      fl.pop_back();
-    }
-  }
-};
-
-struct Act {  // channels-last activation [N][R][R][R][C]
-  size_t off = 0, bytes = 0;
-  size_t stats_off = 0, stats_bytes = 0;  // GroupNorm partial sums [N][stats_B][C][2] doubles
-  int stats_B = 0;
-  int C = 0, R = 0;
-  int refs = 0;
-};
-
-struct Tape {  // one layer of the training forward (what its backward needs); b.kind tells which
-  Block b;
-  Act x0, x1, h1, out;
-  bool has_x1 = false;
-  size_t coefA = 0, coefB = 0, momA = 0, momB = 0;
-  const float* film = nullptr;
-  size_t qkv = 0, a = 0;
-  bool has_skip = false;
-};
-
-// One launch of the forward.  The numbers are public (HoloOpTiming.op, SimpleUnet3D.OP_NAMES); 0 was a memset and stays reserved.
-enum OpKind { OP_IN = 1, OP_TEMB, OP_EMBLIN, OP_STATS, OP_FINAL, OP_CONV, OP_GEMM, OP_SOFTMAX, OP_FLASH, OP_OUT };
-// caller's NCDHW x -> the plan's channels-last input buffer, and that of the output -> caller's NCDHW y
-struct LayoutIn { float* dst; int C; int64_t V; int dst_bf16; };
-struct LayoutOut { const float* src; int C; int64_t V; };
-struct TimeEmbed {
-  const float *w1, *b1, *w2, *b2;
-  float *emb, *emb_silu;
-  int load_kind;  // HOLO_DEBUG_TIMESTEP_LOAD of the plan (0 in production)
-};
-struct EmbLinears {  // every ResBlock's emb_layers as one [emb_rows][ted] product
-  const float *emb_silu, *w, *b;
-  float* out;
-};
-struct GnStats {  // GroupNorm partial sums by a pass of their own (where the producing conv cannot write them)
-  const float* x;
-  double* part;
-  int C, x_bf16;
-  int64_t V;
-};
-struct GnFinalize {  // partial sums of the (virtual concat) input -> per-(sample, channel) affine, GroupNorm folded with FiLM
-  const double *part0, *part1;  // [N][B0][C0][2], [N][B1][C1][2] (part1 may be null)
-  int C0, B0, C1, B1;
-  int64_t V;
-  const float *gamma, *beta, *film;
-  int film_stride, film_cout;
-  float *coef, *moments;  // moments: (mean, rstd) kept for the backward in a training plan, else null
-  int groups;             // 32, or fewer where one half of a split concat is normalised alone (Planner::plan_side_lane)
-};
-struct Softmax { float* S; int64_t rows; int cols; };  // in place
-struct Flash {
-  AttnParams attn;
-  int form;             // 0: exact-fp32 kernel; 2: packed-operand bf16 kernel
-  float* packed;        // form 2: scratch of the packed operands and split partials
-  int out_bf16;         // form 2: attn.out is bf16
-  int operands_packed;  // form 2: the qkv convolution wrote the packed operands itself
-  int ksplit, lazy;     // form 2: key splits (`packed` is sized and laid out for them); the LAZY pass runs before the exact kernel
-};
-struct Op {  // trivially copyable: holo_unet_forward_cl patches copies of two of them
-  OpKind kind;
-  union {
-    LayoutIn in;
-    TimeEmbed temb;
-    EmbLinears emblin;
-    GnStats stats;
-    GnFinalize fin;
-    ConvParams conv;
-    GemmParams gemm;
-    Softmax softmax;
-    Flash flash;
-    LayoutOut out;
-  };
-  // The lane of the op (run_lanes): the caller's stream, or the handle's side stream.  `fork`: the side stream starts in front
-  // of this op (it waits for everything the caller's stream was given before).  `join`: on a side op, the event recorded
-  // behind it; on a main op, the event the caller's stream waits for in front of it (-1: none).
-  unsigned char side, fork;
-  short join;
-};
-static Op make_op(OpKind kind) {
-  Op op;
-  memset(&op, 0, sizeof op);
-  op.kind = kind;
-  op.join = -1;
-  return op;
-}
-
-// A built forward plan.  Planner fills one; nothing else of it lives on the net.
-struct Plan {
-  int batch = -1;
-  void* ws = nullptr;  // workspace base it was built for (null: a sizing pass)
-  std::vector<Op> ops;
-  size_t bytes = 0;  // workspace it needs
-  std::map<std::string, Act> block_outputs;  // holo_unet_fetch_block
-  // holo_unet_forward_cl: the convolutions that read the plan's input buffer / write its output buffer, and why the
-  // entry cannot use this plan (null: it can)
-  int first_conv = -1, last_conv = -1;
-  const char* cl_refusal = nullptr;
-  int n_joins = 0;  // join events of the side lane (0: every op runs on the caller's stream)
-  bool built_for(int b, const void* w) const { return batch == b && ws == w && !ops.empty(); }
-  void invalidate() { *this = Plan(); }
-};
 // The training plan: the forward with every intermediate kept + the backward launches in execution order.
 struct TrainPlan {
   Plan fwd;
@@ -241,29 +71,10 @@ struct TrainPlan {
 
 struct HoloUnet {
   HoloCtx* ctx;
-  HoloUnetCfg cfg;
-  std::vector<std::vector<Block>> inputs, outputs;
-  std::vector<Block> middle;
-  int final_ch;
-  int ted;
-  std::vector<ParamSlot> params;
-  std::map<std::string, int> pindex;
+  UnetDesc d;  // everything a plan is built from (unet_plan.h)
   float* pstore = nullptr;       // one allocation for all private parameter copies
   uint16_t* pstore_bf = nullptr;  // bf16 copies of the conv weights
   float* pstore_wino = nullptr;  // Winograd copies of the conv weights
-  // holo_unet_set_compute_dtype: 0 exact fp32 MFMA; 1 bf16: activations stored as bf16 in HBM, bf16 products with fp32
-  // accumulation in the 3x3x3 convolutions and the long-sequence attention, fp32 GroupNorm statistics; 2 bf16x3 split
-  // (fp32 storage, fp32-accurate)
-  int compute_mode = 0;
-  // holo_unet_set_batch_invariant: the forward plan makes every geometry choice for ONE sample and launches it over the
-  // batch, so row b of a batched forward is bit-identical to the batch-1 forward of that row (exact-fp32 mode only)
-  bool batch_invariant = false;
-  // concatenated emb_layers
-  int emb_rows = 0;
-  std::map<std::string, int> emb_row_off;  // resblock prefix -> first row
-  float* emb_w = nullptr;                  // [emb_rows][ted]
-  float* emb_b = nullptr;                  // [emb_rows]
-  Knobs knobs;  // snapshot of holo_unet_create (holo_knobs.h): which weight copies exist, whether plans release activations
   Plan plan;                                        // inference (holo_unet_forward, _forward_cl, _fetch_block, _time_*)
   std::map<std::pair<int, bool>, size_t> ws_cache;  // (batch, batch_invariant) -> workspace bytes
   // ---- training (holo_unet_backward): weights of the transposed convolutions, packed like the forward ones
@@ -285,986 +96,6 @@ struct HoloUnet {
 
 namespace {
 
-void build_structure(HoloUnet* u) {
-  const HoloUnetCfg& c = u->cfg;
-  const int mc = c.model_channels;
-  int ch = c.channel_mult[0] * mc;
-  char buf[128];
-  u->inputs.clear();
-  u->outputs.clear();
-  u->middle.clear();
-  u->inputs.push_back({Block{B_CONV, "input_blocks.0.0", c.in_channels, ch}});
-  std::vector<int> chans{ch};
-  int ds = 1, idx = 1;
-  auto has_attn = [&](int d) {
-    for (int i = 0; i < c.n_attention_resolutions; ++i)
-      if (c.attention_resolutions[i] == d) return true;
-    return false;
-  };
-  for (int level = 0; level < c.n_channel_mult; ++level) {
-    const int mult = c.channel_mult[level];
-    for (int r = 0; r < c.num_res_blocks; ++r) {
-      std::vector<Block> layers;
-      snprintf(buf, sizeof buf, "input_blocks.%d.0", idx);
-      layers.push_back(Block{B_RES, buf, ch, mult * mc});
-      ch = mult * mc;
-      if (has_attn(ds)) {
-        snprintf(buf, sizeof buf, "input_blocks.%d.1", idx);
-        layers.push_back(Block{B_ATTN, buf, ch, ch});
-      }
-      u->inputs.push_back(layers);
-      chans.push_back(ch);
-      ++idx;
-    }
-    if (level != c.n_channel_mult - 1) {
-      snprintf(buf, sizeof buf, "input_blocks.%d.0", idx);
-      u->inputs.push_back({Block{B_DOWN, buf, ch, ch}});
-      chans.push_back(ch);
-      ds *= 2;
-      ++idx;
-    }
-  }
-  u->middle.push_back(Block{B_RES, "middle_block.0", ch, ch});
-  u->middle.push_back(Block{B_ATTN, "middle_block.1", ch, ch});
-  u->middle.push_back(Block{B_RES, "middle_block.2", ch, ch});
-  int oidx = 0;
-  for (int level = c.n_channel_mult - 1; level >= 0; --level) {
-    const int mult = c.channel_mult[level];
-    for (int i = 0; i < c.num_res_blocks + 1; ++i) {
-      const int ich = chans.back();
-      chans.pop_back();
-      std::vector<Block> layers;
-      snprintf(buf, sizeof buf, "output_blocks.%d.0", oidx);
-      layers.push_back(Block{B_RES, buf, ch + ich, mc * mult});
-      ch = mc * mult;
-      if (has_attn(ds)) {
-        snprintf(buf, sizeof buf, "output_blocks.%d.%d", oidx, (int)layers.size());
-        layers.push_back(Block{B_ATTN, buf, ch, ch});
-      }
-      if (level && i == c.num_res_blocks) {
-        snprintf(buf, sizeof buf, "output_blocks.%d.%d", oidx, (int)layers.size());
-        layers.push_back(Block{B_UP, buf, ch, ch});
-        ds /= 2;
-      }
-      u->outputs.push_back(layers);
-      ++oidx;
-    }
-  }
-  u->final_ch = ch;
-}
-
-void add_param(HoloUnet* u, const std::string& name, std::vector<int64_t> shape, ParamKind kind) {
-  ParamSlot s;
-  s.name = name;
-  s.shape = shape;
-  s.numel = 1;
-  for (auto d : shape) s.numel *= d;
-  s.kind = kind;
-  s.set = false;
-  u->pindex[name] = (int)u->params.size();
-  u->params.push_back(s);
-}
-
-void enumerate_params(HoloUnet* u) {
-  const HoloUnetCfg& c = u->cfg;
-  const int64_t mc = c.model_channels, ted = 4 * mc;
-  u->ted = (int)ted;
-  add_param(u, "time_embed.0.weight", {ted, mc}, P_PLAIN);
-  add_param(u, "time_embed.0.bias", {ted}, P_PLAIN);
-  add_param(u, "time_embed.2.weight", {ted, ted}, P_PLAIN);
-  add_param(u, "time_embed.2.bias", {ted}, P_PLAIN);
-  u->emb_rows = 0;
-  auto add_block = [&](const Block& b) {
-    const std::string& p = b.prefix;
-    const int64_t ci = b.cin, co = b.cout;
-    switch (b.kind) {
-      case B_CONV:
-        add_param(u, p + ".weight", {co, ci, 3, 3, 3}, P_CONV3);
-        add_param(u, p + ".bias", {co}, P_PLAIN);
-        break;
-      case B_RES:
-        add_param(u, p + ".in_layers.0.weight", {ci}, P_PLAIN);
-        add_param(u, p + ".in_layers.0.bias", {ci}, P_PLAIN);
-        add_param(u, p + ".in_layers.2.weight", {co, ci, 3, 3, 3}, P_CONV3);
-        add_param(u, p + ".in_layers.2.bias", {co}, P_PLAIN);
-        add_param(u, p + ".emb_layers.1.weight", {2 * co, ted}, P_EMB_W);
-        add_param(u, p + ".emb_layers.1.bias", {2 * co}, P_EMB_B);
-        u->emb_row_off[p] = u->emb_rows;
-        u->emb_rows += (int)(2 * co);
-        add_param(u, p + ".out_layers.0.weight", {co}, P_PLAIN);
-        add_param(u, p + ".out_layers.0.bias", {co}, P_PLAIN);
-        add_param(u, p + ".out_layers.3.weight", {co, co, 3, 3, 3}, P_CONV3);
-        add_param(u, p + ".out_layers.3.bias", {co}, P_PLAIN);
-        if (ci != co) {
-          add_param(u, p + ".skip_connection.weight", {co, ci, 1, 1, 1}, P_CONV1);
-          add_param(u, p + ".skip_connection.bias", {co}, P_PLAIN);
-        }
-        break;
-      case B_ATTN:
-        add_param(u, p + ".norm.weight", {ci}, P_PLAIN);
-        add_param(u, p + ".norm.bias", {ci}, P_PLAIN);
-        add_param(u, p + ".qkv.weight", {3 * ci, ci, 1}, P_CONV1);
-        add_param(u, p + ".qkv.bias", {3 * ci}, P_PLAIN);
-        add_param(u, p + ".proj_out.weight", {ci, ci, 1}, P_CONV1);
-        add_param(u, p + ".proj_out.bias", {ci}, P_PLAIN);
-        break;
-      case B_DOWN:
-        add_param(u, p + ".op.weight", {co, ci, 3, 3, 3}, P_CONV3);
-        add_param(u, p + ".op.bias", {co}, P_PLAIN);
-        break;
-      case B_UP:
-        add_param(u, p + ".conv.weight", {co, ci, 3, 3, 3}, P_CONV3);
-        add_param(u, p + ".conv.bias", {co}, P_PLAIN);
-        break;
-      case B_HEAD:
-        break;
-    }
-  };
-  for (auto& l : u->inputs)
-    for (auto& b : l) add_block(b);
-  for (auto& b : u->middle) add_block(b);
-  for (auto& l : u->outputs)
-    for (auto& b : l) add_block(b);
-  add_param(u, "out.0.weight", {u->final_ch}, P_PLAIN);
-  add_param(u, "out.0.bias", {u->final_ch}, P_PLAIN);
-  add_param(u, "out.2.weight", {c.out_channels, u->final_ch, 3, 3, 3}, P_CONV3);
-  add_param(u, "out.2.bias", {c.out_channels}, P_PLAIN);
-}
-
-// Hands every parameter its private copies out of the three stores - f32 (HoloUnet::pstore), bf16 planes (pstore_bf),
-// Winograd packs (pstore_wino) - and returns the element count of each.  holo_unet_create runs it twice, like a planner: on
-// null bases to size the stores (the pointers it leaves are null), then on the allocations.  All arithmetic is in offsets.
-struct StoreSizes {
-  int64_t f32 = 0, bf = 0, wino = 0;
-};
-StoreSizes carve_params(HoloUnet* u, float* f32, uint16_t* bf, float* wino) {
-  StoreSizes n;
-  auto take = [](auto* base, int64_t& top, int64_t count) {
-    auto* p = base ? base + top : nullptr;
-    top += round64(count);
-    return p;
-  };
-  for (ParamSlot& s : u->params) {
-    if (s.kind == P_EMB_W || s.kind == P_EMB_B) continue;  // rows of emb_w / emb_b (below)
-    if (!s.is_conv()) {
-      s.w.f32 = take(f32, n.f32, s.numel);
-      continue;
-    }
-    const ConvWeightLayout l = s.w.layout = s.layout();
-    const ConvCopies c = forward_copies(l, s.name.find("skip_connection") != std::string::npos, u->knobs);
-    s.w.f32 = take(f32, n.f32, l.f32_floats());
-    if (c.bf16) {
-      s.w.bf = take(bf, n.bf, l.bf16_elems());
-      s.w.bft = s.w.bf ? s.w.bf + l.bft_offset() : nullptr;
-    }
-    if (c.wino2) s.w.wino2 = take(wino, n.wino, l.wino2_floats());
-    if (c.wino3) s.w.wino3 = take(wino, n.wino, l.wino3_floats());
-  }
-  u->emb_w = take(f32, n.f32, (int64_t)u->emb_rows * u->ted);
-  u->emb_b = take(f32, n.f32, u->emb_rows);
-  for (ParamSlot& s : u->params)
-    if (f32 && (s.kind == P_EMB_W || s.kind == P_EMB_B)) {
-      const int row = u->emb_row_off[s.name.substr(0, s.name.rfind(".emb_layers"))];
-      s.w.f32 = s.kind == P_EMB_W ? u->emb_w + (int64_t)row * u->ted : u->emb_b + row;
-    }
-  return n;
-}
-
-// the private copies of parameter `name`: P its fp32 copy, W the whole set of a convolution weight
-ConvWeights W(const HoloUnet* u, const std::string& name) {
-  auto it = u->pindex.find(name);
-  return it == u->pindex.end() ? ConvWeights() : u->params[it->second].w;
-}
-const float* P(const HoloUnet* u, const std::string& name) { return W(u, name).f32; }
-
-// ---------------------------------------------------------------------------------------------
-// plan builder
-// ---------------------------------------------------------------------------------------------
-// One convolution as its call site describes it: only what differs from a plain 3x3x3 stride-1 conv of x0 is set, by name.
-struct ConvDesc {
-  const Act* x0 = nullptr;
-  const Act* x1 = nullptr;  // second source of the virtual channel concat
-  int in_R = 0;             // logical input size (AFTER the upsampling when ups); 0: x0's
-  int ups = 0;
-  int out_R = 0;  // 0: the logical input size
-  int stride = 1, ksz = 3;
-  ConvWeights w;
-  const float* bias = nullptr;
-  std::optional<size_t> coef;  // workspace offset of the GroupNorm (+ FiLM) coefficients applied on load
-  int act = 0;                 // 1: SiLU after them
-  const float* residual = nullptr;
-  float* out = nullptr;
-  int Cout = 0;
-  Act* stats_of = nullptr;  // the output activation, when its GroupNorm statistics are wanted
-  struct {                  // 1x1x1 skip connection fused as extra K chunks (w.f32 null: none)
-    const Act* x0 = nullptr;
-    const Act* x1 = nullptr;
-    ConvWeights w;
-    const float* bias = nullptr;
-  } skip;
-  bool in_f32 = false, out_f32 = false;  // bf16 storage mode: this operand stays fp32
-  const ConvParams* qkv_pack = nullptr;  // an attention block's qkv convolution: where it may write the packed operands
-  // One half of a split concat convolution (Planner::plan_side_lane): the launch sums the input channels [w_cin0, w_cin0 + x0->C)
-  // of `w` only.  conv_wino3_kernel's pack is chunk-major, so the half is the same pack entered at its first chunk.
-  bool w_slice = false;
-  int w_cin0 = 0;
-  int cus = 0;  // CUs the launch is planned for (0: the context's)
-  int in_size() const { return in_R ? in_R : x0->R; }
-  int out_size() const { return out_R ? out_R : in_size(); }
-};
-
-// a workspace range seen as an activation (attention internals, gradients)
-static Act view(size_t off, int C, int R) {
-  Act a;
-  a.off = off;
-  a.C = C;
-  a.R = R;
-  return a;
-}
-
-// One operand of the attention GEMMs, batched over (sample, head), and the three layouts they come in
-struct AttnMat {
-  float* p;
-  int ld;
-  int64_t s0, s1;  // leading dimension; strides over samples / heads
-};
-struct AttnDims {
-  int N, H, C;
-  int64_t T;
-  int ch() const { return C / H; }
-  float scale2() const {
-    const double sc = 1.0 / sqrt(sqrt((double)ch()));
-    return (float)(sc * sc);
-  }
-  AttnMat qkv(float* base, int part) const { return AttnMat{base + part * ch(), 3 * C, T * 3 * C, 3 * ch()}; }  // q, k or v of [N][T][3C]
-  AttnMat scores(float* S) const { return AttnMat{S, (int)T, (int64_t)H * T * T, T * T}; }                     // [N][H][T][T]
-  AttnMat heads(float* a) const { return AttnMat{a, C, T * C, ch()}; }                                          // [N][T][C]
-};
-// C = alpha A B^T ([T][T] out of two [T][ch] operands), or with b_kmajor C = alpha A B ([T][ch] out of [T][T] and [T][ch])
-static GemmParams attn_gemm(const AttnDims& d, AttnMat A, AttnMat B, bool b_kmajor, AttnMat C, float alpha) {
-  GemmParams g;
-  memset(&g, 0, sizeof g);
-  g.A = A.p, g.lda = A.ld, g.sa0 = A.s0, g.sa1 = A.s1;
-  g.B = B.p, g.ldb = B.ld, g.sb0 = B.s0, g.sb1 = B.s1;
-  g.C = C.p, g.ldc = C.ld, g.sc0 = C.s0, g.sc1 = C.s1;
-  g.M = (int)d.T;
-  g.Nn = b_kmajor ? d.ch() : (int)d.T;
-  g.K = b_kmajor ? (int)d.T : d.ch();
-  g.nb0 = d.N;
-  g.nb1 = d.H;
-  g.b_kmajor = b_kmajor ? 1 : 0;
-  g.alpha = alpha;
-  return g;
-}
-
-struct Planner {
-  const HoloUnet* u;  // read only: everything a build produces goes into `plan`
-  int N;
-  char* base;  // workspace base (may be null for a sizing pass)
-  Plan& plan;
-  const Knobs knobs = Knobs::from_env();  // THE snapshot of this build: nothing below or behind it reads the environment
-  std::vector<Op>& ops;       // plan.ops
-  Arena arena;                // big activations, after the small region
-  size_t small_top = 0;       // coef / emb buffers
-  size_t small_cap, arena_base;
-  std::vector<Tape>* tape = nullptr;  // training forward: every layer is recorded, nothing is released
-  size_t last_mom = 0;                // moments buffer of the last emit_finalize (training)
-  std::string err;                    // a batch-invariant plan that cannot be kept (ensure_plan reports it)
-  size_t eml_off = 0, embs_off = 0;
-  Act x_in, y_out;
-
-  Planner(const HoloUnet* u_, int N_, void* ws, Plan& plan_) : u(u_), N(N_), base((char*)ws), plan(plan_), ops(plan_.ops) {
-    // a generous fixed region for the small buffers
-    small_cap = Arena::al((size_t)N * 8 * 1024 * 256 * 2 + (size_t)N * (u->emb_rows + 4 * u->ted) * 4 * 2 + 65536);
-    arena_base = small_cap;
-    arena.keep = u->knobs.keep_intermediates;
-  }
-  template <class T>
-  T* ptr(size_t off) {
-    return reinterpret_cast<T*>(base + off);
-  }
-  int64_t vox(int R) const { return (int64_t)R * R * R; }
-  bool bfs() const { return u->compute_mode == 1; }  // bf16 storage of the activations
-  // the sample count the geometry choices are made for: one in a batch-invariant forward (the training plan keeps its own)
-  int plan_n() const { return u->batch_invariant && !tape ? 1 : N; }
-
-  Act new_act(int C, int R, bool f32 = false) {
-    Act a;
-    a.C = C;
-    a.R = R;
-    a.bytes = (size_t)N * vox(R) * C * ((bfs() && !f32) ? 2 : sizeof(float));
-    a.off = guarded(arena_base + arena.alloc(a.bytes), a.bytes);
-    return a;
-  }
-  // GroupNorm partial-sum buffer [N][slabs][C][2] doubles; the slab count depends on the producing kernel
-  void alloc_stats(Act& a, int slabs) {
-    a.stats_B = slabs;
-    a.stats_bytes = (size_t)N * slabs * a.C * 2 * sizeof(double);
-    a.stats_off = guarded(arena_base + arena.alloc(a.stats_bytes), a.stats_bytes);
-  }
-  // LIFETIMES.  The first-fit arena relies on STREAM ORDER: memory released at one point of the plan may be handed to any
-  // launch planned later, because that launch runs behind the last user of the memory on the same stream.  Side-lane ops
-  // (plan_side_lane) run on a second stream between the fork and their consumer's join, in no order against the main ops of
-  // that stretch.  So everything a side op reads or writes - the skip tensor, its statistics records, the partial tensor P
-  // (its coefficients live in the bump-only small region) - is allocated BEFORE the fork in plan order and released only
-  // AFTER the consumer that waits for the join: nothing released after the fork is ever handed to a side op, and nothing a
-  // side op touches is handed out again before its join.  `side_live` holds those ranges while they are protected; every
-  // allocation is checked against them (guarded).
-  void release(Act& a) {
-    arena.free(a.off - arena_base, a.bytes);
-    if (a.stats_bytes) arena.free(a.stats_off - arena_base, a.stats_bytes);
-  }
-  size_t small_alloc(size_t bytes) {
-    size_t off = small_top;
-    small_top += Arena::al(bytes);
-    return off;
-  }
-  size_t scratch_alloc(size_t bytes) { return guarded(arena_base + arena.alloc(bytes), bytes); }
-  struct SideRange {
-    size_t off, bytes;
-    int join;
-  };
-  std::vector<SideRange> side_live;
-  size_t guarded(size_t off, size_t bytes) {
-    for (const SideRange& r : side_live)
-      if (off < r.off + r.bytes && r.off < off + bytes && err.empty())
-        err = "internal: an allocation between the side lane's fork and join " + std::to_string(r.join) + " overlaps a buffer of that side op";
-    return off;
-  }
-  void scratch_free(size_t off, size_t bytes) { arena.free(off - arena_base, bytes); }
-
-  void emit_stats(Act& a) {
-    int B, vpb;
-    gn_stats_geometry(a.C, vox(a.R), &B, &vpb);
-    alloc_stats(a, B);
-    Op op = make_op(OP_STATS);
-    op.stats.x = ptr<float>(a.off);
-    op.stats.part = ptr<double>(a.stats_off);
-    op.stats.C = a.C;
-    op.stats.V = vox(a.R);
-    op.stats.x_bf16 = bfs() ? 1 : 0;
-    ops.push_back(op);
-  }
-  // GroupNorm `norm` (its .weight / .bias) of [x0 | x1], folded with the FiLM rows when given; returns the coef offset
-  size_t emit_finalize(const Act& x0, const Act* x1, const std::string& norm, const float* film = nullptr, int film_cout = 0) {
-    const int Cin = x0.C + (x1 ? x1->C : 0);
-    size_t coef = small_alloc((size_t)N * Cin * 2 * sizeof(float));
-    Op op = make_op(OP_FINAL);
-    GnFinalize& f = op.fin;
-    if (tape) {
-      last_mom = small_alloc((size_t)N * Cin * 2 * sizeof(float));
-      f.moments = ptr<float>(last_mom);
-    }
-    f.part0 = ptr<double>(x0.stats_off);
-    f.C0 = x0.C;
-    f.B0 = x0.stats_B;
-    f.part1 = x1 ? ptr<double>(x1->stats_off) : nullptr;
-    f.C1 = x1 ? x1->C : 0;
-    f.B1 = x1 ? x1->stats_B : 0;
-    f.V = vox(x0.R);
-    f.gamma = P(u, norm + ".weight");
-    f.beta = P(u, norm + ".bias");
-    f.film = film;
-    f.film_stride = u->emb_rows;
-    f.film_cout = film_cout;
-    f.coef = ptr<float>(coef);
-    f.groups = 32;
-    ops.push_back(op);
-    return coef;
-  }
-  // The same GroupNorm of ONE half `x` of a virtual concat whose groups (cpg channels each) do not straddle the seam: the
-  // half's channels start at c_first of the norm's parameters, and the coefficients get a buffer [N][x.C][2] of their own
-  size_t emit_finalize_half(const Act& x, int c_first, int cpg, const std::string& norm) {
-    size_t coef = small_alloc((size_t)N * x.C * 2 * sizeof(float));
-    Op op = make_op(OP_FINAL);
-    GnFinalize& f = op.fin;
-    f.part0 = ptr<double>(x.stats_off);
-    f.C0 = x.C;
-    f.B0 = x.stats_B;
-    f.V = vox(x.R);
-    f.gamma = P(u, norm + ".weight") + c_first;
-    f.beta = P(u, norm + ".bias") + c_first;
-    f.film_stride = u->emb_rows;
-    f.coef = ptr<float>(coef);
-    f.groups = x.C / cpg;
-    ops.push_back(op);
-    return coef;
-  }
-  Tape& record(const Block& b, const Act& x0, const Act& out) {  // training: a layer onto the tape
-    tape->emplace_back();
-    Tape& t = tape->back();
-    t.b = b;
-    t.x0 = x0;
-    t.out = out;
-    return t;
-  }
-  // the convolution `layer` (its .weight / .bias) of x into the activation `out`
-  ConvDesc conv_of(const std::string& layer, const Act& x, const Act& out) {
-    ConvDesc d;
-    d.x0 = &x;
-    d.w = W(u, layer + ".weight");
-    d.bias = P(u, layer + ".bias");
-    d.out = ptr<float>(out.off);
-    d.Cout = out.C;
-    return d;
-  }
-  // One weight's copies into the launch `p`: its main weight, or (`skip`) that of its fused 1x1x1 skip, whose sources are
-  // set.  conv_plan picks kernels from the weight pointers it finds, so which copies are handed over IS the compute mode:
-  // the bf16 ones off the exact mode (halo-path launches multiply on the bf16 matrix cores), the Winograd ones in it (where
-  // conv_plan finds 128-voxel tiles).  The padded extents are the ones the weight was PACKED with, so the weight must be
-  // this launch's own (Cin, Cout) and its CoutP must hold every Cout tile the launch walks: a tile outside it is memory that
-  // no repack wrote.
-  // (`cin0` >= 0: the launch is one half of a split concat convolution and sums the weight's input channels from cin0 on:
-  // whole 32-channel chunks, on conv_wino3_kernel only - its pack is chunk-major, [chunk][16-Cout slice]..., so the half is the
-  // same pack entered at chunk cin0 / 32; every other copy is handed over whole and must not be read: emit_conv checks)
-  void hand_over(const ConvWeights& cw, ConvParams& p, bool skip, int cin0 = -1) {
-    const bool bf = u->compute_mode != 0, wino = u->compute_mode == 0;
-    (skip ? p.skip_w : p.w) = cw.f32;
-    (skip ? p.skip_w_bf : p.w_bf) = bf ? cw.bf : nullptr;
-    (skip ? p.skip_w_bft : p.w_bft) = bf ? cw.bft : nullptr;
-    (skip ? p.skip_w_wino2 : p.w_wino2) = wino ? cw.wino2 : nullptr;
-    (skip ? p.skip_w_wino3 : p.w_wino3) = wino ? cw.wino3 : nullptr;
-    (skip ? p.skip_CinP : p.CinP) = cw.layout.CinP;
-    const ConvWeightLayout& l = cw.layout;
-    const int Cin = skip ? p.skip_C0 + p.skip_C1 : p.C0 + p.C1;
-    const int tile = conv_cout_tile(p.Cout);
-    const bool slice_ok = cin0 >= 0 && !skip && wino && cw.wino3 && l.taps == 27 && (cin0 % 32) == 0 && (Cin % 32) == 0 && cin0 + Cin <= l.Cin;
-    if (slice_ok) {
-      p.w_wino3 = cw.wino3 + conv_wino3_weight_floats(l.CoutP, cin0, l.taps);
-      p.CinP = Cin;
-    }
-    if (err.empty() && (l.Cout != p.Cout || (l.Cin != Cin && !slice_ok) || (cin0 >= 0 && !slice_ok) || (p.Cout + tile - 1) / tile * tile > l.CoutP || l.CoutP != p.CoutP))
-      err = "internal: a " + std::to_string(Cin) + " -> " + std::to_string(p.Cout) + " convolution was handed weights packed for " +
-            std::to_string(l.Cin) + " -> " + std::to_string(l.Cout) + " (padded to " + std::to_string(l.CinP) + " -> " +
-            std::to_string(l.CoutP) + ")";
-  }
-  // the launch of `d` with its kernel and geometry chosen (conv_plan), its split-K scratch not yet placed; returns that scratch's bytes
-  size_t plan_conv(const ConvDesc& d, ConvParams& p) {
-    if (const ConvParams* q = d.qkv_pack) {  // (conv_plan may fuse the attention's operand packing into the launch)
-      p.qkv_q = q->qkv_q, p.qkv_k = q->qkv_k, p.qkv_vt = q->qkv_vt;
-      p.qkv_scale = q->qkv_scale, p.qkv_T = q->qkv_T, p.qkv_CH = q->qkv_CH, p.qkv_H = q->qkv_H;
-    }
-    p.in_bf16 = bfs() && !d.in_f32;
-    p.res_bf16 = bfs();
-    p.out_bf16 = bfs() && !d.out_f32;
-    p.src0 = ptr<float>(d.x0->off);
-    p.src1 = d.x1 ? ptr<float>(d.x1->off) : nullptr;
-    p.C0 = d.x0->C;
-    p.C1 = d.x1 ? d.x1->C : 0;
-    p.N = N;
-    p.ID = p.IH = p.IW = d.in_size();
-    p.ups = d.ups;
-    p.OD = p.OH = p.OW = d.out_size();
-    p.stride = d.stride;
-    p.pad = d.ksz == 3 ? 1 : 0;
-    p.ksz = d.ksz;
-    p.Cout = d.Cout;
-    p.CoutP = d.w.layout.CoutP;
-    hand_over(d.w, p, false, d.w_slice ? d.w_cin0 : -1);
-    p.bf16 = u->compute_mode;
-    p.coef = d.coef ? ptr<float>(*d.coef) : nullptr;
-    p.act = d.act;
-    p.bias = d.bias;
-    p.residual = d.residual;
-    p.out = d.out;
-    if (d.skip.w.f32) {  // halo kernel
-      p.skip_src0 = ptr<float>(d.skip.x0->off);
-      p.skip_src1 = d.skip.x1 ? ptr<float>(d.skip.x1->off) : nullptr;
-      p.skip_C0 = d.skip.x0->C;
-      p.skip_C1 = d.skip.x1 ? d.skip.x1->C : 0;
-      hand_over(d.skip.w, p, true);
-      p.skip_bias = d.skip.bias;
-    }
-    ConvParams one = p;
-    const int cus = d.cus > 0 ? d.cus : u->ctx->num_cus;
-    size_t sb = conv_plan(p, cus, knobs, plan_n());
-    if (plan_n() != N) {  // the batch-invariant plan: the launch must compute each sample as the batch-1 launch does
-      one.N = 1;
-      conv_plan(one, cus, knobs);
-      if (err.empty() && (one.kernel != p.kernel || one.tz != p.tz || one.nsplit != p.nsplit ||
-                          one.chunks_per_split != p.chunks_per_split || one.skip_chunks_per_split != p.skip_chunks_per_split))
-        err = "batch-invariant plan: at batch " + std::to_string(N) + " the " + std::to_string(p.C0 + p.C1) + " -> " +
-              std::to_string(p.Cout) + " convolution at " + std::to_string(p.OD) + "^3 cannot keep its batch-1 choice (kernel " +
-              std::to_string((int)one.kernel) + ", split-K " + std::to_string(one.nsplit) + " -> kernel " +
-              std::to_string((int)p.kernel) + ", split-K " + std::to_string(p.nsplit) + "; an addressing limit of the batch)";
-    }
-    if (d.w_slice && err.empty() && p.kernel != ConvKernel::Wino3)  // (no other kernel can enter its weights at a chunk)
-      err = "internal: one half of a split concat convolution left conv_wino3_kernel";
-    return sb;
-  }
-  void emit_conv(const ConvDesc& d) {
-    Op op = make_op(OP_CONV);
-    ConvParams& p = op.conv;
-    const size_t sb = plan_conv(d, p);
-    size_t so = 0;
-    if (sb) {
-      so = scratch_alloc(sb);
-      p.partial = ptr<float>(so);
-    }
-    // GroupNorm statistics of the output: from the conv / split-K-reduce epilogue when the launch can
-    // produce them, else by a separate pass over the output
-    const int slabs = d.stats_of ? conv_stats_slabs(p) : 0;
-    if (slabs > 0) {
-      alloc_stats(*d.stats_of, slabs);
-      p.stats = ptr<double>(d.stats_of->stats_off);
-    }
-    // The split-K scratch is released only AFTER the statistics buffer has its place: the reduce kernel of this very
-    // launch writes the statistics while other workgroups of it still read partial sums, so the two must not share memory.
-    // (Released before, first fit could hand the scratch's own first bytes to the statistics: sample 0 of a split launch then
-    // came out wrong in ~25 % of the runs of the bf16 mode at 32^3 - scripts/bf16_batch_check.py, found in round 4.)
-    // Stream order protects the scratch against every LATER launch.
-    if (sb) scratch_free(so, sb);
-    ops.push_back(op);
-    if (d.stats_of && slabs == 0) emit_stats(*d.stats_of);
-  }
-
-  // ---- the side lane (exact-fp32 inference plans).  The first convolution of an up-path ResBlock sums over the virtual
-  // concat [h | encoder skip].  GroupNorm(32) over it has Cin / 32 channels per group; where no group straddles the seam, the
-  // skip half's statistics, coefficients and its chunks of the sum depend on the skip tensor alone, which exists since the
-  // descent.  plan_side_lane runs in front of the deep levels (build) and emits, for every such convolution that plans onto
-  // conv_wino3_kernel, gn_finalize of the skip half + an un-split conv_wino3_kernel launch of it into a partial tensor P, on
-  // the side lane and planned for HOLO_SIDE_LANE_CUS CUs, so that they run beside the latency-bound 8^3 / 4^3 stretch.  The
-  // ResBlock later launches the h half alone with P as its residual (resblock).  Parts are emitted in consumption order.
-  // WHERE the sum is split is numerics (one fp32 addition per output element changes its place), so a batch-invariant plan
-  // splits exactly where the batch-1 plan does; which stream runs a part is free.
-  struct SidePart {
-    Act P;
-    int id = 0, join = -1;  // join: the event behind the side launch (-1: it ran on the caller's stream)
-    bool consumed = false;
-  };
-  std::map<std::string, SidePart> side_parts;  // up-path ResBlock prefix -> the skip half of its first convolution
-  // (both lanes on ONE stream cost 12 % of the B = 4 chain rate, DESIGN.md section 8: the parts always take the side stream)
-  bool side_stream_used() const { return true; }
-  bool split_eligible(const Block& b, const Act& x1, int n_for) {
-    const int C0 = b.cin - x1.C, cpg = b.cin / 32;
-    if (x1.R < knobs.side_lane_min_r || C0 <= 0 || (b.cin % 32) || (C0 % 32) || (C0 % cpg)) return false;
-    const std::string saved = err;  // (trial launches: their refusals are answers, not errors)
-    const int saved_N = N;
-    N = n_for;
-    const Act x0 = view(x1.off, C0, x1.R), out = view(x1.off, b.cout, x1.R);
-    const std::string layer = b.prefix + ".in_layers.2";
-    bool ok = true;
-    for (int form = 0; form < 3 && ok; ++form) {  // the whole launch, the h half, the skip half
-      ConvDesc d = conv_of(layer, form == 2 ? x1 : x0, out);
-      d.x1 = form == 0 ? &x1 : nullptr;
-      d.coef = x1.off;  // (any non-null address: conv_plan asks only whether there are coefficients)
-      d.act = 1;
-      d.w_slice = form != 0;
-      d.w_cin0 = form == 2 ? C0 : 0;
-      d.cus = form == 2 ? (int)knobs.side_lane_cus : 0;
-      if (form == 1) d.residual = ptr<float>(x1.off);
-      if (form == 2) d.bias = nullptr;
-      ConvParams p;
-      memset(&p, 0, sizeof p);
-      plan_conv(d, p);
-      // (the skip half is a DIRECT launch: no split-K scratch and no reduce launch on the side lane)
-      ok = err.empty() && p.kernel == ConvKernel::Wino3 && !p.wino3_up && (form != 2 || p.nsplit == 1);
-      err = saved;
-    }
-    N = saved_N;
-    return ok;
-  }
-  void plan_side_lane(const std::vector<Act>& hs) {
-    if (tape || u->compute_mode != 0 || knobs.side_lane_cus <= 0) return;
-    // A free plan of a batch keeps the whole launches (its numerics owe nothing to batch 1, and the deep levels of a batch leave
-    // less of the chip idle); a batch-invariant one must split where batch 1 does.
-    if (N > 1 && !u->batch_invariant) return;
-    const size_t fork_at = ops.size(), n_in = u->inputs.size();
-    int n_parts = 0;
-    for (size_t i = 0; i < u->outputs.size(); ++i) {
-      const size_t j = n_in - 1 - i;  // build(): output block i pops hs[j]
-      const Block& b = u->outputs[i][0];
-      if (j >= hs.size() || b.kind != B_RES) continue;  // (a skip tensor the descent has yet to produce)
-      const Act& x1 = hs[j];
-      const bool ok = split_eligible(b, x1, N);
-      if (plan_n() != N && ok != split_eligible(b, x1, 1) && err.empty())
-        err = "batch-invariant plan: at batch " + std::to_string(N) + " the concat convolution of " + b.prefix +
-              " cannot be split where the batch-1 plan splits it";
-      if (!ok) continue;
-      const int C0 = b.cin - x1.C, cpg = b.cin / 32;
-      SidePart part;
-      part.id = n_parts++;
-      part.P = new_act(b.cout, x1.R);
-      const size_t coef = emit_finalize_half(x1, C0, cpg, b.prefix + ".in_layers.0");
-      ops.back().side = side_stream_used();
-      ConvDesc d = conv_of(b.prefix + ".in_layers.2", x1, part.P);
-      d.bias = nullptr;
-      d.coef = coef;
-      d.act = 1;
-      d.w_slice = true;
-      d.w_cin0 = C0;
-      d.cus = (int)knobs.side_lane_cus;
-      emit_conv(d);
-      if (ops.back().conv.nsplit != 1 && err.empty()) err = "internal: the skip half of " + b.prefix + " is no direct launch";
-      if (side_stream_used()) {
-        ops.back().side = 1;
-        ops.back().join = (short)(part.join = plan.n_joins++);
-        side_live.push_back({part.P.off, part.P.bytes, part.id});
-        side_live.push_back({x1.off, x1.bytes, part.id});
-        if (x1.stats_bytes) side_live.push_back({x1.stats_off, x1.stats_bytes, part.id});
-      }
-      if (knobs.debug_plan)
-        fprintf(stderr, "[plan] side lane: %s %d + %d -> %d @%d^3 split, skip half on %s, grid_x %d, join %d\n", b.prefix.c_str(), C0, x1.C,
-                b.cout, x1.R, side_stream_used() ? "the side stream" : "the caller's stream", ops.back().conv.grid_x, part.join);
-      side_parts[b.prefix] = part;
-    }
-    if (plan.n_joins) ops[fork_at].fork = 1;
-  }
-
-  Act resblock(const Block& b, Act& x0, Act* x1) {
-    const std::string& p = b.prefix;
-    const int R = x0.R;
-    const auto sp = x1 ? side_parts.find(p) : side_parts.end();
-    const bool split = sp != side_parts.end();
-    // (split: the skip half of the sum is the partial tensor P of plan_side_lane; this launch adds the h half, the bias and P)
-    size_t coefA = split ? emit_finalize_half(x0, 0, b.cin / 32, p + ".in_layers.0") : emit_finalize(x0, x1, p + ".in_layers.0");
-    const size_t momA = last_mom;
-    Act h1 = new_act(b.cout, R);
-    ConvDesc c1 = conv_of(p + ".in_layers.2", x0, h1);
-    c1.x1 = split ? nullptr : x1;
-    c1.coef = coefA;
-    c1.act = 1;
-    c1.stats_of = &h1;
-    if (split) {
-      SidePart& part = sp->second;
-      c1.w_slice = true;
-      c1.residual = ptr<float>(part.P.off);
-      const size_t at = ops.size();
-      emit_conv(c1);
-      ops[at].join = (short)part.join;  // (-1 where the side part ran on the caller's stream)
-      // the join is behind us in stream order: P and the skip tensor are ordinary main-lane memory again
-      side_live.erase(std::remove_if(side_live.begin(), side_live.end(), [&](const SideRange& r) { return r.join == part.id; }),
-                      side_live.end());
-      release(part.P);
-      part.consumed = true;
-    } else {
-      emit_conv(c1);
-    }
-    const float* film = ptr<float>(eml_off) + u->emb_row_off.at(p);
-    size_t coefB = emit_finalize(h1, nullptr, p + ".out_layers.0", film, b.cout);
-    const size_t momB = last_mom;
-    const bool has_skip = b.cin != b.cout;
-    // the 1x1x1 skip conv rides inside the second 3x3x3 conv (halo kernel) wherever that kernel applies
-    // (the bf16x3 kernel has no fused-skip variant: its skip connection runs as a separate fp32 1x1x1 conv)
-    // (below 8^3 the convolution runs on the row-tile kernel, which takes the skip's channels as extra K chunks: exact-fp32
-    //  mode; four launches + four reduces less at the 4^3 level of the north-star net)
-    bool fuse_skip = has_skip && ((R % 8) == 0 || (u->compute_mode == 0 && R < 8)) && b.cout >= 64 && u->compute_mode != 2 &&
-                     !knobs.no_skip_fusion;
-    // From 64^3 on (exact-fp32 mode) the skip runs as its own streaming 1x1x1 launch (conv1x1_stream_kernel) whose output is the
-    // second convolution's residual: measured on the north-star net, fused 305 us per launch against 208 (plain) + ~45.
-    // HOLO_SKIP_FUSION_BELOW_R=<R>: development knob for the threshold (A/B of the two forms)
-    if (fuse_skip && u->compute_mode == 0 && R >= knobs.skip_fusion_below_r && (b.cin % 32) == 0 && b.cin <= 256 && (b.cout % 64) == 0)
-      fuse_skip = false;
-    Act s;
-    if (has_skip && !fuse_skip) {
-      s = new_act(b.cout, R);
-      ConvDesc cs = conv_of(p + ".skip_connection", x0, s);
-      cs.x1 = x1;
-      cs.ksz = 1;
-      emit_conv(cs);
-    }
-    Act out = new_act(b.cout, R);
-    ConvDesc c2 = conv_of(p + ".out_layers.3", h1, out);
-    c2.coef = coefB;
-    c2.act = 1;
-    c2.stats_of = &out;
-    if (fuse_skip) {
-      c2.skip.x0 = &x0;
-      c2.skip.x1 = x1;
-      c2.skip.w = W(u, p + ".skip_connection.weight");
-      c2.skip.bias = P(u, p + ".skip_connection.bias");
-    } else {
-      c2.residual = ptr<float>(has_skip ? s.off : x0.off);
-    }
-    emit_conv(c2);
-    release(h1);
-    if (has_skip && !fuse_skip) release(s);
-    if (tape) {
-      Tape& t = record(b, x0, out);
-      t.has_x1 = x1 != nullptr;
-      if (x1) t.x1 = *x1;
-      t.h1 = h1;
-      t.coefA = coefA;
-      t.coefB = coefB;
-      t.momA = momA;
-      t.momB = momB;
-      t.film = film;
-      t.has_skip = has_skip;
-    }
-    return out;
-  }
-
-  Act attention(const Block& b, Act& x) {
-    const std::string& p = b.prefix;
-    const int C = x.C, R = x.R, H = u->cfg.num_heads, ch = C / H;
-    const int64_t T = vox(R);
-    const AttnDims dims{N, H, C, T};
-    size_t coef = emit_finalize(x, nullptr, p + ".norm");
-    const size_t momX = last_mom;
-    const size_t qkv_bytes = (size_t)N * T * 3 * C * sizeof(float);
-    const size_t s_bytes = (size_t)N * H * T * T * sizeof(float);
-    const size_t a_bytes = (size_t)N * T * C * sizeof(float);
-    size_t qkv = scratch_alloc(qkv_bytes);
-    size_t a = scratch_alloc(a_bytes);
-    size_t v2_work = 0, v2_bytes = 0;
-    bool a_is_bf16 = false;
-    const bool flash = flash_attn_supported((int)T, ch) && !knobs.no_flash_attn;
-    Op fop = make_op(OP_FLASH);
-    Flash& fl = fop.flash;
-    fl.attn.qkv = ptr<float>(qkv);
-    fl.attn.out = ptr<float>(a);
-    fl.attn.N = N;
-    fl.attn.T = (int)T;
-    fl.attn.C = C;
-    fl.attn.H = H;
-    fl.attn.scale2 = dims.scale2();
-    fl.attn.nsplit = 1;
-    size_t split_work = 0, split_bytes = 0;
-    // bf16 mode, sequences of 1 024 tokens and more: the packed-operand bf16 kernel (it splits the key range to fill
-    // the chip, so it also serves the shorter of them; below that the exact-fp32 kernel is as fast).
-    // HOLO_BF16_FLASH_MIN_T lowers the threshold (tests).  (A first, shared-tile form of the bf16 kernel was removed in
-    // round 3: no shape reached it any more, and forced on by the tests it showed a rare dependence on stale memory.)
-    ConvParams qp;
-    memset(&qp, 0, sizeof qp);
-    bool offer_pack = false;
-    if (flash) {
-      if (u->compute_mode == 1 && T >= knobs.bf16_flash_min_t && flash_attn_bf16v2_supported((int)T, ch)) {
-        // packed bf16 operands (V transposed) in scratch, bf16 attention output
-        fl.form = 2;
-        fl.ksplit = flash_attn_bf16v2_ksplit(fl.attn, u->ctx->num_cus, knobs);
-        fl.lazy = knobs.attn_exact ? 0 : 1;  // (HOLO_ATTN_EXACT: the exact loop alone)
-        v2_bytes = flash_attn_bf16v2_workspace_bytes(fl.attn, fl.ksplit);
-        v2_work = scratch_alloc(v2_bytes);
-        fl.packed = ptr<float>(v2_work);
-        fl.out_bf16 = 1;
-        a_is_bf16 = true;
-        if (!tape && bfs()) {  // the qkv convolution may write the packed operands itself (the backward's tape keeps fp32 qkv)
-          flash_attn_bf16v2_operands(fl.attn, fl.packed, &qp.qkv_q, &qp.qkv_k, &qp.qkv_vt, &qp.qkv_scale);
-          qp.qkv_T = (int)T, qp.qkv_CH = ch, qp.qkv_H = H;
-          offer_pack = true;
-        }
-      } else {
-        // exact fp32: the key range split across workgroups where one per query tile leaves CUs empty
-        fl.attn.nsplit = flash_attn_splits(plan_n(), (int)T, H, u->ctx->num_cus, knobs);
-        split_bytes = flash_attn_workspace_bytes(fl.attn);
-        if (split_bytes) {
-          split_work = scratch_alloc(split_bytes);
-          fl.attn.part = ptr<float>(split_work);
-          fl.attn.part_ml = fl.attn.part + (size_t)fl.attn.nsplit * N * T * C;
-        }
-      }
-    }
-    // (the attention internals - qkv and the attention output - stay fp32 in every mode)
-    ConvDesc cq = conv_of(p + ".qkv", x, view(qkv, 3 * C, R));
-    cq.ksz = 1;
-    cq.coef = coef;
-    cq.out_f32 = true;
-    if (offer_pack) cq.qkv_pack = &qp;
-    emit_conv(cq);
-    if (flash) {
-      fl.operands_packed = ops.back().conv.kernel == ConvKernel::Qkv ? 1 : 0;
-      if (knobs.debug_plan)
-        fprintf(stderr, "[plan] attention %s: T=%lld C=%d heads=%d -> %s flash kernel, %d key splits\n", p.c_str(),
-                (long long)T, C, H, fl.form == 2 ? "bf16" : "fp32", fl.form == 2 ? 1 : fl.attn.nsplit);
-      ops.push_back(fop);
-    } else {  // S = scale2 q k^T; softmax over its rows; a = S v
-      size_t S = scratch_alloc(s_bytes);
-      float* qkvp = ptr<float>(qkv);
-      Op op = make_op(OP_GEMM);
-      op.gemm = attn_gemm(dims, dims.qkv(qkvp, 0), dims.qkv(qkvp, 1), false, dims.scores(ptr<float>(S)), dims.scale2());
-      ops.push_back(op);
-      Op sm = make_op(OP_SOFTMAX);
-      sm.softmax.S = ptr<float>(S);
-      sm.softmax.rows = (int64_t)N * H * T;
-      sm.softmax.cols = (int)T;
-      ops.push_back(sm);
-      op.gemm = attn_gemm(dims, dims.scores(ptr<float>(S)), dims.qkv(qkvp, 2), true, dims.heads(ptr<float>(a)), 1.0f);
-      ops.push_back(op);
-      scratch_free(S, s_bytes);
-    }
-    Act out = new_act(C, R);
-    const Act av = view(a, C, R);  // `a` as an activation for the 1x1 conv
-    ConvDesc cp = conv_of(p + ".proj_out", av, out);
-    cp.ksz = 1;
-    cp.residual = ptr<float>(x.off);
-    cp.stats_of = &out;
-    cp.in_f32 = !a_is_bf16;
-    emit_conv(cp);
-    if (v2_bytes) scratch_free(v2_work, v2_bytes);
-    if (split_bytes) scratch_free(split_work, split_bytes);
-    scratch_free(qkv, qkv_bytes);
-    scratch_free(a, a_bytes);
-    if (tape) {
-      Tape& t = record(b, x, out);
-      t.coefA = coef;
-      t.momA = momX;
-      t.qkv = qkv;
-      t.a = a;
-    }
-    return out;
-  }
-
-  // runs a TimestepEmbedSequential; consumes (releases) the input activation(s)
-  Act run_layers(const std::vector<Block>& layers, Act h, Act* skip, bool release_h) {
-    bool first = true;
-    for (const Block& b : layers) {
-      Act out;
-      if (b.kind == B_RES) {
-        out = resblock(b, h, first ? skip : nullptr);
-      } else if (b.kind == B_ATTN) {
-        out = attention(b, h);
-      } else {  // a bare convolution: input conv, Downsample (stride 2), Upsample (nearest x2 on load)
-        out = new_act(b.cout, b.kind == B_DOWN ? h.R / 2 : b.kind == B_UP ? h.R * 2 : h.R);
-        ConvDesc d = conv_of(b.prefix + (b.kind == B_DOWN ? ".op" : b.kind == B_UP ? ".conv" : ""), h, out);
-        if (b.kind == B_DOWN) d.out_R = out.R, d.stride = 2;
-        if (b.kind == B_UP) d.in_R = out.R, d.ups = 1;
-        d.stats_of = &out;
-        emit_conv(d);
-        if (tape) record(b, h, out);
-      }
-      if (!first || release_h) release(h);
-      if (first && skip) release(*skip);
-      h = out;
-      first = false;
-    }
-    return h;
-  }
-
-  void build() {
-    const HoloUnetCfg& c = u->cfg;
-    const int R = c.image_size;
-    plan.invalidate();
-    // time embedding
-    size_t emb = small_alloc((size_t)N * u->ted * 4);
-    size_t embs = small_alloc((size_t)N * u->ted * 4);
-    eml_off = small_alloc((size_t)N * u->emb_rows * 4);
-    embs_off = embs;
-    {
-      Op op = make_op(OP_TEMB);
-      op.temb.w1 = P(u, "time_embed.0.weight");
-      op.temb.b1 = P(u, "time_embed.0.bias");
-      op.temb.w2 = P(u, "time_embed.2.weight");
-      op.temb.b2 = P(u, "time_embed.2.bias");
-      op.temb.emb = ptr<float>(emb);
-      op.temb.emb_silu = ptr<float>(embs);
-      op.temb.load_kind = (int)knobs.debug_timestep_load;
-      ops.push_back(op);
-    }
-    {
-      Op op = make_op(OP_EMBLIN);
-      op.emblin.emb_silu = ptr<float>(embs);
-      op.emblin.w = u->emb_w;
-      op.emblin.b = u->emb_b;
-      op.emblin.out = ptr<float>(eml_off);
-      ops.push_back(op);
-    }
-    Act x = new_act(c.in_channels, R);
-    x_in = x;
-    {
-      Op op = make_op(OP_IN);
-      op.in.dst = ptr<float>(x.off);
-      op.in.C = c.in_channels;
-      op.in.V = vox(R);
-      op.in.dst_bf16 = bfs() ? 1 : 0;
-      ops.push_back(op);
-    }
-    std::vector<Act> hs;
-    Act h = x;
-    char tag[64];
-    bool forked = false;
-    for (size_t i = 0; i < u->inputs.size(); ++i) {
-      // the side lane starts in front of the first level whose edge is at most HOLO_SIDE_LANE_FORK_R (else in front of the middle)
-      if (!forked && (u->inputs[i][0].kind == B_DOWN ? h.R / 2 : h.R) <= knobs.side_lane_fork_r) {
-        plan_side_lane(hs);
-        forked = true;
-      }
-      // h is also referenced by hs (except the raw input x): do not release it when consumed
-      h = run_layers(u->inputs[i], h, nullptr, /*release_h=*/i == 0);
-      hs.push_back(h);
-      snprintf(tag, sizeof tag, "input_blocks.%d", (int)i);
-      plan.block_outputs[tag] = h;
-    }
-    if (!forked) plan_side_lane(hs);
-    // middle: h == hs.back(); keep it alive for the skip connection
-    h = run_layers(u->middle, h, nullptr, false);
-    plan.block_outputs["middle_block"] = h;
-    for (size_t i = 0; i < u->outputs.size(); ++i) {
-      Act skip = hs.back();
-      hs.pop_back();
-      h = run_layers(u->outputs[i], h, &skip, true);
-      snprintf(tag, sizeof tag, "output_blocks.%d", (int)i);
-      plan.block_outputs[tag] = h;
-    }
-    for (const auto& kv : side_parts)
-      if (!kv.second.consumed && err.empty()) err = "internal: the side part of " + kv.first + " has no consumer";
-    size_t coef = emit_finalize(h, nullptr, "out.0");
-    Act y = new_act(c.out_channels, R, /*f32=*/true);  // the network output stays fp32
-    if (tape) {
-      Tape& t = record(Block{B_HEAD, "out", u->final_ch, c.out_channels}, h, y);
-      t.coefA = coef;
-      t.momA = last_mom;
-    }
-    ConvDesc head = conv_of("out.2", h, y);
-    head.coef = coef;
-    head.act = 1;
-    head.out_f32 = true;
-    emit_conv(head);
-    y_out = y;
-    release(h);
-    {
-      Op op = make_op(OP_OUT);
-      op.out.src = ptr<float>(y.off);
-      op.out.C = c.out_channels;
-      op.out.V = vox(R);
-      ops.push_back(op);
-    }
-    release(y);
-    if (knobs.debug_plan) {  // development: what the plan launches
-      int n_fin = 0, n_conv = 0, n_split = 0;
-      for (const Op& o : ops) {
-        n_fin += o.kind == OP_FINAL;
-        if (o.kind != OP_CONV) continue;
-        ++n_conv;
-        n_split += o.conv.nsplit > 1;
-      }
-      fprintf(stderr, "[plan] batch %d: %zu ops | %d convs, %d of them split-K (+ a reduce launch) | %d gn_finalize launches\n", N, ops.size(),
-              n_conv, n_split, n_fin);
-    }
-    find_cl_ends();
-    plan.batch = N;
-    plan.ws = base;
-    plan.bytes = arena_base + arena.peak;
-  }
-  // holo_unet_forward_cl points every convolution that reads the plan's input buffer or writes its output buffer at the
-  // caller's channels-last tensors instead (by POSITION in the op list, not by address: the arena hands the input
-  // buffer's memory to later activations).  Which two those are, and whether they can, is a property of the plan.
-  void find_cl_ends() {
-    const float* in_buf = nullptr;
-    const float* out_buf = nullptr;
-    int first = -1, last = -1;
-    for (size_t i = 0; i < ops.size(); ++i) {
-      const Op& op = ops[i];
-      if (op.kind == OP_IN) in_buf = op.in.dst;
-      if (op.kind == OP_OUT) out_buf = op.out.src;
-      if (op.kind == OP_CONV) {
-        if (first < 0 && in_buf) first = (int)i;
-        last = (int)i;
-      }
-    }
-    plan.first_conv = first;
-    plan.last_conv = last;
-    // (a split-K launch at either end is fine: its kernel reads src0 like an un-split one, and the reduce launch behind it
-    // writes `out` - the small and the non-tileable grids, whose 16- or 32-channel end convolutions are split to fill the chip)
-    if (first < 0 || !in_buf || !out_buf || ops[first].conv.src0 != in_buf || ops[first].conv.src1 ||
-        ops[last].conv.out != out_buf || first == last) {
-      plan.cl_refusal = "holo_unet_forward_cl: this plan's first / last convolution cannot take the caller's tensors";
-    } else if (bfs() && (ops[last].conv.out_bf16 || !ops[first].conv.in_bf16)) {
-      plan.cl_refusal = "holo_unet_forward_cl: unexpected storage types at the ends of the bf16 plan";
-    }
-  }
-  bool regions_ok() const { return small_top <= small_cap; }
-};
-
 // ---------------------------------------------------------------------------------------------
 // training plan (second half): the forward with every intermediate kept and every layer recorded,
 // then the backward as a list of launches in reverse layer order.  fp32 mode only.
@@ -1285,7 +116,7 @@ struct TrainPlanner {
   std::map<size_t, std::pair<size_t, bool>> grads;  // activation offset -> (gradient offset, already written)
   std::string err;
 
-  TrainPlanner(const HoloUnet* u_, int N_, void* ws, TrainPlan& tp_) : u(u_), N(N_), tp(tp_), pl(u_, N_, ws, tp_.fwd), bops(tp_.bops) {
+  TrainPlanner(const HoloUnet* u_, int N_, void* ws, TrainPlan& tp_) : u(u_), N(N_), tp(tp_), pl(&u_->d, N_, ws, tp_.fwd), bops(tp_.bops) {
     pl.arena.keep = true;
     pl.tape = &tape;
   }
@@ -1296,8 +127,8 @@ struct TrainPlanner {
   size_t alloc(size_t bytes) { return pl.scratch_alloc(bytes); }
   int64_t vox(int R) const { return (int64_t)R * R * R; }
   // gradient buffer of an activation; `acc` tells the caller whether to accumulate (a consumer wrote it before)
-  // (all bookkeeping is in workspace OFFSETS: the sizing pass runs with a null base, and pointer differences against a
-  // null base are undefined behaviour that an optimising compiler does exploit)
+  // (all bookkeeping is in workspace OFFSETS: a sizing pass has no workspace, and Planner::ptr forms addresses from integers,
+  // never by arithmetic on a null pointer - undefined behaviour that an optimising compiler does exploit)
   static constexpr size_t NONE = ~(size_t)0;
   size_t grad_of(const Act& a, int* acc) {
     auto it = grads.find(a.off);
@@ -1319,21 +150,21 @@ struct TrainPlanner {
     return it->second.first;
   }
   float* pgrad(const std::string& name) {
-    auto it = u->pindex.find(name);
-    return it == u->pindex.end() ? nullptr : reinterpret_cast<float*>(pl.base + tp.grad_off[it->second]);
+    auto it = u->d.pindex.find(name);
+    return it == u->d.pindex.end() ? nullptr : ptr<float>(tp.grad_off[it->second]);
   }
-  // The transposed weights under `name`, or null.  A sizing pass (no workspace base) launches nothing and must not fail
+  // The transposed weights under `name`, or null.  A sizing pass (Plan::sizing) launches nothing and must not fail
   // on weights that were not supplied yet, so there every convolution weight counts as present, and so does the stride-1
   // form "<name>#s1" of a Downsample weight whose two leading dims are multiples of 4 (the one holo_unet_set_dgrad_weight
   // creates); they count as plain fp32 copies, without Winograd forms.
   std::optional<ConvWeights> find_dgw(const std::string& name) {
     auto it = u->dgrad.find(name);
     if (it != u->dgrad.end()) return it->second;
-    if (pl.base) return std::nullopt;
+    if (!tp.fwd.sizing) return std::nullopt;
     const bool s1 = name.size() > 3 && name.compare(name.size() - 3, 3, "#s1") == 0;
-    auto pi = u->pindex.find(s1 ? name.substr(0, name.size() - 3) : name);
-    if (pi == u->pindex.end()) return std::nullopt;
-    const ParamSlot& s = u->params[pi->second];
+    auto pi = u->d.pindex.find(s1 ? name.substr(0, name.size() - 3) : name);
+    if (pi == u->d.pindex.end()) return std::nullopt;
+    const ParamSlot& s = u->d.params[pi->second];
     if (!s.is_conv()) return std::nullopt;
     if (s1 && (!is_downsample_weight(s.name) || (s.shape[0] & 3) || (s.shape[1] & 3))) return std::nullopt;
     static float never_read;
@@ -1431,10 +262,10 @@ struct TrainPlanner {
     g.ga = ptr<float>(ga);
     g.coef = ptr<float>(*f.coef);
     g.mom = ptr<float>(mom);
-    g.gamma = P(u, norm + ".weight");
-    g.beta = P(u, norm + ".bias");
+    g.gamma = P(&u->d, norm + ".weight");
+    g.beta = P(&u->d, norm + ".bias");
     g.film = film ? film->film : nullptr;
-    g.film_stride = u->emb_rows;
+    g.film_stride = u->d.emb_rows;
     g.film_cout = film ? film->cout : 0;
     g.act = f.act;
     g.part = ptr<double>(alloc(gn_bwd_scratch_bytes(g)));
@@ -1458,7 +289,7 @@ struct TrainPlanner {
     ConvDesc c2 = fwd_conv(t.h1, nullptr, cout);
     c2.coef = t.coefB;
     c2.act = 1;
-    const FilmGrad fg{t.film, cout, dfilm_base + u->emb_row_off.at(p)};
+    const FilmGrad fg{t.film, cout, dfilm_base + u->d.emb_row_off.at(p)};
     bwd_norm_conv(gout, c2, p + ".out_layers.3", p + ".out_layers.0", t.momB, &fg);
     const size_t gh1 = grad_ready(t.h1);
     if (gh1 == NONE) return;
@@ -1494,7 +325,7 @@ struct TrainPlanner {
 
   void bwd_attn(const Tape& t) {
     const std::string& p = t.b.prefix;
-    const int C = t.x0.C, R = t.x0.R, H = u->cfg.num_heads;
+    const int C = t.x0.C, R = t.x0.R, H = u->d.cfg.num_heads;
     const int64_t T = vox(R), M = (int64_t)N * T;
     const AttnDims dims{N, H, C, T};
     const size_t gout = grad_ready(t.out);
@@ -1601,18 +432,18 @@ struct TrainPlanner {
   }
 
   int build() {
-    const HoloUnetCfg& c = u->cfg;
+    const HoloUnetCfg& c = u->d.cfg;
     tp.invalidate();
     pl.build();
     // parameter gradients: one region in the reference's layouts; emb_layers rows alias the concatenated matrix
-    tp.grad_off.assign(u->params.size(), 0);
-    const size_t gembw = alloc((size_t)u->emb_rows * u->ted * sizeof(float));
-    const size_t gembb = alloc((size_t)u->emb_rows * sizeof(float));
-    for (size_t i = 0; i < u->params.size(); ++i) {
-      const ParamSlot& s = u->params[i];
+    tp.grad_off.assign(u->d.params.size(), 0);
+    const size_t gembw = alloc((size_t)u->d.emb_rows * u->d.ted * sizeof(float));
+    const size_t gembb = alloc((size_t)u->d.emb_rows * sizeof(float));
+    for (size_t i = 0; i < u->d.params.size(); ++i) {
+      const ParamSlot& s = u->d.params[i];
       if (s.kind == P_EMB_W || s.kind == P_EMB_B) {
-        const int row = u->emb_row_off.at(s.name.substr(0, s.name.rfind(".emb_layers")));
-        tp.grad_off[i] = s.kind == P_EMB_W ? gembw + (size_t)row * u->ted * sizeof(float) : gembb + (size_t)row * sizeof(float);
+        const int row = u->d.emb_row_off.at(s.name.substr(0, s.name.rfind(".emb_layers")));
+        tp.grad_off[i] = s.kind == P_EMB_W ? gembw + (size_t)row * u->d.ted * sizeof(float) : gembb + (size_t)row * sizeof(float);
       } else {
         tp.grad_off[i] = alloc((size_t)s.numel * sizeof(float));
       }
@@ -1623,7 +454,7 @@ struct TrainPlanner {
     const size_t gy = alloc((size_t)N * V * c.out_channels * sizeof(float));
     grads[pl.y_out.off] = std::make_pair(gy, true);
     tp.gy_off = gy;
-    const size_t dfilm = alloc((size_t)N * u->emb_rows * sizeof(float));
+    const size_t dfilm = alloc((size_t)N * u->d.emb_rows * sizeof(float));
     float* dfilm_base = ptr<float>(dfilm);
     for (int i = (int)tape.size() - 1; i >= 0 && err.empty(); --i) {
       const Tape& t = tape[i];
@@ -1642,18 +473,18 @@ struct TrainPlanner {
     // embedding path
     {
       const float* embs = ptr<float>(pl.embs_off);
-      float* gembs = ptr<float>(alloc((size_t)N * u->ted * sizeof(float)));
+      float* gembs = ptr<float>(alloc((size_t)N * u->d.ted * sizeof(float)));
       float* dw = ptr<float>(gembw);
       float* db = ptr<float>(gembb);
-      const float* w = u->emb_w;
-      const int rows = u->emb_rows, K = u->ted, Nn = N;
+      const float* w = u->d.emb_w;
+      const int rows = u->d.emb_rows, K = u->d.ted, Nn = N;
       bops.push_back([dfilm_base, embs, w, dw, db, gembs, Nn, rows, K](void* st) {
         return film_bwd_launch(dfilm_base, embs, w, dw, db, gembs, Nn, rows, K, st);
       });
       const HoloUnet* uu = u;  // (t_dev is the running call's)
       const int mc = c.model_channels;
-      const float *w1 = P(u, "time_embed.0.weight"), *b1 = P(u, "time_embed.0.bias"), *w2 = P(u, "time_embed.2.weight"),
-                  *b2 = P(u, "time_embed.2.bias");
+      const float *w1 = P(&u->d, "time_embed.0.weight"), *b1 = P(&u->d, "time_embed.0.bias"), *w2 = P(&u->d, "time_embed.2.weight"),
+                  *b2 = P(&u->d, "time_embed.2.bias");
       float *dw1 = pgrad("time_embed.0.weight"), *db1 = pgrad("time_embed.0.bias"), *dw2 = pgrad("time_embed.2.weight"),
             *db2 = pgrad("time_embed.2.bias");
       bops.push_back([uu, Nn, mc, K, w1, b1, w2, b2, gembs, dw1, db1, dw2, db2](void* st) {
@@ -1672,7 +503,7 @@ struct TrainPlanner {
 };
 
 bool params_set(const HoloUnet* u, const char* entry) {
-  for (auto& s : u->params)
+  for (auto& s : u->d.params)
     if (!s.set) {
       set_error("%s: parameter '%s' has not been set", entry, s.name.c_str());
       return false;
@@ -1683,7 +514,7 @@ bool params_set(const HoloUnet* u, const char* entry) {
 // the training plan of (batch, ws), rebuilt when either changed; `entry` names the caller in the workspace message
 int ensure_train_plan(HoloUnet* u, const char* entry, int batch, void* ws, size_t ws_bytes) {
   if (!u->tplan.built_for(batch, ws)) {
-    if (u->compute_mode != 0) {
+    if (u->d.compute_mode != 0) {
       set_error("holo_unet_backward: the backward pass runs in the fp32 mode only");
       return HOLO_E_UNSUPPORTED;
     }
@@ -1710,11 +541,11 @@ int ensure_train_plan(HoloUnet* u, const char* entry, int batch, void* ws, size_
 int ensure_plan(HoloUnet* u, int batch, void* ws) {
   if (u->plan.built_for(batch, ws)) return 0;
   if (!params_set(u, "holo_unet_forward")) return HOLO_E_STATE;
-  if (u->batch_invariant && u->compute_mode != 0) {  // (both setters refuse this; a guard for the plan itself)
+  if (u->d.batch_invariant && u->d.compute_mode != 0) {  // (both setters refuse this; a guard for the plan itself)
     set_error("holo_unet_forward: the batch-invariant plan is exact-fp32 only");
     return HOLO_E_UNSUPPORTED;
   }
-  Planner pl(u, batch, ws, u->plan);
+  Planner pl(&u->d, batch, ws, u->plan);
   pl.build();
   int rc = 0;
   if (!pl.err.empty()) {
@@ -1733,10 +564,10 @@ int run_op(const HoloUnet* u, const Op& op, int N, const float* x, const int64_t
     case OP_IN:
       return ncdhw_to_ndhwc_launch(x, op.in.dst, N, op.in.C, op.in.V, 0, stream, op.in.dst_bf16);
     case OP_TEMB:
-      return time_embed_launch(t, N, u->cfg.model_channels, u->ted, op.temb.w1, op.temb.b1, op.temb.w2, op.temb.b2,
+      return time_embed_launch(t, N, u->d.cfg.model_channels, u->d.ted, op.temb.w1, op.temb.b1, op.temb.w2, op.temb.b2,
                                op.temb.emb, op.temb.emb_silu, op.temb.load_kind, stream);
     case OP_EMBLIN:
-      return rows_linear_launch(op.emblin.emb_silu, op.emblin.w, op.emblin.b, op.emblin.out, N, u->emb_rows, u->ted, stream);
+      return rows_linear_launch(op.emblin.emb_silu, op.emblin.w, op.emblin.b, op.emblin.out, N, u->d.emb_rows, u->d.ted, stream);
     case OP_STATS:
       return gn_stats_launch(op.stats.x, op.stats.part, N, op.stats.C, op.stats.V, stream, op.stats.x_bf16);
     case OP_FINAL: {
@@ -1832,7 +663,7 @@ int run_plan(HoloUnet* u, const Plan& plan, const float* x, const int64_t* t, fl
 }
 // the backward launches of a training plan whose taped forward has run on `workspace`
 int run_backward(const HoloUnet* u, const TrainPlan& tp, const float* grad_out, float* grad_x, void* workspace, void* stream) {
-  const HoloUnetCfg& c = u->cfg;
+  const HoloUnetCfg& c = u->d.cfg;
   const int batch = tp.fwd.batch;
   const int64_t V = (int64_t)c.image_size * c.image_size * c.image_size;
   if (ncdhw_to_ndhwc_launch(grad_out, (float*)((char*)workspace + tp.gy_off), batch, c.out_channels, V, 0, stream))
@@ -1913,12 +744,13 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
   }
   HoloUnet* u = new HoloUnet;
   u->ctx = ctx;
-  u->cfg = *cfg;
-  build_structure(u);
-  enumerate_params(u);
-  u->knobs = Knobs::from_env();
+  u->d.cfg = *cfg;
+  u->d.num_cus = ctx->num_cus;
+  build_structure(&u->d);
+  enumerate_params(&u->d);
+  u->d.knobs = Knobs::from_env();
   // private parameter storage
-  const StoreSizes n = carve_params(u, nullptr, nullptr, nullptr);
+  const StoreSizes n = carve_params(&u->d, nullptr, nullptr, nullptr);
   if (hipMalloc((void**)&u->pstore, (size_t)n.f32 * sizeof(float)) != hipSuccess ||
       (n.bf && hipMalloc((void**)&u->pstore_bf, (size_t)n.bf * sizeof(uint16_t)) != hipSuccess) ||
       (n.wino && hipMalloc((void**)&u->pstore_wino, (size_t)n.wino * sizeof(float)) != hipSuccess)) {
@@ -1927,7 +759,7 @@ int holo_unet_create(HoloCtx* ctx, const HoloUnetCfg* cfg, HoloUnet** out) {
     holo_unet_destroy(u);
     return HOLO_E_HIP;
   }
-  carve_params(u, u->pstore, u->pstore_bf, u->pstore_wino);
+  carve_params(&u->d, u->pstore, u->pstore_bf, u->pstore_wino);
   *out = u;
   return 0;
 }
@@ -1954,14 +786,14 @@ int holo_unet_destroy(HoloUnet* net) {
   return 0;
 }
 
-int holo_unet_num_params(const HoloUnet* net) { return net ? (int)net->params.size() : 0; }
+int holo_unet_num_params(const HoloUnet* net) { return net ? (int)net->d.params.size() : 0; }
 
 int holo_unet_param_info(const HoloUnet* net, int index, char* name, int name_cap, int64_t shape[8], int* ndim) {
-  if (!net || index < 0 || index >= (int)net->params.size()) {
+  if (!net || index < 0 || index >= (int)net->d.params.size()) {
     set_error("holo_unet_param_info: bad index");
     return HOLO_E_INVALID;
   }
-  const ParamSlot& s = net->params[index];
+  const ParamSlot& s = net->d.params[index];
   if (name && name_cap > 0) {
     strncpy(name, s.name.c_str(), name_cap - 1);
     name[name_cap - 1] = 0;
@@ -1982,12 +814,12 @@ int holo_unet_set_param(HoloUnet* net, const char* name, const void* dev_ptr, in
     set_error("holo_unet_set_param: only fp32 parameters are supported");
     return HOLO_E_UNSUPPORTED;
   }
-  auto it = net->pindex.find(name);
-  if (it == net->pindex.end()) {
+  auto it = net->d.pindex.find(name);
+  if (it == net->d.pindex.end()) {
     set_error("holo_unet_set_param: unknown parameter '%s'", name);
     return HOLO_E_INVALID;
   }
-  ParamSlot& s = net->params[it->second];
+  ParamSlot& s = net->d.params[it->second];
   bool ok = ndim == (int)s.shape.size();
   for (int i = 0; ok && i < ndim; ++i) ok = shape[i] == s.shape[i];
   if (!ok) {
@@ -2010,13 +842,13 @@ int holo_unet_set_compute_dtype(HoloUnet* net, int dtype) {
     return HOLO_E_INVALID;
   }
   const int mode = dtype == HOLO_DTYPE_BF16 ? 1 : dtype == HOLO_DTYPE_F32_BF16X3 ? 2 : 0;
-  if (mode != 0 && net->batch_invariant) {
+  if (mode != 0 && net->d.batch_invariant) {
     set_error("holo_unet_set_compute_dtype: the batch-invariant plan is exact-fp32 only; turn it off first "
               "(holo_unet_set_batch_invariant(net, 0))");
     return HOLO_E_UNSUPPORTED;
   }
-  if (mode != net->compute_mode) {
-    net->compute_mode = mode;
+  if (mode != net->d.compute_mode) {
+    net->d.compute_mode = mode;
     net->plan.invalidate();  // re-plan: the conv ops carry the choice
     net->ws_cache.clear();   // ... and the plan's workspace differs between modes (fused skips, statistics slabs)
   }
@@ -2031,13 +863,13 @@ int holo_unet_set_batch_invariant(HoloUnet* net, int on) {
   // Exact fp32 only.  The bf16 modes are refused rather than half supported: their plans pick kernels (the persistent
   // bf16 convolution, the streaming bf16 1x1x1 GEMMs, the packed bf16 attention) whose geometry helpers size their
   // work per launch, and no test pins the rows of those modes.
-  if (on && net->compute_mode != 0) {
+  if (on && net->d.compute_mode != 0) {
     set_error("holo_unet_set_batch_invariant: batch-invariant plans are exact-fp32 only (compute dtype HOLO_DTYPE_F32); "
               "the bf16 and bf16x3 modes are not supported");
     return HOLO_E_UNSUPPORTED;
   }
-  if ((on != 0) != net->batch_invariant) {
-    net->batch_invariant = on != 0;
+  if ((on != 0) != net->d.batch_invariant) {
+    net->d.batch_invariant = on != 0;
     net->plan.invalidate();  // re-plan: the conv ops carry the choices (ws_cache is keyed on the flag)
   }
   return 0;
@@ -2045,11 +877,11 @@ int holo_unet_set_batch_invariant(HoloUnet* net, int on) {
 
 size_t holo_unet_workspace_bytes(HoloUnet* net, int batch) {
   if (!net || batch < 1) return 0;
-  const std::pair<int, bool> key(batch, net->batch_invariant);
+  const std::pair<int, bool> key(batch, net->d.batch_invariant);
   auto it = net->ws_cache.find(key);
   if (it != net->ws_cache.end()) return it->second;
-  Plan sizing;  // built on a null base and dropped
-  Planner(net, batch, nullptr, sizing).build();
+  Plan sizing;  // built on no workspace and dropped
+  Planner(&net->d, batch, nullptr, sizing).build();
   net->ws_cache[key] = sizing.bytes;
   return sizing.bytes;
 }
@@ -2088,7 +920,7 @@ int holo_unet_forward_cl(HoloUnet* net, int batch, const float* x_cl, const int6
   }
   // the first / last convolution (Planner::find_cl_ends) run on the caller's channels-last tensors instead of the plan's
   // own input / output buffers, and the two layout passes are skipped
-  const bool bf16_storage = net->compute_mode == 1;  // the plan's input buffer is bf16: a cast replaces the layout pass
+  const bool bf16_storage = net->d.compute_mode == 1;  // the plan's input buffer is bf16: a cast replaces the layout pass
   return run_lanes(net, plan, stream, [&](int i, const Op& op, void* st) {
     if (op.kind == OP_IN && bf16_storage)  // fp32 channels-last -> the plan's bf16 channels-last input buffer
       return f32_to_bf16_launch(x_cl, op.in.dst, (int64_t)batch * op.in.C * op.in.V, st) ? (int)HOLO_E_INVALID : 0;
@@ -2109,7 +941,7 @@ int holo_unet_fetch_block(HoloUnet* net, const char* tag, float* dst, int64_t ds
     set_error("holo_unet_fetch_block: null argument");
     return HOLO_E_INVALID;
   }
-  if (!net->knobs.keep_intermediates) {
+  if (!net->d.knobs.keep_intermediates) {
     set_error("holo_unet_fetch_block: create the net with HOLO_KEEP_INTERMEDIATES=1");
     return HOLO_E_STATE;
   }
@@ -2132,7 +964,7 @@ int holo_unet_fetch_block(HoloUnet* net, const char* tag, float* dst, int64_t ds
     return HOLO_E_INVALID;
   }
   return ndhwc_to_ncdhw_launch((const float*)((char*)workspace + a.off), dst, plan.batch, a.C, V, stream,
-                               net->compute_mode == 1 ? 1 : 0);
+                               net->d.compute_mode == 1 ? 1 : 0);
 }
 
 int holo_unet_time_convs(HoloUnet* net, int batch, void* workspace, size_t workspace_bytes, int iters, void* stream,
@@ -2259,7 +1091,7 @@ static int prepare_dgrad_weight(HoloUnet* net, const ParamSlot& s, const void* d
   // dgrad of a wide-level 3x3x3 conv runs on conv_wino2_kernel / conv_wino3_kernel like the forward conv.
   ConvWeights& dw = net->dgrad[down ? nm + "#s1" : nm];
   const ConvWeightLayout l = dw.layout = s.layout(true);
-  const ConvCopies c = dgrad_copies(l, net->compute_mode, net->knobs);
+  const ConvCopies c = dgrad_copies(l, net->d.compute_mode, net->d.knobs);
   if (!dw.f32) HIP_TRY(hipMalloc((void**)&dw.f32, (size_t)l.f32_floats() * sizeof(float)));
   if ((c.wino2 && !dw.wino2) || (c.wino3 && !dw.wino3)) {  // a plan sized before these copies existed chose other kernels
     net->tws_cache.clear();                                 // (and scratch sizes)
@@ -2269,7 +1101,7 @@ static int prepare_dgrad_weight(HoloUnet* net, const ParamSlot& s, const void* d
   }
   if (!net->dgrad_tmp) {
     int64_t largest = 0;
-    for (const ParamSlot& q : net->params)
+    for (const ParamSlot& q : net->d.params)
       if (q.is_conv() && q.numel > largest) largest = q.numel;
     HIP_TRY(hipMalloc((void**)&net->dgrad_tmp, (size_t)largest * sizeof(float)));
   }
@@ -2283,19 +1115,19 @@ int holo_unet_set_dgrad_weight(HoloUnet* net, const char* name, const void* dev_
     set_error("holo_unet_set_dgrad_weight: null argument");
     return HOLO_E_INVALID;
   }
-  auto it = net->pindex.find(name);
-  if (it == net->pindex.end() || !net->params[it->second].is_conv()) {
+  auto it = net->d.pindex.find(name);
+  if (it == net->d.pindex.end() || !net->d.params[it->second].is_conv()) {
     set_error("holo_unet_set_dgrad_weight: '%s' is not a convolution weight", name);
     return HOLO_E_INVALID;
   }
-  return prepare_dgrad_weight(net, net->params[it->second], dev_ptr, stream);
+  return prepare_dgrad_weight(net, net->d.params[it->second], dev_ptr, stream);
 }
 
 size_t holo_unet_backward_workspace_bytes(HoloUnet* net, int batch) {
   if (!net || batch < 1) return 0;
   auto it = net->tws_cache.find(batch);
   if (it != net->tws_cache.end()) return it->second;
-  TrainPlan sizing;  // built on a null base (TrainPlanner::find_dgw: no transposed weight is missed there) and dropped
+  TrainPlan sizing;  // built on no workspace (TrainPlanner::find_dgw: no transposed weight is missed there) and dropped
   if (TrainPlanner(net, batch, nullptr, sizing).build()) return 0;  // the message is in holo_last_error()
   net->tws_cache[batch] = sizing.bytes;
   return sizing.bytes;
@@ -2352,16 +1184,16 @@ int holo_unet_get_grad(HoloUnet* net, const char* name, float* dst, int64_t nume
     set_error("holo_unet_get_grad: null argument");
     return HOLO_E_INVALID;
   }
-  auto it = net->pindex.find(name);
-  if (it == net->pindex.end()) {
+  auto it = net->d.pindex.find(name);
+  if (it == net->d.pindex.end()) {
     set_error("holo_unet_get_grad: unknown parameter '%s'", name);
     return HOLO_E_INVALID;
   }
-  if (net->tplan.fwd.ws != workspace || net->tplan.grad_off.size() != net->params.size()) {
+  if (net->tplan.fwd.ws != workspace || net->tplan.grad_off.size() != net->d.params.size()) {
     set_error("holo_unet_get_grad: no backward pass has run on this workspace");
     return HOLO_E_STATE;
   }
-  const ParamSlot& s = net->params[it->second];
+  const ParamSlot& s = net->d.params[it->second];
   if (numel != s.numel) {
     set_error("holo_unet_get_grad: '%s' has %lld elements, not %lld", name, (long long)s.numel, (long long)numel);
     return HOLO_E_INVALID;
@@ -2458,14 +1290,14 @@ int holo_unet_adam_step(HoloUnet* net, const HoloAdamTensor* tensors, int n, con
     set_error("holo_unet_adam_step: null argument");
     return HOLO_E_INVALID;
   }
-  if (n != (int)net->params.size()) {
-    set_error("holo_unet_adam_step: %d tensors for %d parameters (holo_unet_param_info order)", n, (int)net->params.size());
+  if (n != (int)net->d.params.size()) {
+    set_error("holo_unet_adam_step: %d tensors for %d parameters (holo_unet_param_info order)", n, (int)net->d.params.size());
     return HOLO_E_INVALID;
   }
   AdamScalars sc;
   if (const int rc = adam_scalars("holo_unet_adam_step", cfg, &sc, nullptr)) return rc;
   for (int i = 0; i < n; ++i) {
-    const ParamSlot& s = net->params[i];
+    const ParamSlot& s = net->d.params[i];
     if (!s.set) {
       set_error("holo_unet_adam_step: parameter '%s' was never bound (holo_unet_set_param)", s.name.c_str());
       return HOLO_E_STATE;
@@ -2476,14 +1308,14 @@ int holo_unet_adam_step(HoloUnet* net, const HoloAdamTensor* tensors, int n, con
     }
   }
   // (a) the update; a parameter the library keeps as a plain copy is written there by the same kernel
-  if (net->adam_copies.size() != net->params.size()) {
+  if (net->adam_copies.size() != net->d.params.size()) {
     net->adam_copies.clear();
-    for (const ParamSlot& s : net->params) net->adam_copies.push_back(s.is_conv() ? nullptr : s.w.f32);
+    for (const ParamSlot& s : net->d.params) net->adam_copies.push_back(s.is_conv() ? nullptr : s.w.f32);
   }
   net->tape_valid = false;  // (d) the taped activations belong to the old weights
   if (adam_step_launch(tensors, net->adam_copies.data(), n, sc, clip_coef_dev, stream)) return HOLO_E_INVALID;
   for (int i = 0; i < n; ++i) {
-    const ParamSlot& s = net->params[i];
+    const ParamSlot& s = net->d.params[i];
     if (!s.is_conv()) continue;
     // (b) the forward packs, (c) the transposed-convolution packs that exist (a Downsample weight: "<name>" and "<name>#s1")
     if (const int rc = pack_conv_weights(tensors[i].param, s.w, stream)) return rc;

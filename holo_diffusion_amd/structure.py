@@ -3,7 +3,7 @@
 Host-side restatement of the block construction in
 /root/reference/holo_diffusion/guided_diffusion/unet.py:645-798 (as SimpleUnet3D configures it,
 utils/diffusion_utils.py:56-75: dims=3, use_scale_shift_norm, conv_resample, no resblock_updown,
-num_head_channels=-1).  The C++ planner (csrc/unet_exec.cpp) builds the same list; SimpleUnet3D
+num_head_channels=-1).  The C++ planner (csrc/unet_plan.cpp) builds the same list; SimpleUnet3D
 cross-checks the two when it creates its native handle.
 """
 from __future__ import annotations

@@ -4,7 +4,7 @@
 // UndefinedBehaviorSanitizer by tests/test_conv_plan_cpu.py:
 //   conv_plan_check <golden table>      checks (a), (b), (c) below and that every kernel is chosen at least 20 times
 //   conv_plan_check                     prints the table only
-// It builds launches the way the denoiser's planner does (unet_exec.cpp: plan_conv / hand_over) over
+// It builds launches the way the denoiser's planner does (unet_plan.cpp: Planner::plan_conv / hand_over) over
 //   compute mode 0 / 1 / 2 with the weight copies hand_over gives each mode; 1x1x1 stride 1, 3x3x3 stride 1 and 2; nearest x2
 //   upsampling; grid edges 2 .. 64; 4 .. 384 channels of the first source alone and with an equal concat half; 4 .. 256
 //   output channels; GroupNorm affine, SiLU, residual, fused 1x1x1 skip, offered qkv packing; batch 1 and 3, planned for the
@@ -91,7 +91,7 @@ T* fake(uintptr_t a) {  // never dereferenced: the planner looks at which operan
   return reinterpret_cast<T*>(a);
 }
 
-// the launch as Planner::plan_conv / hand_over (unet_exec.cpp) build it
+// the launch as Planner::plan_conv / hand_over (unet_plan.cpp) build it
 ConvParams make_params(const Case& c, const Knobs& k) {
   ConvParams p;
   memset(&p, 0, sizeof p);
