@@ -7,6 +7,7 @@
 
 #include "../../include/holo_abi.h"
 #include "attn_plan.h"
+#include "bwd_plan.h"
 #include "conv_plan.h"
 #include "conv_weights.h"
 #include "holo_knobs.h"
@@ -448,53 +449,11 @@ int transpose_small_launch(const float* in, float* out, int rows, int cols, void
 // ---------------------------------------------------------------------------------------------
 // backward of the denoiser (kernels_bwd.hip)
 // ---------------------------------------------------------------------------------------------
-struct WgradParams {   // dW[co][ci][tap] = sum_m gy[m][co] act(coef . x)[m + tap][ci]; geometry as ConvParams
-  const float* gy;     // [M_out][Cout]
-  const float* src0;
-  const float* src1;   // virtual concat (may be null); C0 % 32 == 0 then
-  int C0, C1;
-  int N, ID, IH, IW, ups, OD, OH, OW, stride, pad, ksz, ntaps;
-  int Cout;
-  const float* coef;   // [N][Cin][2] or null
-  int act;
-  float* partial;      // [splits][Cout][Cin][ntaps] scratch (wgrad_partial_bytes)
-};
-struct WgradPlan {  // what wgrad_plan chose for a WgradParams: the scratch is sized and the launch shaped from the same value
-  int rows;         // 1: the row-staged kernel (conv_wgrad_rows_kernel), 0: the tile kernel
-  int splits;       // slabs of rows, one partial each
-  int reduce_tile;  // row-staged kernel: the tile form of the reduce
-};
-WgradPlan wgrad_plan(const WgradParams& p, int num_cus, const Knobs& k);
-size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& g);
+// (WgradParams, WgradPlan, GnBwdParams and the sizing rules the training planner shares with these launchers: bwd_plan.h)
 int conv_wgrad_launch(const WgradParams& p, const WgradPlan& g, float* dw, int accumulate, void* stream);
 int flip_transpose_weight_launch(const float* in, float* out, int Co, int Ci, int T, void* stream);
 int weight_tco_ci_launch(const float* in, float* out, int Co, int Ci, int T, void* stream);
-size_t colsum_scratch_bytes(int C);
 int colsum_launch(const float* g, int64_t M, int C, double* scratch, float* out, int accumulate, void* stream);
-struct GnBwdParams {   // GroupNorm32 (+ FiLM) (+ SiLU) backward over the virtual concat [x0 | x1]
-  const float* x0;
-  const float* x1;
-  int C0, C1, N;
-  int64_t V;
-  const float* ga;     // [N][V][C0 + C1] gradient w.r.t. the activated tensor
-  const float* coef;   // forward (a, b)
-  const float* mom;    // forward (mean, rstd) per channel
-  const float* gamma;
-  const float* beta;
-  const float* film;   // [N][film_stride]: scale at +c, shift at +film_cout + c (null: no FiLM)
-  int film_stride, film_cout;
-  int act;
-  double* part;        // scratch (gn_bwd_scratch_bytes)
-  float* grp;          // scratch [N][Cin][2]
-  float* dgamma;
-  float* dbeta;
-  float* dfilm;        // [N][film_stride] gradient of the FiLM rows (null without FiLM)
-  int acc_params;
-  float* gx0;          // gradient w.r.t. x0 / x1 (raw tensors)
-  float* gx1;
-  int acc0, acc1;      // accumulate into gx0 / gx1 instead of overwriting
-};
-size_t gn_bwd_scratch_bytes(const GnBwdParams& p);
 int gn_bwd_launch(const GnBwdParams& p, void* stream);
 int add_launch(float* dst, const float* src, int64_t n, int accumulate, void* stream);
 int split_cat_launch(const float* g, float* g0, float* g1, int64_t M, int C0, int C1, int acc0, int acc1, void* stream);

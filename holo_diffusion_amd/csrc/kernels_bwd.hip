@@ -146,7 +146,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradParams p) {
 // shift) from LDS, both bank-conflict free (a voxel is one 128-byte row, the pair's two voxels cover the 64 banks).
 // Three shapes: rows up to 64 voxels - 8 waves (4 / 3 taps each), 84 KB: one workgroup per CU, two waves per SIMD;
 // up to 32 and up to 16 - 4 waves (7 / 6 taps), 43 / 23 KB: two workgroups per CU (168 registers would spill).
-constexpr int WR_MAXW = 64;
 template <int MAXW>
 struct WgradRowLds {
   float gy[MAXW * 32];
@@ -904,39 +903,7 @@ int weight_tco_ci_launch(const float* in, float* out, int Co, int Ci, int T, voi
   return 0;
 }
 
-// the row-staged kernel serves the stride-1 3x3x3 convolutions of rows up to 64 voxels (HOLO_WGRAD_TILES=1: tile kernel)
-static bool wgrad_rows_ok(const WgradParams& p, const Knobs& k) {
-  if (k.wgrad_tiles > 0) return false;
-  const int Cin = p.C0 + p.C1;
-  return p.ksz == 3 && p.stride == 1 && p.pad == 1 && p.OW <= WR_MAXW && (p.OW & 1) == 0 && p.ID == p.OD && p.IH == p.OH &&
-         p.IW == p.OW && (Cin & 3) == 0 && (p.Cout & 3) == 0 && (p.C0 & 3) == 0 && (p.C1 & 3) == 0 && (!p.src1 || (p.C0 & 31) == 0);
-}
-WgradPlan wgrad_plan(const WgradParams& p, int num_cus, const Knobs& k) {
-  const int Cin = p.C0 + p.C1;
-  const int64_t nrows = (int64_t)p.N * p.OD * p.OH;
-  const int ncu = num_cus > 0 ? num_cus : 256;
-  WgradPlan g;
-  g.rows = wgrad_rows_ok(p, k) ? 1 : 0;
-  // row-staged kernel: the tile form of the reduce from HOLO_WGRAD_REDUCE_TILE_MIN 64-element tiles on (development / test knob)
-  g.reduce_tile = g.rows && ((int64_t)p.Cout * Cin + 63) / 64 >= k.wgrad_reduce_tile_min && p.ntaps <= 28;
-  int64_t s;
-  if (g.rows) {  // workgroups per CU by LDS / registers (1 or 2); slabs of at least 8 rows keep the row ring useful
-    const int64_t pairs = (int64_t)((p.Cout + 31) / 32) * ((Cin + 31) / 32);
-    s = ((p.OW > 32 ? 1 : 2) * (int64_t)ncu + pairs - 1) / pairs;
-    if (s > nrows / 8) s = nrows / 8;
-  } else {
-    const int64_t tiles = (int64_t)((p.Cout + 31) / 32) * ((Cin + 31) / 32) * p.ntaps;
-    s = (8LL * ncu + tiles - 1) / tiles;  // ~8 workgroups per CU in flight over the launch
-    if (s > nrows / 4) s = nrows / 4;
-  }
-  if (s < 1) s = 1;
-  if (s > 64) s = 64;
-  g.splits = (int)s;
-  return g;
-}
-size_t wgrad_partial_bytes(const WgradParams& p, const WgradPlan& g) {
-  return (size_t)g.splits * p.Cout * (p.C0 + p.C1) * p.ntaps * sizeof(float);
-}
+// (which kernel, how many slabs, how large the partials: wgrad_plan / wgrad_partial_bytes, bwd_plan.h)
 // dw: OIDHW [Cout][C0 + C1][ntaps]
 int conv_wgrad_launch(const WgradParams& p, const WgradPlan& g, float* dw, int accumulate, void* stream) {
   const int Cin = p.C0 + p.C1;
@@ -978,7 +945,6 @@ int partial_reduce_launch(const float* partial, float* dw, int64_t n, int splits
   return 0;
 }
 
-size_t colsum_scratch_bytes(int C) { return (size_t)256 * C * sizeof(double); }
 int colsum_launch(const float* g, int64_t M, int C, double* scratch, float* out, int accumulate, void* stream) {
   int nb = (int)(M < 256 ? M : 256);
   if (nb < 1) nb = 1;
@@ -987,15 +953,6 @@ int colsum_launch(const float* g, int64_t M, int C, double* scratch, float* out,
   return 0;
 }
 
-int gn_bwd_blocks(int64_t V) {
-  int64_t b = V / 64;
-  if (b > 512) b = 512;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-size_t gn_bwd_scratch_bytes(const GnBwdParams& p) {
-  return (size_t)gn_bwd_blocks(p.V) * p.N * (p.C0 + p.C1) * 2 * sizeof(double);
-}
 int gn_bwd_launch(const GnBwdParams& p, void* stream) {
   const int Cin = p.C0 + p.C1;
   if (Cin % 32 || Cin > 2048) {

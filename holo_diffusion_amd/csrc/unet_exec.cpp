@@ -1,6 +1,6 @@
 // unet_exec.cpp — native runtime of the denoiser: replays the static launch plan of UNetModel.forward (built by Planner,
-// unet_plan.h) on streams, builds the training plan on top of it, and holds the C ABI of the denoiser, the sampler steps,
-// Adam and the timers.
+// unet_plan.h) and the training plan (built by TrainPlanner, unet_train_plan.h) on streams, and holds the C ABI of the
+// denoiser, the sampler steps, Adam and the timers.
 //
 // The plan is a flat vector of ops; forward() only patches the three caller pointers (x, timesteps, y) and launches.  No
 // allocation, no host synchronisation inside forward().
@@ -11,7 +11,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <functional>
 #include <map>
 #include <optional>
 #include <string>
@@ -22,6 +21,7 @@
 #include "holo_common.h"
 #include "holo_kernels.h"
 #include "unet_plan.h"
+#include "unet_train_plan.h"
 
 namespace holo {
 
@@ -50,25 +50,6 @@ int holo::pack_conv_weights(const float* src, const ConvWeights& dst, void* stre
 
 // struct HoloCtx { device, num_cus }: holo_kernels.h (shared with render_exec.cpp)
 
-namespace {
-
-static bool is_downsample_weight(const std::string& name) {  // Downsample: the stride-2 convolution
-  return name.size() > 10 && name.compare(name.size() - 10, 10, ".op.weight") == 0;
-}
-
-// The training plan: the forward with every intermediate kept + the backward launches in execution order.
-struct TrainPlan {
-  Plan fwd;
-  std::vector<std::function<int(void*)>> bops;
-  std::vector<size_t> grad_off;  // per parameter: byte offset of its gradient in the workspace
-  size_t gy_off = 0, gx_off = 0;  // gradient of the output (laid out channels-last) / of the input
-  size_t bytes = 0;
-  bool built_for(int b, const void* w) const { return fwd.built_for(b, w); }
-  void invalidate() { *this = TrainPlan(); }
-};
-
-}  // namespace
-
 struct HoloUnet {
   HoloCtx* ctx;
   UnetDesc d;  // everything a plan is built from (unet_plan.h)
@@ -80,7 +61,7 @@ struct HoloUnet {
   // ---- training (holo_unet_backward): weights of the transposed convolutions, packed like the forward ones
   // ([Cin][Cout] flipped taps for the stride-1 convs; [tap][Cout][Cin] for the stride-2 Downsample convs, whose stride-1
   // form lives under "<name>#s1"), supplied by holo_unet_set_dgrad_weight; this table owns every buffer it points to
-  std::map<std::string, ConvWeights> dgrad;
+  DgradTable dgrad;
   std::vector<float*> adam_copies;  // holo_unet_adam_step: per parameter, its plain private copy (null for a conv weight)
   float* dgrad_tmp = nullptr;  // the flipped / transposed OIDHW weight on its way into the packs: the largest conv weight's numel
   TrainPlan tplan;
@@ -95,412 +76,6 @@ struct HoloUnet {
 };
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// training plan (second half): the forward with every intermediate kept and every layer recorded,
-// then the backward as a list of launches in reverse layer order.  fp32 mode only.
-//   * dgrad of a stride-1 convolution = the forward conv kernels on the flipped / transposed weights
-//     (holo_unet_set_dgrad_weight);  Downsample: conv_dgrad_s2_kernel;  Upsample: dgrad at the fine size + sumpool2
-//   * wgrad: conv_wgrad_kernel re-applies GroupNorm . FiLM . SiLU to the raw input like the forward's staging does
-//   * GroupNorm (+ FiLM + SiLU): gn_bwd_launch;  attention: batched fp32 MFMA GEMMs around the softmax rows
-// Gradients of activations are allocated on first use and ACCUMULATED by later consumers (skip connections, the
-// identity branches of ResBlock / AttentionBlock).  Parameter gradients live in the workspace in the reference's layouts.
-// ---------------------------------------------------------------------------------------------
-struct TrainPlanner {
-  const HoloUnet* u;  // read only: everything a build produces goes into `tp`
-  int N;
-  TrainPlan& tp;
-  Planner pl;
-  std::vector<Tape> tape;
-  std::vector<std::function<int(void*)>>& bops;      // tp.bops
-  std::map<size_t, std::pair<size_t, bool>> grads;  // activation offset -> (gradient offset, already written)
-  std::string err;
-
-  TrainPlanner(const HoloUnet* u_, int N_, void* ws, TrainPlan& tp_) : u(u_), N(N_), tp(tp_), pl(&u_->d, N_, ws, tp_.fwd), bops(tp_.bops) {
-    pl.arena.keep = true;
-    pl.tape = &tape;
-  }
-  template <class T>
-  T* ptr(size_t off) {
-    return pl.ptr<T>(off);
-  }
-  size_t alloc(size_t bytes) { return pl.scratch_alloc(bytes); }
-  int64_t vox(int R) const { return (int64_t)R * R * R; }
-  // gradient buffer of an activation; `acc` tells the caller whether to accumulate (a consumer wrote it before)
-  // (all bookkeeping is in workspace OFFSETS: a sizing pass has no workspace, and Planner::ptr forms addresses from integers,
-  // never by arithmetic on a null pointer - undefined behaviour that an optimising compiler does exploit)
-  static constexpr size_t NONE = ~(size_t)0;
-  size_t grad_of(const Act& a, int* acc) {
-    auto it = grads.find(a.off);
-    if (it == grads.end()) {
-      const size_t off = alloc((size_t)N * vox(a.R) * a.C * sizeof(float));
-      grads[a.off] = std::make_pair(off, true);
-      *acc = 0;
-      return off;
-    }
-    *acc = 1;
-    return it->second.first;
-  }
-  size_t grad_ready(const Act& a) {  // gradient of a layer OUTPUT: must have been written by its consumers
-    auto it = grads.find(a.off);
-    if (it == grads.end()) {
-      err = "internal: a layer output has no gradient";
-      return NONE;
-    }
-    return it->second.first;
-  }
-  float* pgrad(const std::string& name) {
-    auto it = u->d.pindex.find(name);
-    return it == u->d.pindex.end() ? nullptr : ptr<float>(tp.grad_off[it->second]);
-  }
-  // The transposed weights under `name`, or null.  A sizing pass (Plan::sizing) launches nothing and must not fail
-  // on weights that were not supplied yet, so there every convolution weight counts as present, and so does the stride-1
-  // form "<name>#s1" of a Downsample weight whose two leading dims are multiples of 4 (the one holo_unet_set_dgrad_weight
-  // creates); they count as plain fp32 copies, without Winograd forms.
-  std::optional<ConvWeights> find_dgw(const std::string& name) {
-    auto it = u->dgrad.find(name);
-    if (it != u->dgrad.end()) return it->second;
-    if (!tp.fwd.sizing) return std::nullopt;
-    const bool s1 = name.size() > 3 && name.compare(name.size() - 3, 3, "#s1") == 0;
-    auto pi = u->d.pindex.find(s1 ? name.substr(0, name.size() - 3) : name);
-    if (pi == u->d.pindex.end()) return std::nullopt;
-    const ParamSlot& s = u->d.params[pi->second];
-    if (!s.is_conv()) return std::nullopt;
-    if (s1 && (!is_downsample_weight(s.name) || (s.shape[0] & 3) || (s.shape[1] & 3))) return std::nullopt;
-    static float never_read;
-    ConvWeights assumed;
-    assumed.f32 = &never_read;
-    assumed.layout = s.layout(true);
-    return assumed;
-  }
-  std::optional<ConvWeights> dgw(const std::string& name) {
-    const std::optional<ConvWeights> w = find_dgw(name);
-    if (!w) err = "holo_unet_backward: call holo_unet_set_dgrad_weight for '" + name + "' first";
-    return w;
-  }
-
-  // dgrad of a stride-1 conv (3x3x3 pad 1 or 1x1x1): out[M][cin] = conv(gy[M][cout], flipped weights)
-  void emit_dgrad(size_t gy_off, int cout, int R, const std::string& wname, int cin, int ksz, size_t out_off,
-                  bool accumulate = false) {
-    const std::optional<ConvWeights> w = dgw(wname);
-    if (!w) return;
-    const Act g = view(gy_off, cout, R);
-    ConvDesc d;
-    d.x0 = &g;
-    d.ksz = ksz;
-    d.w = *w;
-    d.residual = accumulate ? ptr<float>(out_off) : nullptr;
-    d.out = ptr<float>(out_off);
-    d.Cout = cin;
-    pl.emit_conv(d);
-    const ConvParams cp = pl.ops.back().conv;
-    pl.ops.pop_back();
-    bops.push_back([cp](void* st) { return conv_launch(cp, st); });
-  }
-  // wgrad of the forward convolution `f` (sources, geometry, coefficients on load, Cout) into the gradients of
-  // `layer`.weight / .bias
-  void emit_wgrad(size_t gy_off, const ConvDesc& f, const std::string& layer) {
-    const float* gy = ptr<float>(gy_off);
-    const int cout = f.Cout;
-    WgradParams w;
-    memset(&w, 0, sizeof w);
-    w.gy = gy;
-    w.src0 = ptr<float>(f.x0->off);
-    w.src1 = f.x1 ? ptr<float>(f.x1->off) : nullptr;
-    w.C0 = f.x0->C;
-    w.C1 = f.x1 ? f.x1->C : 0;
-    w.N = N;
-    w.ID = w.IH = w.IW = f.in_size();
-    w.ups = f.ups;
-    w.OD = w.OH = w.OW = f.out_size();
-    w.stride = f.stride;
-    w.pad = f.ksz == 3 ? 1 : 0;
-    w.ksz = f.ksz;
-    w.ntaps = f.ksz == 3 ? 27 : 1;
-    w.Cout = cout;
-    w.coef = f.coef ? ptr<float>(*f.coef) : nullptr;
-    w.act = f.act;
-    const WgradPlan wg = wgrad_plan(w, u->ctx->num_cus, pl.knobs);
-    w.partial = ptr<float>(alloc(wgrad_partial_bytes(w, wg)));
-    float* dw = pgrad(layer + ".weight");
-    float* db = pgrad(layer + ".bias");
-    double* cs = ptr<double>(alloc(colsum_scratch_bytes(cout)));
-    const int64_t M = (int64_t)N * vox(f.out_size());
-    bops.push_back([w, wg, dw](void* st) { return conv_wgrad_launch(w, wg, dw, 0, st); });
-    bops.push_back([gy, M, cout, cs, db](void* st) { return colsum_launch(gy, M, cout, cs, db, 0, st); });
-  }
-  // the forward convolution of `cout` channels out of [x0 | x1], as emit_wgrad wants it
-  static ConvDesc fwd_conv(const Act& x0, const Act* x1, int cout) {
-    ConvDesc f;
-    f.x0 = &x0;
-    f.x1 = x1;
-    f.Cout = cout;
-    return f;
-  }
-  struct FilmGrad {  // a FiLM-modulated GroupNorm: the rows it was modulated with, and where their gradient goes
-    const float* film;
-    int cout;
-    float* dfilm;
-  };
-  // Backward of the stride-1 convolution `layer` = f(act(norm([x0 | x1]))) from the gradient of its output at gy_off:
-  // dgrad into a scratch ga [M][Cin], wgrad, then GroupNorm `norm` (+FiLM) (+SiLU) backward: ga -> gradients of x0 / x1
-  void bwd_norm_conv(size_t gy_off, const ConvDesc& f, const std::string& layer, const std::string& norm, size_t mom,
-                     const FilmGrad* film = nullptr) {
-    const Act &x0 = *f.x0, *x1 = f.x1;
-    const int Cin = x0.C + (x1 ? x1->C : 0);
-    const size_t ga = alloc((size_t)N * vox(x0.R) * Cin * sizeof(float));
-    emit_dgrad(gy_off, f.Cout, x0.R, layer + ".weight", Cin, f.ksz, ga);
-    emit_wgrad(gy_off, f, layer);
-    GnBwdParams g;
-    memset(&g, 0, sizeof g);
-    g.x0 = ptr<float>(x0.off);
-    g.x1 = x1 ? ptr<float>(x1->off) : nullptr;
-    g.C0 = x0.C;
-    g.C1 = x1 ? x1->C : 0;
-    g.N = N;
-    g.V = vox(x0.R);
-    g.ga = ptr<float>(ga);
-    g.coef = ptr<float>(*f.coef);
-    g.mom = ptr<float>(mom);
-    g.gamma = P(&u->d, norm + ".weight");
-    g.beta = P(&u->d, norm + ".bias");
-    g.film = film ? film->film : nullptr;
-    g.film_stride = u->d.emb_rows;
-    g.film_cout = film ? film->cout : 0;
-    g.act = f.act;
-    g.part = ptr<double>(alloc(gn_bwd_scratch_bytes(g)));
-    g.grp = ptr<float>(alloc((size_t)N * Cin * 2 * sizeof(float)));
-    g.dgamma = pgrad(norm + ".weight");
-    g.dbeta = pgrad(norm + ".bias");
-    g.dfilm = film ? film->dfilm : nullptr;
-    g.gx0 = ptr<float>(grad_of(x0, &g.acc0));
-    if (x1) g.gx1 = ptr<float>(grad_of(*x1, &g.acc1));
-    bops.push_back([g](void* st) { return gn_bwd_launch(g, st); });
-  }
-
-  void bwd_res(const Tape& t, float* dfilm_base) {
-    const std::string& p = t.b.prefix;
-    const int R = t.x0.R, cin = t.b.cin, cout = t.b.cout;
-    const int64_t M = (int64_t)N * vox(R);
-    const size_t gout = grad_ready(t.out);
-    if (gout == NONE) return;
-    const Act* x1 = t.has_x1 ? &t.x1 : nullptr;
-    // second conv: out = skip(x) + conv2(silu(film(gn2(h1))))
-    ConvDesc c2 = fwd_conv(t.h1, nullptr, cout);
-    c2.coef = t.coefB;
-    c2.act = 1;
-    const FilmGrad fg{t.film, cout, dfilm_base + u->d.emb_row_off.at(p)};
-    bwd_norm_conv(gout, c2, p + ".out_layers.3", p + ".out_layers.0", t.momB, &fg);
-    const size_t gh1 = grad_ready(t.h1);
-    if (gh1 == NONE) return;
-    // first conv: h1 = conv1(silu(gn1([x0 | x1])))
-    ConvDesc c1 = fwd_conv(t.x0, x1, cout);
-    c1.coef = t.coefA;
-    c1.act = 1;
-    bwd_norm_conv(gh1, c1, p + ".in_layers.2", p + ".in_layers.0", t.momA);
-    // skip connection: identity, or a 1x1x1 conv of the raw input
-    int a0 = 0, a1 = 0;
-    float* gx0 = ptr<float>(grad_of(t.x0, &a0));
-    float* gx1 = x1 ? ptr<float>(grad_of(*x1, &a1)) : nullptr;
-    const float* goutp = ptr<float>(gout);
-    if (!t.has_skip) {
-      const int64_t n = M * cin;
-      bops.push_back([gx0, goutp, n, a0](void* st) { return add_launch(gx0, goutp, n, a0, st); });
-    } else {
-      const size_t gso = alloc((size_t)M * cin * sizeof(float));
-      const float* gs = ptr<float>(gso);
-      emit_dgrad(gout, cout, R, p + ".skip_connection.weight", cin, 1, gso);
-      ConvDesc cs = fwd_conv(t.x0, x1, cout);
-      cs.ksz = 1;
-      emit_wgrad(gout, cs, p + ".skip_connection");
-      if (x1) {
-        const int C0 = t.x0.C, C1 = t.x1.C;
-        bops.push_back([gs, gx0, gx1, M, C0, C1, a0, a1](void* st) { return split_cat_launch(gs, gx0, gx1, M, C0, C1, a0, a1, st); });
-      } else {
-        const int64_t n = M * cin;
-        bops.push_back([gx0, gs, n, a0](void* st) { return add_launch(gx0, gs, n, a0, st); });
-      }
-    }
-  }
-
-  void bwd_attn(const Tape& t) {
-    const std::string& p = t.b.prefix;
-    const int C = t.x0.C, R = t.x0.R, H = u->d.cfg.num_heads;
-    const int64_t T = vox(R), M = (int64_t)N * T;
-    const AttnDims dims{N, H, C, T};
-    const size_t gout = grad_ready(t.out);
-    if (gout == NONE) return;
-    int ax = 0;
-    float* gx = ptr<float>(grad_of(t.x0, &ax));
-    {  // identity branch
-      const int64_t n = M * C;
-      const float* goutp = ptr<float>(gout);
-      bops.push_back([gx, goutp, n, ax](void* st) { return add_launch(gx, goutp, n, ax, st); });
-    }
-    // proj_out (1x1 over the attention output a)
-    const Act av = view(t.a, C, R);
-    const size_t ga_off = alloc((size_t)M * C * sizeof(float));
-    float* ga = ptr<float>(ga_off);
-    emit_dgrad(gout, C, R, p + ".proj_out.weight", C, 1, ga_off);
-    ConvDesc cp = fwd_conv(av, nullptr, C);
-    cp.ksz = 1;
-    emit_wgrad(gout, cp, p + ".proj_out");
-    // attention core: P = softmax(s2 q k^T); dP = ga v^T; dS = P (dP - rowsum(dP P)); dv = P^T ga; dq = s2 dS k; dk = s2 dS^T q
-    const size_t sb = (size_t)N * H * T * T * sizeof(float);
-    float* Pm = ptr<float>(alloc(sb));
-    float* dS = ptr<float>(alloc(sb));
-    float* Tm = ptr<float>(alloc(sb));
-    const size_t gqkv_off = alloc((size_t)M * 3 * C * sizeof(float));
-    float* gqkv = ptr<float>(gqkv_off);
-    float* qkv = ptr<float>(t.qkv);
-    const float s2 = dims.scale2();
-    auto gemm = [&](AttnMat A, AttnMat B, bool b_kmajor, AttnMat Cc, float alpha) {
-      const GemmParams g = attn_gemm(dims, A, B, b_kmajor, Cc, alpha);
-      bops.push_back([g](void* st) { return gemm_launch(g, st); });
-    };
-    const int Ti = (int)T, NH = N * H;
-    const int64_t rows = (int64_t)NH * T;
-    gemm(dims.qkv(qkv, 0), dims.qkv(qkv, 1), false, dims.scores(Pm), s2);
-    bops.push_back([Pm, rows, Ti](void* st) { return softmax_rows_launch(Pm, rows, Ti, st); });
-    gemm(dims.heads(ga), dims.qkv(qkv, 2), false, dims.scores(dS), 1.0f);
-    bops.push_back([Pm, dS, rows, Ti](void* st) { return attn_ds_launch(Pm, dS, rows, Ti, st); });
-    bops.push_back([Pm, Tm, NH, Ti](void* st) { return transpose_launch(Pm, Tm, NH, Ti, st); });
-    gemm(dims.scores(Tm), dims.heads(ga), true, dims.qkv(gqkv, 2), 1.0f);  // dv
-    gemm(dims.scores(dS), dims.qkv(qkv, 1), true, dims.qkv(gqkv, 0), s2);    // dq
-    bops.push_back([dS, Tm, NH, Ti](void* st) { return transpose_launch(dS, Tm, NH, Ti, st); });
-    gemm(dims.scores(Tm), dims.qkv(qkv, 0), true, dims.qkv(gqkv, 1), s2);  // dk
-    // qkv conv (1x1, C -> 3C, GroupNorm applied on load, no activation)
-    ConvDesc cq = fwd_conv(t.x0, nullptr, 3 * C);
-    cq.ksz = 1;
-    cq.coef = t.coefA;
-    bwd_norm_conv(gqkv_off, cq, p + ".qkv", p + ".norm", t.momA);
-  }
-
-  void bwd_conv(const Tape& t) {  // input conv / Downsample / Upsample / output head
-    const BlockKind kind = t.b.kind;
-    const int cin = t.b.cin, cout = t.b.cout, Ri = t.x0.R, Ro = t.out.R, Nn = N;
-    const size_t gout = grad_ready(t.out);
-    if (gout == NONE) return;
-    ConvDesc f = fwd_conv(t.x0, nullptr, cout);
-    if (kind == B_HEAD) {  // y = conv(silu(gn(h)))
-      f.coef = t.coefA;
-      f.act = 1;
-      bwd_norm_conv(gout, f, "out.2", "out.0", t.momA);
-      return;
-    }
-    int ax = 0;
-    const size_t gx_off = grad_of(t.x0, &ax);
-    float* gx = ptr<float>(gx_off);
-    const float* goutp = ptr<float>(gout);
-    const std::string layer = t.b.prefix + (kind == B_DOWN ? ".op" : kind == B_UP ? ".conv" : "");
-    const std::string wn = layer + ".weight";
-    if (kind == B_CONV) {
-      if (ax) {
-        err = "internal: the input conv's source already has a gradient";
-        return;
-      }
-      emit_dgrad(gout, cout, Ri, wn, cin, 3, gx_off);
-    } else if (kind == B_DOWN) {
-      const std::optional<ConvWeights> wt = dgw(wn);
-      if (!wt) return;
-      // (HOLO_DGRAD_S2_DIRECT=1, development / test knob: conv_dgrad_s2_kernel everywhere)
-      if (!pl.knobs.dgrad_s2_direct && find_dgw(wn + "#s1") && Ri == 2 * Ro && (Ri % 8) == 0) {
-        // zero insertion + the stride-1 transposed convolution on the forward's conv kernels (8x the multiply-adds, on the
-        // Winograd kernels: 0.24 instead of 1.35 ms at 64^3 <- 32^3)
-        const size_t gz_off = alloc((size_t)N * vox(Ri) * cout * sizeof(float));
-        float* gz = ptr<float>(gz_off);
-        bops.push_back([goutp, gz, Nn, Ro, cout](void* st) { return zero_insert2_launch(goutp, gz, Nn, Ro, cout, st); });
-        emit_dgrad(gz_off, cout, Ri, wn + "#s1", cin, 3, gx_off, ax != 0);
-      } else {
-        const float* wtp = wt->f32;
-        bops.push_back([goutp, wtp, gx, Nn, Ri, Ro, cin, cout, ax](void* st) {
-          return conv_dgrad_s2_launch(goutp, wtp, gx, Nn, Ri, Ro, cin, cout, ax, st);
-        });
-      }
-      f.out_R = Ro;
-      f.stride = 2;
-    } else {  // B_UP: conv at the fine size of the nearest-upsampled input
-      const int64_t Mf = (int64_t)N * vox(Ro);
-      const size_t gup_off = alloc((size_t)Mf * cin * sizeof(float));
-      float* gup = ptr<float>(gup_off);
-      emit_dgrad(gout, cout, Ro, wn, cin, 3, gup_off);
-      bops.push_back([gup, gx, Nn, Ri, cin, ax](void* st) { return sumpool2_launch(gup, gx, Nn, Ri, cin, ax, st); });
-      f.in_R = Ro;
-      f.ups = 1;
-    }
-    emit_wgrad(gout, f, layer);
-  }
-
-  int build() {
-    const HoloUnetCfg& c = u->d.cfg;
-    tp.invalidate();
-    pl.build();
-    // parameter gradients: one region in the reference's layouts; emb_layers rows alias the concatenated matrix
-    tp.grad_off.assign(u->d.params.size(), 0);
-    const size_t gembw = alloc((size_t)u->d.emb_rows * u->d.ted * sizeof(float));
-    const size_t gembb = alloc((size_t)u->d.emb_rows * sizeof(float));
-    for (size_t i = 0; i < u->d.params.size(); ++i) {
-      const ParamSlot& s = u->d.params[i];
-      if (s.kind == P_EMB_W || s.kind == P_EMB_B) {
-        const int row = u->d.emb_row_off.at(s.name.substr(0, s.name.rfind(".emb_layers")));
-        tp.grad_off[i] = s.kind == P_EMB_W ? gembw + (size_t)row * u->d.ted * sizeof(float) : gembb + (size_t)row * sizeof(float);
-      } else {
-        tp.grad_off[i] = alloc((size_t)s.numel * sizeof(float));
-      }
-    }
-    // the gradient of the output arrives NCDHW and is laid out channels-last as the gradient of y
-    const int R = c.image_size;
-    const int64_t V = vox(R);
-    const size_t gy = alloc((size_t)N * V * c.out_channels * sizeof(float));
-    grads[pl.y_out.off] = std::make_pair(gy, true);
-    tp.gy_off = gy;
-    const size_t dfilm = alloc((size_t)N * u->d.emb_rows * sizeof(float));
-    float* dfilm_base = ptr<float>(dfilm);
-    for (int i = (int)tape.size() - 1; i >= 0 && err.empty(); --i) {
-      const Tape& t = tape[i];
-      if (t.b.kind == B_RES)
-        bwd_res(t, dfilm_base);
-      else if (t.b.kind == B_ATTN)
-        bwd_attn(t);
-      else
-        bwd_conv(t);
-    }
-    if (err.empty()) err = pl.err;  // (emit_conv's refusals)
-    if (!err.empty()) {
-      set_error("%s", err.c_str());
-      return HOLO_E_STATE;
-    }
-    // embedding path
-    {
-      const float* embs = ptr<float>(pl.embs_off);
-      float* gembs = ptr<float>(alloc((size_t)N * u->d.ted * sizeof(float)));
-      float* dw = ptr<float>(gembw);
-      float* db = ptr<float>(gembb);
-      const float* w = u->d.emb_w;
-      const int rows = u->d.emb_rows, K = u->d.ted, Nn = N;
-      bops.push_back([dfilm_base, embs, w, dw, db, gembs, Nn, rows, K](void* st) {
-        return film_bwd_launch(dfilm_base, embs, w, dw, db, gembs, Nn, rows, K, st);
-      });
-      const HoloUnet* uu = u;  // (t_dev is the running call's)
-      const int mc = c.model_channels;
-      const float *w1 = P(&u->d, "time_embed.0.weight"), *b1 = P(&u->d, "time_embed.0.bias"), *w2 = P(&u->d, "time_embed.2.weight"),
-                  *b2 = P(&u->d, "time_embed.2.bias");
-      float *dw1 = pgrad("time_embed.0.weight"), *db1 = pgrad("time_embed.0.bias"), *dw2 = pgrad("time_embed.2.weight"),
-            *db2 = pgrad("time_embed.2.bias");
-      bops.push_back([uu, Nn, mc, K, w1, b1, w2, b2, gembs, dw1, db1, dw2, db2](void* st) {
-        return time_embed_bwd_launch(uu->t_dev, Nn, mc, K, w1, b1, w2, b2, gembs, dw1, db1, dw2, db2, st);
-      });
-    }
-    auto gi = grads.find(pl.x_in.off);
-    if (gi == grads.end()) {
-      set_error("internal: the network input has no gradient");
-      return HOLO_E_STATE;
-    }
-    tp.gx_off = gi->second.first;
-    tp.bytes = tp.fwd.bytes = pl.arena_base + pl.arena.peak;  // (the backward's buffers grew the arena after pl.build())
-    return 0;
-  }
-};
 
 bool params_set(const HoloUnet* u, const char* entry) {
   for (auto& s : u->d.params)
@@ -519,9 +94,13 @@ int ensure_train_plan(HoloUnet* u, const char* entry, int batch, void* ws, size_
       return HOLO_E_UNSUPPORTED;
     }
     if (!params_set(u, "holo_unet_backward")) return HOLO_E_STATE;
-    TrainPlanner tp(u, batch, ws, u->tplan);
-    int rc = tp.build();
-    if (!rc && !tp.pl.regions_ok()) {
+    TrainPlanner tp(&u->d, u->dgrad, batch, ws, u->tplan);
+    tp.build();
+    int rc = 0;
+    if (!tp.err.empty()) {
+      set_error("%s", tp.err.c_str());
+      rc = HOLO_E_STATE;
+    } else if (!tp.pl.regions_ok()) {
       set_error("internal: small-buffer regions overflow");
       rc = HOLO_E_INVALID;
     }
@@ -661,15 +240,54 @@ int run_plan(HoloUnet* u, const Plan& plan, const float* x, const int64_t* t, fl
     return op.kind == OP_OUT && !y ? 0 : run_op(u, op, plan.batch, x, t, y, st);
   });
 }
-// the backward launches of a training plan whose taped forward has run on `workspace`
+int run_bwd_op(const BwdOp& op, const int64_t* t, void* stream) {
+  switch (op.kind) {
+    case BOP_CONV:
+      return conv_launch(op.conv, stream);
+    case BOP_WGRAD:
+      return conv_wgrad_launch(op.wgrad.p, op.wgrad.plan, op.wgrad.dw, 0, stream);
+    case BOP_COLSUM:
+      return colsum_launch(op.colsum.g, op.colsum.M, op.colsum.C, op.colsum.scratch, op.colsum.out, 0, stream);
+    case BOP_GN_BWD:
+      return gn_bwd_launch(op.gn, stream);
+    case BOP_ADD:
+      return add_launch(op.add.dst, op.add.src, op.add.n, op.add.acc, stream);
+    case BOP_SPLIT_CAT:
+      return split_cat_launch(op.split.g, op.split.g0, op.split.g1, op.split.M, op.split.C0, op.split.C1, op.split.acc0, op.split.acc1, stream);
+    case BOP_SUMPOOL2:
+      return sumpool2_launch(op.pool.gup, op.pool.gin, op.pool.N, op.pool.R, op.pool.C, op.pool.acc, stream);
+    case BOP_ZERO_INSERT2:
+      return zero_insert2_launch(op.zins.gy, op.zins.out, op.zins.N, op.zins.Rs, op.zins.C, stream);
+    case BOP_DGRAD_S2:
+      return conv_dgrad_s2_launch(op.s2.gy, op.s2.wt, op.s2.gx, op.s2.N, op.s2.RI, op.s2.RO, op.s2.Ci, op.s2.Co, op.s2.acc, stream);
+    case BOP_GEMM:
+      return gemm_launch(op.gemm, stream);
+    case BOP_SOFTMAX:
+      return softmax_rows_launch(op.softmax.S, op.softmax.rows, op.softmax.cols, stream);
+    case BOP_ATTN_DS:
+      return attn_ds_launch(op.ds.P, op.ds.dP, op.ds.rows, op.ds.cols, stream);
+    case BOP_TRANSPOSE:
+      return transpose_launch(op.tr.in, op.tr.out, op.tr.batch, op.tr.T, stream);
+    case BOP_FILM_BWD: {
+      const FilmBwd& f = op.film;
+      return film_bwd_launch(f.dfilm, f.embs, f.w, f.dw, f.db, f.gembs, f.N, f.rows, f.K, stream);
+    }
+    case BOP_TEMB_BWD: {
+      const TimeEmbedBwd& e = op.temb;
+      return time_embed_bwd_launch(t, e.N, e.mc, e.ted, e.w1, e.b1, e.w2, e.b2, e.gembs, e.dw1, e.db1, e.dw2, e.db2, stream);
+    }
+  }
+  return 0;
+}
+// the backward launches of a training plan whose taped forward has run on `workspace` (u->t_dev: that forward's timesteps)
 int run_backward(const HoloUnet* u, const TrainPlan& tp, const float* grad_out, float* grad_x, void* workspace, void* stream) {
   const HoloUnetCfg& c = u->d.cfg;
   const int batch = tp.fwd.batch;
   const int64_t V = (int64_t)c.image_size * c.image_size * c.image_size;
   if (ncdhw_to_ndhwc_launch(grad_out, (float*)((char*)workspace + tp.gy_off), batch, c.out_channels, V, 0, stream))
     return HOLO_E_INVALID;
-  for (auto& f : tp.bops) {
-    const int rc = f(stream);
+  for (const BwdOp& op : tp.bops) {
+    const int rc = run_bwd_op(op, u->t_dev, stream);
     if (rc) return rc < 0 ? rc : HOLO_E_INVALID;
   }
   if (grad_x && ndhwc_to_ncdhw_launch((const float*)((char*)workspace + tp.gx_off), grad_x, batch, c.in_channels, V, stream))
@@ -1128,7 +746,12 @@ size_t holo_unet_backward_workspace_bytes(HoloUnet* net, int batch) {
   auto it = net->tws_cache.find(batch);
   if (it != net->tws_cache.end()) return it->second;
   TrainPlan sizing;  // built on no workspace (TrainPlanner::find_dgw: no transposed weight is missed there) and dropped
-  if (TrainPlanner(net, batch, nullptr, sizing).build()) return 0;  // the message is in holo_last_error()
+  TrainPlanner tp(&net->d, net->dgrad, batch, nullptr, sizing);
+  tp.build();
+  if (!tp.err.empty()) {
+    set_error("%s", tp.err.c_str());
+    return 0;
+  }
   net->tws_cache[batch] = sizing.bytes;
   return sizing.bytes;
 }

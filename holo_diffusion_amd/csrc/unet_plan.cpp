@@ -420,9 +420,9 @@ size_t Planner::plan_conv(const ConvDesc& d, ConvParams& p) {
     err = "internal: one half of a split concat convolution left conv_wino3_kernel";
   return sb;
 }
-void Planner::emit_conv(const ConvDesc& d) {
-  Op op = make_op(OP_CONV);
-  ConvParams& p = op.conv;
+ConvParams Planner::place_conv(const ConvDesc& d, int* stats_slabs) {
+  ConvParams p;
+  memset(&p, 0, sizeof p);
   const size_t sb = plan_conv(d, p);
   size_t so = 0;
   if (sb) {
@@ -442,6 +442,13 @@ void Planner::emit_conv(const ConvDesc& d) {
   // came out wrong in ~25 % of the runs of the bf16 mode at 32^3 - scripts/bf16_batch_check.py, found in round 4.)
   // Stream order protects the scratch against every LATER launch.
   if (sb) scratch_free(so, sb);
+  if (stats_slabs) *stats_slabs = slabs;
+  return p;
+}
+void Planner::emit_conv(const ConvDesc& d) {
+  Op op = make_op(OP_CONV);
+  int slabs = 0;
+  op.conv = place_conv(d, &slabs);
   ops.push_back(op);
   if (d.stats_of && slabs == 0) emit_stats(*d.stats_of);
 }

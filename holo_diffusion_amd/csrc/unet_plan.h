@@ -1,8 +1,9 @@
 // unet_plan.h — the denoiser's static launch plan as a value: the network structure and its parameter table, the
 // first-fit arena, the ops of a plan, and the Planner that builds the plan of UNetModel.forward for one (description, batch,
 // workspace base).  Host-only arithmetic (definitions in unet_plan.cpp): no HIP header, so a plain C++ program builds plans
-// and checks them on the CPU (tests/cpu/unet_plan_check.cpp).  unet_exec.cpp replays a plan on streams and builds the
-// training plan on top of Planner.
+// and checks them on the CPU (tests/cpu/unet_plan_check.cpp).  The training plan (TrainPlan: that forward with every
+// intermediate kept + the backward's launches as BwdOp values) is built on top of Planner by TrainPlanner
+// (unet_train_plan.h).  unet_exec.cpp replays both on streams.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -17,6 +18,7 @@
 
 #include "../../include/holo_abi.h"
 #include "attn_plan.h"
+#include "bwd_plan.h"
 #include "conv_plan.h"
 #include "conv_weights.h"
 #include "holo_knobs.h"
@@ -198,6 +200,66 @@ struct Plan {
   void invalidate() { *this = Plan(); }
 };
 
+// One launch of the backward (kernels_bwd.hip, and the forward's conv / GEMM / softmax launchers on gradients).  A kind of
+// its own: the forward's OpKind numbers are public and stay what they are.  Every accumulate flag (`acc*`, a conv whose
+// residual is its out) says that an earlier op of the list wrote the destination and this one adds to it.
+enum BwdOpKind {
+  BOP_CONV = 1, BOP_WGRAD, BOP_COLSUM, BOP_GN_BWD, BOP_ADD, BOP_SPLIT_CAT, BOP_SUMPOOL2, BOP_ZERO_INSERT2, BOP_DGRAD_S2, BOP_GEMM,
+  BOP_SOFTMAX, BOP_ATTN_DS, BOP_TRANSPOSE, BOP_FILM_BWD, BOP_TEMB_BWD
+};
+struct Wgrad { WgradParams p; WgradPlan plan; float* dw; };                             // dw: OIDHW, overwritten
+struct Colsum { const float* g; int64_t M; int C; double* scratch; float* out; };       // bias gradient: column sums of g [M][C]
+struct AddGrad { float* dst; const float* src; int64_t n; int acc; };                   // dst (+)= src
+struct SplitCat { const float* g; float *g0, *g1; int64_t M; int C0, C1, acc0, acc1; };  // g [M][C0 + C1] -> g0 [M][C0], g1 [M][C1]
+struct SumPool2 { const float* gup; float* gin; int N, R, C, acc; };                    // gup (2R)^3 -> gin R^3
+struct ZeroInsert2 { const float* gy; float* out; int N, Rs, C; };                      // gy Rs^3 -> out (2 Rs)^3
+struct DgradS2 { const float *gy, *wt; float* gx; int N, RI, RO, Ci, Co, acc; };
+struct AttnDs { const float* P; float* dP; int64_t rows; int cols; };  // dP in place: dS = P (dP - rowsum(dP P))
+struct Transpose { const float* in; float* out; int batch, T; };
+struct FilmBwd { const float *dfilm, *embs, *w; float *dw, *db, *gembs; int N, rows, K; };
+struct TimeEmbedBwd {  // (the timesteps are an argument of the run, like the forward's)
+  int N, mc, ted;
+  const float *w1, *b1, *w2, *b2, *gembs;
+  float *dw1, *db1, *dw2, *db2;
+};
+struct BwdOp {  // trivially copyable
+  BwdOpKind kind;
+  union {
+    ConvParams conv;  // dgrad of a stride-1 convolution: the forward's kernels on the transposed weights
+    Wgrad wgrad;
+    Colsum colsum;
+    GnBwdParams gn;
+    AddGrad add;
+    SplitCat split;
+    SumPool2 pool;
+    ZeroInsert2 zins;
+    DgradS2 s2;
+    GemmParams gemm;
+    Softmax softmax;
+    AttnDs ds;
+    Transpose tr;
+    FilmBwd film;
+    TimeEmbedBwd temb;
+  };
+};
+inline BwdOp make_bwd_op(BwdOpKind kind) {
+  BwdOp op;
+  memset(&op, 0, sizeof op);
+  op.kind = kind;
+  return op;
+}
+
+// The training plan: the forward with every intermediate kept + the backward launches in execution order.
+struct TrainPlan {
+  Plan fwd;
+  std::vector<BwdOp> bops;
+  std::vector<size_t> grad_off;  // per parameter: byte offset of its gradient in the workspace
+  size_t gy_off = 0, gx_off = 0;  // gradient of the output (laid out channels-last) / of the input
+  size_t bytes = 0;
+  bool built_for(int b, const void* w) const { return fwd.built_for(b, w); }
+  void invalidate() { *this = TrainPlan(); }
+};
+
 // Everything a plan depends on, as plain data: what HoloUnet (unet_exec.cpp) holds by value next to its device stores,
 // caches, streams and events.  Planner reads nothing else.
 struct UnetDesc {
@@ -235,6 +297,9 @@ struct StoreSizes {
 StoreSizes carve_params(UnetDesc* u, float* f32, uint16_t* bf, float* wino);
 // the private copies of parameter `name`: P its fp32 copy, W the whole set of a convolution weight
 ConvWeights W(const UnetDesc* u, const std::string& name);
+inline bool is_downsample_weight(const std::string& name) {  // Downsample: the stride-2 convolution
+  return name.size() > 10 && name.compare(name.size() - 10, 10, ".op.weight") == 0;
+}
 inline const float* P(const UnetDesc* u, const std::string& name) { return W(u, name).f32; }
 
 // ---------------------------------------------------------------------------------------------
@@ -359,7 +424,8 @@ struct Planner {
   ConvDesc conv_of(const std::string& layer, const Act& x, const Act& out);
   void hand_over(const ConvWeights& cw, ConvParams& p, bool skip, int cin0 = -1);
   size_t plan_conv(const ConvDesc& d, ConvParams& p);
-  void emit_conv(const ConvDesc& d);
+  ConvParams place_conv(const ConvDesc& d, int* stats_slabs = nullptr);  // plan_conv + the launch's scratch and statistics placed
+  void emit_conv(const ConvDesc& d);                                     // ... appended to the plan as an op
 
   // (both lanes on ONE stream cost 12 % of the B = 4 chain rate, DESIGN.md section 8: the parts always take the side stream)
   bool side_stream_used() const { return true; }
