@@ -11,6 +11,7 @@
 #include "conv_plan.h"
 #include "conv_weights.h"
 #include "holo_knobs.h"
+#include "render_plan.h"
 
 // per-device context of the C ABI (holo_ctx_create)
 struct HoloCtx {
@@ -484,9 +485,7 @@ int surface_count_launch(const float* field, int m, float level, int64_t* counts
 // verts / faces null: that pass is not launched
 int surface_emit_launch(const float* field, int m, float level, float half_extent, float* verts, int64_t verts_capacity,
                         int32_t* faces, int64_t tris_capacity, void* workspace, void* stream);
-// (`k`: the renderer handle's snapshot of the knobs - the three must see the same one)
-int render_launch(const RenderKernelParams& p, const Knobs& k, void* stream, int n_workgroups);
-int render_waves_per_wg(const Knobs& k, int C, int n_fine, int with_normals, int split3 = 0, int train = 0);
-int render_rays_per_tile(const Knobs& k, int C, int n_fine, int with_normals, int split3, int train);
+// one launch of a planned call (render_plan.h: render_plan, render_launches)
+int render_launch(const RenderKernelParams& p, const RenderPlan& plan, const RenderLaunch& launch, void* stream);
 
 }  // namespace holo

@@ -45,6 +45,8 @@ namespace {
 constexpr int HD = 256;  // RenderMLP.dnet_hidden_dim
 constexpr int NTILE = HD / 32;
 constexpr int MAXC = 64;  // max coarse samples per ray held in LDS (cdf rows)
+static_assert(HD == RENDER_HD && MAXC == RENDER_MAXC && RenderKernelParams::MAX_CAMS == RENDER_MAX_CAMS,
+              "render_plan.h plans for the sizes these kernels are compiled with");
 
 __device__ __forceinline__ float lin_space(float start, float end, float step, int i, int steps) {
   // torch.linspace: symmetric evaluation around the midpoint
@@ -391,16 +393,10 @@ __device__ __forceinline__ void eval_point(const MlpLds<CH, SP>& L, const float*
 // composited; the coarse values stream back through a two-deep register prefetch.
 // Reference arithmetic kept: torch's CPU cumsum accumulates fp32 inputs in double (both the raymarcher's
 // cumsum(delta * sigma) and sample_pdf's cdf), so both running sums are doubles here.
-// waves per workgroup (= per CU): 12 (3 per SIMD, 168 VGPRs) for the released configurations; the normals variant and
-// 64-feature grids need more registers per wave (2 per SIMD, 256 VGPRs); 128 new samples per ray need twice the LDS rows
-template <int CH, int ZCAP, bool NRM>
-constexpr int render_waves() {
-  return (CH <= 16 && !NRM) ? (ZCAP <= 64 ? 12 : 6) : (ZCAP <= 64 ? 8 : 4);
-}
-
+// (waves per workgroup: render_waves, render_plan.h)
 template <int CH, bool SP, bool NRM, int ZCAP>
-__global__ __launch_bounds__((64 * render_waves<CH, ZCAP, NRM>())) void render_kernel(RenderKernelParams p) {
-  constexpr int NW = render_waves<CH, ZCAP, NRM>();
+__global__ __launch_bounds__((64 * render_waves(CH, ZCAP, NRM))) void render_kernel(RenderKernelParams p) {
+  constexpr int NW = render_waves(CH, ZCAP, NRM);
   constexpr int ZS = ZCAP + 1;
   // ONE LDS object with the RenderMLP image FIRST: the workgroup uses more than 64 KB of LDS and a ds_read carries a
   // 16-bit offset, so everything the evaluation loop reads (20 reads per 32-row tile) has to sit below 64 KB to be
@@ -858,18 +854,7 @@ __device__ __forceinline__ void r2_unpack_normal(uint32_t c, float (&n)[3]) {
   n[0] = x * k, n[1] = y * k, n[2] = z * k;
 }
 
-// waves per workgroup (= per CU): the per-wave rows are 9.4 KB (64 new samples per ray) / 14.6 KB (128), + 2 KB with
-// normals; with the 40 KB RenderMLP image of 32 grid features 12 / 8 waves fit (64 grid features: 73 KB image, 8 / 4 waves)
-// NRM: built for <= 32 grid features and <= 64 new samples per ray (the BASELINE / released configurations; anything else
-// renders its normals on the ray-per-column kernel, render_rays_per_tile).  10 waves per CU (what the LDS holds): with the
-// per-corner scalars read from the density scalar field the evaluation fits the 168 registers of three waves per SIMD
-// (84 bytes of scratch outside the MFMA loops; with the scalars formed per sample it was 580 bytes and 25 M rays/s).
-// Measured at 400^2, 8 frames: 40.2 M rays/s on 10 waves, 39.0 M on 8 (HOLO_RENDER2_NRM_NW=8, the emulation's choice)
-template <int CH, int ZF, bool NRM = false>
-constexpr int render2_waves() {
-  return NRM ? 10 : (ZF <= 64 ? (CH <= 16 ? 12 : 8) : (CH <= 16 ? 8 : 4));
-}
-
+// (waves per workgroup: render2_waves, render_plan.h)
 template <int CH, int ZF, bool TRAIN, int NW, bool NRM = false>
 __global__ __launch_bounds__((64 * NW)) void render2_kernel(RenderKernelParams p) {
   static_assert(!(TRAIN && NRM), "training-mode rendering returns no normals");
@@ -1445,88 +1430,40 @@ int bias_leaky_launch(float* y, const float* bias, int64_t rows, int cols, void*
   return 0;
 }
 
-// waves per workgroup of render2_kernel at run time (HOLO_RENDER2_NW=8: development knob, the 8-wave form of the
-// 12-wave configurations)
-static int render2_waves_rt(const Knobs& k, int C, int n_fine, int with_normals = 0) {
-  const int ch = C / 2;
-  // render2_waves<CH, 64, true>(); HOLO_RENDER2_NRM_NW=8: the two-waves-per-SIMD form (development knob; what the
-  // emulation build always runs)
-  if (with_normals) return k.render2_nrm_nw == 8 || EMU_BUILD ? 8 : 10;
-  const int nw = n_fine <= 64 ? (ch <= 16 ? 12 : 8) : (ch <= 16 ? 8 : 4);
-  return k.render2_nw == 8 && nw == 12 ? 8 : nw;
-}
-
+// The instantiations of one feature width.  The plan has passed render_can_launch: every combination of its fields that
+// reaches this switch exists, and pl.waves is the NW of the instantiation picked here.
 template <int CH, bool SP>
-static int render_launch_t(const RenderKernelParams& p, const Knobs& k, void* stream, int n_wgs) {
-  const bool nrm = p.nrm != nullptr || p.nrm_c != nullptr;
-  if (render_rays_per_tile(k, 2 * CH, p.n_fine, nrm ? 1 : 0, SP ? 1 : 0, p.train.n_rays > 0 ? 1 : 0) == 4) {
+static void render_launch_t(const RenderKernelParams& p, const RenderPlan& pl, dim3 grid, void* stream) {
+  if (pl.family == RenderFamily::Tiled) {
     // the (ray, depth)-tiled kernel: exact fp32, with or without rendered normals
-    const int nw = render2_waves_rt(k, 2 * CH, p.n_fine);
-#define HOLO_R2(ZFV, TRV, NWV) HOLO_LAUNCH((render2_kernel<CH, ZFV, TRV, NWV>), dim3((unsigned)n_wgs), dim3(64 * NWV), stream, p)
-    if (nrm) {
-      if (p.train.n_rays > 0) {
-        set_error("render: training-mode rendering returns no normals");
-        return -1;
-      }
+#define HOLO_R2(ZFV, TRV, NWV) HOLO_LAUNCH((render2_kernel<CH, ZFV, TRV, NWV>), grid, dim3(64 * NWV), stream, p)
+    const bool rule64 = pl.waves == render2_waves(CH, 64);  // else: the 8-wave form of a 12-wave configuration
+    if (pl.nrm) {
       if constexpr (CH <= 16) {
-        if (render2_waves_rt(k, 2 * CH, p.n_fine, 1) == 10) {
-          HOLO_LAUNCH((render2_kernel<CH, 64, false, 10, true>), dim3((unsigned)n_wgs), dim3(640), stream, p);
-        } else {
-          HOLO_LAUNCH((render2_kernel<CH, 64, false, 8, true>), dim3((unsigned)n_wgs), dim3(512), stream, p);
-        }
-      } else {
-        set_error("render: rendered normals of %d grid features run on the ray-per-column kernel", 2 * CH);
-        return -1;
+        if (pl.waves == 10) HOLO_LAUNCH((render2_kernel<CH, 64, false, 10, true>), grid, dim3(640), stream, p);
+        else HOLO_LAUNCH((render2_kernel<CH, 64, false, 8, true>), grid, dim3(512), stream, p);
       }
-    } else if (p.train.n_rays > 0) {
-      if (p.n_fine <= 64) {
-        if (nw == 12) HOLO_R2(64, true, (render2_waves<CH, 64>())); else HOLO_R2(64, true, 8);
+    } else if (pl.train) {
+      if (pl.z == 64) {
+        if (rule64) HOLO_R2(64, true, (render2_waves(CH, 64))); else HOLO_R2(64, true, 8);
       } else {
-        HOLO_R2(128, true, (render2_waves<CH, 128>()));
+        HOLO_R2(128, true, (render2_waves(CH, 128)));
       }
-    } else if (p.n_fine <= 64) {
-      if (nw == 12) HOLO_R2(64, false, (render2_waves<CH, 64>())); else HOLO_R2(64, false, 8);
+    } else if (pl.z == 64) {
+      if (rule64) HOLO_R2(64, false, (render2_waves(CH, 64))); else HOLO_R2(64, false, 8);
     } else {
-      HOLO_R2(128, false, (render2_waves<CH, 128>()));
+      HOLO_R2(128, false, (render2_waves(CH, 128)));
     }
 #undef HOLO_R2
-    return 0;
+    return;
   }
-  if (p.n_fine <= 64) {
-    if (nrm) {
-      HOLO_LAUNCH((render_kernel<CH, SP, true, 64>), dim3((unsigned)n_wgs), dim3(64 * render_waves<CH, 64, true>()), stream, p);
-    } else {
-      HOLO_LAUNCH((render_kernel<CH, SP, false, 64>), dim3((unsigned)n_wgs), dim3(64 * render_waves<CH, 64, false>()), stream, p);
-    }
+  if (pl.z == 64) {
+    if (pl.nrm) HOLO_LAUNCH((render_kernel<CH, SP, true, 64>), grid, dim3(64 * render_waves(CH, 64, true)), stream, p);
+    else HOLO_LAUNCH((render_kernel<CH, SP, false, 64>), grid, dim3(64 * render_waves(CH, 64, false)), stream, p);
   } else {
-    if (nrm) {
-      HOLO_LAUNCH((render_kernel<CH, SP, true, 128>), dim3((unsigned)n_wgs), dim3(64 * render_waves<CH, 128, true>()), stream, p);
-    } else {
-      HOLO_LAUNCH((render_kernel<CH, SP, false, 128>), dim3((unsigned)n_wgs), dim3(64 * render_waves<CH, 128, false>()), stream, p);
-    }
+    if (pl.nrm) HOLO_LAUNCH((render_kernel<CH, SP, true, 128>), grid, dim3(64 * render_waves(CH, 128, true)), stream, p);
+    else HOLO_LAUNCH((render_kernel<CH, SP, false, 128>), grid, dim3(64 * render_waves(CH, 128, false)), stream, p);
   }
-  return 0;
-}
-
-// rays of one wave tile: 4 on the (ray, depth)-tiled kernel, 32 on the ray-per-column kernel (the bf16x3 split arithmetic
-// and - development knob HOLO_RENDER_V1=1 - everything)
-int render_rays_per_tile(const Knobs& k, int C, int n_fine, int with_normals, int split3, int train) {
-  if (train) return 4;
-  if (split3) return 32;
-  // rendered normals: on the (ray, depth)-tiled kernel for the BASELINE / released shapes (round 5), else ray-per-column
-  if (with_normals && (C > 32 || n_fine > 64)) return 32;
-  return k.render_v1 ? 32 : 4;
-}
-
-// waves per workgroup of the persistent kernel for this configuration (the scratch has one slot per resident wave)
-int render_waves_per_wg(const Knobs& k, int C, int n_fine, int with_normals, int split3, int train) {
-  const bool z64 = n_fine <= 64;
-  if (render_rays_per_tile(k, C, n_fine, with_normals, split3, train) == 4) return render2_waves_rt(k, C, n_fine, with_normals);
-  if (C <= 32) {
-    if (with_normals) return z64 ? render_waves<16, 64, true>() : render_waves<16, 128, true>();
-    return z64 ? render_waves<16, 64, false>() : render_waves<16, 128, false>();
-  }
-  return z64 ? render_waves<32, 64, false>() : render_waves<32, 128, false>();
 }
 
 int density_field_launch(const float* grid_cl, const float* w_dens, int C, int64_t nvox, float* out, void* stream) {
@@ -1538,31 +1475,29 @@ int density_field_launch(const float* grid_cl, const float* w_dens, int C, int64
   return 0;
 }
 
-int render_launch(const RenderKernelParams& p, const Knobs& k, void* stream, int n_wgs) {
-  if (p.mlp.Hd != HD) {
-    set_error("render: dnet_hidden_dim must be %d (got %d)", HD, p.mlp.Hd);
+// Runs what render_plan chose (render_plan.h): refuses exactly what render_can_launch refuses, then switches on plan fields.
+int render_launch(const RenderKernelParams& p, const RenderPlan& pl, const RenderLaunch& l, void* stream) {
+  if (const char* why = render_refusal(pl)) {
+    set_error("%s (feature_size %d, %d + %d samples, hidden %d)", why, pl.feature_size, pl.n_coarse, pl.n_fine, pl.hidden);
     return -1;
   }
-  if (p.n_coarse < 3 || p.n_coarse > MAXC || p.n_fine < 2 || p.n_fine > 128) {
-    set_error("render: n_pts_coarse must be in [3,%d] and n_pts_fine in [2,128]", MAXC);
+  if (l.n_cams < 1 || l.n_cams > RenderKernelParams::MAX_CAMS || l.n_wgs < 1) {
+    set_error("render: %d cameras per launch (1..%d)", l.n_cams, RenderKernelParams::MAX_CAMS);
     return -1;
   }
-  if (p.n_cams < 1 || p.n_cams > RenderKernelParams::MAX_CAMS || n_wgs < 1) {
-    set_error("render: %d cameras per launch (1..%d)", p.n_cams, RenderKernelParams::MAX_CAMS);
-    return -1;
-  }
-  switch (p.C) {
+  const dim3 grid((unsigned)l.n_wgs);
+  switch (pl.ch) {
+    case 8:
+      render_launch_t<8, false>(p, pl, grid, stream);
+      break;
     case 16:
-      return render_launch_t<8, false>(p, k, stream, n_wgs);
-    case 32:
-      return p.split3 ? render_launch_t<16, true>(p, k, stream, n_wgs) : render_launch_t<16, false>(p, k, stream, n_wgs);
-    case 64:
-      return render_launch_t<32, false>(p, k, stream, n_wgs);
+      if (pl.sp) render_launch_t<16, true>(p, pl, grid, stream);
+      else render_launch_t<16, false>(p, pl, grid, stream);
+      break;
     default:
-      set_error("render: the fused renderer is built for feature_size 16, 32 or 64 (got %d; 128 input features are "
-                "supported by the stand-alone implicit function only)", p.C);
-      return -1;
+      render_launch_t<32, false>(p, pl, grid, stream);
   }
+  return 0;
 }
 
 int implicit_normals_launch(const ImplicitEvalParams& p, float* normals, void* stream) {

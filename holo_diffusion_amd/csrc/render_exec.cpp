@@ -196,23 +196,19 @@ static int ready(const char* entry, const HoloRenderer* r, Needs needs) {
   }
   return 0;
 }
-// The persistent render kernel runs ONE workgroup per CU; every wave of it is a worker with its own scratch slot
-// (64 coarse samples x 32 rays x float4 = 32 KB; the same again for the normals).  The scratch therefore depends on the
-// chip and the configuration only - not on the number of cameras or the image size.
-static int render_workgroups(const HoloRenderer* r) {
-  if (r->knobs.render_wgs > 0) return (int)r->knobs.render_wgs;  // development knob
-  return r->ctx->num_cus > 0 ? r->ctx->num_cus : 256;
+// The plan of this handle's frames (holo_render) or ray lists (holo_render_rays: exact fp32, no normals): kernel, waves,
+// workgroup cap, workspace layout (render_plan.h).  From the handle's own snapshot of the knobs, so the size query, the
+// binding and the launch see one value.
+static RenderPlan frame_plan(const HoloRenderer* r, bool normals) {
+  const HoloRenderCfg& c = r->cfg;
+  const bool split3 = r->split3 && c.feature_size == 32;
+  return render_plan({c.feature_size, c.n_pts_coarse, c.n_pts_fine, normals, split3, false, c.resol, c.dnet_hidden_dim},
+                     r->ctx->num_cus, r->knobs, EMU_BUILD);
 }
-static int split3_active(const HoloRenderer* r) { return (r->split3 && r->cfg.feature_size == 32) ? 1 : 0; }
-static size_t render_slots(const HoloRenderer* r, int with_normals) {
-  return (size_t)render_workgroups(r) *
-         (size_t)render_waves_per_wg(r->knobs, r->cfg.feature_size, r->cfg.n_pts_fine, with_normals, split3_active(r), 0);
-}
-// scratch of the ray-per-column kernel (rendered normals / split arithmetic): one 32 KB slot per resident wave; the
-// (ray, depth)-tiled kernel keeps every per-ray value in LDS and needs none
-static size_t val_ws_bytes(const HoloRenderer* r, int with_normals) {
-  if (render_rays_per_tile(r->knobs, r->cfg.feature_size, r->cfg.n_pts_fine, with_normals, split3_active(r), 0) == 4) return 256;
-  return render_slots(r, with_normals) * 64 * 32 * 4 * sizeof(float);
+static RenderPlan rays_plan(const HoloRenderer* r) {
+  const HoloRenderCfg& c = r->cfg;
+  return render_plan({c.feature_size, c.n_pts_coarse, c.n_pts_fine, false, false, true, c.resol, c.dnet_hidden_dim},
+                     r->ctx->num_cus, r->knobs, EMU_BUILD);
 }
 
 static void fill_cam(const HoloRenderCfg& c, const HoloCamera& cam, RenderKernelParams::Cam& pc) {
@@ -298,9 +294,6 @@ static int timeline_probe(RenderKernelParams& p, int nslots, int rays_per_tile, 
   return 0;
 }
 
-// the per-voxel scalars w_dens . F[v] of the rendered normals on the (ray, depth)-tiled kernel (behind everything else)
-static size_t dens_field_bytes(const HoloRenderer* r) { return align256((size_t)grid_voxels(r) * sizeof(float)); }
-
 extern "C" {
 
 int holo_renderer_set_compute_dtype(HoloRenderer* r, int dtype) {
@@ -315,7 +308,7 @@ int holo_renderer_set_compute_dtype(HoloRenderer* r, int dtype) {
 size_t holo_render_workspace_bytes(const HoloRenderer* r, int n_cameras, int with_normals) {
   (void)n_cameras;  // the scratch is per resident wave: any number of cameras renders out of the same buffer
   if (!r) return 0;
-  return grid_cl_bytes(r) + val_ws_bytes(r, with_normals) * (with_normals ? 2 : 1) + 256 + (with_normals ? dens_field_bytes(r) : 0);
+  return frame_plan(r, with_normals != 0).layout.total;
 }
 
 int holo_render(HoloRenderer* r, const float* grid, const HoloCamera* cameras, int n_cameras, float* images,
@@ -328,37 +321,36 @@ int holo_render(HoloRenderer* r, const float* grid, const HoloCamera* cameras, i
   int rc = ready("holo_render", r, COLOURS);
   if (rc) return rc;
   const bool want_nrm = normals != nullptr || normals_coarse != nullptr;
-  if (workspace_bytes < holo_render_workspace_bytes(r, n_cameras, want_nrm ? 1 : 0)) {
+  const RenderPlan plan = frame_plan(r, want_nrm);
+  const RenderLayout& L = plan.layout;
+  if (workspace_bytes < L.total) {
     set_error("holo_render: workspace too small");
     return HOLO_E_WORKSPACE;
   }
+  const bool have_coarse = images_coarse && depths_coarse && masks_coarse;
+  // Two statements of "normals" that disagree, kept as they were: workspace, tiles and workgroups follow want_nrm; the
+  // instantiation follows the outputs the launch can write, and normals_coarse without the coarse planes leaves both null.
+  // Such a call runs the kernel without normals on the geometry planned with them (no caller in this repository makes it).
+  const bool launch_nrm = normals != nullptr || (normals_coarse != nullptr && have_coarse);
+  const RenderPlan kernel_plan = launch_nrm == want_nrm ? plan : frame_plan(r, launch_nrm);
   const HoloRenderCfg& c = r->cfg;
-  const int C = c.feature_size;
+  auto at = [&](const RenderRegion& g) { return g.bytes ? (char*)workspace + g.off : nullptr; };
   const float* grid_cl = grid_to_channels_last(r, grid, workspace, stream);
   if (!grid_cl) return HOLO_E_INVALID;
   const int H = c.image_height, Wd = c.image_width;
   const int64_t npix = (int64_t)H * Wd;
   float* dens_field = nullptr;
-  if (want_nrm && render_rays_per_tile(r->knobs, C, c.n_pts_fine, 1, split3_active(r), 0) == 4) {
+  if (want_nrm && plan.family == RenderFamily::Tiled) {
     MlpParams mp;
     fill_mlp(r, mp);
-    dens_field = (float*)((char*)workspace + grid_cl_bytes(r) + val_ws_bytes(r, 1) * 2 + 256);
-    if (density_field_launch(grid_cl, mp.w_dens, C, grid_voxels(r), dens_field, stream)) return HOLO_E_INVALID;
+    dens_field = (float*)at(L.dens_field);
+    if (density_field_launch(grid_cl, mp.w_dens, c.feature_size, grid_voxels(r), dens_field, stream)) return HOLO_E_INVALID;
   }
-  // frames per launch: the launch parameters hold MAX_CAMS cameras; more cameras are split EVENLY over the launches
-  // (40 frames = 20 + 20, not 32 + 8: every launch then ends on an almost full round of wave tiles)
-  const int n_launches = (n_cameras + RenderKernelParams::MAX_CAMS - 1) / RenderKernelParams::MAX_CAMS;
-  const int G = (n_cameras + n_launches - 1) / n_launches;
-  const int n_wgs_max = render_workgroups(r);
-  const int sp3 = split3_active(r);
-  const int waves_per_wg = render_waves_per_wg(r->knobs, C, c.n_pts_fine, want_nrm ? 1 : 0, sp3, 0);
-  const int rays_per_tile = render_rays_per_tile(r->knobs, C, c.n_pts_fine, want_nrm ? 1 : 0, sp3, 0);
   const bool timeline = r->knobs.render_timeline;  // development probe (synchronises!)
-  const int xcd = r->knobs.render_xcd != KNOB_UNSET ? (int)r->knobs.render_xcd : EMU_BUILD ? 2 : 8;
-  for (int c0 = 0; c0 < n_cameras; c0 += G) {
-    const int ng = n_cameras - c0 < G ? n_cameras - c0 : G;
+  for (const RenderLaunch& l : render_launches(plan, n_cameras, npix)) {
+    const int c0 = l.cam0;
     RenderKernelParams p;
-    frame_params(r, grid_cl, cameras + c0, ng, p);
+    frame_params(r, grid_cl, cameras + c0, l.n_cams, p);
     if (Wd >= H) {
       p.range_x = (float)Wd / (float)H;
       p.range_y = 1.f;
@@ -366,38 +358,31 @@ int holo_render(HoloRenderer* r, const float* grid, const HoloCamera* cameras, i
       p.range_x = 1.f;
       p.range_y = (float)H / (float)Wd;
     }
-    p.split3 = sp3;
-    p.val_ws = (float*)((char*)workspace + grid_cl_bytes(r));
-    p.nrm_ws = want_nrm ? (float*)((char*)workspace + grid_cl_bytes(r) + val_ws_bytes(r, 1)) : nullptr;
+    p.split3 = plan.sp ? 1 : 0;
+    p.val_ws = (float*)at(L.val_ws);
+    p.nrm_ws = (float*)at(L.nrm_ws);
     p.dens_field = dens_field;
     p.rgb = images + (size_t)c0 * 3 * npix;  // the kernel adds the per-frame offsets
     p.depth = depths + (size_t)c0 * npix;
     p.mask = masks + (size_t)c0 * npix;
-    if (images_coarse && depths_coarse && masks_coarse) {
+    if (have_coarse) {
       p.rgb_c = images_coarse + (size_t)c0 * 3 * npix;
       p.depth_c = depths_coarse + (size_t)c0 * npix;
       p.mask_c = masks_coarse + (size_t)c0 * npix;
     }
     p.nrm = normals ? normals + (size_t)c0 * 3 * npix : nullptr;
     p.nrm_c = (normals_coarse && p.rgb_c) ? normals_coarse + (size_t)c0 * 3 * npix : nullptr;
-    p.n_tiles = (int64_t)ng * ((npix + rays_per_tile - 1) / rays_per_tile);
-    // no more workgroups than there is work for (a tiny launch must not stage the MLP on idle CUs)
-    int n_wgs = (int)((p.n_tiles + waves_per_wg - 1) / waves_per_wg);
-    if (n_wgs > n_wgs_max) n_wgs = n_wgs_max;
-    p.xcd = (xcd > 1 && n_wgs == n_wgs_max && n_wgs % xcd == 0) ? xcd : 1;
-    if (rays_per_tile == 4 && !r->knobs.render_static_tiles) {  // dynamic tile hand-out: the counters live in the (otherwise unused) scratch area
-      p.tile_ctr = (int*)p.val_ws;
+    p.n_tiles = l.n_tiles;
+    p.xcd = l.xcd;
+    if (l.dynamic) {  // every launch starts from zeroed counters
+      p.tile_ctr = (int*)at(L.tile_ctr);
       HIP_TRY(hipMemsetAsync(p.tile_ctr, 0, 8 * sizeof(int), (hipStream_t)stream));
-      // the end of every XCD range in single-ray items: about two rounds of them on the range's resident waves
-      // (HOLO_RENDER_TAIL=<quads per range>: development knob, 0 = off)
-      const int ranges = p.xcd > 1 ? p.xcd : 1;
-      p.tail_quads = EMU_BUILD ? 3 : (n_wgs * waves_per_wg / ranges) / 2;  // (the emulation's tiny frames: a few tail tiles in every test)
-      if (r->knobs.render_tail != KNOB_UNSET) p.tail_quads = (int)r->knobs.render_tail;
+      p.tail_quads = l.tail_quads;
     }
-    const int nslots = n_wgs * waves_per_wg;
-    if (timeline && (rc = timeline_probe(p, nslots, rays_per_tile, stream))) return rc;
-    if (render_launch(p, r->knobs, stream, n_wgs)) return HOLO_E_INVALID;
-    if (timeline && (rc = timeline_probe(p, nslots, rays_per_tile, stream))) return rc;
+    const int nslots = l.n_wgs * plan.waves;
+    if (timeline && (rc = timeline_probe(p, nslots, plan.rays_per_tile, stream))) return rc;
+    if (render_launch(p, kernel_plan, l, stream)) return HOLO_E_INVALID;
+    if (timeline && (rc = timeline_probe(p, nslots, plan.rays_per_tile, stream))) return rc;
   }
   return 0;
 }
@@ -496,16 +481,14 @@ struct RayOutputs {
 // grid_cl: the channels-last grid, already converted
 static int render_rays_impl(HoloRenderer* r, const float* grid_cl, const RayBatch& in, const RayOutputs& out, void* stream) {
   const HoloRenderCfg& c = r->cfg;
-  const int G = RenderKernelParams::MAX_CAMS, n_rays = in.n_rays;
-  const int waves_per_wg = render_waves_per_wg(r->knobs, c.feature_size, c.n_pts_fine, 0, 0, 1);
-  const int n_wgs_max = render_workgroups(r);
+  const int n_rays = in.n_rays;
+  const RenderPlan plan = rays_plan(r);
   const int64_t nm = (int64_t)c.n_pts_coarse + c.n_pts_fine;
   const bool noisy = in.density_noise_std > 0.f;
-  for (int c0 = 0; c0 < in.n_cameras; c0 += G) {
-    const int ng = in.n_cameras - c0 < G ? in.n_cameras - c0 : G;
+  for (const RenderLaunch& l : render_launches(plan, in.n_cameras, n_rays)) {
     RenderKernelParams p;
-    frame_params(r, grid_cl, in.cameras + c0, ng, p);
-    const int64_t o = (int64_t)c0 * n_rays;
+    frame_params(r, grid_cl, in.cameras + l.cam0, l.n_cams, p);
+    const int64_t o = (int64_t)l.cam0 * n_rays;
     p.train.n_rays = n_rays;
     p.train.xys = in.xys + o * 2;
     p.train.u_coarse = in.u_coarse ? in.u_coarse + o * c.n_pts_coarse : nullptr;
@@ -523,11 +506,9 @@ static int render_rays_impl(HoloRenderer* r, const float* grid_cl, const RayBatc
       p.depth_c = out.depths_coarse + o;
       p.mask_c = out.masks_coarse + o;
     }
-    p.n_tiles = (int64_t)ng * ((n_rays + 3) / 4);
-    int n_wgs = (int)((p.n_tiles + waves_per_wg - 1) / waves_per_wg);
-    if (n_wgs > n_wgs_max) n_wgs = n_wgs_max;
-    p.xcd = 1;
-    if (render_launch(p, r->knobs, stream, n_wgs)) return HOLO_E_INVALID;
+    p.n_tiles = l.n_tiles;
+    p.xcd = l.xcd;
+    if (render_launch(p, plan, l, stream)) return HOLO_E_INVALID;
   }
   return 0;
 }
@@ -544,7 +525,7 @@ int holo_render_rays(HoloRenderer* r, const float* grid, const HoloCamera* camer
     return HOLO_E_INVALID;
   }
   if (const int rc = ready("holo_render_rays", r, COLOURS_UP_TO_64)) return rc;
-  if (workspace_bytes < grid_cl_bytes(r) + 256) {
+  if (workspace_bytes < rays_plan(r).layout.total) {
     set_error("holo_render_rays: workspace too small (holo_render_workspace_bytes)");
     return HOLO_E_WORKSPACE;
   }
@@ -576,7 +557,9 @@ int holo_implicit_normals(HoloRenderer* r, const float* grid, const float* pts, 
 }
 
 // workspace of holo_density_lattice: the channels-last grid | S[v] = w_dens . F[v]
-size_t holo_density_lattice_workspace_bytes(const HoloRenderer* r) { return r ? grid_cl_bytes(r) + dens_field_bytes(r) : 0; }
+size_t holo_density_lattice_workspace_bytes(const HoloRenderer* r) {
+  return r ? grid_cl_bytes(r) + align256((size_t)grid_voxels(r) * sizeof(float)) : 0;
+}
 
 int holo_density_lattice(HoloRenderer* r, const float* grid, int m, float* field, void* workspace, size_t workspace_bytes,
                          void* stream) {

@@ -15,6 +15,7 @@
 #include "holo_kernels.h"
 #include "host_params.h"
 #include "mlp_folds.h"
+#include "viewpool_layout.h"
 
 using namespace holo;
 
@@ -24,11 +25,6 @@ static size_t maps_bytes(const HoloViewFeature* feats, int n_feats, int n_views,
   for (int k = 0; k < n_feats; ++k)
     b += align256((size_t)n_views * feats[k].height * feats[k].width * ((feats[k].channels + 3) / 4 * 4) * elem_bytes);
   return b;
-}
-static int sum_channels(const HoloViewFeature* feats, int n_feats) {
-  int c = 0;
-  for (int k = 0; k < n_feats; ++k) c += feats[k].channels;
-  return c;
 }
 // the channels-last copy of one map at ws (advanced behind it)
 static int stage_map(const HoloViewFeature& f, int n_views, ViewPoolParams::Feat& o, char*& ws, void* stream) {
@@ -52,22 +48,23 @@ static void fill_pool_cam(const HoloCamera& c, ViewPoolParams::Cam& o) {
   for (int j = 0; j < 3; ++j) o.centre[j] = -(c.T[0] * c.R[j * 3 + 0] + c.T[1] * c.R[j * 3 + 1] + c.T[2] * c.R[j * 3 + 2]);
 }
 
+static_assert(VIEW_POOL_MAX_FEATS == ViewPoolParams::MAX_FEATS, "viewpool_layout.h lays out the maps of ViewPoolParams");
+
 extern "C" {
 
 size_t holo_view_pool_workspace_bytes(const HoloViewPoolCfg* cfg, const HoloViewFeature* feats, int n_feats, int n_views) {
   if (!cfg || !feats || n_feats < 1 || n_views < 1) return 0;
-  return maps_bytes(feats, n_feats, n_views, sizeof(float)) +
-         align256((size_t)2 * sum_channels(feats, n_feats) * cfg->feature_size * sizeof(float)) + 256;  // + transposed mapper weight
+  return view_pool_layout(*cfg, feats, n_feats, n_views, false, 0, false).total;
 }
 
 }  // extern "C"
 
-// everything of holo_view_pool up to the launch: argument checks, channels-last copies of the feature maps and the transposed
-// mapper weight at the start of the workspace (ws is advanced behind them), cameras
+// everything of holo_view_pool up to the launch: argument checks, the layout L of the workspace (forward or backward),
+// channels-last copies of the feature maps and the transposed mapper weight at its head, cameras
 static int setup_view_pool(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloViewFeature* feats, int n_feats,
                            const HoloCamera* cameras, int n_views, const float* mapper_weight, const float* mapper_bias,
-                           void* workspace, size_t workspace_bytes, size_t workspace_need, void* stream, ViewPoolParams& p,
-                           char*& ws) {
+                           void* workspace, size_t workspace_bytes, bool backward, void* stream, ViewPoolParams& p,
+                           ViewPoolLayout& L) {
   if (!ctx || !cfg || !feats || !cameras || !mapper_weight || !workspace) {
     set_error("holo_view_pool: null argument");
     return HOLO_E_INVALID;
@@ -78,12 +75,13 @@ static int setup_view_pool(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloV
               ViewPoolParams::MAX_FEATS);
     return HOLO_E_UNSUPPORTED;
   }
-  if (workspace_bytes < workspace_need) {
+  L = view_pool_layout(*cfg, feats, n_feats, n_views, backward, ctx->num_cus, ctx->deterministic);
+  if (workspace_bytes < L.total) {
     set_error("holo_view_pool: workspace too small");
     return HOLO_E_WORKSPACE;
   }
   memset(&p, 0, sizeof p);
-  ws = (char*)workspace;
+  char* const base = (char*)workspace;
   int quad = 0, outc = 0;
   for (int k = 0; k < n_feats; ++k) {
     const HoloViewFeature& f = feats[k];
@@ -94,7 +92,8 @@ static int setup_view_pool(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloV
     ViewPoolParams::Feat& o = p.feat[k];
     o.quad0 = quad;
     o.out0 = outc;
-    if (stage_map(f, n_views, o, ws, stream)) return HOLO_E_INVALID;
+    char* at = base + L.map[k];
+    if (stage_map(f, n_views, o, at, stream)) return HOLO_E_INVALID;
     quad += o.Cp / 4;
     outc += 2 * o.C;
   }
@@ -106,9 +105,9 @@ static int setup_view_pool(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloV
   p.n_quads = quad;
   p.A = outc;
   p.F = cfg->feature_size;
-  if (transpose_small_launch(mapper_weight, (float*)ws, p.F, p.A, stream)) return HOLO_E_INVALID;  // (F, A) -> (A, F)
-  p.wt = (const float*)ws;
-  ws += align256((size_t)p.A * p.F * sizeof(float));
+  float* wt = (float*)(base + L.wt);
+  if (transpose_small_launch(mapper_weight, wt, p.F, p.A, stream)) return HOLO_E_INVALID;  // (F, A) -> (A, F)
+  p.wt = wt;
   p.bias = mapper_bias;
   p.n_views = n_views;
   for (int v = 0; v < n_views; ++v) fill_pool_cam(cameras[v], p.cams[v]);
@@ -130,32 +129,20 @@ int holo_view_pool(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloViewFeatu
     return HOLO_E_INVALID;
   }
   ViewPoolParams p;
-  char* ws;
+  ViewPoolLayout L;
   const int rc = setup_view_pool(ctx, cfg, feats, n_feats, cameras, n_views, mapper_weight, mapper_bias, workspace,
-                                 workspace_bytes, cfg && feats ? holo_view_pool_workspace_bytes(cfg, feats, n_feats, n_views) : 0,
-                                 stream, p, ws);
+                                 workspace_bytes, false, stream, p, L);
   if (rc) return rc;
   p.out = voxel_features;
   return view_pool_launch(p, stream) ? HOLO_E_INVALID : 0;
 }
 
-// ---- backward (kernels_viewpool_bwd.hip).  Workspace: the forward's part, then the zeroed channels-last gradient maps,
-//      then the per-workgroup partials of d weight / d bias.
-static int view_pool_bwd_wgs(HoloCtx* ctx, int resol) {
-  const int64_t groups = ((int64_t)resol * resol * resol + 15) / 16;
-  int64_t n = 4 * (int64_t)ctx->num_cus;  // (view_pool_bwd2_kernel: four resident workgroups per CU)
-  return (int)(groups < n ? groups : n);
-}
-
+// ---- backward (kernels_viewpool_bwd.hip).  Workspace (viewpool_layout.h): the forward's part, then the zeroed
+//      channels-last gradient maps, then the per-workgroup partials of d weight / d bias.
 size_t holo_view_pool_backward_workspace_bytes(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloViewFeature* feats,
                                                int n_feats, int n_views) {
   if (!ctx || !cfg || !feats || n_feats < 1 || n_views < 1) return 0;
-  size_t b = holo_view_pool_workspace_bytes(cfg, feats, n_feats, n_views) + maps_bytes(feats, n_feats, n_views, sizeof(float));
-  const int sumC = sum_channels(feats, n_feats);
-  b += align256((size_t)view_pool_bwd_wgs(ctx, cfg->resol) * ((size_t)2 * sumC * cfg->feature_size + cfg->feature_size) * sizeof(float));
-  // 64-bit fixed-point images of the gradient maps + one word per map (holo_ctx_set_deterministic)
-  if (ctx->deterministic) b += maps_bytes(feats, n_feats, n_views, sizeof(long long)) + 256;
-  return b + 256;
+  return view_pool_layout(*cfg, feats, n_feats, n_views, true, ctx->num_cus, ctx->deterministic).total;
 }
 
 int holo_view_pool_backward(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloViewFeature* feats, int n_feats,
@@ -169,40 +156,30 @@ int holo_view_pool_backward(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const Holo
   const Knobs knobs = Knobs::from_env();  // per call: this entry has no handle (holo_knobs.h, CALL)
   ViewPoolBwdParams b;
   memset(&b, 0, sizeof b);
-  char* ws;
+  ViewPoolLayout L;
   int rc = setup_view_pool(ctx, cfg, feats, n_feats, cameras, n_views, mapper_weight, mapper_bias, workspace, workspace_bytes,
-                           ctx && cfg && feats ? holo_view_pool_backward_workspace_bytes(ctx, cfg, feats, n_feats, n_views) : 0, stream,
-                           b.fwd, ws);
+                           true, stream, b.fwd, L);
   if (rc) return rc;
+  char* const base = (char*)workspace;
   b.gout = grad_voxel_features;
-  for (int k = 0; k < n_feats; ++k) {
-    const ViewPoolParams::Feat& f = b.fwd.feat[k];
-    const size_t bytes = (size_t)n_views * f.H * f.W * f.Cp * sizeof(float);
+  for (int k = 0; k < n_feats; ++k)
     if (grad_feats && grad_feats[k]) {
-      b.gfeat[k] = (float*)ws;
+      b.gfeat[k] = (float*)(base + L.gmap[k]);
       b.want_feats = 1;
-      if (hipMemsetAsync(ws, 0, bytes, (hipStream_t)stream) != hipSuccess) {
+      if (hipMemsetAsync(b.gfeat[k], 0, L.map_bytes[k], (hipStream_t)stream) != hipSuccess) {
         set_error("holo_view_pool_backward: hipMemsetAsync failed");
         return HOLO_E_HIP;
       }
     }
-    ws += align256(bytes);
-  }
-  const int n_wgs = view_pool_bwd_wgs(ctx, cfg->resol);
-  b.partial = (float*)ws;
-  ws += align256((size_t)n_wgs * ((size_t)b.fwd.A * b.fwd.F + b.fwd.F) * sizeof(float));
+  const int n_wgs = L.n_wgs;
+  b.partial = (float*)(base + L.partial);
   b.dW = grad_mapper_weight;
   b.dbias = grad_mapper_bias;
-  if (ctx->deterministic && b.want_feats) {
-    char* w0 = ws;
-    for (int k = 0; k < n_feats; ++k) {
-      const ViewPoolParams::Feat& f = b.fwd.feat[k];
-      if (b.gfeat[k]) b.gfix[k] = (long long*)ws;
-      ws += align256((size_t)n_views * f.H * f.W * f.Cp * sizeof(long long));
-    }
-    b.fix_max = (uint32_t*)ws;
-    ws += 256;
-    if (hipMemsetAsync(w0, 0, (size_t)(ws - w0), (hipStream_t)stream) != hipSuccess) {
+  if (L.fixed && b.want_feats) {
+    for (int k = 0; k < n_feats; ++k)
+      if (b.gfeat[k]) b.gfix[k] = (long long*)(base + L.gfix[k]);
+    b.fix_max = (uint32_t*)(base + L.fix_max);
+    if (hipMemsetAsync(base + L.gfix[0], 0, L.fix_end - L.gfix[0], (hipStream_t)stream) != hipSuccess) {
       set_error("holo_view_pool_backward: hipMemsetAsync failed");
       return HOLO_E_HIP;
     }

@@ -15,7 +15,7 @@ tests/test_gpu_training_mode.py (training mode): rgb / mask 2e-4 absolute, coars
 2e-4 (evaluation) / 1e-3 (training) of the far plane, rendered normals 5e-4; the backward criteria are those inside
 tests/test_gpu_render_backward.py::_render_rays_backward_case.  Every case prints its worst errors.
 
-Which kernel a case reaches (render_rays_per_tile / render_launch_t, kernels_render.hip; CH = feature_size / 2):
+Which kernel a case reaches (render_plan, render_plan.h / render_launch, kernels_render.hip; CH = feature_size / 2):
   training mode                                       render2_kernel<CH, 64 | 128, true, NW>
   f32_bf16x3 at 32 features                           render_kernel<16, true, NRM, 64 | 128>      (ray per column)
   normals with more than 32 features or 64 new samples  render_kernel<CH, false, true, 64 | 128>
@@ -175,7 +175,7 @@ def _scratch_bytes(model, R, C, normals=False):
 
 
 def _on_ray_per_column_kernel(model, R, C, normals=False):
-    """Which kernel family the handle's last configuration selects (render_rays_per_tile), read from its scratch size."""
+    """Which kernel family the handle's last configuration selects (render_plan), read from its scratch size."""
     nbytes = _scratch_bytes(model, R, C, normals)
     assert nbytes == 256 or (nbytes >= 32768 and nbytes % 32768 == 0), nbytes
     return nbytes != 256
@@ -209,7 +209,7 @@ def test_evaluation_mode_counts_exact_fp32(counts, C):
 def test_evaluation_mode_counts_ray_per_column_kernel(counts):
     """The same table at 32 features under compute_dtype = "f32_bf16x3": render_kernel<16, true, false, 64> up to 64 new
     samples and render_kernel<16, true, false, 128> above see a coarse count other than 64 (ZCAP rows, MAXC scratch rows).
-    That the split is active - 32 features, render_rays_per_tile returns 32 - shows in the handle's scratch: 32 KB per
+    That the split is active - 32 features, render_plan picks the ray-per-column family - shows in the handle's scratch: 32 KB per
     resident wave instead of none."""
     nc, nf = counts
     model = _eval_counts_case(nc, nf, 32, "f32_bf16x3")
@@ -339,7 +339,7 @@ NORMALS_CASES = [  # coarse, fine, features, compute, camera (of how many, index
 def test_rendered_normals_on_other_instantiations(nc, nf, C, compute, cam, seed):
     """render_normals = True on a 9 x 11 frame as tests/test_gpu_render.py::test_rendered_normals_vs_oracle checks it: the
     normals of both passes within 5e-4 of the oracle, the other planes within their bounds of the oracle and of the same
-    model rendered without normals.  Instantiations: see NORMALS_CASES; `C > 32 || n_fine > 64` (render_rays_per_tile) sends
+    model rendered without normals.  Instantiations: see NORMALS_CASES; render_instance_exists (more than 32 features or 64 new samples: no tiled normals) sends
     all but the last to the ray-per-column kernel, whose normals variants have only run at 64 coarse and at most 64 new
     samples, never under the split arithmetic; the last one is the (ray, depth)-tiled normals kernel (10 waves; 8 on the
     emulation) at a coarse count other than 64.
@@ -454,7 +454,7 @@ def test_xcd_tile_order(cu, monkeypatch):
     range.  The same rays either way: bit-equal, and both within the bounds of the oracle."""
     n_cams, waves = 4, 12
     tiles = n_cams * ((_SCHED["H"] * _SCHED["W"] + 3) // 4)
-    assert min(-(-tiles // waves), cu.n) == cu.n and cu.n % 8 == 0  # (render_exec.cpp: n_wgs == n_wgs_max && n_wgs % xcd == 0)
+    assert min(-(-tiles // waves), cu.n) == cu.n and cu.n % 8 == 0  # (render_launches: n_wgs == wg_cap && n_wgs % xcd == 0)
     base, inputs, _ = _sched_render(monkeypatch, {}, n_cams=n_cams, own=cu.own)
     ref = _sched_oracle(inputs, False, n_cams)
     _check(base, ref, "scheduling, 8 CUs, default XCD ranges")
@@ -602,3 +602,23 @@ def test_backward_at_the_ends(name, kw):
         assert claims["mask_min"] == 1.0 and claims["mask_c_min"] == 1.0
     else:
         assert claims["grid_max"] > 9.0
+
+
+# ==== E. more cameras than one launch holds =====================================================================================
+@pytest.mark.parametrize("C,compute", [(16, "f32"), (32, "f32_bf16x3")])
+def test_more_cameras_than_one_launch_holds(C, compute):
+    """33 cameras in ONE holo_render call: the launch parameters hold 32, so the call is two launches of 17 + 16 cameras
+    (render_launches, render_plan.h) - what the default fly-around of 40 poses does (20 + 20) and no other test reaches.
+    5 x 6 frames: eight 4-ray tiles per camera, the last one of two rays; 8^3 grid, (9, 7) samples.
+      16 features, exact fp32       the (ray, depth)-tiled kernel: the hand-out counters are zeroed again for the second launch;
+      32 features, f32_bf16x3       the ray-per-column kernel: the second launch reuses the per-wave scratch of the first.
+    Every plane of every camera finite and within EVAL_TOL of the oracle."""
+    R, H, W, nc, nf, n_cams = 8, 5, 6, 9, 7, 33
+    model, msd, rcfg = _eval_model(R, C, H, W, nc, nf, compute=compute)
+    grid, cams = _noise_grid(3101, C, R), _cameras(n_cams)
+    ref = _cached(("two_launches", C), lambda: _oracle_eval(grid, msd, cams, rcfg))
+    got = _render_eval(model, grid, cams)
+    assert got["rgb"].shape[0] == n_cams
+    _check(got, ref, f"{n_cams} cameras, two launches, C={C} {compute}")
+    assert _on_ray_per_column_kernel(model, R, C) == (compute == "f32_bf16x3")
+    assert float(ref["mask"][17:].max()) > 0.5  # (the second launch's frames are not empty)
