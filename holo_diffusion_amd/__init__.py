@@ -14,7 +14,7 @@ from .render import (  # noqa: F401
     RenderMLP, RendererOutput, ImplicitronRayBundle, AdaptiveRaySampler)
 from .model import HoloDiffusionModel  # noqa: F401
 from .cameras import PerspectiveCameras, look_at_view_transform, get_simple_360_camera_trajectory  # noqa: F401
-from .viewpool import ViewPooler, AngleWeightedReductionFeatureAggregator  # noqa: F401,E402
+from .viewpool import ViewPooler, AngleWeightedReductionFeatureAggregator, view_coverage  # noqa: F401,E402
 from . import checkpoint, flyaround_output, generate, mesh, model, render, runtime, viewpool  # noqa: F401,E402
 from .checkpoint import load_experiment  # noqa: F401,E402
 from .optim import HoloAdam  # noqa: F401,E402
@@ -22,4 +22,4 @@ from .guidance import PhotometricGuidance  # noqa: F401,E402
 
 __all__ = ["registry", "SimpleUnet3D", "Unet3DBase", "ImplicitronGaussianDiffusion", "HoloVoxelGridImplicitFunction",
            "HoloMultiPassEmissionAbsorptionRenderer", "HoloDiffusionModel", "RenderMLP", "EvaluationMode",
-           "PerspectiveCameras", "get_simple_360_camera_trajectory", "HoloAdam", "PhotometricGuidance"]
+           "PerspectiveCameras", "get_simple_360_camera_trajectory", "HoloAdam", "PhotometricGuidance", "view_coverage"]

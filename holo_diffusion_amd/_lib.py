@@ -138,6 +138,14 @@ SIGNATURES = {
     "holo_ddim_step_guided": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "holo_ddim_step_guided_philox": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp,
                                                C.c_uint32, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    "holo_ddpm_step_inpaint": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "holo_ddpm_step_inpaint_philox": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, _vp,
+                                                _vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp,
+                                                _vp]),
+    "holo_q_sample": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, _vp]),
+    "holo_q_sample_philox": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32, _vp, _vp,
+                                       C.c_int, _vp]),
     "holo_tanh": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
     "holo_clip": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_float, C.c_int64, _vp]),
     "holo_renderer_create": (C.c_int, [_vp, C.POINTER(HoloRenderCfg), C.POINTER(_vp)]),
@@ -167,6 +175,8 @@ SIGNATURES = {
     "holo_view_pool_workspace_bytes": (C.c_size_t, [C.POINTER(HoloViewPoolCfg), C.POINTER(HoloViewFeature), C.c_int, C.c_int]),
     "holo_view_pool": (C.c_int, [_vp, C.POINTER(HoloViewPoolCfg), C.POINTER(HoloViewFeature), C.c_int,
                                  C.POINTER(HoloCamera), C.c_int, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "holo_view_coverage": (C.c_int, [_vp, C.POINTER(HoloViewPoolCfg), C.POINTER(HoloCamera), C.c_int, C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32), _vp, _vp]),
     "holo_view_pool_backward_workspace_bytes": (C.c_size_t, [_vp, C.POINTER(HoloViewPoolCfg), C.POINTER(HoloViewFeature),
                                                              C.c_int, C.c_int]),
     "holo_view_pool_backward": (C.c_int, [_vp, C.POINTER(HoloViewPoolCfg), C.POINTER(HoloViewFeature), C.c_int,

@@ -121,6 +121,22 @@ int ddim_step_guided_philox_launch(const float* coefs, int batch, int64_t per, c
 // (include/holo_abi.h, holo_dpm_step)
 int dpm_step_launch(const float* coefs, int batch, int64_t per, const float* x_t, const float* model_out,
                     const float* hist1, const float* hist2, int clip, float* sample, float* pred_xstart, void* stream);
+// The masked (inpainting) DDPM step and forward noising (include/holo_abi.h, holo_ddpm_step_inpaint / holo_q_sample):
+// known_coefs / coefs are (batch, 2) fp32 rows {a, b}; mask is (batch, voxels); `ncdhw` says where an element's voxel is
+// (0: element / channels, 1: element % voxels); the Philox forms as above
+int ddpm_step_inpaint_launch(const float* tables, int T, const int64_t* timesteps, const float* known_coefs, int batch,
+                             int64_t per, int channels, int ncdhw, const float* x_t, const float* model_out,
+                             const float* x0_known, const float* mask, const float* noise, const float* noise_known,
+                             int clip, float* sample, float* pred_xstart, void* stream);
+int ddpm_step_inpaint_philox_launch(const float* tables, int T, const int64_t* timesteps, const float* known_coefs, int batch,
+                                    int64_t per, int channels, int ncdhw, const float* x_t, const float* model_out,
+                                    const float* x0_known, const float* mask, uint64_t seed, const uint32_t* row_streams,
+                                    uint64_t offset, int clip, float* sample, float* pred_xstart, float* noise_out,
+                                    float* noise_known_out, void* stream);
+int q_sample_launch(const float* coefs, int batch, int64_t per, const float* x, const float* noise, float* out, void* stream);
+int q_sample_philox_launch(const float* coefs, int batch, int64_t per, const float* x, uint64_t seed,
+                           const uint32_t* row_streams, uint64_t offset, float* out, float* noise_out, int ncdhw_channels,
+                           void* stream);
 int tanh_launch(const float* x, float* y, int64_t n, void* stream);
 // dst = src for a SMALL caller-provided tensor, read with system-scope loads (holo_ld_sys, holo_common.h)
 int copy_sys_launch(const float* src, float* dst, int64_t n, void* stream);
@@ -391,6 +407,15 @@ struct ViewPoolParams {
   float* out;         // (1, F, R, R, R)
 };
 int view_pool_launch(const ViewPoolParams& p, void* stream);
+// holo_view_coverage (include/holo_abi.h): per voxel centre the number of views that see it; H / W are each view's map size
+struct ViewCoverageParams {
+  ViewPoolParams::Cam cams[ViewPoolParams::MAX_VIEWS];
+  int H[ViewPoolParams::MAX_VIEWS], W[ViewPoolParams::MAX_VIEWS];
+  int n_views, R;
+  float half_extent, proj_eps;
+  float* out;  // (1, 1, R, R, R)
+};
+int view_coverage_launch(const ViewCoverageParams& p, void* stream);
 // backward of view_pool_kernel (kernels_viewpool_bwd.hip): fwd as for the forward launch (feature maps channels-last in the
 // workspace, transposed mapper weight), gout = d loss / d voxel_features (1, F, R, R, R)
 struct ViewPoolBwdParams {

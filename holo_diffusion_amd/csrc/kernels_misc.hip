@@ -614,6 +614,139 @@ __global__ __launch_bounds__(256) void ddpm_step_guided_philox_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
+// Masked (inpainting) DDPM update and forward noising (RePaint, Lugmayr et al. 2022; include/holo_abi.h).  Per element
+//   unk = ddpm_update ;  known = a*x0_known + b*e_k (q_lin: q_sample's arithmetic) ;  sample = m*known + (1 - m)*unk
+// every product and sum of the last two rounded, so that m == 0 gives ddpm_update's bits and m == 1 gives `known`'s.  The mask
+// is per VOXEL (batch, voxels).  MODE says how a thread finds the voxels of its four elements:
+//   MASK_QUAD     channels-last tensors, C a multiple of 4: four consecutive floats of one voxel
+//   MASK_QUAD_PL  NCDHW tensors, C a multiple of 4 (Philox only): the same quad from four channel planes (step_quad<true>)
+//   MASK_ELEMS    anything else: four consecutive floats in memory, each with its own voxel (`ncdhw`: element % voxels, else
+//                 element / C)
+// Philox draw domains, by a tag in counter slot 2 (the row, or 0 with per-row streams): none - the step's noise, the draw of
+// ddpm_step_philox_kernel; DRAW_KNOWN - e_k; DRAW_QSAMPLE - q_sample_philox_kernel.  No other kernel sets these bits.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t DRAW_KNOWN = 0x80000000u, DRAW_QSAMPLE = 0x40000000u;
+constexpr int MASK_QUAD = 0, MASK_QUAD_PL = 1, MASK_ELEMS = 2;
+
+__device__ __forceinline__ float q_lin(float a, float x, float b, float e) {
+#pragma clang fp contract(off)
+  return a * x + b * e;
+}
+__device__ __forceinline__ float4 q_lin4(float a, float4 x, float b, float4 e) {
+  return make_float4(q_lin(a, x.x, b, e.x), q_lin(a, x.y, b, e.y), q_lin(a, x.z, b, e.z), q_lin(a, x.w, b, e.w));
+}
+__device__ __forceinline__ float inpaint_blend(float m, float known, float unk) {
+#pragma clang fp contract(off)
+  const float om = 1.f - m;
+  return m * known + om * unk;
+}
+__device__ __forceinline__ float4 inpaint_blend4(float4 m, float4 known, float4 unk) {
+  return make_float4(inpaint_blend(m.x, known.x, unk.x), inpaint_blend(m.y, known.y, unk.y),
+                     inpaint_blend(m.z, known.z, unk.z), inpaint_blend(m.w, known.w, unk.w));
+}
+// the mask values of the four elements of thread `tid` of sample b (tid * 4 < per; channels divides per)
+template <int MODE>
+__device__ __forceinline__ float4 mask4(const float* __restrict__ mask, int b, int64_t tid, int64_t per, int channels,
+                                        int ncdhw) {
+  const int64_t V = per / channels;
+  const float* mb = mask + (int64_t)b * V;
+  if (MODE == MASK_QUAD || MODE == MASK_QUAD_PL) {
+    const float m = mb[MODE == MASK_QUAD ? tid * 4 / channels : tid % V];
+    return make_float4(m, m, m, m);
+  }
+  const int64_t i = tid * 4;
+  auto vox = [&](int64_t e) { return ncdhw ? e % V : e / channels; };
+  return make_float4(mb[vox(i)], mb[vox(i + 1)], mb[vox(i + 2)], mb[vox(i + 3)]);
+}
+__device__ __forceinline__ bool all4(float4 m, float v) { return m.x == v && m.y == v && m.z == v && m.w == v; }
+
+template <int MODE>
+__global__ __launch_bounds__(256) void ddpm_step_inpaint_kernel(
+    const float* __restrict__ tables, int T, const int64_t* __restrict__ timesteps, const float* __restrict__ known_coefs,
+    int64_t per, const float* __restrict__ x_t, const float* __restrict__ model_out, const float* __restrict__ x0_known,
+    const float* __restrict__ mask, const float* __restrict__ noise, const float* __restrict__ noise_known, int clip,
+    float* __restrict__ sample, float* __restrict__ pred, int channels, int ncdhw) {
+  const int b = blockIdx.y;
+  const DdpmCoefs c = ddpm_coefs(tables, T, timesteps, b);
+  const float ka = holo_ld_sys(known_coefs + b * 2), kb = holo_ld_sys(known_coefs + b * 2 + 1);  // (a small host table)
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid * 4 >= per) return;
+  const int64_t o = (int64_t)b * per + tid * 4;
+  const float4 x = ld4(x_t, o);
+  float4 m = ld4(model_out, o);
+  const float4 e = ld4(noise, o);
+  const float4 k0 = ld4(x0_known, o);
+  const float4 ek = noise_known ? ld4(noise_known, o) : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 mk = mask4<MODE>(mask, b, tid, per, channels, ncdhw);
+  if (clip) m = clamp4(m);
+  st4(sample, o, inpaint_blend4(mk, q_lin4(ka, k0, kb, ek), ddpm_update4(x, m, e, c)));
+  if (pred) st4(pred, o, m);
+}
+
+// The same update with both noises drawn in the kernel.  A draw that cannot reach the sample is skipped unless its output is
+// wanted (two Philox blocks and four Box-Muller pairs per thread would make the kernel ALU-bound): e_k where b == 0 or the
+// mask is 0 on the whole quad, e_u where it is 1 on the whole quad; the skipped noise enters as 0
+template <int MODE, bool ROWS>
+__global__ __launch_bounds__(256) void ddpm_step_inpaint_philox_kernel(
+    const float* __restrict__ tables, int T, const int64_t* __restrict__ timesteps, const float* __restrict__ known_coefs,
+    int64_t per, const float* __restrict__ x_t, const float* __restrict__ model_out, const float* __restrict__ x0_known,
+    const float* __restrict__ mask, uint32_t seed_lo, uint32_t seed_hi, uint32_t offset, int clip, float* __restrict__ sample,
+    float* __restrict__ pred, float* __restrict__ noise_out, float* __restrict__ noise_known_out, int channels, int ncdhw,
+    const uint32_t* __restrict__ row_streams) {
+  constexpr bool PL = MODE == MASK_QUAD_PL;
+  const int b = blockIdx.y;
+  const uint32_t key_hi = row_key<ROWS>(seed_hi, row_streams, b);
+  const DdpmCoefs c = ddpm_coefs(tables, T, timesteps, b);
+  const float ka = holo_ld_sys(known_coefs + b * 2), kb = holo_ld_sys(known_coefs + b * 2 + 1);
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid * 4 >= per) return;
+  const StepQuad q = step_quad<PL>(tid, b, per, channels);
+  const float4 x = ld4<PL>(x_t, q.o, q.es);
+  float4 m = ld4<PL>(model_out, q.o, q.es);
+  const float4 k0 = ld4<PL>(x0_known, q.o, q.es);
+  const float4 mk = mask4<MODE>(mask, b, tid, per, channels, ncdhw);
+  const uint32_t slot = ROWS ? 0u : (uint32_t)b;
+  float4 e = make_float4(0.f, 0.f, 0.f, 0.f), ek = e;
+  if (noise_out || !all4(mk, 1.f)) draw4(q.qd, slot, offset, seed_lo, key_hi, e);
+  if (noise_known_out || (kb != 0.f && !all4(mk, 0.f))) draw4(q.qd, slot | DRAW_KNOWN, offset, seed_lo, key_hi, ek);
+  if (clip) m = clamp4(m);
+  st4<PL>(sample, q.o, inpaint_blend4(mk, q_lin4(ka, k0, kb, ek), ddpm_update4(x, m, e, c)), q.es);
+  if (pred) st4<PL>(pred, q.o, m, q.es);
+  if (noise_out) st4<PL>(noise_out, q.o, e, q.es);
+  if (noise_known_out) st4<PL>(noise_known_out, q.o, ek, q.es);
+}
+
+// q_sample (gaussian_diffusion.py:189-204) and the composed forward jump of a resampling schedule: out = a*x + b*noise with
+// the row (a, b) of sample b; elementwise, any layout
+__global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ coefs, int64_t per,
+                                                       const float* __restrict__ x, const float* __restrict__ noise,
+                                                       float* __restrict__ out) {
+  const int b = blockIdx.y;
+  const float ka = holo_ld_sys(coefs + b * 2), kb = holo_ld_sys(coefs + b * 2 + 1);
+  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= per) return;
+  const int64_t o = (int64_t)b * per + i;
+  st4(out, o, q_lin4(ka, ld4(x, o), kb, ld4(noise, o)));
+}
+// the same with the noise drawn in the kernel, in the DRAW_QSAMPLE domain
+template <bool NCDHW, bool ROWS = false>
+__global__ __launch_bounds__(256) void q_sample_philox_kernel(const float* __restrict__ coefs, int64_t per,
+                                                              const float* __restrict__ x, uint32_t seed_lo,
+                                                              uint32_t seed_hi, uint32_t offset, float* __restrict__ out,
+                                                              float* __restrict__ noise_out, int channels,
+                                                              const uint32_t* __restrict__ row_streams) {
+  const int b = blockIdx.y;
+  const float ka = holo_ld_sys(coefs + b * 2), kb = holo_ld_sys(coefs + b * 2 + 1);
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid * 4 >= per) return;
+  const StepQuad q = step_quad<NCDHW>(tid, b, per, channels);
+  float4 e;
+  draw4(q.qd, (ROWS ? 0u : (uint32_t)b) | DRAW_QSAMPLE, offset, seed_lo, row_key<ROWS>(seed_hi, row_streams, b), e);
+  st4<NCDHW>(out, q.o, q_lin4(ka, ld4<NCDHW>(x, q.o, q.es), kb, e), q.es);
+  if (noise_out) st4<NCDHW>(noise_out, q.o, e, q.es);
+}
+
+// ---------------------------------------------------------------------------------------------
 // DDIM update (gaussian_diffusion.py:645-727: ddim_sample, and ddim_reverse_sample with c4 = 0).  Sample b reads its row
 // coefs[b*8 + 0..4] = (sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t], sqrt(abar_prev),
 // sqrt(1 - abar_prev - sigma^2), [t != 0] * sigma), computed on the host in float32 in the reference's order, so strided
@@ -1067,6 +1200,75 @@ int ddpm_step_guided_philox_launch(const float* tables, int T, const int64_t* ti
   HOLO_LAUNCH_PHILOX_STEP(ddpm_step_guided_philox_kernel, ncdhw_channels, row_streams, step_grid(per, batch), dim3(256),
                           stream, tables, T, timesteps, variances, per, x_t, model_out, grad, k0, k1, (uint32_t)offset,
                           clip, sample, pred_xstart, noise_out, ncdhw_channels, row_streams);
+  return 0;
+}
+
+// The masked steps (include/holo_abi.h): the mask is per voxel, so the launcher needs the channel count in every layout
+static bool inpaint_shape_ok(const char* name, int64_t per, int channels, int ncdhw) {
+  if (!step_shape_ok(name, per)) return false;
+  if (channels < 1 || per % channels || (ncdhw != 0 && ncdhw != 1)) {
+    set_error("%s: channels must be >= 1 and divide elems_per_sample, layout 0 (channels-last) or 1 (NCDHW)", name);
+    return false;
+  }
+  return true;
+}
+
+int ddpm_step_inpaint_launch(const float* tables, int T, const int64_t* timesteps, const float* known_coefs, int batch,
+                             int64_t per, int channels, int ncdhw, const float* x_t, const float* model_out,
+                             const float* x0_known, const float* mask, const float* noise, const float* noise_known,
+                             int clip, float* sample, float* pred_xstart, void* stream) {
+  if (!inpaint_shape_ok("ddpm_step_inpaint", per, channels, ncdhw)) return -1;
+  if (!ncdhw && !(channels & 3))
+    HOLO_LAUNCH(ddpm_step_inpaint_kernel<MASK_QUAD>, step_grid(per, batch), dim3(256), stream, tables, T, timesteps,
+                known_coefs, per, x_t, model_out, x0_known, mask, noise, noise_known, clip, sample, pred_xstart, channels,
+                ncdhw);
+  else
+    HOLO_LAUNCH(ddpm_step_inpaint_kernel<MASK_ELEMS>, step_grid(per, batch), dim3(256), stream, tables, T, timesteps,
+                known_coefs, per, x_t, model_out, x0_known, mask, noise, noise_known, clip, sample, pred_xstart, channels,
+                ncdhw);
+  return 0;
+}
+
+int ddpm_step_inpaint_philox_launch(const float* tables, int T, const int64_t* timesteps, const float* known_coefs, int batch,
+                                    int64_t per, int channels, int ncdhw, const float* x_t, const float* model_out,
+                                    const float* x0_known, const float* mask, uint64_t seed, const uint32_t* row_streams,
+                                    uint64_t offset, int clip, float* sample, float* pred_xstart, float* noise_out,
+                                    float* noise_known_out, void* stream) {
+  if (!inpaint_shape_ok("ddpm_step_inpaint_philox", per, channels, ncdhw)) return -1;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);  // (as ddpm_step_philox)
+  const int mode = (channels & 3) ? MASK_ELEMS : ncdhw ? MASK_QUAD_PL : MASK_QUAD;
+#define HOLO_LAUNCH_INPAINT(MODE)                                                                                          \
+  do {                                                                                                                     \
+    if (row_streams)                                                                                                       \
+      HOLO_LAUNCH((ddpm_step_inpaint_philox_kernel<MODE, true>), step_grid(per, batch), dim3(256), stream, tables, T,      \
+                  timesteps, known_coefs, per, x_t, model_out, x0_known, mask, k0, k1, (uint32_t)offset, clip, sample,     \
+                  pred_xstart, noise_out, noise_known_out, channels, ncdhw, row_streams);                                  \
+    else                                                                                                                   \
+      HOLO_LAUNCH((ddpm_step_inpaint_philox_kernel<MODE, false>), step_grid(per, batch), dim3(256), stream, tables, T,     \
+                  timesteps, known_coefs, per, x_t, model_out, x0_known, mask, k0, k1, (uint32_t)offset, clip, sample,     \
+                  pred_xstart, noise_out, noise_known_out, channels, ncdhw, row_streams);                                  \
+  } while (0)
+  if (mode == MASK_QUAD) HOLO_LAUNCH_INPAINT(MASK_QUAD);
+  else if (mode == MASK_QUAD_PL) HOLO_LAUNCH_INPAINT(MASK_QUAD_PL);
+  else HOLO_LAUNCH_INPAINT(MASK_ELEMS);
+#undef HOLO_LAUNCH_INPAINT
+  return 0;
+}
+
+int q_sample_launch(const float* coefs, int batch, int64_t per, const float* x, const float* noise, float* out,
+                    void* stream) {
+  if (!step_shape_ok("q_sample", per)) return -1;
+  HOLO_LAUNCH(q_sample_kernel, step_grid(per, batch), dim3(256), stream, coefs, per, x, noise, out);
+  return 0;
+}
+
+int q_sample_philox_launch(const float* coefs, int batch, int64_t per, const float* x, uint64_t seed,
+                           const uint32_t* row_streams, uint64_t offset, float* out, float* noise_out, int ncdhw_channels,
+                           void* stream) {
+  if (!step_shape_ok("q_sample_philox", per, ncdhw_channels)) return -1;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32);  // (as ddpm_step_philox)
+  HOLO_LAUNCH_PHILOX_STEP(q_sample_philox_kernel, ncdhw_channels, row_streams, step_grid(per, batch), dim3(256), stream,
+                          coefs, per, x, k0, k1, (uint32_t)offset, out, noise_out, ncdhw_channels, row_streams);
   return 0;
 }
 

@@ -171,12 +171,14 @@ constexpr int MM_NH = 128;  // MLPMeanFeatureAggregator.n_hidden
 
 struct ViewProj {
   float ndcx, ndcy, dx, dy, dz;
+  float z;  // camera-space depth before the |z| clamp
 };
 __device__ __forceinline__ ViewProj project_view(const ViewPoolParams::Cam& c, float px, float py, float pz, float eps) {
   ViewProj o;
   const float cx = px * c.Rm[0] + py * c.Rm[3] + pz * c.Rm[6] + c.T[0];  // X_cam = X R + T (row vectors)
   const float cy = px * c.Rm[1] + py * c.Rm[4] + pz * c.Rm[7] + c.T[1];
   float cz = px * c.Rm[2] + py * c.Rm[5] + pz * c.Rm[8] + c.T[2];
+  o.z = cz;
   if (fabsf(cz) < eps) cz = cz < 0.f ? -eps : eps;
   o.ndcx = c.focal[0] * cx / cz + c.pp[0];
   o.ndcy = c.focal[1] * cy / cz + c.pp[1];
@@ -187,11 +189,15 @@ __device__ __forceinline__ ViewProj project_view(const ViewPoolParams::Cam& c, f
   o.dz = dz / nrm;
   return o;
 }
-// one channel quad of a bilinear sample (ndc_grid_sample: grid = -ndc, longer side divided by the aspect ratio,
-// align_corners = False, zeros padding as tap weights)
+// the sampling coordinate of ndc_grid_sample on an H x W map: grid = -ndc, longer side divided by the aspect ratio
+__device__ __forceinline__ void grid_coord(int H, int W, float ndcx, float ndcy, float& gx, float& gy) {
+  gx = -ndcx, gy = -ndcy;
+  if (W >= H) gx /= (float)W / (float)H; else gy /= (float)H / (float)W;
+}
+// one channel quad of a bilinear sample at that coordinate (align_corners = False, zeros padding as tap weights)
 __device__ __forceinline__ float4 bilinear_quad(const ViewPoolParams::Feat& f, int vi, int cq, float ndcx, float ndcy) {
-  float gx = -ndcx, gy = -ndcy;
-  if (f.W >= f.H) gx /= (float)f.W / (float)f.H; else gy /= (float)f.H / (float)f.W;
+  float gx, gy;
+  grid_coord(f.H, f.W, ndcx, ndcy, gx, gy);
   const float ix = ((gx + 1.f) * (float)f.W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)f.H - 1.f) * 0.5f;
   const float fx0 = floorf(ix), fy0 = floorf(iy);
   const float tx = ix - fx0, ty = iy - fy0;
@@ -208,6 +214,28 @@ __device__ __forceinline__ float4 bilinear_quad(const ViewPoolParams::Feat& f, i
   const float w00 = wx0 * wy0, w01 = wx1 * wy0, w10 = wx0 * wy1, w11 = wx1 * wy1;
   return make_float4(t00.x * w00 + t01.x * w01 + t10.x * w10 + t11.x * w11, t00.y * w00 + t01.y * w01 + t10.y * w10 + t11.y * w11,
                      t00.z * w00 + t01.z * w01 + t10.z * w10 + t11.z * w11, t00.w * w00 + t01.w * w01 + t10.w * w10 + t11.w * w11);
+}
+
+// holo_view_coverage: per voxel centre the number of views whose frustum holds it - depth above the projection's clamp and
+// the sampling coordinate of the pooling kernels inside the map.  One thread per voxel; no occlusion test.
+__global__ __launch_bounds__(256) void view_coverage_kernel(ViewCoverageParams p) {
+  const int R = p.R;
+  const int64_t nvox = (int64_t)R * R * R;
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nvox) return;
+  const int x = (int)(v % R), y = (int)((v / R) % R), z = (int)(v / ((int64_t)R * R));
+  const float step = 2.0f / (float)(R - 1);  // voxel centre: as the pooling kernels
+  auto lin = [&](int i) { return (i < R / 2 ? -1.0f + step * (float)i : 1.0f - step * (float)(R - 1 - i)) * p.half_extent; };
+  const float px = lin(x), py = lin(y), pz = lin(z);
+  int seen = 0;
+#pragma unroll 1
+  for (int vi = 0; vi < p.n_views; ++vi) {
+    const ViewProj pr = project_view(p.cams[vi], px, py, pz, p.proj_eps);
+    float gx, gy;
+    grid_coord(p.H[vi], p.W[vi], pr.ndcx, pr.ndcy, gx, gy);
+    seen += (pr.z > p.proj_eps && fabsf(gx) <= 1.f && fabsf(gy) <= 1.f) ? 1 : 0;
+  }
+  p.out[v] = (float)seen;
 }
 
 template <int DH>  // DH = Dp / 2: the K slice of one lane half
@@ -424,6 +452,16 @@ int view_pool_launch(const ViewPoolParams& p, void* stream) {
   }
   const int64_t nvox = (int64_t)p.R * p.R * p.R;
   HOLO_LAUNCH(view_pool_kernel, dim3((unsigned)cdiv(nvox, 16)), dim3(256), stream, p);
+  return 0;
+}
+
+int view_coverage_launch(const ViewCoverageParams& p, void* stream) {
+  if (p.n_views < 1 || p.n_views > ViewPoolParams::MAX_VIEWS || p.R < 2 || !p.out) {
+    set_error("view_coverage: 1..%d views, resol >= 2", ViewPoolParams::MAX_VIEWS);
+    return -1;
+  }
+  const int64_t nvox = (int64_t)p.R * p.R * p.R;
+  HOLO_LAUNCH(view_coverage_kernel, dim3((unsigned)cdiv(nvox, 256)), dim3(256), stream, p);
   return 0;
 }
 

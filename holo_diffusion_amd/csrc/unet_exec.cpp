@@ -1069,6 +1069,54 @@ int holo_ddim_step_guided_philox(HoloCtx*, const float* coefs, int batch, int64_
   });
 }
 
+// masked (inpainting) DDPM step: the known part noised to level t - 1 blended with the DDPM update by a per-voxel mask
+int holo_ddpm_step_inpaint(HoloCtx*, const float* tables, int num_timesteps, const int64_t* timesteps,
+                           const float* known_coefs, int batch, int64_t elems_per_sample, int channels, int layout,
+                           const float* x_t, const float* model_out, const float* x0_known, const float* mask,
+                           const float* noise, const float* noise_known, int clip_denoised, float* sample,
+                           float* pred_xstart, void* stream) {
+  return step_entry("holo_ddpm_step_inpaint", tables && timesteps && known_coefs && x_t && model_out && x0_known && mask &&
+                                                  noise && sample && batch >= 1, [&] {
+    return ddpm_step_inpaint_launch(tables, num_timesteps, timesteps, known_coefs, batch, elems_per_sample, channels, layout,
+                                    x_t, model_out, x0_known, mask, noise, noise_known, clip_denoised, sample, pred_xstart,
+                                    stream);
+  });
+}
+
+// the same with both noises drawn in the kernel; row_streams as holo_ddpm_step_guided_philox
+int holo_ddpm_step_inpaint_philox(HoloCtx*, const float* tables, int num_timesteps, const int64_t* timesteps,
+                                  const float* known_coefs, int batch, int64_t elems_per_sample, int channels, int layout,
+                                  const float* x_t, const float* model_out, const float* x0_known, const float* mask,
+                                  uint64_t seed, uint64_t stream_offset, const uint32_t* row_streams, uint32_t timestep_index,
+                                  int clip_denoised, float* sample, float* pred_xstart, float* noise_out,
+                                  float* noise_known_out, void* stream) {
+  return step_entry("holo_ddpm_step_inpaint_philox",
+                    tables && timesteps && known_coefs && x_t && model_out && x0_known && mask && sample && batch >= 1, [&] {
+    return ddpm_step_inpaint_philox_launch(tables, num_timesteps, timesteps, known_coefs, batch, elems_per_sample, channels,
+                                           layout, x_t, model_out, x0_known, mask, seed, row_streams,
+                                           row_streams ? (uint64_t)timestep_index : stream_offset, clip_denoised, sample,
+                                           pred_xstart, noise_out, noise_known_out, stream);
+  });
+}
+
+// q_sample (gaussian_diffusion.py:189-204) on a row (a, b) per sample, and its form with the noise drawn in the kernel
+int holo_q_sample(HoloCtx*, const float* coefs, int batch, int64_t elems_per_sample, const float* x, const float* noise,
+                  float* out, void* stream) {
+  return step_entry("holo_q_sample", coefs && x && noise && out && batch >= 1 && elems_per_sample >= 4, [&] {
+    return q_sample_launch(coefs, batch, elems_per_sample, x, noise, out, stream);
+  });
+}
+
+int holo_q_sample_philox(HoloCtx*, const float* coefs, int batch, int64_t elems_per_sample, const float* x, uint64_t seed,
+                         uint64_t stream_offset, const uint32_t* row_streams, uint32_t timestep_index, float* out,
+                         float* noise_out, int ncdhw_channels, void* stream) {
+  return step_entry("holo_q_sample_philox", coefs && x && out && batch >= 1 && elems_per_sample >= 4, [&] {
+    return q_sample_philox_launch(coefs, batch, elems_per_sample, x, seed, row_streams,
+                                  row_streams ? (uint64_t)timestep_index : stream_offset, out, noise_out, ncdhw_channels,
+                                  stream);
+  });
+}
+
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream) {
   (void)ctx;
   return tanh_launch(x, y, n, stream);

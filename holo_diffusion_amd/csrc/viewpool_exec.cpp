@@ -137,6 +137,36 @@ int holo_view_pool(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloViewFeatu
   return view_pool_launch(p, stream) ? HOLO_E_INVALID : 0;
 }
 
+// how many source views see each voxel centre of holo_view_pool's grid (the frustum test only)
+int holo_view_coverage(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloCamera* cameras, int n_views,
+                       const int32_t* heights, const int32_t* widths, float* coverage, void* stream) {
+  if (!ctx || !cfg || !cameras || !heights || !widths || !coverage) {
+    set_error("holo_view_coverage: null argument");
+    return HOLO_E_INVALID;
+  }
+  if (n_views < 1 || n_views > ViewPoolParams::MAX_VIEWS || cfg->resol < 2) {
+    set_error("holo_view_coverage: 1..%d source views, resol >= 2", ViewPoolParams::MAX_VIEWS);
+    return HOLO_E_UNSUPPORTED;
+  }
+  ViewCoverageParams p;
+  memset(&p, 0, sizeof p);
+  for (int v = 0; v < n_views; ++v) {
+    if (heights[v] < 1 || widths[v] < 1) {
+      set_error("holo_view_coverage: view %d has an empty map", v);
+      return HOLO_E_INVALID;
+    }
+    fill_pool_cam(cameras[v], p.cams[v]);
+    p.H[v] = heights[v];
+    p.W[v] = widths[v];
+  }
+  p.n_views = n_views;
+  p.R = cfg->resol;
+  p.half_extent = grid_half_extent(cfg->resol, cfg->volume_extent);
+  p.proj_eps = cfg->projection_eps;
+  p.out = coverage;
+  return view_coverage_launch(p, stream) ? HOLO_E_INVALID : 0;
+}
+
 // ---- backward (kernels_viewpool_bwd.hip).  Workspace (viewpool_layout.h): the forward's part, then the zeroed
 //      channels-last gradient maps, then the per-workgroup partials of d weight / d bias.
 size_t holo_view_pool_backward_workspace_bytes(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloViewFeature* feats,

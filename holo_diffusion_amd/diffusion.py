@@ -32,6 +32,12 @@ Guidance (``cond_fn``; gaussian_diffusion.py:420-457, used at :502-505 and :669-
 reference's ``cond_fn(x, t, **model_kwargs)``, called once per step after the model, and hand its gradient to the guided forms
 of the two step kernels (``holo_ddpm_step_guided``: condition_mean; ``holo_ddim_step_guided``: condition_score on
 ``ddim_guided_coefs`` rows).  A guided chain runs NCDHW.  Without ``cond_fn`` every path is the unguided one above.
+
+Masked sampling (``repaint_schedule``, ``inpaint_sample_loop*``; build-side extension after RePaint, no reference counterpart):
+a per-voxel mask holds part of a clean grid fixed while the DDPM chain generates the rest, with resampling jumps, and
+``start_level`` starts the chain from a partly noised grid.  The step is ``holo_ddpm_step_inpaint`` (the DDPM update blended
+with the known grid noised one level down), a forward jump one ``holo_q_sample`` launch on ``jump_coefs`` rows; ``_chain``
+runs it through its ``pre`` hook.
 """
 from __future__ import annotations
 
@@ -341,7 +347,7 @@ class ImplicitronGaussianDiffusion(Configurable):
         return indices
 
     def _chain(self, model, shape, indices, rows, step, *, noise=None, noise_sampler=None, device=None, progress=False,
-               denoised_fn=None, model_kwargs=None, channels_last_ok=True, materialize=True) -> Iterator[dict]:
+               denoised_fn=None, model_kwargs=None, channels_last_ok=True, materialize=True, pre=None) -> Iterator[dict]:
         """The chain loop of every sampler.  Starts from ``noise``, else ``noise_sampler(T, shape, device)``, else
         ``torch.randn``; uploads the timesteps ``indices`` and the sampler's host ``rows`` ((steps, batch, 8), or None) once, so
         that no step talks to the host; then per step k calls the model and ``step(k, x, t, model_output, rows[k] on the
@@ -349,7 +355,8 @@ class ImplicitronGaussianDiffusion(Configurable):
         With ``channels_last_ok`` and a plain ``forward_channels_last`` model the chain stays in the library's channels-last
         layout - the step kernels are elementwise, hence layout-agnostic, and the model runs without its two layout passes -
         and the dicts are yielded in NCDHW all the same: contiguous copies, or with ``materialize`` off (the non-progressive
-        loops, which convert the last sample only) views of the channels-last buffers."""
+        loops, which convert the last sample only) views of the channels-last buffers.  ``pre(k, x, channels_last)`` (the
+        masked loop's forward jumps) may replace x in front of step k's model call; nothing is yielded for it."""
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
@@ -377,6 +384,8 @@ class ImplicitronGaussianDiffusion(Configurable):
         with torch.no_grad():
             for k in it:
                 t = ts_all[k]
+                if pre is not None:
+                    img = pre(k, img, use_cl)
                 if use_cl:
                     model_output = model.forward_channels_last(img, t)
                 else:
@@ -433,6 +442,227 @@ class ImplicitronGaussianDiffusion(Configurable):
             model_kwargs=model_kwargs, device=device, progress=progress, max_iter=max_iter, noise_sampler=noise_sampler,
             _materialize_every_step=return_all_samples), samples)
         return (final, samples) if return_all_samples else final
+
+    # ---- masked ancestral sampling (build-side extension; RePaint, Lugmayr et al. 2022, arXiv:2201.09865) -----------------
+    def repaint_schedule(self, jump_length: int = 10, n_resample: int = 1, start_level: Optional[int] = None) -> list:
+        """RePaint's jump schedule in LEVEL terms: level L runs from T (noise) to 0 (clean); ``("reverse", t)`` is the step at
+        timestep index t = L - 1 that takes level L to L - 1, ``("forward", L, L + j)`` the jump of ``jump_length`` back up.
+        Every level in ``range(0, T - j, j)`` is left ``n_resample - 1`` times by a forward jump, so ``n_resample == 1`` is the
+        plain descending list; the schedule ends with ``("reverse", 0)``.  ``start_level`` (None: T) starts the walk there and
+        drops the jumps that would go above it."""
+        T, j, r = self.num_timesteps, int(jump_length), int(n_resample)
+        if j < 1:
+            raise ValueError(f"jump_length must be >= 1, got {jump_length}")
+        if r < 1:
+            raise ValueError(f"n_resample must be >= 1, got {n_resample}")
+        top = T if start_level is None else int(start_level)
+        if not 1 <= top <= T:
+            raise ValueError(f"start_level must be in [1, {T}], got {start_level}")
+        jumps = {L: r - 1 for L in range(0, T - j, j) if L + j <= top}
+        ops, L = [], top
+        while L >= 1:
+            ops.append(("reverse", L - 1))
+            L -= 1
+            if jumps.get(L, 0) > 0:
+                jumps[L] -= 1
+                ops.append(("forward", L, L + j))
+                L += j
+        return ops
+
+    @staticmethod
+    def _ab_rows(a: np.ndarray, b: np.ndarray) -> torch.Tensor:
+        """(n, 2) float32 rows {a, b} of holo_ddpm_step_inpaint / holo_q_sample: float64 values cast once."""
+        return torch.from_numpy(np.stack([np.asarray(a, np.float64), np.asarray(b, np.float64)], axis=-1).astype(np.float32))
+
+    def known_coefs(self, t: Sequence[int]) -> torch.Tensor:
+        """The rows of the masked step's known part at timesteps ``t``: q_sample's coefficients one level down,
+        (sqrt(alphas_cumprod_prev[t]), sqrt(1 - alphas_cumprod_prev[t])) - (1, 0) at t = 0."""
+        t = np.asarray(t, dtype=np.int64).reshape(-1)
+        return self._ab_rows(np.sqrt(self.alphas_cumprod_prev[t]), np.sqrt(1.0 - self.alphas_cumprod_prev[t]))
+
+    def q_sample_coefs(self, t: Sequence[int]) -> torch.Tensor:
+        """The rows with which holo_q_sample is ``q_sample`` at timesteps ``t``."""
+        t = np.asarray(t, dtype=np.int64).reshape(-1)
+        return self._ab_rows(self.sqrt_alphas_cumprod[t], self.sqrt_one_minus_alphas_cumprod[t])
+
+    def jump_coefs(self, level_from: Sequence[int], level_to: Sequence[int]) -> torch.Tensor:
+        """The rows of the composed forward jump from level L to a higher level L': a = sqrt(abar[L' - 1] / abar[L - 1]) with
+        abar[-1] = 1, b = sqrt(1 - a^2), in float64 - in distribution the L' - L single q steps between the two levels."""
+        lo = np.asarray(level_from, dtype=np.int64).reshape(-1)
+        hi = np.asarray(level_to, dtype=np.int64).reshape(-1)
+        if lo.shape != hi.shape or (lo < 0).any() or (hi <= lo).any() or (hi > self.num_timesteps).any():
+            raise ValueError(f"invalid forward jump levels {lo.tolist()} -> {hi.tolist()}")
+        abar = np.append(self.alphas_cumprod, 1.0)  # (abar[-1] = 1: level 0 is the clean grid)
+        a = np.sqrt(abar[hi - 1] / abar[lo - 1])
+        return self._ab_rows(a, np.sqrt(1.0 - a * a))
+
+    def _philox_key(self, batch: int, device, timestep_index: int):
+        """(stream_offset, row_streams pointer | None, timestep_index) of the entries that take both stream forms, as
+        ``_launch_device_noise`` forms them; the table is returned too, to keep it alive over the launch."""
+        rows = self._row_streams(batch, device)
+        tidx = int(timestep_index) & 0xFFFFFFFF
+        offset = 0 if rows is not None else (int(self.device_noise_stream) << 32) | tidx
+        return (offset, None if rows is None else runtime.ptr(rows), tidx), rows
+
+    def _step_inpaint(self, x, t, model_output, known, mask, coefs_dev, noise, noise_known, clip_denoised, want_pred=True,
+                      channels_last: bool = False, timestep_index: Optional[int] = None, want_noise: bool = False):
+        """holo_ddpm_step_inpaint: (sample, pred_xstart | None) from the injected ``noise`` / ``noise_known`` (None where every
+        row is at t = 0).  With ``timestep_index`` instead: holo_ddpm_step_inpaint_philox, both noises drawn in the kernel,
+        (sample, pred_xstart | None, noise | None, noise_known | None).  ``known`` in x's layout (``channels_last``), ``mask``
+        (N, 1, R, R, R), ``coefs_dev`` the (N, 2) ``known_coefs`` rows on the device."""
+        runtime.require_device(x, "ImplicitronGaussianDiffusion")
+        L = runtime.lib()
+        dev = x.device
+        x, model_output, known, mask = x.contiguous(), model_output.contiguous(), known.contiguous(), mask.contiguous()
+        if known.shape != x.shape or mask.numel() * (x.shape[-1] if channels_last else x.shape[1]) != x.numel():
+            raise ValueError(f"known {tuple(known.shape)} / mask {tuple(mask.shape)} do not belong to x {tuple(x.shape)}")
+        sample = torch.empty_like(x)
+        pred = torch.empty_like(x) if want_pred else None
+        opt = lambda a: None if a is None else runtime.ptr(a)  # noqa: E731
+        head = (runtime.ctx(dev), *self._ddpm_head(x, t), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(),
+                int(x.shape[-1] if channels_last else x.shape[1]), 0 if channels_last else 1, runtime.ptr(x),
+                runtime.ptr(model_output), runtime.ptr(known), runtime.ptr(mask))
+        if timestep_index is None:
+            noise, noise_known = noise.contiguous(), None if noise_known is None else noise_known.contiguous()
+            _lib.check(L, L.holo_ddpm_step_inpaint(*head, runtime.ptr(noise), opt(noise_known), 1 if clip_denoised else 0,
+                                                   runtime.ptr(sample), opt(pred), runtime.stream_ptr(dev)),
+                       "holo_ddpm_step_inpaint")
+            return sample, pred
+        e_u = torch.empty_like(x) if want_noise else None
+        e_k = torch.empty_like(x) if want_noise else None
+        key, _rows = self._philox_key(x.shape[0], dev, timestep_index)
+        _lib.check(L, L.holo_ddpm_step_inpaint_philox(*head, int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, *key,
+                                                      1 if clip_denoised else 0, runtime.ptr(sample), opt(pred), opt(e_u),
+                                                      opt(e_k), runtime.stream_ptr(dev)), "holo_ddpm_step_inpaint_philox")
+        return sample, pred, e_u, e_k
+
+    def _q_sample_rows(self, x, coefs_dev, noise=None, channels_last: bool = False, timestep_index: Optional[int] = None,
+                       want_noise: bool = False):
+        """holo_q_sample: a*x + b*noise on the (N, 2) rows ``coefs_dev``.  With ``timestep_index`` instead of ``noise``:
+        holo_q_sample_philox, (out, noise | None), the draw keyed on the logical element as in ``_launch_device_noise``."""
+        runtime.require_device(x, "ImplicitronGaussianDiffusion")
+        L = runtime.lib()
+        dev = x.device
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        if timestep_index is None:
+            noise = noise.contiguous()
+            _lib.check(L, L.holo_q_sample(runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x),
+                                          runtime.ptr(noise), runtime.ptr(out), runtime.stream_ptr(dev)), "holo_q_sample")
+            return out
+        e = torch.empty_like(x) if want_noise else None
+        ncdhw = 0 if (channels_last or x.dim() < 3 or x.shape[1] % 4) else int(x.shape[1])
+        key, _rows = self._philox_key(x.shape[0], dev, timestep_index)
+        _lib.check(L, L.holo_q_sample_philox(runtime.ctx(dev), runtime.ptr(coefs_dev), x.shape[0], x[0].numel(), runtime.ptr(x),
+                                             int(self.device_noise_seed) & 0xFFFFFFFFFFFFFFFF, *key, runtime.ptr(out),
+                                             None if e is None else runtime.ptr(e), ncdhw, runtime.stream_ptr(dev)),
+                   "holo_q_sample_philox")
+        return out, e
+
+    def inpaint_sample_loop_progressive(self, model, shape, known, mask, jump_length=10, n_resample=1, start_level=None,
+                                        init=None, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                                        device=None, progress=False, noise_sampler=None, cond_fn=None, max_iter=None,
+                                        _materialize_every_step: bool = True) -> Iterator[dict]:
+        """Masked DDPM sampling: where ``mask`` ((N, 1, R, R, R) or (1, 1, R, R, R), float in [0, 1], broadcast over the
+        channels) is 1 the chain carries the clean grid ``known`` ((N | 1, C, R, R, R)) noised to the step's level, where it
+        is 0 the diffusion prior generates - one ``holo_ddpm_step_inpaint*`` launch per step beside the model call.  The walk
+        is ``repaint_schedule(jump_length, n_resample, start_level)``; a forward jump is ONE composed ``holo_q_sample*``
+        launch (``jump_coefs``).  ``start_level = L0 < T`` starts from ``q_sample(init, L0 - 1)`` (``init`` None: ``known``)
+        instead of from noise: editing.  One dict per reverse step, as ``p_sample_loop_progressive``.
+        Noise: with ``device_noise_seed`` (perf mode; the chain runs channels-last) everything is drawn in the kernels, at
+        Philox timestep index t + T * visit, visit = the earlier visits of timestep t in the schedule (forward jumps: of
+        their target level, the start counting as one) - a first visit draws what the unmasked chain draws.  Otherwise
+        ``noise_sampler(i, shape, device)``, else ``torch.randn_like``; i = t for a first visit's step noise (as
+        ``p_sample_loop`` asks) and t + (T + 1) * (3 * visit + d) for the known part's (d = 1), a jump's or the start's
+        (d = 2) and any revisit's noise; ``noise`` is x_T, or the start's noise when ``start_level < T``.
+        Refused (ValueError): ``cond_fn``, ``max_iter``, a mask of another shape, ``jump_length`` / ``n_resample`` < 1,
+        ``start_level`` outside [1, T].  Whether ``jump_length=10, n_resample=1`` (or RePaint's 10 / 10) suits a trained
+        checkpoint is not measured: there is no checkpoint to measure it on."""
+        if cond_fn is not None:
+            raise ValueError("cond_fn: guidance is not supported by the masked loops; use p_sample_loop or ddim_sample_loop")
+        if max_iter is not None:
+            raise ValueError("max_iter: the masked loops walk the full schedule; shorten the chain with start_level")
+        T = self.num_timesteps
+        ops = self.repaint_schedule(jump_length, n_resample, start_level)
+        shape = tuple(int(s) for s in shape)
+        B = shape[0]
+        if len(shape) != 5 or mask.dim() != 5 or tuple(mask.shape[1:]) != (1, *shape[2:]) or mask.shape[0] not in (1, B):
+            raise ValueError(f"mask must be ({B}, 1, R, R, R) or (1, 1, R, R, R) for shape {shape}, got {tuple(mask.shape)}")
+        if known.dim() != 5 or tuple(known.shape[1:]) != shape[1:] or known.shape[0] not in (1, B):
+            raise ValueError(f"known must be ({B} | 1, C, R, R, R) for shape {shape}, got {tuple(known.shape)}")
+        if device is None:
+            device = next(model.parameters()).device
+        known = known.to(device=device, dtype=torch.float32).expand(shape).contiguous()
+        mask = mask.to(device=device, dtype=torch.float32).expand(B, *mask.shape[1:]).contiguous()
+        device_noise = self._device_noise(noise_sampler)
+
+        # the reverse steps are the chain's steps; a forward jump rides in front of the step that follows it
+        indices, visits, jump_before, seen = [], [], {}, {}
+        top = ops[0][1] + 1
+        fwd_seen = {top: 1} if top < T else {}
+        for op in ops:
+            if op[0] == "reverse":
+                indices.append(op[1])
+                visits.append(seen.get(op[1], 0))
+                seen[op[1]] = visits[-1] + 1
+            else:
+                jump_before[len(indices)] = (len(jump_before), op[2] - 1, fwd_seen.get(op[2], 0))
+                fwd_seen[op[2]] = fwd_seen.get(op[2], 0) + 1
+        rows = torch.stack([self.known_coefs([t] * B) for t in indices])  # (steps, B, 2)
+        jumps = [op for op in ops if op[0] == "forward"]
+        jump_rows = torch.stack([self.jump_coefs([op[1]] * B, [op[2]] * B) for op in jumps]).to(device) if jumps else None
+
+        def draw(d, t, visit, like):
+            if noise_sampler is None:
+                return torch.randn_like(like)
+            i = t if (d == 0 and visit == 0) else t + (T + 1) * (3 * visit + d)
+            return noise_sampler(i, like.shape, like.device)
+
+        def forward_noised(x, coefs, t, visit, channels_last, given=None):
+            if given is not None:
+                return self._q_sample_rows(x, coefs, given)
+            if device_noise:
+                return self._q_sample_rows(x, coefs, channels_last=channels_last, timestep_index=t + T * visit)[0]
+            return self._q_sample_rows(x, coefs, draw(2, t, visit, x))
+
+        if top < T:  # editing: the chain starts from the partly noised grid
+            start = known if init is None else init.to(device=device, dtype=torch.float32).expand(shape)
+            noise = forward_noised(start.contiguous(), self.q_sample_coefs([top - 1] * B).to(device), top - 1, 0, False, noise)
+        known_by_layout = {False: known}
+
+        def pre(k, img, channels_last):
+            jump = jump_before.get(k)
+            if jump is None:
+                return img
+            return forward_noised(img, jump_rows[jump[0]], jump[1], jump[2], channels_last)
+
+        def step(k, img, t, model_output, coefs, channels_last):
+            kn = known_by_layout.get(channels_last)
+            if kn is None:  # (the one conversion of the known grid; the mask is per voxel: the same memory in both layouts)
+                kn = known_by_layout[channels_last] = known.permute(0, 2, 3, 4, 1).contiguous()
+            tt, visit = indices[k], visits[k]
+            if device_noise:  # ("noise": None - it never leaves the kernel)
+                sample, pred, eps, _ = self._step_inpaint(img, t, model_output, kn, mask, coefs, None, None, clip_denoised,
+                                                          channels_last=channels_last, timestep_index=tt + T * visit)
+            else:
+                eps = draw(0, tt, visit, img)
+                sample, pred = self._step_inpaint(img, t, model_output, kn, mask, coefs, eps,
+                                                  draw(1, tt, visit, img) if tt != 0 else None, clip_denoised)
+            return {"sample": sample, "pred_xstart": pred, "noise": eps}
+
+        yield from self._chain(model, shape, indices, rows, step, noise=noise, noise_sampler=noise_sampler, device=device,
+                               progress=progress, denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                               channels_last_ok=device_noise, materialize=_materialize_every_step, pre=pre)
+
+    def inpaint_sample_loop(self, model, shape, known, mask, jump_length=10, n_resample=1, start_level=None, init=None,
+                            noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None, device=None, progress=False,
+                            noise_sampler=None, cond_fn=None, max_iter=None):
+        """The last sample of ``inpaint_sample_loop_progressive``: ``known`` where the mask is 1, generated where it is 0."""
+        return self._last_sample(self.inpaint_sample_loop_progressive(
+            model, shape, known, mask, jump_length=jump_length, n_resample=n_resample, start_level=start_level, init=init,
+            noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, model_kwargs=model_kwargs, device=device,
+            progress=progress, noise_sampler=noise_sampler, cond_fn=cond_fn, max_iter=max_iter,
+            _materialize_every_step=False))
 
     # ---- DDIM (gaussian_diffusion.py:645-815) ----------------------------------------------------
     def ddim_schedule(self, ddim_steps: Optional[int] = None, timesteps: Optional[Sequence[int]] = None) -> List[int]:

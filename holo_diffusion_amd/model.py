@@ -193,6 +193,58 @@ class HoloDiffusionModel(ImplicitronModelBase, torch.nn.Module):
         assert self.net_3d_enabled and self.diffusion_enabled
         return self.diffusion.ddim_reverse_sample_loop(self.net_3d, voxel_features, ddim_steps=ddim_steps)
 
+    # ---- completion and editing (build-side extension: masked DDPM sampling, diffusion.inpaint_sample_loop) --------------
+    def complete_voxel_features(self, known: torch.Tensor, mask: torch.Tensor, jump_length: int = 10, n_resample: int = 1,
+                                batch_size: Optional[int] = None, **loop_kwargs) -> torch.Tensor:
+        """Holds ``known`` ((N | 1, C, R, R, R)) fixed where ``mask`` ((N | 1, 1, R, R, R), 1 = keep) is set and lets the
+        diffusion prior generate the rest: masked ancestral sampling with RePaint's resampling jumps (``jump_length``,
+        ``n_resample``; ``ImplicitronGaussianDiffusion.inpaint_sample_loop`` takes the remaining keywords).  At about the
+        cost of unconditional sampling: one elementwise kernel per step beside the denoiser.  ``batch_size`` chains run
+        together (default: the larger batch of ``known`` / ``mask``), each with its stream of ``device_noise_stream``.
+        Whether ``jump_length=10, n_resample=1`` suits a trained checkpoint is not measured (there is no checkpoint to
+        measure it on); RePaint itself uses 10 / 10 at ten times the cost."""
+        assert self.net_3d_enabled and self.diffusion_enabled
+        n = int(batch_size) if batch_size is not None else max(int(known.shape[0]), int(mask.shape[0]))
+        return self.diffusion.inpaint_sample_loop(model=self.net_3d, shape=self._shape(n), known=known, mask=mask,
+                                                  jump_length=jump_length, n_resample=n_resample, clip_denoised=True,
+                                                  progress=loop_kwargs.pop("progress", False), **loop_kwargs)
+
+    def edit_voxel_features(self, voxel_features: torch.Tensor, strength: float, mask: Optional[torch.Tensor] = None,
+                            jump_length: int = 10, n_resample: int = 1, **loop_kwargs) -> torch.Tensor:
+        """Regenerates ``voxel_features`` from a partly noised copy of itself: the chain starts at level
+        ``clamp(round(strength * T), 1, T)`` instead of at noise, so ``strength`` in (0, 1] trades fidelity for freedom
+        (1.0: from pure noise, the grid's values outside the mask play no part).  ``mask`` marks what to KEEP exactly; None
+        regenerates everything.  Keywords as ``complete_voxel_features``."""
+        assert self.net_3d_enabled and self.diffusion_enabled
+        T = self.diffusion.num_timesteps
+        start_level = min(max(int(round(float(strength) * T)), 1), T)
+        if mask is None:
+            mask = torch.zeros((1, 1) + tuple(voxel_features.shape[2:]), device=voxel_features.device)
+        return self.complete_voxel_features(voxel_features, mask, jump_length=jump_length, n_resample=n_resample,
+                                            start_level=start_level, init=voxel_features, **loop_kwargs)
+
+    @torch.no_grad()
+    def view_coverage(self, image_features: Dict[str, torch.Tensor], source_cameras) -> torch.Tensor:
+        """(1, 1, R, R, R): per voxel the number of source views whose frustum holds it (``viewpool.view_coverage``, on the
+        first feature map's height and width: the maps of one extractor share their aspect ratio)."""
+        from .viewpool import view_coverage
+        first = next(iter(image_features.values()))
+        return view_coverage(source_cameras, (int(first.shape[2]), int(first.shape[3])), self.resol, self.volume_extent,
+                             device=first.device)
+
+    @torch.no_grad()
+    def reconstruct_from_views(self, image_features: Dict[str, torch.Tensor], source_cameras, min_views: int = 1,
+                               **complete_kwargs) -> Dict[str, torch.Tensor]:
+        """A few posed source views -> a complete grid: pools the views (``pool_views_to_voxel_features``), keeps the voxels
+        at least ``min_views`` frustums hold (``view_coverage``; occluders are not tested, so ``min_views`` is the lever
+        for a stricter "observed") and completes the rest (``complete_voxel_features``, which takes the other keywords).
+        Returns ``{"voxel_features", "known", "mask", "coverage"}``."""
+        known = self.pool_views_to_voxel_features(image_features, source_cameras)
+        coverage = self.view_coverage(image_features, source_cameras)
+        mask = (coverage >= float(min_views)).to(torch.float32)
+        out = self.complete_voxel_features(known, mask, **complete_kwargs)
+        return {"voxel_features": out, "known": known, "mask": mask, "coverage": coverage}
+
     # ---- render (holo_diffusion_model.py:201-540, evaluation branch) ------------------------
     def _weights_epoch(self):
         net = self.net_3d

@@ -11,6 +11,7 @@ Reference interfaces mirrored (paths relative to /root/reference/holo_diffusion)
 All arithmetic - projection, bilinear gather, angle-weighted AVG/STD reduction, the mapper's Linear and the tanh - runs
 in ONE kernel (``holo_view_pool``, csrc/kernels_viewpool.hip); the classes here carry the configuration.  The image
 feature extractor (PyTorch3D's ResNetFeatureExtractor) is outside this path: its output dict is the input here.
+``view_coverage`` (build-side extension) tells which voxels of that grid the source views' frustums hold at all.
 """
 from __future__ import annotations
 
@@ -137,6 +138,36 @@ class MLPMeanFeatureAggregator(torch.nn.Module, FeatureAggregatorBase):
 
     def __del__(self):
         self.close()
+
+
+@torch.no_grad()
+def view_coverage(camera, image_sizes, resol: int, volume_extent: float, device=None,
+                  projection_eps: float = 1e-2) -> torch.Tensor:
+    """How many of the source views SEE each voxel centre of the grid ``pool_to_voxel_features`` fills, as a
+    (1, 1, R, R, R) float32 grid (``holo_view_coverage``, build-side extension).  A view sees a voxel when the voxel lies in
+    front of the camera (camera-space z above ``projection_eps``) and projects inside the view's feature map, i.e. where the
+    pooling kernel's bilinear sample reads the map and not its zero padding.  ``image_sizes``: one (height, width) for all
+    views or one per view - only the aspect ratio matters.  Visibility through occluders is NOT tested: a voxel behind the
+    object counts as seen by every view whose frustum holds it; a caller who wants a stricter notion of "observed" raises
+    the view count it asks for (``min_views`` of ``HoloDiffusionModel.reconstruct_from_views``)."""
+    from .render import _camera_array
+    cams = _camera_array(camera)
+    n = len(cams)
+    sizes = [tuple(int(v) for v in image_sizes)] * n if isinstance(image_sizes[0], (int, float)) else \
+        [tuple(int(v) for v in s) for s in image_sizes]
+    if len(sizes) != n or any(len(s) != 2 for s in sizes):
+        raise ValueError(f"image_sizes: one (height, width) or one per view ({n}), got {image_sizes}")
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    out = torch.empty(1, 1, resol, resol, resol, device=device)
+    runtime.require_device(out, "view_coverage")
+    cfg = _lib.HoloViewPoolCfg(int(resol), float(volume_extent), 1, 1.0, 0.0, float(projection_eps))
+    hs, ws = (C.c_int32 * n)(*[s[0] for s in sizes]), (C.c_int32 * n)(*[s[1] for s in sizes])
+    L = runtime.lib()
+    _lib.check(L, L.holo_view_coverage(runtime.ctx(device), C.byref(cfg), cams, n, hs, ws, runtime.ptr(out),
+                                       runtime.stream_ptr(device)), "holo_view_coverage")
+    return out
 
 
 class ViewPooler(Configurable, torch.nn.Module):

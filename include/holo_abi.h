@@ -356,6 +356,66 @@ int holo_ddim_step_guided_philox(HoloCtx* ctx, const float* coefs, int batch, in
                                  const uint32_t* row_streams, uint32_t timestep_index, int clip_denoised, float* sample,
                                  float* pred_xstart, float* noise_out, int ncdhw_channels, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Masked (inpainting) DDPM step and forward noising: masked ancestral sampling as in RePaint (Lugmayr et al. 2022,
+ * arXiv:2201.09865; build-side extension, no reference counterpart).  Where the mask is 1 the step returns the clean known
+ * grid noised to level t - 1, where it is 0 the plain DDPM update; resampling jumps go forward again with holo_q_sample.
+ *   tables, num_timesteps, timesteps : as holo_ddpm_step
+ *   known_coefs : (batch, 2) fp32 on the device, one row {a, b} per sample, cast on the host from the float64 schedule:
+ *                 a = sqrt(alphas_cumprod_prev[t]), b = sqrt(1 - alphas_cumprod_prev[t])   ({1, 0} at t = 0)
+ *   x0_known    : the clean known grid, x_t's shape and layout
+ *   mask        : (batch, 1, R, R, R) fp32 in [0, 1], one value per VOXEL, broadcast over the channels
+ *   channels, layout : where the voxel of an element is.  layout = HOLO_LAYOUT_CHANNELS_LAST: the tensors are
+ *                 (N, R, R, R, C), element i of a sample belongs to voxel i / C;  HOLO_LAYOUT_NCDHW: (N, C, R, R, R), voxel
+ *                 i % (elems_per_sample / C).  channels >= 1 divides elems_per_sample, which is a multiple of 4.
+ *   unk   = holo_ddpm_step's sample: fma(sigma, e_u, fma(c2, x_t, c1*pred)), pred = clip ? clamp(model_out, -1, 1) : model_out
+ *   known = a*x0_known + b*e_k       (products rounded, sum rounded, no fma: q_sample at t - 1, x0_known itself at t = 0)
+ *   sample = m*known + (1 - m)*unk   ((1 - m) formed once, products rounded, sum rounded, no fma)
+ *   pred_xstart = pred (may be null).  m == 0 gives holo_ddpm_step bit for bit, m == 1 gives `known` bit for bit (up to the
+ *   sign of a zero).  noise = e_u; noise_known = e_k, which may be null when every row has b == 0 (e_k = 0 is used).
+ * ------------------------------------------------------------------------------------------ */
+#define HOLO_LAYOUT_CHANNELS_LAST 0
+#define HOLO_LAYOUT_NCDHW 1
+int holo_ddpm_step_inpaint(HoloCtx* ctx, const float* tables, int num_timesteps, const int64_t* timesteps,
+                           const float* known_coefs, int batch, int64_t elems_per_sample, int channels, int layout,
+                           const float* x_t, const float* model_out, const float* x0_known, const float* mask,
+                           const float* noise, const float* noise_known, int clip_denoised, float* sample,
+                           float* pred_xstart, void* stream);
+
+/* The same step with both noises drawn inside the kernel.  Stream forms as holo_ddpm_step_guided_philox: row_streams null -
+ * keyed by stream_offset (timestep_index unused); non-null - one stream per row, keyed by row_streams[b] and timestep_index
+ * (stream_offset unused).  THE THREE DRAW DOMAINS of the Philox kernels, told apart by counter slot 2 (the sample index b
+ * in the offset form, 0 in the per-row form; batch < 2^30):
+ *   e_u (the step's noise)        slot 2 as it is: the draw of holo_ddpm_step_philox / _rows for the same (seed, stream,
+ *                                 timestep index, row, logical element) - an all-zero mask gives the unmasked chain's bits
+ *   e_k (the known part's noise)  slot 2 | 0x80000000
+ *   holo_q_sample_philox's noise  slot 2 | 0x40000000
+ * No other kernel sets either bit, so no (seed, stream, timestep, row) makes two domains share a Philox block.
+ * Quads: channels a multiple of 4 - the canonical channels-last quads of holo_ddpm_step_philox in either layout (one voxel
+ * per quad); otherwise the tensor's memory order is the key, as there with ncdhw_channels = 0, and a thread's four elements
+ * take the mask of their four voxels.  A draw that cannot reach the sample is skipped unless its output is asked for:
+ * e_k where b == 0 or the quad's mask values are all 0 (e_k = 0 enters `known`), e_u where they are all 1 (e_u = 0 enters
+ * `unk`); that changes at most the sign of a zero.  noise_out (e_u), noise_known_out (e_k) and pred_xstart may be null. */
+int holo_ddpm_step_inpaint_philox(HoloCtx* ctx, const float* tables, int num_timesteps, const int64_t* timesteps,
+                                  const float* known_coefs, int batch, int64_t elems_per_sample, int channels, int layout,
+                                  const float* x_t, const float* model_out, const float* x0_known, const float* mask,
+                                  uint64_t seed, uint64_t stream_offset, const uint32_t* row_streams, uint32_t timestep_index,
+                                  int clip_denoised, float* sample, float* pred_xstart, float* noise_out,
+                                  float* noise_known_out, void* stream);
+
+/* Forward noising: out = a*x + b*noise per sample, coefs (batch, 2) fp32 rows {a, b} on the device (products rounded, sum
+ * rounded, no fma).  With a = sqrt_alphas_cumprod[t], b = sqrt_one_minus_alphas_cumprod[t] it is q_sample
+ * (gaussian_diffusion.py:189-204) bit for bit; with a = sqrt(abar[L+j-1] / abar[L-1]), b = sqrt(1 - a^2) it is the jump
+ * from level L to L + j of a resampling schedule in one launch.  Elementwise: any layout. */
+int holo_q_sample(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x, const float* noise,
+                  float* out, void* stream);
+
+/* The same with the noise drawn inside the kernel, in the third draw domain (above); stream forms as above, quads and
+ * ncdhw_channels as holo_ddpm_step_philox.  noise_out may be null. */
+int holo_q_sample_philox(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x, uint64_t seed,
+                         uint64_t stream_offset, const uint32_t* row_streams, uint32_t timestep_index, float* out,
+                         float* noise_out, int ncdhw_channels, void* stream);
+
 /* Elementwise helpers on the path: torch.tanh (holo_diffusion_model.py:425) and
  * torch.clip(x,-1,1) (holo_diffusion_model.py:186). */
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream);
@@ -580,6 +640,15 @@ size_t holo_view_pool_workspace_bytes(const HoloViewPoolCfg* cfg, const HoloView
 int holo_view_pool(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloViewFeature* feats, int n_feats,
                    const HoloCamera* cameras, int n_views, const float* mapper_weight, const float* mapper_bias,
                    float* voxel_features, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Frustum coverage of the grid holo_view_pool fills (build-side extension): coverage (1, 1, R, R, R) fp32 = per voxel centre
+ * the number of source views that SEE it.  View v sees a voxel when its camera-space z is above cfg->projection_eps and the
+ * sampling coordinate of the pooling kernel, g = -ndc with the long side of the (heights[v], widths[v]) map divided by its
+ * aspect ratio (ndc_grid_sample), lies in [-1, 1]^2.  Only resol, volume_extent and projection_eps of cfg are read; the
+ * projection is the pooling kernels' own.  Occluders are not considered: a voxel behind the object counts as seen.
+ * cameras, heights, widths: host arrays of n_views entries (1..16). */
+int holo_view_coverage(HoloCtx* ctx, const HoloViewPoolCfg* cfg, const HoloCamera* cameras, int n_views,
+                       const int32_t* heights, const int32_t* widths, float* coverage, void* stream);
 
 /* Backward of holo_view_pool for a gradient on its output: what autograd computes in the reference behind
  * `tanh(pooled_feature_mapper(view_pooler(...)))` (holo_diffusion_model.py:358-373) when the encoder side is trained -
