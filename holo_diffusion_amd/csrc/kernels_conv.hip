@@ -25,8 +25,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "holo_common.h"
 #include "holo_kernels.h"
+#include "rowtile_silu.h"
 
 namespace holo {
 
@@ -36,7 +39,7 @@ namespace {
 
 constexpr int LDK = 36;
 
-__device__ __forceinline__ float silu_f(float v) { return v / (1.0f + __expf(-v)); }
+// (silu_f, the SiLU with the correctly rounded quotient: rowtile_silu.h)
 // bf16 paths: v_rcp_f32 (1 ulp) instead of the IEEE division sequence (the result is rounded to bf16 anyway)
 __device__ __forceinline__ float silu_fast(float v) { return v * holo_rcp(1.0f + __expf(-v)); }
 
@@ -1869,9 +1872,17 @@ __global__ __launch_bounds__(256 * TZ, 2 / TZ) void conv_halo_split_kernel(ConvP
 }
 
 // ---------------------------------------------------------------------------------------------
-// Row-tile kernel for the latency-bound launches: the deepest UNet levels (4^3 / 2^3 voxels: M = 64 rows, K up
-// to 27*1024, pure weight streaming: 28-56 MB of weights for ~1 GFLOP) and every 1x1x1 convolution (attention
-// qkv / proj_out, un-fused skip connections).  The design goal is round trips, not MFMA rate:
+// Row-tile kernel for the under-filled launches: the deepest UNet levels (4^3 / 2^3 voxels: M = 64 rows, K up
+// to 27*1024, pure weight streaming: 28-56 MB of weights for ~1 GFLOP), the stride-2 convolutions and every 1x1x1
+// convolution (attention qkv / proj_out, un-fused skip connections).
+// What bounds it, measured with phase stamps on wave 0 (profiles/rowtile_staging.txt; tools/rowtile_probe.cpp): NOT the
+// latency of a round trip - the waits are 1 - 7 % of a workgroup's cycles - but the work around the MFMAs.  Per staging
+// group the 256 MFMAs span ~8 700 cycles; issuing the group's requests (address arithmetic + ~64 vector-memory
+// instructions per wave through the CU's one address path) takes 11 000 - 16 000 and the activation + commit of a
+// GroupNorm + SiLU launch another ~10 000, and none of it overlaps the MFMAs of the same wave.  Hence the staging below:
+// one 32-bit offset per request through buffer resources, everything uniform over a launch decided at compile time, a
+// chunk's coefficients loaded once for both rows of a thread, the division of the SiLU shortened where that is exact, the
+// whole group requested in one batch.  The design goal is round trips and issue slots, not MFMA rate:
 //   * block tile 64 voxels x 64 Cout; each wave OWNS 16 output channels (v_mfma_f32_16x16x4_f32 over the four
 //     16-voxel tiles), so its weights go global -> registers with no LDS and no sharing;
 //   * K is walked in groups of SG = 8 chunks (256 channels of one tap).  For a group, ALL weights (16 x 16 B per
@@ -1881,15 +1892,95 @@ __global__ __launch_bounds__(256 * TZ, 2 / TZ) void conv_halo_split_kernel(ConvP
 //   * split-K over (tap, chunk) fills the chip with ~2 workgroups per CU; un-split launches produce the
 //     GroupNorm statistics of their output in the epilogue.
 // ---------------------------------------------------------------------------------------------
-constexpr int SGH = 4;  // activation chunks requested per staging batch (register budget)
+constexpr int SGH = 4;  // activation chunks per staging batch where a group is staged in two (register budget)
+
+// Activation and coefficient requests go through buffer resources - one per source of the virtual concat, one for the
+// coefficients: a request's address is one 32-bit byte offset (conv_launch: every source lies within 4 GB).  No address is
+// clamped: the offsets are formed modulo 2^32, so the offset of a padding tap either fails the resource's range check
+// (the request returns 0 without touching memory) or names some other element of the SAME tensor, and the padding mask
+// behind the activation zeroes the row either way.  A null source is a resource of zero records.
+#ifdef HOLO_EMU
+struct rt_rsrc {
+  const char* base;
+  unsigned n;
+};
+static inline rt_rsrc rt_make_rsrc(const void* p, unsigned nbytes) {
+  return rt_rsrc{reinterpret_cast<const char*>(p), p ? nbytes : 0u};
+}
+static inline float4 rt_ld16(const rt_rsrc& r, unsigned off) {
+  if ((uint64_t)off + 16u > r.n) return make_float4(0.f, 0.f, 0.f, 0.f);
+  return *reinterpret_cast<const float4*>(r.base + off);
+}
+static inline uint2 rt_ld8(const rt_rsrc& r, unsigned off) {
+  if ((uint64_t)off + 8u > r.n) return make_uint2(0u, 0u);
+  return *reinterpret_cast<const uint2*>(r.base + off);
+}
+#define RT_PROBE_BEGIN() ((void)0)
+#define RT_STAMP(k) ((void)0)
+#define RT_WAIT_VM(n) ((void)0)
+#define RT_PROBE_END() ((void)0)
+#else
+typedef __amdgpu_buffer_rsrc_t rt_rsrc;
+typedef unsigned rt_u4 __attribute__((ext_vector_type(4)));
+typedef unsigned rt_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ rt_rsrc rt_make_rsrc(const void* p, unsigned nbytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, p ? nbytes : 0u, 0x00020000);
+}
+__device__ __forceinline__ float4 rt_ld16(rt_rsrc r, unsigned off) {
+  const rt_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+}
+__device__ __forceinline__ uint2 rt_ld8(rt_rsrc r, unsigned off) {
+  const rt_u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0);
+  return make_uint2(v.x, v.y);
+}
+// Development probe (tools/rowtile_probe.cpp, -DHOLO_ROWTILE_PROBE): shader-clock stamps around the phases of a group, summed
+// per workgroup in scalar registers and written by thread 0 to p.dbg[workgroup][8]:
+//   0 prologue | 1 issue of the requests | 2 wait for the activations | 3 activation + commit | 4 barrier + the weights'
+//   arrival | 5 MFMAs | 6 epilogue | 7 groups staged.
+// The stamps fence the scheduler, so the build's SHARES are read, never its run time; production builds hold none.
+#ifdef HOLO_ROWTILE_PROBE
+#define RT_PROBE_BEGIN()                                                                   \
+  unsigned long long rt_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rt_last;                          \
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_last)::"memory")
+#define RT_STAMP(k)                                                                        \
+  do {                                                                                     \
+    __builtin_amdgcn_sched_barrier(0);                                                     \
+    unsigned long long t_;                                                                 \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");             \
+    __builtin_amdgcn_sched_barrier(0);                                                     \
+    rt_sum[k] += t_ - rt_last;                                                             \
+    rt_last = t_;                                                                          \
+  } while (0)
+#define RT_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+#define RT_PROBE_END()                                                                                      \
+  do {                                                                                                      \
+    if (p.dbg && threadIdx.x == 0) {                                                                        \
+      unsigned long long* d_ = p.dbg + (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8; \
+      for (int k_ = 0; k_ < 8; ++k_) d_[k_] = rt_sum[k_];                                                   \
+    }                                                                                                       \
+  } while (0)
+#else
+#define RT_PROBE_BEGIN() ((void)0)
+#define RT_STAMP(k) ((void)0)
+#define RT_WAIT_VM(n) ((void)0)
+#define RT_PROBE_END() ((void)0)
+#endif
+#endif
 
 // BF (bf16 compute mode): the activation rows are rounded to bf16 when they are committed to LDS (80-byte rows), the
 // weights are the bf16 plane packed for v_mfma_f32_16x16x32_bf16 (one 1 KB block per wave, tap and chunk), and one
 // MFMA per 16-voxel tile covers a chunk's 32 channels (eight fp32 ones otherwise).
-template <bool BF>
+// What is uniform over a launch is a template parameter of the staging: INBF (the sources are stored as bf16), ACTM (0: raw
+// input, 1: GroupNorm/FiLM affine, 2: affine + SiLU), UPS (nearest x2 upsampling on load), WHOLE (fp32 mode: no row tile of
+// the launch straddles two samples, so a chunk's coefficients serve both rows of a thread and a group is staged at once).
+template <bool BF, bool INBF, int ACTM, bool UPS, bool WHOLE>
 __global__ __launch_bounds__(256, 2) void conv_small_kernel(ConvParams p) {  // (bf16: 40 KB of LDS, three workgroups per CU)
   constexpr int RW = BF ? 20 : LDK;  // LDS words per activation row
+  constexpr unsigned ESZ = INBF ? 2u : 4u;  // bytes per stored input element
+  typedef typename std::conditional<INBF, uint2, float4>::type raw4;  // four input elements as they are stored
   __shared__ __attribute__((aligned(16))) float s_a[SG * SM_ROWS * RW];
+  RT_PROBE_BEGIN();
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
@@ -1912,14 +2003,23 @@ __global__ __launch_bounds__(256, 2) void conv_small_kernel(ConvParams p) {  // 
 
   const int q = tid & 7;
   const int r0 = tid >> 3;  // rows r0 and r0 + 32
+  // Per thread, ONCE: where its two rows sit.  A row keeps (a) the byte offset of its tap-0 voxel at the thread's channel
+  // quad in either source - a tap then adds a wave-uniform offset, a chunk its channel offset, both folded into one scalar
+  // per chunk (UPS: the halved coordinates are not linear in the tap, the row keeps (n, z, y, x) instead) - and (b) one bit
+  // per tap: the tap reads inside the input (no bit for a row beyond M).
   int an[2], az[2], ay[2], ax[2];
   bool av[2];
+  unsigned mrow[2], vmask[2], arow0[2], arow1[2], crow[2];
+  const int SD = UPS ? (p.ID >> 1) : p.ID;
+  const int SH = UPS ? (p.IH >> 1) : p.IH;
+  const int SW = UPS ? (p.IW >> 1) : p.IW;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int64_t m64 = m0 + r0 + 32 * j;
     av[j] = m64 < M;
-    // (32-bit: M < 2^31, conv_small_launch; a 64-bit division is ~150 instructions and this kernel is all fixed cost)
+    // (32-bit: M < 2^31, conv_plan; a 64-bit division is ~150 instructions)
     const unsigned m = av[j] ? (unsigned)m64 : 0u;
+    mrow[j] = m;
     int ow = (int)(m % (unsigned)p.OW);
     unsigned t = m / (unsigned)p.OW;
     int oh = (int)(t % (unsigned)p.OH);
@@ -1929,83 +2029,129 @@ __global__ __launch_bounds__(256, 2) void conv_small_kernel(ConvParams p) {  // 
     az[j] = od * p.stride - p.pad;
     ay[j] = oh * p.stride - p.pad;
     ax[j] = ow * p.stride - p.pad;
+    unsigned mz = 0, my = 0, mx = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      mz |= ((unsigned)(az[j] + k) < (unsigned)p.ID ? 1u : 0u) << k;
+      my |= ((unsigned)(ay[j] + k) < (unsigned)p.IH ? 1u : 0u) << k;
+      mx |= ((unsigned)(ax[j] + k) < (unsigned)p.IW ? 1u : 0u) << k;
+    }
+    unsigned m27 = 0;  // bit kd*9 + kh*3 + kw (a 1x1x1 convolution reads bit 0)
+#pragma unroll
+    for (int kd = 0; kd < 3; ++kd)
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh) m27 |= ((mz >> kd) & (my >> kh) & 1u) ? mx << (kd * 9 + kh * 3) : 0u;
+    vmask[j] = av[j] ? m27 : 0u;
+    const unsigned vb = (((unsigned)an[j] * (unsigned)SD + (unsigned)az[j]) * (unsigned)SH + (unsigned)ay[j]) * (unsigned)SW + (unsigned)ax[j];
+    arow0[j] = (vb * (unsigned)p.C0 + (unsigned)q * 4u) * ESZ;
+    arow1[j] = (vb * (unsigned)p.C1 + (unsigned)q * 4u) * ESZ;
+    crow[j] = (unsigned)an[j] * (unsigned)Cin * 8u + (unsigned)q * 32u;  // coef[n][c = 4q ..][2]
   }
-  const int SD = p.ups ? (p.ID >> 1) : p.ID;
-  const int SH = p.ups ? (p.IH >> 1) : p.IH;
-  const int SW = p.ups ? (p.IW >> 1) : p.IW;
+  // WHOLE: a tile's rows lie in ONE sample, whose coefficients serve both rows of the thread: the whole group is requested
+  // at once.  Launches with tiles that straddle samples (grids below 4^3 at batch above 1) load them per row, in two batches.
+  const unsigned ctile = ((unsigned)m0 / ((unsigned)p.OD * (unsigned)p.OH * (unsigned)p.OW)) * (unsigned)Cin * 8u + (unsigned)q * 32u;
+  const rt_rsrc rs0 = rt_make_rsrc(p.src0, (unsigned)p.N * (unsigned)SD * (unsigned)SH * (unsigned)SW * (unsigned)p.C0 * ESZ);
+  const rt_rsrc rs1 = rt_make_rsrc(p.src1, (unsigned)p.N * (unsigned)SD * (unsigned)SH * (unsigned)SW * (unsigned)p.C1 * ESZ);
+  const rt_rsrc rsc = rt_make_rsrc(p.coef, (unsigned)p.N * (unsigned)Cin * 8u);
 
-  float4 ra[SGH][2], rc01[SGH][2], rc23[SGH][2];
-  unsigned amask[SGH];
+  raw4 ra[SG][2];
+  float4 rc[SG][2][2];
   int g_tap[SG], g_cc[SG];  // (tap, channel chunk) of the group's chunks (wave-uniform; one division per group, not per chunk)
-  auto load_a = [&](int i, int slot) {
-    const int tap = g_tap[slot];
-    const int cc = g_cc[slot];
-    int kd = 0, kh = 0, kw = 0;
-    if (p.ksz == 3) {
-      kd = tap / 9;
-      kh = (tap - kd * 9) / 3;
-      kw = tap - kd * 9 - kh * 3;
-    }
-    int c = cc * BK + q * 4;
-    const bool cvalid = c < Cin;
-    if (!cvalid) c = 0;
-    const float* src = p.src0;
-    int Cs = p.C0, cs = c;
-    if (c >= p.C0) {
-      src = p.src1;
-      Cs = p.C1;
-      cs = c - p.C0;
-    }
-    amask[i] = 0;
+  unsigned g_off[SG];       // ... and what the chunk adds to a row's byte offset: its tap and its channels within the source
+  bool g_in1[SG];           // ... which is the second one of the concat
+  int g_k[SG];              // (UPS) kd | kh << 2 | kw << 4
+  // requests of the chunk in group slot `s` into register slot `i`; PR: the coefficients per row
+  auto request = [&](int i, int s, auto pr_c) {
+    constexpr bool PR = decltype(pr_c)::value;
+    const bool in1 = g_in1[s];
+    const rt_rsrc rs = in1 ? rs1 : rs0;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      int z = az[j] + kd, y = ay[j] + kh, x = ax[j] + kw;
-      const bool ok = av[j] && cvalid && z >= 0 && z < p.ID && y >= 0 && y < p.IH && x >= 0 && x < p.IW;
-      z = min(max(z, 0), p.ID - 1);
-      y = min(max(y, 0), p.IH - 1);
-      x = min(max(x, 0), p.IW - 1);
-      if (p.ups) {
-        z >>= 1;
-        y >>= 1;
-        x >>= 1;
+      unsigned vo;
+      if constexpr (UPS) {
+        const int z = (az[j] + (g_k[s] & 3)) >> 1, y = (ay[j] + ((g_k[s] >> 2) & 3)) >> 1, x = (ax[j] + (g_k[s] >> 4)) >> 1;
+        const unsigned vb = (((unsigned)an[j] * (unsigned)SD + (unsigned)z) * (unsigned)SH + (unsigned)y) * (unsigned)SW + (unsigned)x;
+        vo = (vb * (unsigned)(in1 ? p.C1 : p.C0) + (unsigned)q * 4u) * ESZ + g_off[s];
+      } else {
+        vo = (in1 ? arow1[j] : arow0[j]) + g_off[s];
       }
-      // unconditional load from a clamped address, masked afterwards (see the halo kernel)
-      ra[i][j] = ld_act4(src, ((((int64_t)an[j] * SD + z) * SH + y) * SW + x) * Cs + cs, p.in_bf16);
-      amask[i] |= (ok ? 1u : 0u) << j;
-      if (p.coef) {
-        const float4* cf = reinterpret_cast<const float4*>(p.coef + ((int64_t)an[j] * Cin + c) * 2);
-        rc01[i][j] = cf[0];
-        rc23[i][j] = cf[1];
+      if constexpr (INBF)
+        ra[i][j] = rt_ld8(rs, vo);
+      else
+        ra[i][j] = rt_ld16(rs, vo);
+    }
+    if constexpr (ACTM != 0) {
+      const unsigned co = (unsigned)g_cc[s] * (BK * 8u);
+#pragma unroll
+      for (int j = 0; j < (PR ? 2 : 1); ++j) {
+        rc[i][j][0] = rt_ld16(rsc, (PR ? crow[j] : ctile) + co);
+        rc[i][j][1] = rt_ld16(rsc, (PR ? crow[j] : ctile) + co + 16u);
       }
     }
   };
-  auto store_a = [&](int i, int slot, bool plain = false) {  // plain: a chunk of the fused skip (no GroupNorm / SiLU)
+  // activation and commit of register slot `i` to LDS slot `slot`; keep[j]: 1 or 0 - zero padding AFTER the activation;
+  // PLAIN: a chunk of the fused skip (no GroupNorm / SiLU)
+  auto commit = [&](int i, int slot, const float (&keep)[2], auto pr_c, auto plain_c) {
+    constexpr bool PR = decltype(pr_c)::value, PLAIN = decltype(plain_c)::value;
+    f32x2 lo[2], hi[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      float4 v = ra[i][j];
-      if (p.coef && !plain) {
-        v.x = v.x * rc01[i][j].x + rc01[i][j].y;
-        v.y = v.y * rc01[i][j].z + rc01[i][j].w;
-        v.z = v.z * rc23[i][j].x + rc23[i][j].y;
-        v.w = v.w * rc23[i][j].z + rc23[i][j].w;
-        if (p.act) {
-          v.x = silu_f(v.x);
-          v.y = silu_f(v.y);
-          v.z = silu_f(v.z);
-          v.w = silu_f(v.w);
+      if constexpr (INBF) {
+        const uint2 u = ra[i][j];
+        lo[j] = f32x2{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u)};
+        hi[j] = f32x2{__uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u)};
+      } else {
+        lo[j] = f32x2{ra[i][j].x, ra[i][j].y};
+        hi[j] = f32x2{ra[i][j].z, ra[i][j].w};
+      }
+      if constexpr (ACTM != 0 && !PLAIN) {
+        const float4 c01 = rc[i][PR ? j : 0][0], c23 = rc[i][PR ? j : 0][1];  // (a, b) of channels 0, 1 | 2, 3
+        lo[j] = pk_fma(lo[j], f32x2{c01.x, c01.z}, f32x2{c01.y, c01.w});
+        hi[j] = pk_fma(hi[j], f32x2{c23.x, c23.z}, f32x2{c23.y, c23.w});
+      }
+    }
+    if constexpr (ACTM == 2 && !PLAIN) {
+      // SiLU of the chunk's eight values.  Where EVERY lane's values lie in the range in which the scaling and the fix-up of
+      // the IEEE division do nothing (rowtile_silu.h), the wave runs the shortened division: the same quotients in 6
+      // instructions instead of 11.  Any other wave takes the whole sequence.
+      float amax = 0.f, amin = SILU_FAST_MAX;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        amax = fmaxf(fmaxf(fabsf(lo[j].x), fabsf(lo[j].y)), fmaxf(fmaxf(fabsf(hi[j].x), fabsf(hi[j].y)), amax));
+        amin = fminf(fminf(fabsf(lo[j].x), fabsf(lo[j].y)), fminf(fminf(fabsf(hi[j].x), fabsf(hi[j].y)), amin));
+      }
+      if (__builtin_expect(!__any(!(amax <= SILU_FAST_MAX && amin >= SILU_FAST_MIN)), 1)) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          lo[j] = f32x2{silu_div_core(lo[j].x, silu_den(lo[j].x)), silu_div_core(lo[j].y, silu_den(lo[j].y))};
+          hi[j] = f32x2{silu_div_core(hi[j].x, silu_den(hi[j].x)), silu_div_core(hi[j].y, silu_den(hi[j].y))};
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          lo[j] = f32x2{silu_f(lo[j].x), silu_f(lo[j].y)};
+          hi[j] = f32x2{silu_f(hi[j].x), silu_f(hi[j].y)};
         }
       }
-      const float keep = ((amask[i] >> j) & 1u) ? 1.f : 0.f;  // zero padding AFTER the activation
-      v.x *= keep;
-      v.y *= keep;
-      v.z *= keep;
-      v.w *= keep;
-      if (BF)
-        *reinterpret_cast<uint2*>(s_a + slot * (SM_ROWS * RW) + (r0 + 32 * j) * RW + q * 2) =
-            make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
-      else
-        *reinterpret_cast<float4*>(s_a + slot * (SM_ROWS * RW) + (r0 + 32 * j) * RW + q * 4) = v;
     }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const f32x2 k2 = f32x2{keep[j], keep[j]};
+      lo[j] = pk_mul(lo[j], k2);
+      hi[j] = pk_mul(hi[j], k2);
+      if constexpr (BF)
+        *reinterpret_cast<uint2*>(s_a + slot * (SM_ROWS * RW) + (r0 + 32 * j) * RW + q * 2) =
+            make_uint2(pack_bf16x2(lo[j].x, lo[j].y), pack_bf16x2(hi[j].x, hi[j].y));
+      else
+        *reinterpret_cast<float4*>(s_a + slot * (SM_ROWS * RW) + (r0 + 32 * j) * RW + q * 4) =
+            make_float4(lo[j].x, lo[j].y, hi[j].x, hi[j].y);
+    }
+  };
+  // the padding mask of the chunk in group slot `s`
+  auto keep_of = [&](int s, float (&keep)[2]) {
+    const bool cvalid = q * 4 + g_cc[s] * BK < Cin;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) keep[j] = (((vmask[j] >> g_tap[s]) & 1u) != 0u && cvalid) ? 1.f : 0.f;
   };
 
   f32x4 acc[4];
@@ -2016,7 +2162,10 @@ __global__ __launch_bounds__(256, 2) void conv_small_kernel(ConvParams p) {  // 
 
   const int wncc = p.CinP / BK, wnsl = p.CoutP >> 4;
   constexpr int WBLK = BF ? 256 : 512;  // words per (tap, chunk, 16-Cout slice) block
-  const float* w_lane = (BF ? reinterpret_cast<const float*>(p.w_bf) : p.w) + (int64_t)((n0 >> 4) + wave) * WBLK + lane * 4;  // 1 KB contiguous per wave instruction
+  // 1 KB contiguous per wave instruction: a wave-uniform base (a scalar pair) + the lane's 16 bytes
+  const int slice = (n0 >> 4) + HOLO_UNIFORM(wave);
+  const float* w_wave = (BF ? reinterpret_cast<const float*>(p.w_bf) : p.w) + (int64_t)slice * WBLK;
+  const unsigned w_lane = (unsigned)lane * 4u;
 
   // The main (tap, chunk) list and the skip's chunks behind it are walked by two loops over the same staging tile: the main
   // loop is exactly the kernel without a skip (a variant with both kinds in one load path lost 1.5 - 3 us on EVERY launch).
@@ -2027,6 +2176,19 @@ __global__ __launch_bounds__(256, 2) void conv_small_kernel(ConvParams p) {  // 
 #pragma unroll
     for (int i = 0; i < SG; ++i) {
       g_tap[i] = tap, g_cc[i] = cc;
+      {
+        int kd = 0, kh = 0, kw = 0;
+        if (p.ksz == 3) {
+          kd = tap / 9;
+          kh = (tap - kd * 9) / 3;
+          kw = tap - kd * 9 - kh * 3;
+        }
+        const bool in1 = p.src1 != nullptr && cc * BK >= p.C0;
+        const unsigned cs0 = (unsigned)(cc * BK - (in1 ? p.C0 : 0));
+        g_in1[i] = in1;
+        g_k[i] = kd | kh << 2 | kw << 4;
+        g_off[i] = UPS ? cs0 * ESZ : ((unsigned)((kd * p.IH + kh) * p.IW + kw) * (unsigned)(in1 ? p.C1 : p.C0) + cs0) * ESZ;
+      }
       if (g0 + i + 1 < kc_main_end) {  // (chunks beyond the split's last one repeat it: loaded, never used)
         ++cc;
         if (cc == ncc) cc = 0, ++tap;
@@ -2069,90 +2231,121 @@ __global__ __launch_bounds__(256, 2) void conv_small_kernel(ConvParams p) {  // 
       }
     }
   };
+  RT_STAMP(0);
   for (int g = kc_begin; g < kc_main_end; g += SG) {
     if (g != kc_begin) __syncthreads();  // previous group's activation tile fully consumed
     group_chunks(g);
-    // 1. the (small, L2-resident) activation rows of the whole group, in batches of SGH chunks (register budget).
+    // 1. the (small, L2-resident) activation rows and coefficients of the WHOLE group are requested at once where a tile lies
+    //    in one sample (fp32 mode), else in two batches of SGH chunks (register budget).
     //    (Requesting the next group's first batch under this group's MFMAs was tried: 96 more live registers, no gain - the
     //    second resident workgroup already fills the gap.)
-    // 2. every weight of the group is requested at once, right BEHIND the requests of the last activation batch and before
-    //    that batch is waited for: memory returns a wave's loads in order, so the activations are not held behind 28+ MB
-    //    of weights, the wait for them overlaps the weights' round trip (a 1x1x1 convolution is then ONE round trip plus
-    //    its MFMAs), and the chunk loop below starts on chunk 0 as soon as ITS weights are back while the rest streams.
+    // 2. every weight of the group is requested right BEHIND the requests of the last activation batch and before that
+    //    batch is waited for: memory returns a wave's loads in order, so the activations are not held behind 28+ MB of
+    //    weights, the wait for them overlaps the weights' round trip (a group is then ONE round trip plus its MFMAs), and
+    //    the chunk loop below starts on chunk 0 as soon as ITS weights are back while the rest streams.
     float4 bw[SG][2];
     auto load_w = [&]() {
 #pragma unroll
       for (int i = 0; i < SG; ++i) {
-        const float* wp = w_lane + (int64_t)(g_tap[i] * wncc + g_cc[i]) * wnsl * WBLK;
-        bw[i][0] = *reinterpret_cast<const float4*>(wp);
-        if (!BF) bw[i][1] = *reinterpret_cast<const float4*>(wp + 256);
+        const float* wp = w_wave + (int64_t)(g_tap[i] * wncc + g_cc[i]) * wnsl * WBLK;
+        bw[i][0] = *reinterpret_cast<const float4*>(wp + w_lane);
+        if (!BF) bw[i][1] = *reinterpret_cast<const float4*>(wp + w_lane + 256);
       }
     };
+    // one staging batch: the requests of NB chunks from group slot h on, the weights behind them (with_w), then activation
+    // and commit in request order
+    auto stage = [&](auto nb_c, auto pr_c, int h, bool with_w) {
+      constexpr int NB = decltype(nb_c)::value;
 #pragma unroll
-    for (int h = 0; h < SG; h += SGH) {
-      if (g + h < kc_main_end) {  // uniform
+      for (int i = 0; i < NB; ++i) request(i, h + i, pr_c);
+      if (with_w) load_w();
+      RT_STAMP(1);
+#ifdef HOLO_ROWTILE_PROBE
+      if (with_w)
+        RT_WAIT_VM(16);
+      else
+        RT_WAIT_VM(0);
+#endif
+      RT_STAMP(2);
 #pragma unroll
-        for (int i = 0; i < SGH; ++i) load_a(i, h + i);
-        if (!BF && (h + SGH >= SG || g + h + SGH >= kc_main_end)) load_w();  // (uniform) the group's last batch
-#pragma unroll
-        for (int i = 0; i < SGH; ++i) store_a(i, h + i);
+      for (int i = 0; i < NB; ++i) {
+        float keep[2];
+        keep_of(h + i, keep);
+        commit(i, h + i, keep, pr_c, std::false_type());
       }
+      RT_STAMP(3);
+    };
+    if constexpr (WHOLE) {
+      stage(std::integral_constant<int, SG>(), std::false_type(), 0, true);
+    } else {
+#pragma unroll
+      for (int h = 0; h < SG; h += SGH)
+        if (g + h < kc_main_end)  // uniform
+          stage(std::integral_constant<int, SGH>(), std::true_type(), h, !BF && (h + SGH >= SG || g + h + SGH >= kc_main_end));
     }
     // (bf16 mode: its launches are the large-M ones of the 128^3 net, throughput bound: the weights are requested behind the
     //  stores, which keeps the kernel at 3 - 4 workgroups per CU instead of 2)
     if (BF) load_w();
     __syncthreads();
+    RT_WAIT_VM(0);
+    RT_STAMP(4);
     mfma_group(g, kc_main_end, bw);
+    RT_STAMP(5);
+#ifdef HOLO_ROWTILE_PROBE
+    rt_sum[7] += 1;
+#endif
   }
   // ---- the fused skip's chunks (p.skip_w; launches without one never enter): raw block input at the row's OWN voxel (stride 1,
   //      same resolution: conv_launch), zero for rows / channels beyond the ends, its own packed weights
   if (!BF && kc_end > nmain) {  // (fp32 mode only: unet_plan.cpp fuses the skip below 8^3 there)
-    const float* skw_lane = (BF ? reinterpret_cast<const float*>(p.skip_w_bf) : p.skip_w) + (int64_t)((n0 >> 4) + wave) * WBLK + lane * 4;
+    const float* skw_wave = (BF ? reinterpret_cast<const float*>(p.skip_w_bf) : p.skip_w) + (int64_t)slice * WBLK;
     const int sk_lo = (kc_begin > nmain ? kc_begin : nmain) - nmain, sk_hi = kc_end - nmain;  // skip chunks [sk_lo, sk_hi)
+    // (the row's own voxel is row m of a source; the second source starts at a multiple of 32 channels: conv_launch)
+    const rt_rsrc rk0 = rt_make_rsrc(p.skip_src0, (unsigned)M * (unsigned)p.skip_C0 * ESZ);
+    const rt_rsrc rk1 = rt_make_rsrc(p.skip_src1, (unsigned)M * (unsigned)p.skip_C1 * ESZ);
+    unsigned krow0[2], krow1[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      krow0[j] = (mrow[j] * (unsigned)p.skip_C0 + (unsigned)q * 4u) * ESZ;
+      krow1[j] = (mrow[j] * (unsigned)p.skip_C1 + (unsigned)q * 4u) * ESZ;
+    }
     for (int g = sk_lo; g < sk_hi; g += SG) {
       if (g != sk_lo || kc_begin < nmain) __syncthreads();
       float4 bw[SG][2];
+      // the whole group in one batch (raw input: no coefficients to hold); chunks beyond the last repeat it
 #pragma unroll
-      for (int h = 0; h < SG; h += SGH) {
-        if (g + h < sk_hi) {  // uniform
+      for (int i = 0; i < SG; ++i) {
+        const int sc = g + i < sk_hi ? g + i : sk_hi - 1;
+        const bool in1 = p.skip_src1 != nullptr && sc * BK >= p.skip_C0;
+        const rt_rsrc rs = in1 ? rk1 : rk0;
+        const unsigned so = (unsigned)(sc * BK - (in1 ? p.skip_C0 : 0)) * ESZ;
 #pragma unroll
-          for (int i = 0; i < SGH; ++i) {
-            const int sc = g + h + i < sk_hi ? g + h + i : sk_hi - 1;
-            int c = sc * BK + q * 4;
-            const bool cvalid = c < SCin;
-            if (!cvalid) c = 0;
-            const float* src = p.skip_src0;
-            int Cs = p.skip_C0, cs = c;
-            if (c >= p.skip_C0) {
-              src = p.skip_src1;
-              Cs = p.skip_C1;
-              cs = c - p.skip_C0;
-            }
-            amask[i] = 0;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              const int z = az[j] + p.pad, y = ay[j] + p.pad, x = ax[j] + p.pad;
-              ra[i][j] = ld_act4(src, ((((int64_t)an[j] * p.OD + z) * p.OH + y) * p.OW + x) * Cs + cs, p.in_bf16);
-              amask[i] |= (av[j] && cvalid ? 1u : 0u) << j;
-            }
-          }
-          if (h + SGH >= SG || g + h + SGH >= sk_hi) {
-#pragma unroll
-            for (int i = 0; i < SG; ++i) {
-              const int sc = g + i < sk_hi ? g + i : sk_hi - 1;
-              const float* wp = skw_lane + (int64_t)sc * wnsl * WBLK;
-              bw[i][0] = *reinterpret_cast<const float4*>(wp);
-              if (!BF) bw[i][1] = *reinterpret_cast<const float4*>(wp + 256);
-            }
-          }
-#pragma unroll
-          for (int i = 0; i < SGH; ++i) store_a(i, h + i, true);
+        for (int j = 0; j < 2; ++j) {
+          if constexpr (INBF)
+            ra[i][j] = rt_ld8(rs, (in1 ? krow1[j] : krow0[j]) + so);
+          else
+            ra[i][j] = rt_ld16(rs, (in1 ? krow1[j] : krow0[j]) + so);
         }
+      }
+#pragma unroll
+      for (int i = 0; i < SG; ++i) {
+        const int sc = g + i < sk_hi ? g + i : sk_hi - 1;
+        const float* wp = skw_wave + (int64_t)sc * wnsl * WBLK;
+        bw[i][0] = *reinterpret_cast<const float4*>(wp + w_lane);
+        if (!BF) bw[i][1] = *reinterpret_cast<const float4*>(wp + w_lane + 256);
+      }
+#pragma unroll
+      for (int i = 0; i < SG; ++i) {
+        const int sc = g + i < sk_hi ? g + i : sk_hi - 1;
+        const bool cvalid = q * 4 + sc * BK < SCin;
+        const float keep[2] = {av[0] && cvalid ? 1.f : 0.f, av[1] && cvalid ? 1.f : 0.f};
+        commit(i, i, keep, std::false_type(), std::true_type());
       }
       __syncthreads();
       mfma_group(g, sk_hi, bw);
     }
   }
+  RT_STAMP(5);
 
   // ---- epilogue: col = lane&15 (Cout), row = 4*(lane>>4) + r inside each 16-voxel tile
   const int co = n0 + wave * 16 + lj;
@@ -2217,6 +2410,8 @@ __global__ __launch_bounds__(256, 2) void conv_small_kernel(ConvParams p) {  // 
       d[1] = (double)ssq;
     }
   }
+  RT_STAMP(6);
+  RT_PROBE_END();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2635,11 +2830,48 @@ int conv_launch(const ConvParams& p, void* stream) {
     }
     case ConvKernel::RowTile: {
       dim3 sgrid((unsigned)cdiv(M, SM_ROWS), (unsigned)cdiv(p.Cout, 64), (unsigned)p.nsplit);
-      if (p.bf16 == 1 && p.w_bf) {  // bf16 compute mode
-        HOLO_LAUNCH(conv_small_kernel<true>, sgrid, block, stream, p);
-      } else {
-        HOLO_LAUNCH(conv_small_kernel<false>, sgrid, block, stream, p);
+      // the kernel addresses its inputs with 32-bit byte offsets through buffer resources: every source within 4 GB, and a
+      // fused skip's second source starts at a chunk boundary
+      const int64_t esz = p.in_bf16 ? 2 : 4;
+      const int64_t in_vox = (int64_t)p.N * (p.ID >> (p.ups ? 1 : 0)) * (p.IH >> (p.ups ? 1 : 0)) * (p.IW >> (p.ups ? 1 : 0));
+      const int64_t lim = (int64_t)1 << 32;
+      if (in_vox * (p.C0 > p.C1 ? p.C0 : p.C1) * esz >= lim || (int64_t)p.N * Cin * 8 >= lim ||
+          (p.skip_w && (M * (p.skip_C0 > p.skip_C1 ? p.skip_C0 : p.skip_C1) * esz >= lim || (p.skip_src1 && p.skip_C0 % BK != 0)))) {
+        set_error("conv_launch: conv_small_kernel needs every input within 4 GB (%lld voxels of %d+%d channels) and a fused skip's "
+                  "second source at a multiple of 32 channels (%d+%d)", (long long)in_vox, p.C0, p.C1, p.skip_C0, p.skip_C1);
+        return -1;
       }
+      const int actm = p.coef ? (p.act ? 2 : 1) : 0;
+      // fp32 mode: a group is staged at once where no coefficients are held or no tile straddles two samples
+      const bool whole = actm == 0 || p.N == 1 || ((int64_t)p.OD * p.OH * p.OW) % SM_ROWS == 0;
+      // (BF_: bf16 compute mode, INBF_: bf16 storage of the sources, W0_: WHOLE of the raw-input instances, W_: of the others)
+#define HOLO_ROWTILE(BF_, INBF_, W0_, W_)                                                                     \
+  switch (actm * 2 + (p.ups ? 1 : 0)) {                                                                      \
+    case 0: HOLO_LAUNCH((conv_small_kernel<BF_, INBF_, 0, false, W0_>), sgrid, block, stream, p); break;     \
+    case 1: HOLO_LAUNCH((conv_small_kernel<BF_, INBF_, 0, true, W0_>), sgrid, block, stream, p); break;      \
+    case 2: HOLO_LAUNCH((conv_small_kernel<BF_, INBF_, 1, false, W_>), sgrid, block, stream, p); break;      \
+    case 3: HOLO_LAUNCH((conv_small_kernel<BF_, INBF_, 1, true, W_>), sgrid, block, stream, p); break;       \
+    case 4: HOLO_LAUNCH((conv_small_kernel<BF_, INBF_, 2, false, W_>), sgrid, block, stream, p); break;      \
+    default: HOLO_LAUNCH((conv_small_kernel<BF_, INBF_, 2, true, W_>), sgrid, block, stream, p); break;      \
+  }
+      if (p.bf16 == 1 && p.w_bf) {  // bf16 compute mode
+        if (p.in_bf16) {
+          HOLO_ROWTILE(true, true, false, false)
+        } else {
+          HOLO_ROWTILE(true, false, false, false)
+        }
+      } else if (p.in_bf16) {
+        if (whole) {
+          HOLO_ROWTILE(false, true, true, true)
+        } else {
+          HOLO_ROWTILE(false, true, true, false)
+        }
+      } else if (whole) {
+        HOLO_ROWTILE(false, false, true, true)
+      } else {
+        HOLO_ROWTILE(false, false, true, false)
+      }
+#undef HOLO_ROWTILE
       break;
     }
     case ConvKernel::Wino2:
