@@ -60,6 +60,19 @@ int holo_renderer_create(HoloCtx* ctx, const HoloRenderCfg* cfg, HoloRenderer** 
               "3<=n_pts_coarse<=64, n_pts_fine>=2, feature_dim a multiple of 4)");
     return HOLO_E_UNSUPPORTED;
   }
+  // the scene: each of these reaches the kernels as a divisor, a depth bound or a compositing constant
+  const char* bad = nullptr;
+  if (!(isfinite(cfg->volume_extent) && cfg->volume_extent > 0.f)) bad = "volume_extent must be finite and > 0";
+  else if (!(isfinite(cfg->scene_extent) && cfg->scene_extent > 0.f)) bad = "scene_extent must be finite and > 0";
+  else if (!(isfinite(cfg->background_opacity) && cfg->background_opacity >= 0.f)) bad = "background_opacity must be finite and >= 0";
+  for (int k = 0; k < 3 && !bad; ++k) {
+    if (!isfinite(cfg->scene_center[k])) bad = "scene_center must be finite";
+    else if (!isfinite(cfg->bg_color[k])) bad = "bg_color must be finite";
+  }
+  if (bad) {
+    set_error("holo_renderer_create: %s", bad);
+    return HOLO_E_INVALID;
+  }
   HoloRenderer* r = new HoloRenderer;
   r->ctx = ctx;
   r->cfg = *cfg;

@@ -525,7 +525,9 @@ class HoloMultiPassEmissionAbsorptionRenderer(BaseRenderer, torch.nn.Module):
 
     def _bg_color(self) -> Tuple[float, float, float]:
         bg = tuple(float(v) for v in self._raymarcher_args["bg_color"])
-        return bg * 3 if len(bg) == 1 else bg
+        if len(bg) not in (1, COLOUR_DIMS):  # (EmissionAbsorptionRaymarcher: one value for all channels, or one per channel)
+            raise ValueError(f"raymarcher bg_color must have 1 or {COLOUR_DIMS} entries, got {len(bg)}")
+        return bg * COLOUR_DIMS if len(bg) == 1 else bg
 
     def _ensure_handle(self, fn: HoloVoxelGridImplicitFunction, bundle: ImplicitronRayBundle, device) -> C.c_void_p:
         L = runtime.lib()

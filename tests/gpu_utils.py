@@ -1,4 +1,6 @@
 """Helpers shared by the -m gpu parity tests."""
+import dataclasses
+
 import torch
 
 import holo_diffusion_amd as hda
@@ -25,11 +27,17 @@ def make_unet(cfg: uo.UNetCfg, seed: int = 1234, compute_dtype: str = "f32"):
 
 
 def make_model(resol, feature_size, H, W, unet_args, diffusion_args=None, n_fine=64, seed=1234, mlp_seed=4321,
-               density_bias=0.0):
+               density_bias=0.0, model_kw=None, rcfg_kw=None):
+    """``model_kw``: further HoloDiffusionModel arguments (volume_extent, bg_color, raysampler_AdaptiveRaySampler_args, and
+    renderer_HoloMultiPassEmissionAbsorptionRenderer_args with its nested raymarcher_EmissionAbsorptionRaymarcher_args, merged
+    over the renderer arguments set here); ``rcfg_kw``: the same scene as fields of the oracle's RenderCfg."""
+    model_kw = dict(model_kw or {})
+    r_args = dict(n_pts_per_ray_fine_evaluation=n_fine)
+    r_args.update(model_kw.pop("renderer_HoloMultiPassEmissionAbsorptionRenderer_args", None) or {})
     model = hda.HoloDiffusionModel(
         resol=resol, feature_size=feature_size, render_image_width=W, render_image_height=H,
         net_3d_SimpleUnet3D_args=unet_args, diffusion_args=diffusion_args or {},
-        renderer_HoloMultiPassEmissionAbsorptionRenderer_args=dict(n_pts_per_ray_fine_evaluation=n_fine))
+        renderer_HoloMultiPassEmissionAbsorptionRenderer_args=r_args, **model_kw)
     ucfg = uo.UNetCfg(image_size=resol, in_channels=feature_size, out_channels=feature_size,
                       model_channels=unet_args["model_channels"], num_res_blocks=unet_args.get("num_res_blocks", 2),
                       channel_mult=tuple(unet_args["channel_mult"]),
@@ -37,6 +45,7 @@ def make_model(resol, feature_size, H, W, unet_args, diffusion_args=None, n_fine
                       num_heads=unet_args.get("num_heads", 2))
     usd = synth_state_dict(uo.unet_param_shapes(ucfg), seed)
     rcfg = ro.RenderCfg(resol=resol, feature_size=feature_size, image_height=H, image_width=W, n_pts_fine=n_fine)
+    rcfg = dataclasses.replace(rcfg, **(rcfg_kw or {}))
     msd = synth_state_dict(ro.render_mlp_param_shapes(rcfg), mlp_seed)
     msd["_density_net.mlp.3.0.bias"][-1] += density_bias
     full = {"net_3d._net." + k: v for k, v in usd.items()}
@@ -49,6 +58,12 @@ def make_model(resol, feature_size, H, W, unet_args, diffusion_args=None, n_fine
 def cam_dict(cams, i):
     return {"R": cams.R[i:i + 1].cpu(), "T": cams.T[i:i + 1].cpu(), "focal": cams.focal_xy()[i:i + 1].cpu(),
             "pp": cams.principal_point[i:i + 1].cpu()}
+
+
+def far_plane(cams, rcfg) -> float:
+    """The largest far depth bound (AdaptiveRaySampler: distance of the camera centre from the scene centre + scene extent)
+    over ``cams``: the scale of the depth tolerances."""
+    return max(ro.depth_bounds(cams.R[i].cpu(), cams.T[i].cpu(), rcfg)[1] for i in range(len(cams)))
 
 
 def rel_err(got: torch.Tensor, ref: torch.Tensor) -> float:

@@ -159,10 +159,10 @@ def test_refusals(gu):
     assert L.holo_density_lattice(h, null, 4, runtime.ptr(fd), runtime.ptr(lw), lw.numel(), st) < 0
 
 
-def make_implicit_function(gu, R, Cf, seed=811):
+def make_implicit_function(gu, R, Cf, seed=811, volume_extent=8.0):
     sd = gu.synth_state_dict(ro.render_mlp_param_shapes(ro.RenderCfg(resol=R, feature_size=Cf)), seed + Cf)
     sd["_density_net.mlp.3.0.bias"][-1] += 0.05
-    fn = hda.HoloVoxelGridImplicitFunction(resol=R, n_hidden=Cf, feature_dim=0)
+    fn = hda.HoloVoxelGridImplicitFunction(resol=R, n_hidden=Cf, feature_dim=0, volume_extent=volume_extent)
     fn.render_mlp.load_state_dict(sd)
     return fn.to(gu.DEV), sd
 
@@ -187,11 +187,17 @@ def test_density_lattice_equals_the_implicit_function(gu, Cf, m):
     implicit function interpolates the C features (8 terms each) and then takes the dot product.  With |F| <= 1 and weights
     that sum to <= 1, every one of the C + 8 + 8 roundings is at most 2^-24 of a partial sum bounded by A = sum|we| + |be|,
     on either side: |difference| <= (C + 16) * 2^-23 * A.  The LeakyReLU (slope <= 1) does not widen it."""
+    assert mesh.half_extent(8, 8.0) == 3.5
+    lattice_equals_the_implicit_function(gu, Cf, m, 8.0)
+
+
+def lattice_equals_the_implicit_function(gu, Cf, m, volume_extent):
+    """The body of test_density_lattice_equals_the_implicit_function (shared with tests/test_gpu_render_scene.py) on an
+    8^3 grid of ``volume_extent``."""
     R = 8
-    fn, sd = make_implicit_function(gu, R, Cf)
+    fn, sd = make_implicit_function(gu, R, Cf, volume_extent=volume_extent)
     grid = torch.tanh(torch.from_numpy(np_noise(60 + Cf, (1, Cf, R, R, R)))).to(gu.DEV)
-    h = mesh.half_extent(R, 8.0)
-    assert h == 3.5
+    h = mesh.half_extent(R, volume_extent)
     field = mesh.density_lattice(fn, grid, m)
     assert tuple(field.shape) == (m, m, m)
     ax = ref.lattice_axis(h, m)

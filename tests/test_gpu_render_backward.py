@@ -43,19 +43,25 @@ CASES = [(12, 10, 16, 8, 3, 13, "all")] if EMU else [(12, 10, 16, 8, 3, 13, "all
 
 
 def _render_rays_backward_case(gu, P, Pf, C, R, n_cam, n_rays, which, seed=0, own=lambda model: model, grid_scale=1.0,
-                               density_bias=0.0, probe=None):
-    """The body of test_render_rays_backward_vs_oracle_autograd (shared with tests/test_gpu_cu_counts.py and
-    tests/test_gpu_render_sample_counts.py).  ``seed``: added to the seeds of the grid, the ray positions, the random streams
-    and the cotangents; ``own``: called with the model; ``grid_scale``: factor on the tanh noise grid; ``density_bias``: added
-    to the density output's bias; ``probe``: called with (grid, msd, cams, xys, rs, rcfg) before anything runs (a caller's
-    check that the inputs are the case it means)."""
-    model, _, _, _, msd = gu.make_model(R, C, 16, 16, TINY_UNET, n_fine=64, density_bias=density_bias)
+                               density_bias=0.0, probe=None, model_kw=None, rcfg_kw=None, cams=None):
+    """The body of test_render_rays_backward_vs_oracle_autograd (shared with tests/test_gpu_cu_counts.py,
+    tests/test_gpu_render_sample_counts.py and tests/test_gpu_render_scene.py).  ``seed``: added to the seeds of the grid, the
+    ray positions, the random streams and the cotangents; ``own``: called with the model; ``grid_scale``: factor on the tanh
+    noise grid; ``density_bias``: added to the density output's bias; ``probe``: called with (grid, msd, cams, xys, rs, rcfg)
+    before anything runs (a caller's check that the inputs are the case it means); ``model_kw`` / ``rcfg_kw``: a scene other
+    than the default one, for the model and for the oracle (gpu_utils.make_model); ``cams``: ``n_cam`` cameras in place of the
+    orbit's.  No criterion below is a fraction of the far plane: the sample displacement `moved` counts is an absolute
+    depth, 1e-3, whatever the scene."""
+    model, _, _, _, msd = gu.make_model(R, C, 16, 16, TINY_UNET, n_fine=64, density_bias=density_bias, model_kw=model_kw)
     own(model)
     model.raysampler.n_pts_per_ray_training = P
     model.renderer.n_pts_per_ray_fine_training = Pf
-    rcfg = ro.RenderCfg(resol=R, feature_size=C, image_height=16, image_width=16, n_pts_coarse=P, n_pts_fine=Pf)
+    rcfg = ro.RenderCfg(resol=R, feature_size=C, image_height=16, image_width=16, n_pts_coarse=P, n_pts_fine=Pf,
+                        **(rcfg_kw or {}))
     grid = torch.tanh(torch.from_numpy(np_noise(7 + seed, (1, C, R, R, R)))) * grid_scale
-    cams = hda.get_simple_360_camera_trajectory(2 * math.pi, n_cam, -0.5, 10, (0.0, -1.0, 0.0), 3.2)
+    if cams is None:
+        cams = hda.get_simple_360_camera_trajectory(2 * math.pi, n_cam, -0.5, 10, (0.0, -1.0, 0.0), 3.2)
+    assert len(cams) == n_cam
     xys = (torch.from_numpy(np_noise(11 + seed, (n_cam, n_rays, 2))).clamp(-2, 2) * 0.45).contiguous()
     rs = _streams(n_cam, n_rays, P, Pf, 500 + P + seed)
     std = 1.0

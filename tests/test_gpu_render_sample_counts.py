@@ -95,15 +95,16 @@ def _blob_grid(seed, C, R, scale=4.0, centre=(3.3, 4.1, 3.6), radius=1.6):
     return _noise_grid(seed, C, R, scale) * ball[None, None].float()
 
 
-def _eval_model(R, C, H, W, nc, nf, bias=0.05, compute="f32", own=lambda m: m):
+def _eval_model(R, C, H, W, nc, nf, bias=0.05, compute="f32", own=lambda m: m, model_kw=None, rcfg_kw=None):
     """The model of tests/test_gpu_render.py::_render_pair with ``nc`` coarse samples in evaluation mode, and the oracle's
-    configuration and weights of the same renderer."""
-    model, _, _, _, msd = gu.make_model(R, C, H, W, TINY_UNET, n_fine=nf, density_bias=bias)
+    configuration and weights of the same renderer.  ``model_kw`` / ``rcfg_kw``: the scene, see gpu_utils.make_model."""
+    model, _, _, _, msd = gu.make_model(R, C, H, W, TINY_UNET, n_fine=nf, density_bias=bias, model_kw=model_kw)
     own(model)
     model.net_3d_enabled = False
     model.raysampler.n_pts_per_ray_evaluation = nc
     model.renderer.compute_dtype = compute
-    rcfg = ro.RenderCfg(resol=R, feature_size=C, image_height=H, image_width=W, n_pts_coarse=nc, n_pts_fine=nf)
+    rcfg = ro.RenderCfg(resol=R, feature_size=C, image_height=H, image_width=W, n_pts_coarse=nc, n_pts_fine=nf,
+                        **(rcfg_kw or {}))
     return model, msd, rcfg
 
 
@@ -144,17 +145,19 @@ EVAL_TOL = {"rgb": 2e-4, "mask": 2e-4, "rgb_c": 2e-4, "mask_c": 2e-4, "depth": 2
 TRAIN_TOL = dict(EVAL_TOL, depth=1e-3 * FAR)
 
 
-def _check(got, ref, what, tol=EVAL_TOL, keys=None):
+def _check(got, ref, what, tol=EVAL_TOL, keys=None, far=FAR):
     """Every plane finite and within its bound of the reference; prints the worst error of each (depths as a fraction of
-    the far plane).  Returns the errors."""
+    the far plane).  ``far``: the case's own far plane (gpu_utils.far_plane) where it is not the default scene's 14 - the
+    depth bounds of ``tol`` are fractions of it.  Returns the errors."""
     errs = {}
     for k in (keys or ref):
         assert got[k].shape == ref[k].shape, (what, k, got[k].shape, ref[k].shape)
         assert torch.isfinite(got[k]).all(), (what, k)
         errs[k] = (got[k] - ref[k]).abs().max().item()
-    print(f"\n{what}: " + ", ".join(f"{k} {e / (FAR if 'depth' in k else 1.0):.1e}" for k, e in errs.items()))
+    print(f"\n{what}: " + ", ".join(f"{k} {e / (far if 'depth' in k else 1.0):.1e}" for k, e in errs.items()))
     for k, e in errs.items():
-        assert e < tol[k], (what, k, e, tol[k])
+        bound = tol[k] * (far / FAR) if "depth" in k else tol[k]
+        assert e < bound, (what, k, e, bound)
     return errs
 
 
@@ -217,16 +220,24 @@ def test_evaluation_mode_counts_ray_per_column_kernel(counts):
     assert _on_ray_per_column_kernel(model, 8, 32)
 
 
-def _training_case(P, Pf, C, which, seed, n_cam=2, n_rays=13):
+def _training_case(P, Pf, C, which, seed, n_cam=2, n_rays=13, case="", model_kw=None, rcfg_kw=None, cams=None,
+                   density_bias=0.0, grid_scale=1.0, probe=None):
     """The body of tests/test_gpu_training_mode.py::test_training_mode_render_vs_oracle at 2 x 13 rays (four tiles per camera,
-    the last one of a single ray)."""
+    the last one of a single ray).  ``case``: the name of a scene other than the default one, given by ``model_kw`` /
+    ``rcfg_kw`` (gpu_utils.make_model), ``cams`` (``n_cam`` cameras in place of the orbit's), ``density_bias`` and
+    ``grid_scale``; its depth bounds are fractions of its own far plane.  ``probe``: called with (the oracle's planes, grid,
+    msd, cams, xys, rs, rcfg) - a caller's check that the inputs are the case it means."""
     R = 8
-    model, _, _, _, msd = gu.make_model(R, C, 16, 16, TINY_UNET, n_fine=64)
+    model, _, _, _, msd = gu.make_model(R, C, 16, 16, TINY_UNET, n_fine=64, density_bias=density_bias, model_kw=model_kw)
     model.raysampler.n_pts_per_ray_training = P
     model.renderer.n_pts_per_ray_fine_training = Pf
-    rcfg = ro.RenderCfg(resol=R, feature_size=C, image_height=16, image_width=16, n_pts_coarse=P, n_pts_fine=Pf)
-    grid = _noise_grid(2201 + P, C, R)
-    cams = hda.get_simple_360_camera_trajectory(2 * math.pi, n_cam, -0.5, 10, UP, 3.2)
+    rcfg = ro.RenderCfg(resol=R, feature_size=C, image_height=16, image_width=16, n_pts_coarse=P, n_pts_fine=Pf,
+                        **(rcfg_kw or {}))
+    grid = _noise_grid(2201 + P, C, R, grid_scale)
+    if cams is None:
+        cams = hda.get_simple_360_camera_trajectory(2 * math.pi, n_cam, -0.5, 10, UP, 3.2)
+    assert len(cams) == n_cam
+    far = gu.far_plane(cams, rcfg) if case else FAR
     xys = (torch.from_numpy(np_noise(2211 + P, (n_cam, n_rays, 2))).clamp(-2, 2) * 0.45).contiguous()
     rs = _streams(n_cam, n_rays, P, Pf, seed)
     if which == "no_u_coarse":  # un-jittered coarse depths under stratified importance samples and noise
@@ -237,13 +248,15 @@ def _training_case(P, Pf, C, which, seed, n_cam=2, n_rays=13):
     bundle = model.raysampler(cams.to(gu.DEV), EvaluationMode.TRAINING, xys=xys.to(gu.DEV))
     out = model.renderer(ray_bundle=bundle, implicit_functions=list(model._implicit_functions),
                          evaluation_mode=EvaluationMode.TRAINING, rng_streams={k: v.to(gu.DEV) for k, v in rs.items()})
-    ref = _cached(("train", P, Pf, C, which, seed),
+    ref = _cached(("train", P, Pf, C, which, seed, case),
                   lambda: {k: v.reshape(n_cam, n_rays, -1) for k, v in
                            _oracle_training_render(grid, msd, cams, xys, rs, rcfg, 1.0, gu).items()})
     g = lambda t: t.reshape(n_cam, n_rays, -1).cpu().clone()  # noqa: E731
     got = {"rgb": g(out.features), "depth": g(out.depths), "mask": g(out.masks), "rgb_c": g(out.prev_stage.features),
            "depth_c": g(out.prev_stage.depths), "mask_c": g(out.prev_stage.masks)}
-    _check(got, ref, f"training ({P},{Pf}) C={C} [{which}]", TRAIN_TOL)
+    _check(got, ref, f"training ({P},{Pf}) C={C} [{which}]" + (" " + case if case else ""), TRAIN_TOL, far=far)
+    if probe is not None:
+        probe(ref, grid, msd, cams, xys, rs, rcfg)
     return got
 
 
