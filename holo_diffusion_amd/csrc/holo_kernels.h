@@ -76,8 +76,12 @@ int gn_stats_launch(const float* x, double* partial, int N, int C, int64_t V, vo
 // (unet.py:248-250): y = GN(x)*(1+scale)+shift.  Channels [0,C0) use part0 (B0 slabs), [C0,C0+C1) part1.
 int gn_finalize_launch(const double* part0, int C0, int B0, const double* part1, int C1, int B1, int N, int64_t V,
                        int groups, float eps, const float* gamma, const float* beta, const float* film,
-                       int film_stride, int film_cout, float* coef, void* stream, float* moments = nullptr);
+                       int film_stride, int film_cout, float* coef, void* stream, float* moments = nullptr,
+                       const float* x0 = nullptr, const float* x1 = nullptr, float* act = nullptr, int act_silu = 0);
 // moments (training forward): [N][C0 + C1][2] = (mean, rstd) of the channel's group, for the backward pass
+// act (optional): the launch also writes act[n][v][c] = a*x + b (act_silu: SiLU of it) over the virtual concat x = [x0 | x1],
+// channels-last fp32 of C0 / C1 channels, with the arithmetic of the row-tile convolution's staging: the one convolution
+// that would apply (a, b) on load reads `act` as raw input instead.  Needs (C0 + C1) / groups % 4 == 0 and C0 % 4 == 0.
 
 // emb = Linear2(SiLU(Linear1(timestep_embedding(t, mc))));  writes silu(emb) (all consumers apply SiLU first:
 // unet.py:199-205) and emb itself.  load_kind: the HOLO_DEBUG_TIMESTEP_LOAD of the plan (0 in production, see the kernel).

@@ -83,6 +83,8 @@ constexpr int64_t KNOB_UNSET = INT64_MIN;
   X(side_lane_min_r, "HOLO_SIDE_LANE_MIN_R", INT, 32, PLAN, "smallest grid edge whose concat convolutions are split")      \
   X(side_lane_fork_r, "HOLO_SIDE_LANE_FORK_R", INT, 8, PLAN,                                                               \
     "the side lane starts in front of the first descent level whose grid edge is at most this")                            \
+  X(rowtile_preact, "HOLO_ROWTILE_PREACT", INT, 1, PLAN,                                                                   \
+    "0: row-tile convolutions of the deepest level apply GroupNorm + SiLU themselves, per tap and Cout tile")              \
   X(no_flash_attn, "HOLO_NO_FLASH_ATTN", SET, 0, PLAN, "attention as GEMM + softmax + GEMM")                               \
   X(bf16_flash_min_t, "HOLO_BF16_FLASH_MIN_T", RAW, 1024, PLAN, "tokens from which the bf16 mode takes its bf16 attention") \
   X(flash_split, "HOLO_FLASH_SPLIT", INT, 0, PLAN, "key splits of the fp32 attention, clamped to [1, T/128] (0: by fill)") \

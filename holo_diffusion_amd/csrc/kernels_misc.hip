@@ -13,6 +13,7 @@
 
 #include "holo_common.h"
 #include "holo_kernels.h"
+#include "rowtile_silu.h"
 
 namespace holo {
 namespace {
@@ -178,18 +179,55 @@ __device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
   return r;
 }
 
+// The pre-activated form (PRE, gn_finalize_act_kernel): the block that has just computed its group's (a, b) also writes
+// act[n][v][c] = silu(fma(x, a, b)) (or the affine alone) for its cpg channels over all V voxels of its sample, so that the
+// ONE convolution reading the tensor takes it as raw input instead of repeating the activation per (tap, Cout tile)
+// (unetplan::preactivate_rowtile).  x is the virtual concat [x0 | x1], channels-last fp32; cpg % 4 == 0 and C0 % 4 == 0, so a
+// 4-channel quad has one source.  The arithmetic is the row-tile kernel's `commit` (kernels_conv.hip) on the same fp32
+// (a, b): one fused multiply-add, then silu_f - the quotient that its shortened division equals wherever it is taken
+// (rowtile_silu.h) - so the convolution's results are bit-identical either way.
+struct GnPreact {
+  const float *x0, *x1;
+  float* act;
+  int silu;
+};
+constexpr int GN_PRE_TOP = 2;  // quads per thread up to which x is requested at the top, to come back under the reduction
+
 // coef[n][c] = (a, b) with GN(x)*(1+scale)+shift = a*x + b.  grid = (groups, N), block = 256
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ part0, int C0, int B0,
-                                                          const double* __restrict__ part1, int C1, int B1, int64_t V,
-                                                          int groups, float eps, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta,
-                                                          const float* __restrict__ film, int film_stride,
-                                                          int film_cout, float* __restrict__ coef,
-                                                          float* __restrict__ moments) {
-  __shared__ double rs[4], rq[4];
+// (rs, rq: 4 doubles each of LDS; s_ab: 2 x 256 floats of it in the PRE form, else unused)
+template <bool PRE>
+__device__ __forceinline__ void gn_finalize_body(double* rs, double* rq, float* s_ab, const double* __restrict__ part0, int C0,
+                                                 int B0, const double* __restrict__ part1, int C1, int B1, int64_t V,
+                                                 int groups, float eps, const float* __restrict__ gamma,
+                                                 const float* __restrict__ beta, const float* __restrict__ film,
+                                                 int film_stride, int film_cout, float* __restrict__ coef,
+                                                 float* __restrict__ moments, const GnPreact& pre) {
   const int g = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
   const int Cin = C0 + C1;
   const int cpg = Cin / groups;
+  // PRE: item i of the block is quad i % qpg of voxel i / qpg (items < 2^31: gn_finalize_launch)
+  const unsigned qpg = (unsigned)cpg >> 2, items = PRE ? (unsigned)V * qpg : 0u;
+  auto item_at = [&](unsigned i, int64_t& row, int& c) {
+    const unsigned v = i / qpg;
+    c = g * cpg + 4 * (int)(i - v * qpg);
+    row = (int64_t)n * V + v;
+  };
+  auto item_src = [&](int64_t row, int c) { return c < C0 ? pre.x0 + row * C0 + c : pre.x1 + row * C1 + (c - C0); };
+  float4 xr[GN_PRE_TOP];
+  const bool x_at_top = PRE && items <= (unsigned)GN_PRE_TOP * 256u;
+  if (PRE && x_at_top) {
+#pragma unroll
+    for (int u = 0; u < GN_PRE_TOP; ++u) {
+      const unsigned i = (unsigned)tid + (unsigned)u * 256u;
+      xr[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (i < items) {
+        int64_t row;
+        int c;
+        item_at(i, row, c);
+        xr[u] = *reinterpret_cast<const float4*>(item_src(row, c));
+      }
+    }
+  }
   // the channel's affine / FiLM rows are requested FIRST: they come back under the reduction instead of after it (this
   // kernel is nothing but dependent round trips: ~66 launches per forward)
   float pg = 0.f, pb = 0.f, psc = 0.f, psh = 0.f;
@@ -298,7 +336,63 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restri
       moments[((int64_t)n * Cin + c) * 2 + 0] = (float)mean;
       moments[((int64_t)n * Cin + c) * 2 + 1] = (float)rstd;
     }
+    if (PRE) {  // the fp32 (a, b) the convolution would have read from coef
+      s_ab[tid * 2 + 0] = (float)a;
+      s_ab[tid * 2 + 1] = (float)b;
+    }
   }
+  if (PRE) {
+    __syncthreads();
+    auto apply = [&](unsigned i, float4 x) {
+      int64_t row;
+      int c;
+      item_at(i, row, c);
+      const float4* ab = reinterpret_cast<const float4*>(s_ab + (c - g * cpg) * 2);
+      const float4 c01 = ab[0], c23 = ab[1];  // (a, b) of channels 0, 1 | 2, 3
+      float4 y = make_float4(__builtin_fmaf(x.x, c01.x, c01.y), __builtin_fmaf(x.y, c01.z, c01.w),
+                             __builtin_fmaf(x.z, c23.x, c23.y), __builtin_fmaf(x.w, c23.z, c23.w));
+      if (pre.silu) y = make_float4(silu_f(y.x), silu_f(y.y), silu_f(y.z), silu_f(y.w));
+      *reinterpret_cast<float4*>(pre.act + row * Cin + c) = y;
+    };
+    if (x_at_top) {
+#pragma unroll
+      for (int u = 0; u < GN_PRE_TOP; ++u) {
+        const unsigned i = (unsigned)tid + (unsigned)u * 256u;
+        if (i < items) apply(i, xr[u]);
+      }
+    } else {
+      for (unsigned i = (unsigned)tid; i < items; i += 256u) {
+        int64_t row;
+        int c;
+        item_at(i, row, c);
+        apply(i, *reinterpret_cast<const float4*>(item_src(row, c)));
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ part0, int C0, int B0,
+                                                          const double* __restrict__ part1, int C1, int B1, int64_t V,
+                                                          int groups, float eps, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta,
+                                                          const float* __restrict__ film, int film_stride,
+                                                          int film_cout, float* __restrict__ coef,
+                                                          float* __restrict__ moments) {
+  __shared__ double rs[4], rq[4];
+  gn_finalize_body<false>(rs, rq, nullptr, part0, C0, B0, part1, C1, B1, V, groups, eps, gamma, beta, film, film_stride,
+                          film_cout, coef, moments, GnPreact{nullptr, nullptr, nullptr, 0});
+}
+__global__ __launch_bounds__(256) void gn_finalize_act_kernel(const double* __restrict__ part0, int C0, int B0,
+                                                              const double* __restrict__ part1, int C1, int B1, int64_t V,
+                                                              int groups, float eps, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta,
+                                                              const float* __restrict__ film, int film_stride,
+                                                              int film_cout, float* __restrict__ coef,
+                                                              float* __restrict__ moments, GnPreact pre) {
+  __shared__ double rs[4], rq[4];
+  __shared__ __attribute__((aligned(16))) float s_ab[512];
+  gn_finalize_body<true>(rs, rq, s_ab, part0, C0, B0, part1, C1, B1, V, groups, eps, gamma, beta, film, film_stride, film_cout,
+                         coef, moments, pre);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1083,13 +1177,31 @@ int gn_stats_launch(const float* x, double* partial, int N, int C, int64_t V, vo
 
 int gn_finalize_launch(const double* part0, int C0, int B0, const double* part1, int C1, int B1, int N, int64_t V,
                        int groups, float eps, const float* gamma, const float* beta, const float* film,
-                       int film_stride, int film_cout, float* coef, void* stream, float* moments) {
+                       int film_stride, int film_cout, float* coef, void* stream, float* moments, const float* x0,
+                       const float* x1, float* act, int act_silu) {
   const int Cin = C0 + C1;
   if (Cin % groups || Cin / groups > 256) {
     set_error("gn_finalize: C=%d not compatible with %d groups", Cin, groups);
     return -1;
   }
+  const int cpg = Cin / groups;
+  // the kernel numbers the (slab, channel) records of a run in 32 bits
+  if ((int64_t)(B0 > B1 ? B0 : B1) * cpg >= ((int64_t)1 << 31)) {
+    set_error("gn_finalize: %d slabs of %d channels per group: more than 2^31 records per run", B0 > B1 ? B0 : B1, cpg);
+    return -1;
+  }
   dim3 grid((unsigned)groups, (unsigned)N);
+  if (act) {
+    // quads of one source each, numbered in 32 bits
+    if ((cpg & 3) || (C0 & 3) || !x0 || (C1 > 0 && !x1) || V * (cpg >> 2) >= ((int64_t)1 << 31)) {
+      set_error("gn_finalize: the activated tensor needs whole 4-channel quads per group and source (%d + %d channels, %d groups) "
+                "and fewer than 2^31 of them per group (%lld voxels)", C0, C1, groups, (long long)V);
+      return -1;
+    }
+    HOLO_LAUNCH(gn_finalize_act_kernel, grid, dim3(256), stream, part0, C0, B0, part1, C1, B1, V, groups, eps, gamma, beta,
+                film, film_stride, film_cout, coef, moments, GnPreact{x0, x1, act, act_silu});
+    return 0;
+  }
   HOLO_LAUNCH(gn_finalize_kernel, grid, dim3(256), stream, part0, C0, B0, part1, C1, B1, V, groups, eps, gamma, beta,
               film, film_stride, film_cout, coef, moments);
   return 0;

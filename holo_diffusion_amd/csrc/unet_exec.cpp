@@ -126,6 +126,7 @@ int ensure_plan(HoloUnet* u, int batch, void* ws) {
   }
   Planner pl(&u->d, batch, ws, u->plan);
   pl.build();
+  if (pl.err.empty()) preactivate_rowtile(u->plan, pl.knobs);
   int rc = 0;
   if (!pl.err.empty()) {
     set_error("holo_unet_forward: %s", pl.err.c_str());
@@ -152,7 +153,7 @@ int run_op(const HoloUnet* u, const Op& op, int N, const float* x, const int64_t
     case OP_FINAL: {
       const GnFinalize& f = op.fin;
       return gn_finalize_launch(f.part0, f.C0, f.B0, f.part1, f.C1, f.B1, N, f.V, f.groups, 1e-5f, f.gamma, f.beta, f.film,
-                                f.film_stride, f.film_cout, f.coef, stream, f.moments);
+                                f.film_stride, f.film_cout, f.coef, stream, f.moments, f.x0, f.x1, f.act, f.act_silu);
     }
     case OP_CONV:
       return conv_launch(op.conv, stream);
@@ -499,7 +500,9 @@ size_t holo_unet_workspace_bytes(HoloUnet* net, int batch) {
   auto it = net->ws_cache.find(key);
   if (it != net->ws_cache.end()) return it->second;
   Plan sizing;  // built on no workspace and dropped
-  Planner(&net->d, batch, nullptr, sizing).build();
+  Planner pl(&net->d, batch, nullptr, sizing);
+  pl.build();
+  preactivate_rowtile(sizing, pl.knobs);
   net->ws_cache[key] = sizing.bytes;
   return sizing.bytes;
 }

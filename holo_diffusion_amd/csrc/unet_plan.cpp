@@ -891,5 +891,57 @@ void Planner::find_cl_ends() {
   }
 }
 
+
+const char* preact_refusal(const PreactShape& s) {
+  // the finalize block walks its group in 4-channel quads, each from one source of the virtual concat
+  if (s.cpg % 4 != 0) return "a group is no whole number of 4-channel quads";
+  if (s.C0 % 4 != 0) return "a quad would straddle the seam of the concat";
+  // one block per (group, sample) writes V x cpg elements behind its reduction: beyond the deepest level that is a serial
+  // pass of its own in front of the convolution
+  if (s.V > PREACT_MAX_VOX) return "the tensor is too large for the finalize launch";
+  // the extra write and read of the tensor must replace many activations per element
+  if (s.redundancy < PREACT_MIN_REDUNDANCY) return "the convolution repeats too little of the activation";
+  return nullptr;
+}
+
+Preact preactivate_rowtile(Plan& plan, const Knobs& knobs) {
+  Preact r;
+  std::vector<Op>& ops = plan.ops;
+  const int N = plan.batch;
+  const uintptr_t base = reinterpret_cast<uintptr_t>(plan.ws);
+  r.scratch_off = Arena::al(plan.bytes);
+  float* const scratch = reinterpret_cast<float*>(base + r.scratch_off);
+  for (size_t i = 0; knobs.rowtile_preact && i < ops.size(); ++i) {
+    if (ops[i].kind != OP_FINAL || ops[i].side || ops[i].fin.act) continue;
+    GnFinalize& f = ops[i].fin;
+    int readers = 0;
+    for (const Op& o : ops) readers += o.kind == OP_CONV && o.conv.coef == f.coef;
+    size_t j = i + 1;
+    while (j < ops.size() && (ops[j].side || ops[j].kind != OP_CONV)) ++j;  // the next convolution of the caller's stream
+    if (readers != 1 || j == ops.size() || ops[j].conv.coef != f.coef) continue;
+    ConvParams& p = ops[j].conv;
+    const int Cin = p.C0 + p.C1;
+    const int64_t V = (int64_t)p.ID * p.IH * p.IW;
+    if (p.kernel != ConvKernel::RowTile || p.bf16 != 0 || p.in_bf16 != 0 || p.ups || p.N != N || f.moments) continue;
+    if (Cin != f.C0 + f.C1 || V != f.V || f.groups < 1 || Cin % f.groups) continue;  // (the finalize of this very input)
+    const PreactShape shape{Cin / f.groups, p.C0, V, p.ksz * p.ksz * p.ksz * ((p.Cout + 63) / 64)};
+    if (preact_refusal(shape)) continue;
+    ConvParams q = p;
+    q.src0 = scratch, q.C0 = Cin, q.src1 = nullptr, q.C1 = 0, q.coef = nullptr;
+    if (!conv_can_launch(q)) continue;
+    f.x0 = p.src0, f.x1 = p.src1, f.act = scratch, f.act_silu = p.act;
+    q.act = 0;  // (only with coef)
+    p = q;
+    const size_t bytes = (size_t)N * (size_t)V * Cin * sizeof(float);
+    if (bytes > r.scratch_bytes) r.scratch_bytes = bytes;
+    ++r.pairs;
+  }
+  if (r.pairs) plan.bytes = r.scratch_off + Arena::al(r.scratch_bytes);
+  if (knobs.debug_plan)
+    fprintf(stderr, "[plan] batch %d: %d finalize + row-tile convolution pairs pre-activated (%zu bytes of scratch behind the plan)\n",
+            N, r.pairs, r.pairs ? Arena::al(r.scratch_bytes) : (size_t)0);
+  return r;
+}
+
 }  // namespace unetplan
 }  // namespace holo

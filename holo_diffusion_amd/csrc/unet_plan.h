@@ -145,6 +145,11 @@ struct GnFinalize {  // partial sums of the (virtual concat) input -> per-(sampl
   int film_stride, film_cout;
   float *coef, *moments;  // moments: (mean, rstd) kept for the backward in a training plan, else null
   int groups;             // 32, or fewer where one half of a split concat is normalised alone (Planner::plan_side_lane)
+  // preactivate_rowtile: the launch also writes act[N][V][C0 + C1] = a*x + b (act_silu: SiLU of it) of the raw sources x0 / x1
+  // (channels-last fp32, C0 / C1 channels), which its one consumer reads as raw input.  All null / 0: coefficients only.
+  const float *x0, *x1;
+  float* act;
+  int act_silu;
 };
 struct Softmax { float* S; int64_t rows; int cols; };  // in place
 struct Flash {
@@ -437,6 +442,35 @@ struct Planner {
   Act run_layers(const std::vector<Block>& layers, Act h, Act* skip, bool release_h);
   void find_cl_ends();
 };
+
+// ---------------------------------------------------------------------------------------------
+// rewrite pass: deep levels apply GroupNorm (+ SiLU) once per tensor
+// ---------------------------------------------------------------------------------------------
+// The row-tile convolution applies (a, b) and SiLU while it stages, once per (tap, Cout tile) workgroup: at 4^3 every input
+// element of a 512 -> 512 3x3x3 convolution is activated 216 times.  Where that redundancy is high and the tensor small, the
+// finalize launch in front - one block per (group, sample), which has just computed the group's (a, b) - writes the
+// activated tensor once, and the convolution reads it as raw input (its ACTM = 0 instance).  Same arithmetic, same bits.
+struct PreactShape {
+  int cpg, C0;     // channels per GroupNorm group; channels of the first source
+  int64_t V;       // voxels per sample
+  int redundancy;  // taps x 64-channel Cout tiles: how often the convolution would activate an element
+};
+// Voxels per sample up to which a pair is rewritten, and the redundancy from which (DESIGN.md section 4f'': the shapes
+// measured as a pair, finalize + convolution, against the pair they replace)
+constexpr int64_t PREACT_MAX_VOX = 64;
+constexpr int PREACT_MIN_REDUNDANCY = 16;
+// null: the shape is rewritten; else why not
+const char* preact_refusal(const PreactShape& s);
+struct Preact {
+  int pairs = 0;
+  size_t scratch_off = 0, scratch_bytes = 0;  // the activated tensor of every pair (they are serial on the caller's stream)
+};
+// Rewrites a plan Planner::build() made (not a training plan: the tape keeps coefficients and raw inputs).  For every
+// main-lane OP_FINAL whose coefficients have exactly one reader, that reader being the next main-lane OP_CONV, on
+// ConvKernel::RowTile, exact fp32 on fp32 storage, of a shape preact_refusal admits: the finalize gets the convolution's
+// sources and the scratch, the convolution the scratch as its one raw source.  The scratch lies behind the plan's workspace:
+// plan.bytes grows by it, in a sizing pass as in a placed one.  knobs.rowtile_preact == 0: nothing is rewritten.
+Preact preactivate_rowtile(Plan& plan, const Knobs& knobs);
 
 }  // namespace unetplan
 }  // namespace holo
