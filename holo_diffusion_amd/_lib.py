@@ -146,6 +146,9 @@ SIGNATURES = {
     "holo_q_sample": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, _vp]),
     "holo_q_sample_philox": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint32, _vp, _vp,
                                        C.c_int, _vp]),
+    "holo_diffusion_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "holo_diffusion_loss": (C.c_int, [_vp, C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "holo_vb_terms": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
     "holo_tanh": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
     "holo_clip": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_float, C.c_int64, _vp]),
     "holo_renderer_create": (C.c_int, [_vp, C.POINTER(HoloRenderCfg), C.POINTER(_vp)]),

@@ -141,6 +141,15 @@ int q_sample_launch(const float* coefs, int batch, int64_t per, const float* x, 
 int q_sample_philox_launch(const float* coefs, int batch, int64_t per, const float* x, uint64_t seed,
                            const uint32_t* row_streams, uint64_t offset, float* out, float* noise_out, int ncdhw_channels,
                            void* stream);
+// Diffusion losses and the variational bound's terms (include/holo_abi.h, holo_diffusion_loss / holo_vb_terms).  A workgroup
+// owns kLossTile elements of one sample and leaves one double per term in `partial` (loss_partials(batch, per) doubles: a
+// function of the shapes alone); a one-workgroup finalize launch writes `terms` ((batch, 2) / (batch, 3) doubles)
+constexpr int kLossTile = 2048;
+int64_t loss_partials(int batch, int64_t per);
+int diffusion_loss_launch(int batch, int64_t per, const float* target, const float* model_out, const float* row_scale,
+                          double* terms, float* grad_out, double* partial, void* stream);
+int vb_terms_launch(const float* coefs, int batch, int64_t per, const float* x_start, const float* x_t, const float* noise,
+                    const float* model_out, int clip, double* terms, double* partial, void* stream);
 int tanh_launch(const float* x, float* y, int64_t n, void* stream);
 // dst = src for a SMALL caller-provided tensor, read with system-scope loads (holo_ld_sys, holo_common.h)
 int copy_sys_launch(const float* src, float* dst, int64_t n, void* stream);

@@ -1026,6 +1026,200 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(const float* __restrict__
   if (pred) st4(pred, o, m);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Diffusion losses and the terms of the variational bound (include/holo_abi.h: holo_diffusion_loss, holo_vb_terms;
+// gaussian_diffusion.py:817-850, :941-952, :1027-1029, losses.py:18-83).  Bandwidth kernels like the steps above: a float4 per
+// lane and round, any layout.  A workgroup owns kLossTile consecutive elements of ONE sample: per-lane double accumulators, a
+// fixed-order LDS tree, one partial per (sample, term, workgroup) in the caller's workspace; loss_finalize_kernel (one
+// workgroup) adds a sample's partials in a fixed order and scales.  No atomics, no last-block trick: the number of partials
+// depends on (batch, elems_per_sample) alone, so the bits depend on neither the run nor the CU count, and a sample's
+// terms depend on neither the batch nor the row it runs in.
+// ---------------------------------------------------------------------------------------------
+constexpr int kLossRounds = kLossTile / 1024;  // 256 lanes x 16 bytes per round
+static_assert(kLossTile % 1024 == 0, "whole rounds of 256 float4");
+
+// fixed-order sums of a workgroup's 256 x K doubles (block_sum256 of kernels_optim.hip, K sums behind one set of barriers)
+template <int K>
+__device__ __forceinline__ void block_sums256(double (&acc)[K], double* red) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < K; ++k) red[k * 256 + tid] = acc[k];
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) red[k * 256 + tid] += red[k * 256 + tid + o];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = red[k * 256];
+}
+__device__ __forceinline__ double sum4d(float4 v) { return ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w); }
+
+// mean_flat((target - model_out)**2) and mean_flat(_huber(.., scaling=0.001)) (gaussian_diffusion.py:949-952, :1062-1076):
+// every operation rounded, in the reference's order; sqrtf and the division are the correctly rounded ones
+__device__ __forceinline__ float loss_sq(float t, float m) {
+#pragma clang fp contract(off)
+  const float d = t - m;
+  return d * d;
+}
+__device__ __forceinline__ float loss_huber(float sq) {
+#pragma clang fp contract(off)
+  const float s = 0.001f;
+  const float a = 1.f + sq / (float)(0.001 * 0.001);
+  return (sqrtf(fmaxf(a, 0.f) + 1e-4f) - 1.f) * s;  // (_safe_sqrt(a, eps=1e-4) - 1) * scaling
+}
+// the cotangent of w_b * mse_b: (model_out - target) * s_b with s_b = float(2 * w_b / n)
+__device__ __forceinline__ float4 loss_grad4(float4 t, float4 m, float s) {
+#pragma clang fp contract(off)
+  return make_float4((m.x - t.x) * s, (m.y - t.y) * s, (m.z - t.z) * s, (m.w - t.w) * s);
+}
+
+// grid = (cdiv(per, kLossTile), batch).  partial[(b * 2 + k) * gridDim.x + blockIdx.x], k = 0: sum sq, 1: sum huber
+template <bool TERMS, bool GRAD>
+__global__ __launch_bounds__(256) void diffusion_loss_kernel(int64_t per, const float* __restrict__ target,
+                                                             const float* __restrict__ model_out,
+                                                             const float* __restrict__ row_scale, float unit_scale,
+                                                             double* __restrict__ partial, float* __restrict__ grad_out) {
+  __shared__ double red[TERMS ? 2 * 256 : 1];
+  const int b = blockIdx.y;
+  const float s = !GRAD ? 0.f : row_scale ? holo_ld_sys(row_scale + b) : unit_scale;
+  double acc[2] = {0.0, 0.0};
+#pragma unroll
+  for (int r = 0; r < kLossRounds; ++r) {
+    const int64_t i = (int64_t)blockIdx.x * kLossTile + (int64_t)(r * 256 + (int)threadIdx.x) * 4;
+    if (i < per) {
+      const int64_t o = (int64_t)b * per + i;
+      const float4 t = ld4(target, o), m = ld4(model_out, o);
+      if (TERMS) {
+        const float4 sq = make_float4(loss_sq(t.x, m.x), loss_sq(t.y, m.y), loss_sq(t.z, m.z), loss_sq(t.w, m.w));
+        acc[0] += sum4d(sq);
+        acc[1] += sum4d(make_float4(loss_huber(sq.x), loss_huber(sq.y), loss_huber(sq.z), loss_huber(sq.w)));
+      }
+      if (GRAD) st4(grad_out, o, loss_grad4(t, m, s));
+    }
+  }
+  if (TERMS) {
+    block_sums256<2>(acc, red);
+    if (threadIdx.x == 0) {
+      partial[((int64_t)b * 2 + 0) * gridDim.x + blockIdx.x] = acc[0];
+      partial[((int64_t)b * 2 + 1) * gridDim.x + blockIdx.x] = acc[1];
+    }
+  }
+}
+
+// One sample's row of holo_vb_terms: coefs[b*8 + 0..7] = (posterior_mean_coef1, posterior_mean_coef2, logvar, exp(-logvar),
+// exp(-0.5*logvar), sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, [t == 0]) with logvar =
+// posterior_log_variance_clipped[t]; every transcendental of a per-row scalar was taken on the host
+struct VbRow {
+  float c1, c2, einv, istd, sr, srm1;
+  bool t0;
+};
+// losses.py:48-53 in float32, th.pow(x, 3) as (x*x)*x
+__device__ __forceinline__ float approx_normal_cdf(float x) {
+#pragma clang fp contract(off)
+  return 0.5f * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * ((x * x) * x))));
+}
+// losses.py:56-83: log-likelihood of the Gaussian (mean, 1 / istd) discretised to bins of 2/255 around x in [-1, 1]
+__device__ __forceinline__ float discretized_log_likelihood(float x, float mean, float istd) {
+#pragma clang fp contract(off)
+  const float centered = x - mean;
+  const float cdf_plus = approx_normal_cdf(istd * (centered + (float)(1.0 / 255.0)));
+  const float cdf_min = approx_normal_cdf(istd * (centered - (float)(1.0 / 255.0)));
+  const float p = x < -0.999f ? cdf_plus : x > 0.999f ? 1.0f - cdf_min : cdf_plus - cdf_min;
+  return logf(fmaxf(p, 1e-12f));
+}
+// One element: acc[0] += the bound's term in nats (t > 0: normal_kl of two Gaussians that share the FIXED_SMALL
+// log-variance, whose -1 + lv2 - lv1 + exp(lv1 - lv2) is 0 and is NOT evaluated - see holo_abi.h; t == 0: the decoder's
+// negative log-likelihood), acc[1] += (pred - x_start)^2, acc[2] += (eps - noise)^2 (gaussian_diffusion.py:409-413)
+template <bool NOISE>
+__device__ __forceinline__ void vb_element(float x0, float xt, float pred, float e, const VbRow& c, float (&v)[3]) {
+#pragma clang fp contract(off)
+  if (c.t0) {
+    const float mean_p = c.c1 * pred + c.c2 * xt;  // q_posterior_mean_variance(pred, x_t, t): products rounded, sum rounded
+    v[0] = -discretized_log_likelihood(x0, mean_p, c.istd);
+  } else {
+    // mean_q - mean_p = (c1*x_start + c2*x_t) - (c1*pred + c2*x_t): the c2*x_t terms cancel exactly, and are left out - in
+    // float32 they leave 2^-24 * |c2*x_t| of rounding in a difference of c1 * |x_start - pred| ~ 1e-4 at t = 999 (1e-3 relative)
+    const float dm = c.c1 * (x0 - pred);
+    v[0] = 0.5f * ((dm * dm) * c.einv);
+  }
+  const float dx = pred - x0;
+  v[1] = dx * dx;
+  if (NOISE) {
+    const float de = (c.sr * xt - pred) / c.srm1 - e;
+    v[2] = de * de;
+  } else {
+    v[2] = 0.f;
+  }
+}
+
+// grid = (cdiv(per, kLossTile), batch).  partial[(b * 3 + k) * gridDim.x + blockIdx.x], k = 0: vb (nats), 1: xstart, 2: eps
+template <bool NOISE>
+__global__ __launch_bounds__(256) void vb_terms_kernel(const float* __restrict__ coefs, int64_t per,
+                                                       const float* __restrict__ x_start, const float* __restrict__ x_t,
+                                                       const float* __restrict__ noise,
+                                                       const float* __restrict__ model_out, int clip,
+                                                       double* __restrict__ partial) {
+  __shared__ double red[3 * 256];
+  const int b = blockIdx.y;
+  float k[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) k[j] = holo_ld_sys(coefs + b * 8 + j);  // (a small table uploaded from the host: see holo_ld_sys)
+  const VbRow c = {k[0], k[1], k[3], k[4], k[5], k[6], k[7] != 0.f};
+  double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int r = 0; r < kLossRounds; ++r) {
+    const int64_t i = (int64_t)blockIdx.x * kLossTile + (int64_t)(r * 256 + (int)threadIdx.x) * 4;
+    if (i < per) {
+      const int64_t o = (int64_t)b * per + i;
+      const float4 x0 = ld4(x_start, o), xt = ld4(x_t, o);
+      float4 m = ld4(model_out, o);
+      const float4 e = NOISE ? ld4(noise, o) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (clip) m = clamp4(m);
+      float vx[3], vy[3], vz[3], vw[3];
+      vb_element<NOISE>(x0.x, xt.x, m.x, e.x, c, vx);
+      vb_element<NOISE>(x0.y, xt.y, m.y, e.y, c, vy);
+      vb_element<NOISE>(x0.z, xt.z, m.z, e.z, c, vz);
+      vb_element<NOISE>(x0.w, xt.w, m.w, e.w, c, vw);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) acc[j] += sum4d(make_float4(vx[j], vy[j], vz[j], vw[j]));
+    }
+  }
+  block_sums256<3>(acc, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) partial[((int64_t)b * 3 + j) * gridDim.x + blockIdx.x] = acc[j];
+  }
+}
+
+// One workgroup.  Per sample, a lane adds every 256th partial of each of the K terms (the K x 8 loads of an unrolled round
+// are independent: the launch is a latency chain, not a bandwidth one), then the tree: a fixed order.  out[b*K + k] = sum / n,
+// and / ln 2 more for k == bits_term (the bound's term in bits; -1: none)
+template <int K>
+__global__ __launch_bounds__(256) void loss_finalize_kernel(const double* __restrict__ partial, int batch, int64_t nblk,
+                                                            int bits_term, int64_t n, double* __restrict__ out) {
+  __shared__ double red[K * 256];
+  for (int b = 0; b < batch; ++b) {
+    const double* __restrict__ p = partial + (int64_t)b * K * nblk;
+    double acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+#pragma unroll 8
+    for (int64_t i = threadIdx.x; i < nblk; i += 256) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) acc[k] += p[k * nblk + i];
+    }
+    block_sums256<K>(acc, red);
+    if (threadIdx.x < K) {
+      const double mean = red[threadIdx.x * 256] / (double)n;
+      out[b * K + threadIdx.x] = (int)threadIdx.x == bits_term ? mean / 0.6931471805599453 : mean;
+    }
+    __syncthreads();  // (red is written again in the next round)
+  }
+}
+
 // copy of a SMALL caller-provided tensor (biases, GroupNorm affine parameters, ...) with system-scope loads (holo_ld_sys)
 __global__ __launch_bounds__(256) void copy_sys_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -1421,6 +1615,43 @@ int f32_to_bf16_launch(const float* in, float* out_bf16, int64_t n, void* stream
   if (blocks > 16384) blocks = 16384;
   HOLO_LAUNCH(f32_to_bf16_kernel, dim3((unsigned)blocks), dim3(256), stream, reinterpret_cast<const float4*>(in),
               reinterpret_cast<float4*>(out_bf16), n >> 3);
+  return 0;
+}
+
+// The loss launchers: `partial` holds loss_partials(batch, per) doubles; the terms come out of the finalize launch
+int64_t loss_partials(int batch, int64_t per) { return (int64_t)batch * 3 * cdiv(per, kLossTile); }
+static dim3 loss_grid(int64_t per, int batch) { return dim3((unsigned)cdiv(per, kLossTile), (unsigned)batch); }
+
+int diffusion_loss_launch(int batch, int64_t per, const float* target, const float* model_out, const float* row_scale,
+                          double* terms, float* grad_out, double* partial, void* stream) {
+  if (!step_shape_ok("diffusion_loss", per)) return -1;
+  const dim3 grid = loss_grid(per, batch);
+  const float unit = (float)(2.0 / (double)per);  // row_scale == NULL: every w_b is 1
+  if (terms && grad_out)
+    HOLO_LAUNCH((diffusion_loss_kernel<true, true>), grid, dim3(256), stream, per, target, model_out, row_scale, unit, partial,
+                grad_out);
+  else if (terms)
+    HOLO_LAUNCH((diffusion_loss_kernel<true, false>), grid, dim3(256), stream, per, target, model_out, row_scale, unit,
+                partial, grad_out);
+  else
+    HOLO_LAUNCH((diffusion_loss_kernel<false, true>), grid, dim3(256), stream, per, target, model_out, row_scale, unit,
+                partial, grad_out);
+  if (terms)
+    HOLO_LAUNCH(loss_finalize_kernel<2>, dim3(1), dim3(256), stream, (const double*)partial, batch, (int64_t)grid.x, -1, per,
+                terms);
+  return 0;
+}
+
+int vb_terms_launch(const float* coefs, int batch, int64_t per, const float* x_start, const float* x_t, const float* noise,
+                    const float* model_out, int clip, double* terms, double* partial, void* stream) {
+  if (!step_shape_ok("vb_terms", per)) return -1;
+  const dim3 grid = loss_grid(per, batch);
+  if (noise)
+    HOLO_LAUNCH(vb_terms_kernel<true>, grid, dim3(256), stream, coefs, per, x_start, x_t, noise, model_out, clip, partial);
+  else
+    HOLO_LAUNCH(vb_terms_kernel<false>, grid, dim3(256), stream, coefs, per, x_start, x_t, noise, model_out, clip, partial);
+  HOLO_LAUNCH(loss_finalize_kernel<3>, dim3(1), dim3(256), stream, (const double*)partial, batch, (int64_t)grid.x, 0, per,
+              terms);
   return 0;
 }
 

@@ -1120,6 +1120,62 @@ int holo_q_sample_philox(HoloCtx*, const float* coefs, int batch, int64_t elems_
   });
 }
 
+// The losses of training_losses (gaussian_diffusion.py:941-959) and the terms of _vb_terms_bpd / calc_bpd_loop (:817-850,
+// :1027-1029): one streaming launch and a one-workgroup finalize each, partial sums in the caller's workspace
+static bool loss_shape_ok(int batch, int64_t per) { return batch >= 1 && batch <= 65535 && per >= 4 && (per & 3) == 0; }
+
+size_t holo_diffusion_loss_workspace_bytes(int batch, int64_t elems_per_sample) {
+  if (!loss_shape_ok(batch, elems_per_sample)) {
+    set_error("holo_diffusion_loss_workspace_bytes: batch in 1 .. 65535 and elems_per_sample a positive multiple of 4");
+    return 0;
+  }
+  return (size_t)loss_partials(batch, elems_per_sample) * sizeof(double);
+}
+
+static int loss_workspace_ok(const char* entry, int batch, int64_t per, const void* workspace, size_t ws_bytes) {
+  if (!loss_shape_ok(batch, per)) {
+    set_error("%s: batch must be in 1 .. 65535 and elems_per_sample a positive multiple of 4", entry);
+    return HOLO_E_INVALID;
+  }
+  const size_t need = (size_t)loss_partials(batch, per) * sizeof(double);
+  if (!workspace || ws_bytes < need || ((uintptr_t)workspace & 7)) {
+    set_error("%s: workspace of %zu bytes (8-byte aligned) needed, got %zu", entry, need, workspace ? ws_bytes : (size_t)0);
+    return HOLO_E_WORKSPACE;
+  }
+  return 0;
+}
+
+int holo_diffusion_loss(HoloCtx*, int batch, int64_t elems_per_sample, const float* target, const float* model_out,
+                        const float* row_scale, double* terms, float* grad_out, void* workspace, size_t ws_bytes,
+                        void* stream) {
+  if (!target || !model_out) {
+    set_error("holo_diffusion_loss: null/invalid argument");
+    return HOLO_E_INVALID;
+  }
+  if (!terms && !grad_out) {
+    set_error("holo_diffusion_loss: at least one of terms and grad_out must be given");
+    return HOLO_E_INVALID;
+  }
+  if (const int rc = loss_workspace_ok("holo_diffusion_loss", batch, elems_per_sample, workspace, ws_bytes)) return rc;
+  return diffusion_loss_launch(batch, elems_per_sample, target, model_out, row_scale, terms, grad_out, (double*)workspace, stream)
+             ? HOLO_E_INVALID
+             : 0;
+}
+
+int holo_vb_terms(HoloCtx*, const float* coefs, int batch, int64_t elems_per_sample, const float* x_start, const float* x_t,
+                  const float* noise, const float* model_out, int clip_denoised, double* terms, void* workspace,
+                  size_t ws_bytes, void* stream) {
+  if (!coefs || !x_start || !x_t || !model_out || !terms) {
+    set_error("holo_vb_terms: null/invalid argument");
+    return HOLO_E_INVALID;
+  }
+  if (const int rc = loss_workspace_ok("holo_vb_terms", batch, elems_per_sample, workspace, ws_bytes)) return rc;
+  return vb_terms_launch(coefs, batch, elems_per_sample, x_start, x_t, noise, model_out, clip_denoised, terms,
+                         (double*)workspace, stream)
+             ? HOLO_E_INVALID
+             : 0;
+}
+
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream) {
   (void)ctx;
   return tanh_launch(x, y, n, stream);

@@ -38,6 +38,12 @@ a per-voxel mask holds part of a clean grid fixed while the DDPM chain generates
 ``start_level`` starts the chain from a partly noised grid.  The step is ``holo_ddpm_step_inpaint`` (the DDPM update blended
 with the known grid noised one level down), a forward jump one ``holo_q_sample`` launch on ``jump_coefs`` rows; ``_chain``
 runs it through its ``pre`` hook.
+
+Losses and the variational bound (``training_losses``, ``_vb_terms_bpd``, ``_prior_bpd``, ``calc_bpd_loop``;
+gaussian_diffusion.py:817-1043 for START_X / FIXED_SMALL / MSE): x_t is a ``holo_q_sample`` launch on rows gathered on the
+device, the per-sample means are double sums in a fixed order (``holo_diffusion_loss``: mse, huber and the cotangent of the
+mse in one pass; ``holo_vb_terms``: the bound's term, xstart_mse and eps_mse on ``vb_coefs`` rows).  ``training_losses``
+carries an autograd node, so ``terms["loss"].mean().backward()`` reaches the denoiser through its own node.
 """
 from __future__ import annotations
 
@@ -952,8 +958,200 @@ class ImplicitronGaussianDiffusion(Configurable):
             device=device, progress=progress, steps=steps, order=order, spacing=spacing, timesteps=timesteps,
             lower_order_final=lower_order_final, noise_sampler=noise_sampler, cond_fn=cond_fn, _materialize_every_step=False))
 
-    def training_losses(self, *args, **kwargs):
-        raise NotImplementedError("training losses are outside the sampling hot path (SURVEY.md §8f)")
+    # ---- losses and the variational bound (gaussian_diffusion.py:817-1043) ---------------------------------------------
+    def vb_coefs(self, t: Sequence[int]) -> torch.Tensor:
+        """(n, 8) float32 rows of holo_vb_terms at timesteps ``t``, float64 values cast once: {posterior_mean_coef1,
+        posterior_mean_coef2, lv, exp(-lv), exp(-0.5*lv), sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, [t == 0]}
+        with lv = posterior_log_variance_clipped[t] - every transcendental of a per-row scalar is taken here."""
+        t = np.asarray(t, dtype=np.int64).reshape(-1)
+        lv = self.posterior_log_variance_clipped[t]
+        rows = np.stack([self.posterior_mean_coef1[t], self.posterior_mean_coef2[t], lv, np.exp(-lv), np.exp(-0.5 * lv),
+                         self.sqrt_recip_alphas_cumprod[t], self.sqrt_recipm1_alphas_cumprod[t], (t == 0).astype(np.float64)],
+                        axis=1)
+        return torch.from_numpy(rows.astype(np.float32))
+
+    def _loss_tables_on(self, device: torch.device):
+        """((T, 2) q_sample rows, (T, 8) vb rows) on ``device``, uploaded once: a batch's rows are gathered by its device
+        timesteps, so ``training_losses`` needs no host copy of ``t``."""
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        cache = self.__dict__.setdefault("_dev_loss_tables", {})
+        tabs = cache.get(idx)
+        if tabs is None:
+            every = np.arange(self.num_timesteps)
+            tabs = cache[idx] = (self.q_sample_coefs(every).to(device), self.vb_coefs(every).to(device))
+        return tabs
+
+    @staticmethod
+    def _loss_workspace(x: torch.Tensor) -> torch.Tensor:
+        nbytes = int(runtime.lib().holo_diffusion_loss_workspace_bytes(x.shape[0], x[0].numel()))
+        if nbytes == 0:
+            raise _lib.HoloError("holo_diffusion_loss_workspace_bytes: " + (runtime.lib().holo_last_error() or b"").decode())
+        return torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+
+    def _diffusion_loss(self, target, model_out, row_scale=None, want_terms=True, want_grad=False):
+        """holo_diffusion_loss: ((N, 2) float64 {mse, huber} | None, grad_out | None) in one launch.  ``row_scale`` (N,) float32
+        on the device: float(2 * w_b / n) of the cotangent of sum_b w_b * mse_b (None: every w_b is 1)."""
+        runtime.require_device(target, "ImplicitronGaussianDiffusion")
+        L = runtime.lib()
+        dev = target.device
+        target, model_out = target.contiguous().float(), model_out.contiguous().float()
+        if target.shape != model_out.shape:
+            raise ValueError(f"model output {tuple(model_out.shape)} does not match the target {tuple(target.shape)}")
+        ws = self._loss_workspace(target)
+        terms = torch.empty((target.shape[0], 2), dtype=torch.float64, device=dev) if want_terms else None
+        grad = torch.empty_like(model_out) if want_grad else None
+        opt = lambda a: None if a is None else runtime.ptr(a)  # noqa: E731
+        row_scale = None if row_scale is None else row_scale.contiguous()
+        _lib.check(L, L.holo_diffusion_loss(runtime.ctx(dev), target.shape[0], target[0].numel(), runtime.ptr(target),
+                                            runtime.ptr(model_out), opt(row_scale), opt(terms), opt(grad), runtime.ptr(ws),
+                                            ws.numel() * 8, runtime.stream_ptr(dev)), "holo_diffusion_loss")
+        return terms, grad
+
+    def _vb_terms(self, coefs_dev, x_start, x_t, noise, model_out, clip_denoised, out=None):
+        """holo_vb_terms on the (N, 8) ``vb_coefs`` rows ``coefs_dev``: (N, 3) float64 {vb in bits, xstart_mse, eps_mse}
+        (into ``out`` when given); ``noise`` None: no eps term."""
+        runtime.require_device(x_start, "ImplicitronGaussianDiffusion")
+        L = runtime.lib()
+        dev = x_start.device
+        x_start, x_t, model_out = x_start.contiguous().float(), x_t.contiguous().float(), model_out.contiguous().float()
+        noise = None if noise is None else noise.contiguous().float()
+        if not (x_start.shape == x_t.shape == model_out.shape) or (noise is not None and noise.shape != x_start.shape):
+            raise ValueError(f"x_t {tuple(x_t.shape)}, the noise and the model output {tuple(model_out.shape)} must have "
+                             f"x_start's shape {tuple(x_start.shape)}")
+        ws = self._loss_workspace(x_start)
+        if out is None:
+            out = torch.empty((x_start.shape[0], 3), dtype=torch.float64, device=dev)
+        _lib.check(L, L.holo_vb_terms(runtime.ctx(dev), runtime.ptr(coefs_dev), x_start.shape[0], x_start[0].numel(),
+                                      runtime.ptr(x_start), runtime.ptr(x_t), None if noise is None else runtime.ptr(noise),
+                                      runtime.ptr(model_out), 1 if clip_denoised else 0, runtime.ptr(out), runtime.ptr(ws),
+                                      ws.numel() * 8, runtime.stream_ptr(dev)), "holo_vb_terms")
+        return out
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """One term of the variational bound in bits per dimension (gaussian_diffusion.py:817-850): the KL between the true
+        and the model's posterior at t > 0, the decoder's negative log-likelihood at t == 0.  ``{"output": (N,),
+        "pred_xstart"}``."""
+        runtime.require_device(x_start, "ImplicitronGaussianDiffusion._vb_terms_bpd")
+        t = t.to(device=x_start.device, dtype=torch.int64)
+        with torch.no_grad():
+            model_output = model(x_t, t, **(model_kwargs or {}))
+            terms = self._vb_terms(self._loss_tables_on(x_start.device)[1][t], x_start, x_t, None, model_output, clip_denoised)
+            pred = model_output.clamp(-1, 1) if clip_denoised else model_output
+        return {"output": terms[:, 0].float(), "pred_xstart": pred}
+
+    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, get_xstart=False, clip_denoised=False,
+                        denoised_fn=None, x_start_for_error=None):
+        """The training losses of one timestep batch (gaussian_diffusion.py:852-968; START_X, MSE): ``{"x_t", "mse", "huber",
+        "loss" (= mse), "noise", "model_output"}`` and ``"pred_xstart"`` with ``get_xstart``.  x_t is one ``holo_q_sample``
+        launch - with ``device_noise_seed`` and no ``noise`` one ``holo_q_sample_philox`` launch that also reports its draw
+        (stream index ``training_draw_index``, which then advances) -, the two losses one ``holo_diffusion_loss`` launch.  With
+        autograd enabled and a model output that requires grad, ``mse`` / ``loss`` carry an autograd node whose backward is the
+        kernel's ``grad_out`` form with the upstream gradient as row weights: ``terms["loss"].mean().backward()`` reaches the
+        denoiser's parameters through its own node.  ``huber`` is detached."""
+        runtime.require_device(x_start, "ImplicitronGaussianDiffusion.training_losses")
+        dev = x_start.device
+        t = t.to(device=dev, dtype=torch.int64)
+        x_start = x_start.contiguous().float()
+        q_rows = self._loss_tables_on(dev)[0][t]
+        if noise is None and self.device_noise_seed is not None:
+            index = self.__dict__.get("training_draw_index", 0)
+            self.__dict__["training_draw_index"] = index + 1
+            x_t, noise = self._q_sample_rows(x_start, q_rows, timestep_index=index, want_noise=True)
+        else:
+            if noise is None:
+                noise = torch.randn_like(x_start)
+            if noise.shape != x_start.shape:
+                raise ValueError(f"noise {tuple(noise.shape)} does not match x_start {tuple(x_start.shape)}")
+            x_t = self._q_sample_rows(x_start, q_rows, noise.to(dev).float())
+        if x_start_for_error is not None:  # (gaussian_diffusion.py:882-883: only the returned noise changes under START_X)
+            noise = ((self._extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t - x_start_for_error)
+                     / self._extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape))
+        terms = {"x_t": x_t}
+        model_output = model(x_t, t, **(model_kwargs or {}))
+        if get_xstart:
+            pred = model_output if denoised_fn is None else denoised_fn(model_output)
+            terms["pred_xstart"] = pred.clamp(-1, 1) if clip_denoised else pred
+        if model_output.shape != x_start.shape:
+            raise ValueError(f"model output {tuple(model_output.shape)} does not match x_start {tuple(x_start.shape)}")
+        if torch.is_grad_enabled() and model_output.requires_grad:
+            terms["mse"], terms["huber"] = _DiffusionLossFn.apply(self, x_start, model_output)
+        else:
+            both, _ = self._diffusion_loss(x_start, model_output)
+            terms["mse"], terms["huber"] = both[:, 0].float(), both[:, 1].float()
+        terms["loss"] = terms["mse"]
+        terms["noise"] = noise
+        terms["model_output"] = model_output
+        return terms
+
+    def _prior_bpd(self, x_start):
+        """The prior term of the bound in bits per dimension (gaussian_diffusion.py:970-986): KL(q(x_T | x_0) || N(0, 1)), a
+        per-row scalar formula on mean(x_0^2) - the loss kernel's mse against a zero target.  (N,) float32."""
+        m2 = self._diffusion_loss(torch.zeros_like(x_start), x_start)[0][:, 0]
+        a = float(self.sqrt_alphas_cumprod[-1])
+        lv = float(self.log_one_minus_alphas_cumprod[-1])
+        return ((0.5 * (-1.0 - lv + float(np.exp(lv))) + (0.5 * a * a) * m2) / float(np.log(2.0))).float()
+
+    @torch.no_grad()
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, noise_sampler=None, timesteps=None):
+        """The variational bound in bits per dimension and its parts (gaussian_diffusion.py:988-1043): ``{"total_bpd",
+        "prior_bpd", "vb", "xstart_mse", "mse"}``, the last three (N, T) with the reference's column order (t = T - 1 first).
+        Build-side extensions: ``noise_sampler(t, shape, device)`` supplies the draws (else the in-kernel draw with
+        ``device_noise_seed``, else ``torch.randn_like``); ``timesteps`` restricts the loop to these timesteps, in this order -
+        then the columns follow them and ``total_bpd`` is left out.  Per timestep: one q_sample launch, one model call, one
+        ``holo_vb_terms`` launch; the rows of the whole loop are uploaded once, the results stay on the device, and nothing
+        synchronises."""
+        runtime.require_device(x_start, "ImplicitronGaussianDiffusion.calc_bpd_loop")
+        dev = x_start.device
+        x_start = x_start.contiguous().float()
+        B, T = x_start.shape[0], self.num_timesteps
+        ts = list(range(T))[::-1] if timesteps is None else [int(v) for v in timesteps]
+        if not ts or min(ts) < 0 or max(ts) >= T:
+            raise ValueError(f"calc_bpd_loop: timesteps must be in [0, {T}), got {ts}")
+        rep = np.repeat(np.asarray(ts, dtype=np.int64), B)
+        t_all = torch.from_numpy(rep).to(dev).view(len(ts), B)
+        q_rows = self.q_sample_coefs(rep).to(dev).view(len(ts), B, 2)
+        vb_rows = self.vb_coefs(rep).to(dev).view(len(ts), B, 8)
+        out = torch.empty((len(ts), B, 3), dtype=torch.float64, device=dev)
+        for k, ti in enumerate(ts):
+            if noise_sampler is not None:
+                noise = noise_sampler(ti, tuple(x_start.shape), dev)
+                x_t = self._q_sample_rows(x_start, q_rows[k], noise.to(dev).float())
+            elif self.device_noise_seed is not None:
+                x_t, noise = self._q_sample_rows(x_start, q_rows[k], timestep_index=ti, want_noise=True)
+            else:
+                noise = torch.randn_like(x_start)
+                x_t = self._q_sample_rows(x_start, q_rows[k], noise)
+            model_output = model(x_t, t_all[k], **(model_kwargs or {}))
+            self._vb_terms(vb_rows[k], x_start, x_t, noise, model_output, clip_denoised, out=out[k])
+        prior = self._prior_bpd(x_start)
+        res = {"prior_bpd": prior, "vb": out[:, :, 0].t().float(), "xstart_mse": out[:, :, 1].t().float(),
+               "mse": out[:, :, 2].t().float()}
+        if timesteps is None:
+            res["total_bpd"] = (out[:, :, 0].sum(dim=0) + prior.double()).float()
+        return res
 
     def sample_timesteps(self, *args, **kwargs):
         return self._schedule_sampler.sample(*args, **kwargs)
+
+
+class _DiffusionLossFn(torch.autograd.Function):
+    """Autograd node of ``training_losses``: forward = the terms form of holo_diffusion_loss, (mse, huber) per sample;
+    backward = its grad_out form, (model_out - target) * float(2 * g_b / n) with g_b the upstream gradient of mse_b, formed
+    in double on the device and rounded once.  ``huber`` is not differentiable; the target gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, diffusion, target, model_out):
+        ctx.diffusion = diffusion
+        target, model_out = target.detach(), model_out.detach()
+        ctx.save_for_backward(target, model_out)
+        terms, _ = diffusion._diffusion_loss(target, model_out)
+        mse, huber = terms[:, 0].float(), terms[:, 1].float()
+        ctx.mark_non_differentiable(huber)
+        return mse, huber
+
+    @staticmethod
+    def backward(ctx, g_mse, _g_huber):
+        target, model_out = ctx.saved_tensors
+        scale = (g_mse.double() * 2.0 / target[0].numel()).float()
+        _, grad = ctx.diffusion._diffusion_loss(target, model_out, row_scale=scale, want_terms=False, want_grad=True)
+        return None, None, grad

@@ -19,6 +19,7 @@ from __future__ import annotations
 import logging
 from typing import Any, Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib, runtime
@@ -501,6 +502,48 @@ class HoloDiffusionModel(ImplicitronModelBase, torch.nn.Module):
         if boot:
             out = one_round(out, "timesteps2", "q_noise2")
         return out
+
+    def voxel_features_bpd(self, voxel_features: torch.Tensor, timesteps=None, clip_denoised: bool = True,
+                           noise_sampler=None) -> Dict[str, torch.Tensor]:
+        """Scores clean grids (N, F, R, R, R) under the prior: the variational bound in bits per dimension with its parts
+        (``ImplicitronGaussianDiffusion.calc_bpd_loop`` on ``net_3d``) - to rank completions or edits, to tell whether a grid
+        lies on the prior, to validate a checkpoint without rendering.  ``timesteps``: a subset of the T terms (no
+        ``total_bpd`` then)."""
+        assert self.net_3d_enabled and self.diffusion_enabled, "voxel_features_bpd: the diffusion branch"
+        return self.diffusion.calc_bpd_loop(self.net_3d, voxel_features, clip_denoised=clip_denoised,
+                                            noise_sampler=noise_sampler, timesteps=timesteps)
+
+    @torch.no_grad()
+    def diffusion_training_step(self, voxel_features: torch.Tensor, rng_streams: Optional[dict] = None) -> Dict[str, Any]:
+        """One step's worth of gradients of the plain DDPM objective on clean grids, mean_b mse(x_start, net_3d(x_t, t))
+        (gaussian_diffusion.py:852-968 with START_X / MSE), all on the HIP path: q_sample, the taped forward, ONE
+        ``holo_diffusion_loss`` launch for the terms and the cotangent (row weights 1 / batch), the taped backward.
+        ``rng_streams``: ``timesteps`` / ``q_noise`` (else drawn).  Returns ``{"loss", "terms": {"mse", "huber", "x_t",
+        "noise", "model_output", "timesteps", "grad_output"}, "unet": {name: grad}}``; ``HoloAdam.step`` takes it as it stands.
+        fp32 mode only."""
+        assert self.net_3d_enabled and self.diffusion_enabled, "diffusion_training_step: the diffusion branch"
+        runtime.require_device(voxel_features, "HoloDiffusionModel.diffusion_training_step")
+        if self.net_3d.compute_dtype != "f32":
+            raise _lib.HoloError("HoloDiffusionModel.diffusion_training_step runs in the fp32 mode only")
+        rs = rng_streams or {}
+        dev = voxel_features.device
+        x0 = voxel_features.contiguous().float()
+        B = x0.shape[0]
+        t = rs.get("timesteps")
+        if t is None:
+            t, _ = self.diffusion.sample_timesteps(B, dev)
+        t = torch.as_tensor(t, device=dev, dtype=torch.int64).reshape(B)
+        noise = rs.get("q_noise")
+        noise = torch.randn_like(x0) if noise is None else noise.to(dev).float()
+        x_t = self.diffusion._q_sample_rows(x0, self.diffusion._loss_tables_on(dev)[0][t], noise)
+        y = self.net_3d.forward_train(x_t, t)
+        w = float(np.float32(1.0 / B))  # (the float32 weight torch's mean() hands back: the autograd route's bits)
+        scale = torch.full((B,), float(np.float32(2.0 * w / x0[0].numel())), dtype=torch.float32, device=dev)
+        both, g_y = self.diffusion._diffusion_loss(x0, y, row_scale=scale, want_terms=True, want_grad=True)
+        _, unet_grads = self.net_3d.backward_taped(g_y)
+        terms = {"mse": both[:, 0].float(), "huber": both[:, 1].float(), "x_t": x_t, "noise": noise, "model_output": y,
+                 "timesteps": t, "grad_output": g_y}
+        return {"loss": both[:, 0].mean().float(), "terms": terms, "unet": unet_grads}
 
     @torch.no_grad()
     def pool_views_to_voxel_features(self, image_features: Dict[str, torch.Tensor], source_cameras) -> torch.Tensor:

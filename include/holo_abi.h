@@ -416,6 +416,56 @@ int holo_q_sample_philox(HoloCtx* ctx, const float* coefs, int batch, int64_t el
                          uint64_t stream_offset, const uint32_t* row_streams, uint32_t timestep_index, float* out,
                          float* noise_out, int ncdhw_channels, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Diffusion losses and the variational bound (START_X, FIXED_SMALL).  Two streaming launches, each followed by a
+ * one-workgroup finalize launch; per-sample sums are taken in double: per-lane accumulators, a fixed-order tree in the
+ * workgroup, one partial per workgroup in `workspace`, the partials added in a fixed order.  No atomics: results are
+ * bit-identical from run to run, the number of partials depends on (batch, elems_per_sample) only (not on the CU count),
+ * and a sample's terms do not depend on the batch or the row it runs in.  Elementwise: any layout.  elems_per_sample is a
+ * positive multiple of 4, batch is 1 .. 65535 (HOLO_E_INVALID otherwise); a workspace smaller than
+ * holo_diffusion_loss_workspace_bytes(batch, elems_per_sample), which serves both entries, is HOLO_E_WORKSPACE.  `terms` are
+ * DOUBLES on the device.  Nothing is allocated, nothing synchronises.
+ *
+ * holo_diffusion_loss - gaussian_diffusion.py:949-952 (terms["mse"], terms["huber"]) and :1062-1076 (_huber, _safe_sqrt):
+ *   d = target - model_out ;  sq = d*d ;  huber = (sqrt(max(1 + sq / (s*s), 0) + 1e-4) - 1) * s with s = 0.001
+ *   (float32, every operation rounded, the reference's order, correctly rounded sqrt and division)
+ *   terms[b] = {mean_flat(sq), mean_flat(huber)}                                      (may be null)
+ *   grad_out = (model_out - target) * row_scale[b]                                    (may be null; not both)
+ *   the cotangent of w_b * mse_b when the caller forms row_scale[b] = float(2 * w_b / elems_per_sample) in double;
+ *   row_scale == NULL means w_b = 1.  Against a zero target, terms[b][0] is mean_flat(model_out**2) (_prior_bpd, :970-986).
+ *
+ * holo_vb_terms - gaussian_diffusion.py:817-850 (_vb_terms_bpd with q_posterior_mean_variance :229-251, p_mean_variance
+ * :253-355), losses.py:18-83 (normal_kl, discretized_gaussian_log_likelihood) and the body of calc_bpd_loop, :1027-1029:
+ *   coefs : (batch, 8) fp32 rows cast once from the float64 schedule at the sample's timestep t,
+ *           {posterior_mean_coef1, posterior_mean_coef2, lv, exp(-lv), exp(-0.5*lv), sqrt_recip_alphas_cumprod,
+ *            sqrt_recipm1_alphas_cumprod, [t == 0]} with lv = posterior_log_variance_clipped[t]
+ *   pred   = clip_denoised ? clamp(model_out, -1, 1) : model_out
+ *   t > 0 : kl  = 0.5 * ((mean_q - mean_p)^2 * exp(-lv)) with mean_q - mean_p formed as c1 * (x_start - pred): the c2*x_t
+ *           terms of the two posterior means cancel exactly and are left out (in float32 they would leave 2^-24 * |c2*x_t|
+ *           of rounding in a difference of ~1e-4 at t = 999)
+ *   t == 0: nll = -discretized_gaussian_log_likelihood(x_start, means=mean_p, log_scales=0.5*lv) with
+ *           mean_p = c1*pred + c2*x_t (products rounded, sum rounded, no fma): the tanh CDF, the branches at
+ *           x < -0.999 and x > 0.999, the clamps at 1e-12
+ *   terms[b] = {mean_flat(kl or nll) / ln 2, mean_flat((pred - x_start)^2),
+ *               mean_flat(((sqrt_recip*x_t - pred) / sqrt_recipm1 - noise)^2)}        (the last is 0 when noise is null)
+ *   Rows with t == 0 and t > 0 mix freely in one launch.
+ *   THE DROPPED TERM.  normal_kl adds -1 + lv2 - lv1 + exp(lv1 - lv2).  Under FIXED_SMALL both log-variances are the same
+ *   table entry, so the term is exactly 0; evaluated in float32 as the reference does, (-1 + lv2) rounds before lv1 is
+ *   subtracted and leaves a residue of up to half an ulp of lv - 3e-5 of the KL at t = 999, where the KL itself is tiny.
+ *   The kernel does not evaluate the term: its KL is closer to the exact value than the reference's float32 one.
+ *   THE t == 0 INPUT CONDITION.  The decoder term is the log of a clamped difference of two tanh CDFs.  Where that
+ *   difference underflows (a prediction many sigma_0 = exp(0.5*lv[0]) ~ 0.0074 away from x_start), one ulp of tanh moves
+ *   the result between log(1e-12) = -27.6 and about -16: the value is then defined by the library's tanh, not by this
+ *   interface, and agrees with the reference only in order of magnitude.  Within a few sigma_0 the term is well conditioned.
+ * ------------------------------------------------------------------------------------------ */
+size_t holo_diffusion_loss_workspace_bytes(int batch, int64_t elems_per_sample);
+int holo_diffusion_loss(HoloCtx* ctx, int batch, int64_t elems_per_sample, const float* target, const float* model_out,
+                        const float* row_scale, double* terms, float* grad_out, void* workspace, size_t ws_bytes,
+                        void* stream);
+int holo_vb_terms(HoloCtx* ctx, const float* coefs, int batch, int64_t elems_per_sample, const float* x_start,
+                  const float* x_t, const float* noise, const float* model_out, int clip_denoised, double* terms,
+                  void* workspace, size_t ws_bytes, void* stream);
+
 /* Elementwise helpers on the path: torch.tanh (holo_diffusion_model.py:425) and
  * torch.clip(x,-1,1) (holo_diffusion_model.py:186). */
 int holo_tanh(HoloCtx* ctx, const float* x, float* y, int64_t n, void* stream);
